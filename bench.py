@@ -30,7 +30,12 @@ Timed region: W warm-up steps, then an untimed spin-up until the device has been
 ranks. Beside the wall-clock value the line carries the median per-step time from HIP events on the launch stream (one event
 after every 4th step: group means).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the outputs of the last timed step when
+--dump-outputs DIR is given (DIR/<name>.npy, float64: what a caller of the timed path receives; a fixed, seeded sample of walkers when
+the whole would exceed 64 MB), and rank 0's JSON line with `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and
+the step-event timings. Everything else is measured only under --full.
+
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it carries these extra objects:
   roofline      the bound that BINDS the dominant kernel k_main: FP64 vector issue. achieved = FP64 flops per evaluation (from
                 the committed PMC instruction counts of exactly this kernel source, profiles/pmc_traffic.json) x evaluations per
                 launch / the kernel's average duration measured live with HIP events on its launch stream; peak = 78.6 TFLOP/s
@@ -70,6 +75,7 @@ HBM_PEAK_GBPS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 
 FP64_VECTOR_PEAK_TFLOPS = 78.6
 BYTES_PER_ROW = 40.0          # epoch, ra, dec, σ_ra, σ_dec  
 BYTES_PER_WALKER = 64.0 + 72.0  # read 8 elements, write ll + 8 adjoints
+DUMP_MAX_BYTES = 64_000_000     # --dump-outputs: at most 64 MB in all, .npy headers included
 
 
 def parse():
@@ -92,7 +98,14 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); gloo only for single-GPU dry runs")
     ap.add_argument("--device", type=int, default=None, help="force the HIP device index (dry runs of the N>1 path on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: roofline (k_main timed with HIP events), parity sample, PCIe-inclusive "
+                         "rates, strong/weak-scaling legs, config-1 latency, CPU baseline, swap-step latency (--no-extras / --no-cpu-baseline trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.walkers is None:      # BASELINE config 5: 64 temperatures x 1024 walkers over 8 GPUs = 8 x 1024 per GPU
         args.walkers = 8192 if args.workload == "pt" else 10_000
     if args.scaling is None:
@@ -160,6 +173,27 @@ def cpu_baseline(cfg, obs_tables, planets, seconds):
             "single_thread_forward_only": {"value": v_one_f, "unit": "evals/s (fwd)", "cores": 1, "ns_per_eval": 1e9 / v_one_f, "sample": s_one_f},
             "reference_remarks": "the reference's own comment puts one Kepler solve at ~200 ns on a CPU core (src/likelihoods/system.jl:245-246; "
                                  "SURVEY.md section 6 infers 32-200 ns); one evaluation here = one solve + projection + density (+ 8 partials with the gradient)"}
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: the arrays the last timed step returned, as <name>.npy (float64, walkers on the last axis). Above DUMP_MAX_BYTES in all, a
+    fixed, seeded sample of walker columns is kept, the same for every array, and its indices travel as walker_index.npy. N > 1: every rank
+    writes its own shard, rank r > 0 with the suffix _rank<r>."""
+    import torch
+    arrays = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float64) for k, v in arrays.items() if v is not None}
+    W = next(iter(arrays.values())).shape[-1]
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_MAX_BYTES - 4096      # room for the .npy headers
+    if total > budget:
+        keep = int(budget // (total / W + 8))      # bytes per walker column + its float64 index
+        idx = np.sort(np.random.default_rng(0).choice(W, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(v[..., idx]) for k, v in arrays.items()}
+        arrays["walker_index"] = idx.astype(np.float64)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 and rank > 0 else ""
+    for k, v in arrays.items():
+        np.save(d / f"{k}{sfx}.npy", v)
 
 
 def parity_sample(fn, cfg, ll_dev, g_dev, n=8):
@@ -316,7 +350,10 @@ def main():
         solver = pkg.OftiLinearSolver(t["epoch"], t["ra"], t["dec"], t["σ_ra"], t["σ_dec"], None, 1000.0, device=dev_index)
         el = cfg0["elems"]
         nl = torch.tensor(np.stack([el[1], el[0], el[5], el[6], el[7]]), device=dev)
-        dt, per_step, n_spin = timed_loop(lambda i: solver.eval_device(nl))
+        last = {}
+        dt, per_step, n_spin = timed_loop(lambda i: last.update(zip(("abfg", "logml"), solver.eval_device(nl))))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last, rank, world)
         if rank == 0:
             emit(base_line("OFTI marginal-likelihood epoch evals/sec (fwd)", args.epochs * args.walkers * args.steps * world / dt, dt, per_step, n_spin,
                            f"ofti_linear_solve: {args.epochs} RA/Dec epochs x {args.walkers} walkers, forward"))
@@ -334,7 +371,10 @@ def main():
                                                                               plx=pkg.truncated(pkg.Normal(50.0, 0.02), lower=0.1)))
         model = pkg.LogDensityModel(sysm, device=dev_index)
         θt = torch.tensor(model.link(model.sample_priors(np.random.default_rng(20260929 + 7), args.walkers)), device=dev)
-        dt, per_step, n_spin = timed_loop(lambda i: model.logpost_device(θt, grad=True))
+        last = {}
+        dt, per_step, n_spin = timed_loop(lambda i: last.update(zip(("lp", "grad_theta_t"), model.logpost_device(θt, grad=True))))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last, rank, world)
         if rank == 0:
             emit(base_line("epoch-likelihood evals/sec, full log-posterior + gradient w.r.t. theta_t (D=11)",
                            args.epochs * args.walkers * args.steps * world / dt, dt, per_step, n_spin,
@@ -510,11 +550,17 @@ def main():
                         "replicated, no collective, 50 back-to-back steps between barriers, max over ranks, best of 3",
                 "n_gpus": world, "walkers_per_gpu": Wf, "us_per_step": best * 1e6, "value": world * Wf * n_rows / best, "unit": "evals/s"}
 
-    fn.timing_enable(TIMED_EVERY)      # HIP events around k_main of every TIMED_EVERY-th evaluation, on its launch stream
-    dt, per_step, n_spin = timed_loop(run_step, on_timed_start=lambda: fn.timing_read(reset=True))
-    kern_med, kern_min, kern_max, kern_n = fn.timing_stats()
-    kern_ms, _ = fn.timing_read(reset=True)
-    fn.timing_enable(False)
+    if args.full:
+        fn.timing_enable(TIMED_EVERY)      # HIP events around k_main of every TIMED_EVERY-th evaluation, on its launch stream
+        dt, per_step, n_spin = timed_loop(run_step, on_timed_start=lambda: fn.timing_read(reset=True))
+        kern_med, kern_min, kern_max, kern_n = fn.timing_stats()
+        kern_ms, _ = fn.timing_read(reset=True)
+        fn.timing_enable(False)
+    else:
+        dt, per_step, n_spin = timed_loop(run_step)
+    if args.dump_outputs:
+        # pt: the replicas' log-likelihoods only — the swap state after the last step depends on the number of (time-bounded) spin-up steps
+        dump_outputs(args.dump_outputs, {"ll": out[0], "grad_elems": out[1], "grad_nuis": out[2]}, rank, world)
 
     if args.scaling == "strong" and cfg is not None:      # ranks may differ by one walker: count what every rank really did
         tw = torch.tensor([float(W)], dtype=torch.float64, device=dev)
@@ -527,12 +573,12 @@ def main():
     metric = "epoch-likelihood evals/sec (fwd+grad), 1e4 epochs x 1e4 walkers" if args.workload == "grad" else f"epoch-likelihood evals/sec ({args.workload})"
     res = base_line(metric, value, dt, per_step, n_spin, workload,
                     {"walkers_per_gpu": W, "walkers_total": (args.walkers if args.scaling == "strong" else W * world), "rows": n_rows, "parallelism": parallelism})
-    if world > 1 and args.scaling == "strong" and cfg is not None and args.workload in ("grad", "fwd") and not args.no_extras:
+    if args.full and world > 1 and args.scaling == "strong" and cfg is not None and args.workload in ("grad", "fwd") and not args.no_extras:
         try:      # every rank takes part (barriers + a MAX all-reduce); rank 0 reports
             res["weak_scaling_measured"] = weak_measured()
         except Exception as ex:
             res["weak_scaling_measured"] = {"error": str(ex)}
-    if world > 1 and args.scaling == "weak" and cfg is not None and args.workload in ("grad", "fwd") and not args.no_extras:
+    if args.full and world > 1 and args.scaling == "weak" and cfg is not None and args.workload in ("grad", "fwd") and not args.no_extras:
         try:      # every rank takes part (barriers + a MAX all-reduce); rank 0 reports
             sm_ = strong_measured()
             sm_["speedup_vs_one_gpu"] = (dt / args.steps) / (sm_["us_per_step"] * 1e-6)
@@ -540,12 +586,12 @@ def main():
             res["strong_scaling_measured"] = sm_
         except Exception as ex:
             res["strong_scaling_measured"] = {"error": str(ex)}
-    if pt is not None:
+    if args.full and pt is not None:
         lat = swap_latency()
         res["swap_step_latency_us"] = lat
         res["swap_step_what"] = ("median over 200 steps, max over ranks: " + ("ncclAllGather of the local replicas' log-likelihoods + " if world > 1 else "")
                                  + "deterministic neighbour-swap kernel, host-synchronised per step")
-    if rank == 0:
+    if rank == 0 and args.full:
         is_cfg3 = args.workload == "grad" and n_rows == 10_000 and cfg is not None
         pmc, pmc_ok, pmc_note, pmc_exact = None, False, None, True
         pmc_path = ROOT / "profiles" / "pmc_traffic.json"
@@ -716,6 +762,7 @@ def main():
                 res["cpu_baseline"] = cpu_baseline(cfg_full, fn.obs_tables, fn.planet_desc, args.cpu_seconds)
             except Exception as ex:  # the checker is optional for the measurement itself
                 res["cpu_baseline"] = {"value": None, "unit": "evals/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {ex}"}
+    if rank == 0:
         emit(res)
     fn.close()
     if world > 1:

@@ -10,6 +10,7 @@ header; no compiled-C consumer pins sizeof/offsetof"):
 """
 import ctypes as C
 import json
+import os
 import re
 import subprocess
 from pathlib import Path
@@ -170,8 +171,8 @@ def test_julia_shim_names_exist_in_the_reference():
     """745+ lines of Julia that cannot run in the build image: every `Octofitter.<name>` the shim calls or extends and every
     field it reads from a reference struct (`obs.trend_function`, `obs.gaussian_process`, `obs.wrapped_like`, `model.arr2nt`, table
     columns, …) must be a name the reference defines. tools/julia_api_manifest.py extracts both sides; the committed manifest
-    (tests/golden/julia_api_names.json: name -> defining file:line) is DATA that travels; where /root/reference is present (the build
-    container) the manifest itself is re-derived and every entry re-checked against the sources, so API drift on either side fails here."""
+    (tests/golden/julia_api_names.json: name -> defining file:line) is DATA that travels; when OCTOFITTER_REFERENCE_DIR names a checkout of
+    the reference, the manifest itself is re-derived and every entry re-checked against the sources, so API drift on either side fails here."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("julia_api_manifest", ROOT / "tools" / "julia_api_manifest.py")
     jm = importlib.util.module_from_spec(spec); spec.loader.exec_module(jm)
@@ -185,8 +186,10 @@ def test_julia_shim_names_exist_in_the_reference():
     assert not missing, f"OctofitterHIP.jl reads fields the manifest does not know: {missing} (run tools/julia_api_manifest.py)"
     for must in ("trend_function", "gaussian_process", "wrapped_like", "hgca", "dist_hip", "table", "priors", "derived"):
         assert must in man["fields"], must
-    if not jm.REF.exists():
-        return                                          # the GPU box: the manifest is the travelling record
+    ref = os.environ.get("OCTOFITTER_REFERENCE_DIR")
+    if not ref:
+        return                                          # no reference checkout named: the manifest is the travelling record
+    jm.REF = Path(ref)
     fresh, not_found = jm.build()
     assert not not_found, f"names the reference does not define: {not_found}"
     assert fresh["names"] == man["names"] and fresh["fields"] == man["fields"], "tests/golden/julia_api_names.json is stale: run tools/julia_api_manifest.py"

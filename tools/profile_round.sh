@@ -10,7 +10,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 B="python $ROOT/bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-extras"
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $out/stats -o k -- python $ROOT/bench.py > $out/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/stats -o k -- python $ROOT/bench.py --full > $out/bench_under_rocprof.log 2>&1
 rocprofv3 --kernel-trace --stats --pmc FETCH_SIZE -d $out/pmc_fetch -o k -- $B > $out/b_fetch.log 2>&1
 rocprofv3 --kernel-trace --stats --pmc WRITE_SIZE -d $out/pmc_write -o k -- $B > $out/b_write.log 2>&1
 rocprofv3 --kernel-trace --stats --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 -d $out/pmc_mix -o k -- $B > $out/b_mix.log 2>&1
