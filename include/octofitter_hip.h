@@ -203,7 +203,9 @@ const char* octo_last_error(const octo_ctx* ctx);
  *   OCTO_OPT_BATCH_INVARIANT  1: ll(θ) and its gradient are independent of the batch's size and composition, bit for bit — checkpoint / resume, a
  *                             1-GPU against an 8-GPU rerun of one chain, two batch sizes: the cold row loop, no tile sort, ONE row partition (64 rows
  *                             per wave) and the throughput kernels for every batch size (no small-batch route: a one-θ call then costs three launches,
- *                             ~40 µs instead of ~16). Default 0. Costs ~25 % of the throughput on dense tables (round 4's rate).
+ *                             ~40 µs instead of ~16). Default 0. Costs ~25 % of the throughput on dense tables (round 4's rate). It covers
+ *                             octo_eval*, octo_eval_multi, octo_model_logpost* and octo_ofti_eval* (a fixed row chunk there) for every planet
+ *                             count 1 … OCTO_MAX_PLANETS.
  *   OCTO_OPT_WARM_START       0: the cold row loop only (round 4's kernels), everything else as usual. Default 1 (environment OCTO_WARM=0 at
  *                             octo_ctx_create sets 0).
  *   OCTO_OPT_TILE_SORT        walkers of big single-planet batches grouped into tiles of 64 by how often their rows would fail the warm start's

@@ -1656,8 +1656,8 @@ int32_t octo_ofti_eval_device(octo_ctx* ctx, const octo_ofti* h, const double* d
     OftiArgs a;
     std::memset(&a, 0, sizeof(a));
     const int64_t cols = (W + WAVE - 1) / WAVE;
-    int chunk = 32;
-    {   // same sizing rule as the likelihood kernel: an exact number of rounds of resident blocks, equal tasks
+    int chunk = 32;      // OCTO_OPT_BATCH_INVARIANT: this fixed chunk whatever the batch size (the partition decides the summation order)
+    if (!ctx->opt_invariant) {   // same sizing rule as the likelihood kernel: an exact number of rounds of resident blocks, equal tasks
         int& blocks_per_cu = ctx->occupancy[0xffff0001u];
         if (blocks_per_cu == 0) {
             int nb = 0;

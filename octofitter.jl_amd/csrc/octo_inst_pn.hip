@@ -109,7 +109,10 @@ int dispatch_many(octo_ctx* ctx, const octo_dataset* ds, EvalArgs& a, bool grad,
     int& blocks_per_cu = ctx->occupancy[(uint32_t)((P << 16) | ((nuis ? 1 : 0) << 15) | km_p)];
     if (blocks_per_cu == 0) blocks_per_cu = mainp_occupancy(ctx, nuis, km_p, P);
     TaskTable* tt = nullptr;
-    int rc = get_tasks(ctx, ds, plan_key_mainp(ctx, a.W, ds->n_rows, blocks_per_cu), &tt, nuis, 1);
+    // OCTO_OPT_BATCH_INVARIANT: launch_all's fixed partition (64 rows per wave) whatever the batch size; the marginalised-RV pre-pass below walks
+    // the same task table
+    const int64_t pkey = ctx->opt_invariant ? (int64_t)-64 : plan_key_mainp(ctx, a.W, ds->n_rows, blocks_per_cu);
+    int rc = get_tasks(ctx, ds, pkey, &tt, nuis, 1);
     if (rc) return rc;
     a.tasks = tt->d_tasks; a.task_const = nuis ? tt->d_const_raw : tt->d_const_pre;
     a.obs_range = tt->d_obs_range; a.obs_const = nuis ? tt->d_obs_const_raw : tt->d_obs_const_pre;
