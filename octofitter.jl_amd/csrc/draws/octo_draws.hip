@@ -1,0 +1,623 @@
+// octo_draws.hip — liboctofitter_hip_draws.so: prior draws on the device and the two batched drivers on top of them
+// (include/octofitter_hip_draws.h). A client of the public C ABI: log-posteriors come from octo_model_logpost_device; of the
+// main library's sources it includes only the device helpers of octo_model.h (prior_bounds, prior_link_lanes,
+// prior_density_lanes), so the prior term it subtracts in the rejection driver is the code the model callback ran.
+//
+//   k_draw      one thread = one draw, one launch = one Philox block of four coordinates: uniform -> inverse CDF -> link -> density.
+//               Store bound: 16·D + 8 bytes per draw, every store coalesced (draw index fastest).
+//   k_topk      the `keep` best (log-posterior descending, draw index ascending: a TOTAL order, so the result is a set
+//               operation — independent of grid, slab and chunk size) of a slab, by `keep` rounds of a block-wide arg-best:
+//               wave shuffles -> LDS -> one partial list per block; the same kernel as ONE block merges the partial lists
+//               and the running list. No atomics.
+//   k_loglike   ll = lp − logprior_t (non-finite -> −Inf) and the per-block maximum; k_max the maximum of those.
+//   k_count / k_scan / k_scatter   accept flags (recomputed, never stored), per-block counts, their exclusive scan, ordered scatter.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "octo_model.h"
+#include "octofitter_hip_draws.h"
+
+namespace {
+using namespace octo;
+
+constexpr uint64_t PHILOX_M0 = 0xD2E7470EE14C6C93ull, PHILOX_M1 = 0xCA5A826395121157ull;
+constexpr uint64_t PHILOX_W0 = 0x9E3779B97F4A7C15ull, PHILOX_W1 = 0xBB67AE8584CAA73Bull;
+constexpr uint64_t KEY1 = 0x6f63746f64726177ull;      // "octodraw"
+constexpr int TPB = 256;
+constexpr int64_t CHUNK = 1 << 18;                    // draws per log-posterior call (a multiple of TPB)
+constexpr int SEL_EPT = 17;                           // candidates per thread of k_topk
+constexpr int64_t SEL_SLAB = (int64_t)TPB * SEL_EPT;  // 4352 per block: 61 blocks per chunk, and (61 + 1)·64 candidates fit the merging block
+constexpr int64_t SEL_BLOCKS = (CHUNK + SEL_SLAB - 1) / SEL_SLAB;
+constexpr uint64_t NO_INDEX = ~0ull;
+constexpr int IC_N = 4;                               // inverse-CDF constants per prior
+static_assert((SEL_BLOCKS + 1) * OCTO_DRAWS_MAX_KEEP <= SEL_SLAB, "the merging block must hold every partial list and the running list");
+static_assert(CHUNK % TPB == 0, "chunk boundaries are block boundaries of the rejection pass");
+
+// Philox4x64-10 (Salmon et al. 2011), the variant NumPy ships: ten rounds, the key bumped after each.
+__device__ __forceinline__ void philox4x64(uint64_t k0, uint64_t k1, uint64_t c0, uint64_t c1, uint64_t c2, uint64_t c3, uint64_t (&o)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t hi0 = __umul64hi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
+        const uint64_t hi1 = __umul64hi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += PHILOX_W0; k1 += PHILOX_W1;
+    }
+    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
+// (2·(x >> 12) + 1)·2⁻⁵³: an odd multiple of 2⁻⁵³ below 1 — exact, never 0 or 1
+__device__ __forceinline__ double u01(uint64_t x) { return (double)(2 * (x >> 12) + 1) * 0x1p-53; }
+
+__device__ __forceinline__ double rejection_uniform(uint64_t seed, uint64_t i) {
+    uint64_t r[4];
+    philox4x64(seed, KEY1, i, 0, OCTO_DRAWS_PURPOSE_UNIFORM, 0, r);
+    return u01(r[0]);
+}
+
+// Quantile of the prior at u, strictly inside the support the bijector assumes (prior_bounds). ic: constants made at octo_draws_create —
+//   Uniform {a, b − a} · LogUniform {log a, log b − log a} · truncated Normal {P0, ΔP, mirrored} with α = (lo − μ)/σ, β = (hi − μ)/σ:
+//   α < 0: z = Φ⁻¹(Φ(α) + u(Φ(β) − Φ(α))) · α >= 0 (a tail): z = −Φ⁻¹(Φ(−α) − u(Φ(−α) − Φ(−β))), so that the tail keeps its digits.
+// The coordinate d is the same for every lane, so the branch on the kind is wave-uniform.
+__device__ __forceinline__ double prior_quantile(const octo_prior& pr, const PriorBounds& B, const double* __restrict__ ic, double u) {
+    double x;
+    switch (pr.kind) {
+    case OCTO_PRIOR_UNIFORM: x = ic[0] + ic[1] * u; break;
+    case OCTO_PRIOR_LOGUNIFORM: x = exp(ic[0] + u * ic[1]); break;
+    case OCTO_PRIOR_NORMAL: x = pr.p0 + pr.p1 * normcdfinv(u); break;
+    case OCTO_PRIOR_TRUNCNORMAL: {
+        const bool mirrored = ic[2] != 0.0;
+        double p = mirrored ? ic[0] - u * ic[1] : ic[0] + u * ic[1];
+        p = fmin(fmax(p, 2.2250738585072014e-308), 1.0 - 0x1p-53);      // a probability that rounded onto 0 or 1 has no finite quantile
+        const double z = normcdfinv(p);
+        x = pr.p0 + pr.p1 * (mirrored ? -z : z);
+        break;
+    }
+    default: x = acos(1.0 - 2.0 * u); break;                              // Sine: distributions.jl:39
+    }
+    if (B.fa && !(x > B.a)) x = nextafter(B.a, INFINITY);
+    if (B.fb && !(x < B.b)) x = nextafter(B.b, -INFINITY);
+    return x;
+}
+
+// Bijectors.link (TruncatedBijector), the inverse of prior_link_lanes; host/priors.py: Prior.link is its executable statement
+__device__ __forceinline__ double prior_link_forward(const PriorBounds& B, double x) {
+    if (B.both) {
+        double u = (x - B.a) / (B.b - B.a);
+        u = fmin(fmax(u, 2.2250738585072014e-308), 1.0 - 0x1p-53);        // x is inside (a, b); the quotient may still round onto 1
+        return log(u) - log1p(-u);
+    }
+    if (B.fa) return log(x - B.a);
+    if (B.fb) return log(B.b - x);
+    return x;
+}
+
+struct DrawArgs {
+    const octo_prior* priors;      // [D]
+    const double* pc;              // [D][PRIOR_NC] constants of prior_density_lanes
+    const double* ic;              // [D][IC_N] constants of prior_quantile
+    const uint64_t* idx;           // [n] draw indices, or null: first + t
+    uint64_t seed, first;
+    int64_t n, ld;
+    int32_t D, d0;                 // this launch: coordinates d0 … d0 + 3 (d0 a multiple of 4)
+    double* theta; double* theta_t; double* lpt;
+};
+
+// One launch = one Philox block of four coordinates [d0, d0 + 4) ∩ [0, D); the host walks the blocks (launch_draw). A loop over the coordinates
+// INSIDE the kernel was tried first: the compiler hoists the ~230 polynomial coefficients of normcdfinv / exp / log / log1p / acos out of it into
+// registers (480 VGPRs + AGPRs, one wave per SIMD; held to 128 it spilled 348 of them). Without a loop there is nothing to hoist them out of.
+// logprior_t is carried through a.lpt from launch to launch, added in declaration order: the model callback's own order of summation.
+__global__ __launch_bounds__(TPB) void k_draw(DrawArgs a) {
+    const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    const bool live = t < a.n;                        // no early exit: prior_density_lanes votes across the wave
+    const int64_t tl = live ? t : a.n - 1;
+    const uint64_t i = a.idx ? a.idx[tl] : a.first + (uint64_t)tl;
+    const bool want_t = a.theta_t != nullptr || a.lpt != nullptr;
+    double lp = 0.0;
+    bool healed = false;
+    if (a.lpt && a.d0 > 0) { lp = a.lpt[tl]; healed = lp == -1.7976931348623157e308; }
+    uint64_t r[4];
+    philox4x64(a.seed, KEY1, i, (uint64_t)(a.d0 >> 2), OCTO_DRAWS_PURPOSE_PRIOR, 0, r);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int d = a.d0 + q;
+        if (d >= a.D) break;
+        const octo_prior pr = a.priors[d];
+        const PriorBounds B = prior_bounds(pr);
+        const double x = prior_quantile(pr, B, a.ic + IC_N * d, u01(r[q]));
+        if (a.theta && live) a.theta[(int64_t)d * a.ld + t] = x;
+        if (!want_t) continue;
+        const double y = prior_link_forward(B, x);
+        if (a.theta_t && live) a.theta_t[(int64_t)d * a.ld + t] = y;
+        if (a.lpt) {
+            // what the model callback does with this θ_t: x' = invlink(y), logpdf_with_trans at x', the healing rule (k_model_fwd)
+            double xv, xd, pv, pd;
+            prior_link_lanes(pr, y, xv, xd);
+            prior_density_lanes(pr, xv, xd, pv, pd, a.pc + PRIOR_NC * d);
+            healed = healed || !isfinite(pv);
+            lp += pv;
+        }
+    }
+    if (a.lpt && live) a.lpt[t] = healed ? -1.7976931348623157e308 : lp;
+}
+
+// ---- selection ---------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool better(double lp1, uint64_t i1, double lp2, uint64_t i2) { return lp1 > lp2 || (lp1 == lp2 && i1 < i2); }
+
+// Block b lists the `keep` best of candidates [b·SEL_SLAB, min(n, (b+1)·SEL_SLAB)) at out[(out_first + b)·keep …], best first; places without
+// a candidate hold (−Inf, NO_INDEX). idx = null: candidate k is draw base + k. A candidate with a non-finite lp is none.
+// One block may run in place on out (every candidate is in a register before the first barrier; the first store follows it).
+__global__ __launch_bounds__(TPB) void k_topk(const double* lp, const uint64_t* idx, uint64_t base, int64_t n, int32_t keep,
+                                              int64_t out_first, double* out_lp, uint64_t* out_idx) {
+    __shared__ double s_lp[2][TPB / WAVE];
+    __shared__ uint64_t s_ix[2][TPB / WAVE];
+    const int64_t lo = (int64_t)blockIdx.x * SEL_SLAB;
+    double v[SEL_EPT];
+    uint64_t ix[SEL_EPT];
+#pragma unroll
+    for (int e = 0; e < SEL_EPT; ++e) {
+        const int64_t k = lo + (int64_t)e * TPB + threadIdx.x;
+        const bool in = k < n;
+        const double x = in ? lp[k] : NAN;
+        v[e] = isfinite(x) ? x : NAN;
+        ix[e] = in ? (idx ? idx[k] : base + (uint64_t)k) : NO_INDEX;
+    }
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    double prev_lp = INFINITY;
+    uint64_t prev_ix = 0;
+    for (int r = 0; r < keep; ++r) {
+        double b_lp = -INFINITY;
+        uint64_t b_ix = NO_INDEX;
+#pragma unroll
+        for (int e = 0; e < SEL_EPT; ++e) {
+            // still to be listed = strictly after the previous winner in the order (NaN compares false: never a candidate)
+            const bool cand = better(prev_lp, prev_ix, v[e], ix[e]) && better(v[e], ix[e], b_lp, b_ix);
+            b_lp = cand ? v[e] : b_lp;
+            b_ix = cand ? ix[e] : b_ix;
+        }
+#pragma unroll
+        for (int m = WAVE / 2; m >= 1; m >>= 1) {
+            const double o_lp = __shfl_xor(b_lp, m, WAVE);
+            const uint64_t o_ix = (uint64_t)__shfl_xor((unsigned long long)b_ix, m, WAVE);
+            const bool take = better(o_lp, o_ix, b_lp, b_ix);
+            b_lp = take ? o_lp : b_lp;
+            b_ix = take ? o_ix : b_ix;
+        }
+        const int buf = r & 1;                          // two buffers: one barrier per round
+        if (lane == 0) { s_lp[buf][wv] = b_lp; s_ix[buf][wv] = b_ix; }
+        __syncthreads();
+        b_lp = s_lp[buf][0]; b_ix = s_ix[buf][0];
+#pragma unroll
+        for (int w = 1; w < TPB / WAVE; ++w) {
+            const double o_lp = s_lp[buf][w];
+            const uint64_t o_ix = s_ix[buf][w];
+            const bool take = better(o_lp, o_ix, b_lp, b_ix);
+            b_lp = take ? o_lp : b_lp;
+            b_ix = take ? o_ix : b_ix;
+        }
+        if (threadIdx.x == 0) {
+            const int64_t o = (out_first + blockIdx.x) * keep + r;
+            out_lp[o] = b_lp; out_idx[o] = b_ix;
+        }
+        if (b_ix == NO_INDEX) { prev_lp = -INFINITY; prev_ix = NO_INDEX; }      // exhausted: nothing is after this
+        else { prev_lp = b_lp; prev_ix = b_ix; }
+    }
+}
+
+// ---- rejection ---------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double block_max(double m, double* s) {
+#pragma unroll
+    for (int k = WAVE / 2; k >= 1; k >>= 1) m = fmax(m, __shfl_xor(m, k, WAVE));
+    if ((threadIdx.x & (WAVE - 1)) == 0) s[threadIdx.x / WAVE] = m;
+    __syncthreads();
+    m = s[0];
+#pragma unroll
+    for (int w = 1; w < TPB / WAVE; ++w) m = fmax(m, s[w]);
+    return m;
+}
+
+// ll[k] = lp[k] − lpt[k] (sampling.jl:260-268: non-finite -> −Inf), pmax[block] = its maximum over the block
+__global__ __launch_bounds__(TPB) void k_loglike(const double* __restrict__ lp, const double* __restrict__ lpt, int64_t n, double* __restrict__ ll, double* __restrict__ pmax) {
+    __shared__ double s[TPB / WAVE];
+    const int64_t k = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    double v = -INFINITY;
+    if (k < n) {
+        v = lp[k] - lpt[k];
+        v = isfinite(v) ? v : -INFINITY;
+        ll[k] = v;
+    }
+    v = block_max(v, s);
+    if (threadIdx.x == 0) pmax[blockIdx.x] = v;
+}
+
+__global__ __launch_bounds__(TPB) void k_max(const double* __restrict__ pmax, int64_t n, double* __restrict__ out) {
+    __shared__ double s[TPB / WAVE];
+    double v = -INFINITY;
+    for (int64_t k = threadIdx.x; k < n; k += TPB) v = fmax(v, pmax[k]);
+    v = block_max(v, s);
+    if (threadIdx.x == 0) *out = v;
+}
+
+// sampling.jl:202-210
+__device__ __forceinline__ bool accepted(double ll, double mx, uint64_t seed, uint64_t i) {
+    return ll != -INFINITY && rejection_uniform(seed, i) < exp(ll - mx);
+}
+
+__global__ __launch_bounds__(TPB) void k_count(const double* __restrict__ ll, int64_t n, const double* __restrict__ mx, uint64_t seed, uint64_t first, int64_t* __restrict__ cnt) {
+    __shared__ int s[TPB / WAVE];
+    const int64_t k = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    const bool f = k < n && accepted(ll[k], *mx, seed, first + (uint64_t)k);
+    const int c = __popcll(__ballot(f));
+    if ((threadIdx.x & (WAVE - 1)) == 0) s[threadIdx.x / WAVE] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < TPB / WAVE; ++w) tot += s[w];
+        cnt[blockIdx.x] = tot;
+    }
+}
+
+// exclusive scan of cnt[0 … n) in place, the total at cnt[n]: one block, a contiguous segment per thread
+__global__ __launch_bounds__(TPB) void k_scan(int64_t* cnt, int64_t n) {
+    __shared__ int64_t s[TPB];
+    const int64_t seg = (n + TPB - 1) / TPB, lo = (int64_t)threadIdx.x * seg, hi = lo + seg < n ? lo + seg : n;
+    int64_t sum = 0;
+    for (int64_t k = lo; k < hi; ++k) sum += cnt[k];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (int step = 1; step < TPB; step <<= 1) {      // Hillis-Steele, inclusive
+        const int64_t add = (int)threadIdx.x >= step ? s[threadIdx.x - step] : 0;
+        __syncthreads();
+        s[threadIdx.x] += add;
+        __syncthreads();
+    }
+    int64_t run = s[threadIdx.x] - sum;
+    for (int64_t k = lo; k < hi; ++k) { const int64_t c = cnt[k]; cnt[k] = run; run += c; }
+    if (threadIdx.x == TPB - 1) cnt[n] = s[TPB - 1];
+}
+
+__global__ __launch_bounds__(TPB) void k_scatter(const double* __restrict__ ll, const double* __restrict__ lp, int64_t n, const double* __restrict__ mx, uint64_t seed,
+                                                 uint64_t first, const int64_t* __restrict__ offs, int64_t cap, uint64_t* __restrict__ o_idx,
+                                                 double* __restrict__ o_ll, double* __restrict__ o_lp) {
+    __shared__ int s[TPB / WAVE];
+    const int64_t k = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    const double v = k < n ? ll[k] : -INFINITY;
+    const bool f = k < n && accepted(v, *mx, seed, first + (uint64_t)k);
+    const unsigned long long mask = __ballot(f);
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    if (lane == 0) s[wv] = __popcll(mask);
+    __syncthreads();
+    int64_t pos = offs[blockIdx.x] + __popcll(mask & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wv; ++w) pos += s[w];
+    if (f && pos < cap) { o_idx[pos] = first + (uint64_t)k; o_ll[pos] = v; o_lp[pos] = lp[k]; }
+}
+
+thread_local std::string g_create_error;
+
+}  // namespace
+
+struct octo_draws {
+    octo_ctx* ctx = nullptr;
+    octo_model* model = nullptr;
+    int device = 0, D = 0;
+    hipStream_t stream = nullptr;
+    bool ctx_on_stream = false;      // the context was handed `stream` (octo_model_logpost_device) and may still name it as its last stream
+    octo_prior* d_priors = nullptr;
+    double *d_pc = nullptr, *d_ic = nullptr;
+    // chunk buffers
+    double *d_tt = nullptr, *d_lpt = nullptr;      // [D][CHUNK], [CHUNK]
+    // selection: candidate lists [(1 + SEL_BLOCKS)·keep], list 0 = the running list
+    double* d_clp = nullptr; uint64_t* d_cix = nullptr;
+    // per-draw arrays of a call (grown on demand): lp | ll, the block maxima, the block counts (+1)
+    double *d_lp = nullptr, *d_ll = nullptr, *d_pmax = nullptr; int64_t* d_cnt = nullptr;
+    int64_t cap_n = 0;
+    // outputs before they go to the host (grown on demand): index, ll, lp, θ [D][n]
+    uint64_t* d_oix = nullptr; double *d_oll = nullptr, *d_olp = nullptr, *d_oth = nullptr;
+    int64_t cap_o = 0;
+    double* d_max = nullptr;
+    std::string err;
+};
+
+namespace {
+
+int fail(octo_draws* h, int code, const std::string& msg) {
+    if (h) h->err = msg; else g_create_error = msg;
+    return code;
+}
+
+#define DCHK(h, expr)                                                                                                   \
+    do {                                                                                                                \
+        const hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess) return fail(h, e_ == hipErrorOutOfMemory ? OCTO_ENOMEM : OCTO_EHIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
+    } while (0)
+
+int main_call(octo_draws* h, int rc, const char* what) {
+    h->ctx_on_stream = true;
+    if (rc == OCTO_OK) return rc;
+    const char* m = octo_last_error(h->ctx);
+    return fail(h, rc, std::string(what) + ": " + (m ? m : ""));
+}
+
+template <class T>
+int regrow(octo_draws* h, T*& p, int64_t n) {
+    if (p) { DCHK(h, hipFree(p)); p = nullptr; }
+    DCHK(h, hipMalloc((void**)&p, sizeof(T) * (size_t)n));
+    return OCTO_OK;
+}
+
+int ensure_chunk(octo_draws* h) {
+    if (h->d_tt) return OCTO_OK;
+    int rc;
+    if ((rc = regrow(h, h->d_tt, (int64_t)h->D * CHUNK))) return rc;
+    if ((rc = regrow(h, h->d_lpt, CHUNK))) return rc;
+    if ((rc = regrow(h, h->d_clp, (1 + SEL_BLOCKS) * OCTO_DRAWS_MAX_KEEP))) return rc;
+    if ((rc = regrow(h, h->d_cix, (1 + SEL_BLOCKS) * OCTO_DRAWS_MAX_KEEP))) return rc;
+    return regrow(h, h->d_max, 1);
+}
+
+int ensure_draw_arrays(octo_draws* h, int64_t n) {
+    if (n <= h->cap_n) return OCTO_OK;
+    DCHK(h, hipStreamSynchronize(h->stream));
+    h->cap_n = 0;
+    int rc;
+    if ((rc = regrow(h, h->d_lp, n))) return rc;
+    if ((rc = regrow(h, h->d_ll, n))) return rc;
+    if ((rc = regrow(h, h->d_pmax, (n + TPB - 1) / TPB))) return rc;
+    if ((rc = regrow(h, h->d_cnt, (n + TPB - 1) / TPB + 1))) return rc;
+    h->cap_n = n;
+    return OCTO_OK;
+}
+
+int ensure_outputs(octo_draws* h, int64_t n) {
+    if (n <= h->cap_o) return OCTO_OK;
+    DCHK(h, hipStreamSynchronize(h->stream));
+    h->cap_o = 0;
+    int rc;
+    if ((rc = regrow(h, h->d_oix, n))) return rc;
+    if ((rc = regrow(h, h->d_oll, n))) return rc;
+    if ((rc = regrow(h, h->d_olp, n))) return rc;
+    if ((rc = regrow(h, h->d_oth, n * h->D))) return rc;
+    h->cap_o = n;
+    return OCTO_OK;
+}
+
+// draws [first, first + n) or the listed ones, enqueued on st in launches of at most 2³⁰ draws
+int launch_draw(octo_draws* h, hipStream_t st, uint64_t seed, uint64_t first, const uint64_t* d_idx, int64_t n, int64_t ld,
+                double* d_theta, double* d_theta_t, double* d_lpt) {
+    constexpr int64_t PIECE = (int64_t)1 << 30;
+    for (int64_t o = 0; o < n; o += PIECE) {
+        DrawArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.priors = h->d_priors; a.pc = h->d_pc; a.ic = h->d_ic; a.D = h->D;
+        a.idx = d_idx ? d_idx + o : nullptr;
+        a.seed = seed; a.first = first + (uint64_t)o;
+        a.n = std::min(PIECE, n - o); a.ld = ld;
+        a.theta = d_theta ? d_theta + o : nullptr; a.theta_t = d_theta_t ? d_theta_t + o : nullptr; a.lpt = d_lpt ? d_lpt + o : nullptr;
+        for (a.d0 = 0; a.d0 < h->D; a.d0 += 4) hipLaunchKernelGGL(k_draw, dim3((unsigned)((a.n + TPB - 1) / TPB)), dim3(TPB), 0, st, a);
+    }
+    DCHK(h, hipGetLastError());
+    return OCTO_OK;
+}
+
+int check_range(octo_draws* h, const char* who, uint64_t first, int64_t N, bool need_model) {
+    if (N < 1) return fail(h, OCTO_EINVAL, std::string(who) + ": N >= 1");
+    if (first + (uint64_t)N < first) return fail(h, OCTO_EINVAL, std::string(who) + ": first + N overflows the draw index");
+    if (need_model && (!h->model || !h->ctx)) return fail(h, OCTO_EINVAL, std::string(who) + ": the handle has no model (created without one, or detached)");
+    return OCTO_OK;
+}
+
+double normcdf_host(double z) { return 0.5 * std::erfc(-z * 0.70710678118654752440); }
+
+}  // namespace
+
+extern "C" {
+
+int32_t octo_draws_create(octo_ctx* ctx, octo_model* model, const octo_prior* priors, int32_t D, int32_t device_id, octo_draws** out) {
+    if (!ctx || !priors || !out) return fail(nullptr, OCTO_EINVAL, "octo_draws_create: null argument");
+    *out = nullptr;
+    if (D < 1 || D > 64) return fail(nullptr, OCTO_EINVAL, "octo_draws_create: 1 <= D <= 64");
+    for (int k = 0; k < D; ++k) {
+        const octo_prior& pr = priors[k];
+        if (pr.kind < OCTO_PRIOR_UNIFORM || pr.kind > OCTO_PRIOR_SINE) return fail(nullptr, OCTO_EINVAL, "octo_draws_create: unknown prior kind");
+        const bool ok = (pr.kind == OCTO_PRIOR_UNIFORM) ? (std::isfinite(pr.p0) && std::isfinite(pr.p1) && pr.p0 < pr.p1)
+                      : (pr.kind == OCTO_PRIOR_LOGUNIFORM) ? (std::isfinite(pr.p1) && 0.0 < pr.p0 && pr.p0 < pr.p1)
+                      : (pr.kind == OCTO_PRIOR_NORMAL) ? (std::isfinite(pr.p0) && std::isfinite(pr.p1) && pr.p1 > 0.0)
+                      : (pr.kind == OCTO_PRIOR_TRUNCNORMAL) ? (std::isfinite(pr.p0) && std::isfinite(pr.p1) && pr.p1 > 0.0 && pr.lo < pr.hi)
+                      : true;
+        if (!ok) return fail(nullptr, OCTO_EINVAL, "octo_draws_create: prior " + std::to_string(k) + " has no proper support");
+    }
+    // constants of each prior: pc as octo_model_create forms them for prior_density_lanes (−log(Φ(hi) − Φ(lo)), 1/(b − a),
+    // −log(b − a) | log(b/a) | −log σ, 1/σ), ic for prior_quantile
+    std::vector<double> pc((size_t)D * PRIOR_NC, std::nan("")), ic((size_t)D * IC_N, 0.0);
+    for (int k = 0; k < D; ++k) {
+        const octo_prior& pr = priors[k];
+        double* c = &pc[(size_t)k * PRIOR_NC];
+        double* q = &ic[(size_t)k * IC_N];
+        double a = -INFINITY, b = INFINITY;
+        if (pr.kind == OCTO_PRIOR_UNIFORM || pr.kind == OCTO_PRIOR_LOGUNIFORM) { a = pr.p0; b = pr.p1; }
+        else if (pr.kind == OCTO_PRIOR_TRUNCNORMAL) { a = pr.lo; b = pr.hi; }
+        else if (pr.kind == OCTO_PRIOR_SINE) { a = 0.0 + 2.220446049250313e-16; b = PI - 2.220446049250313e-16; }
+        c[1] = 1.0 / (b - a);
+        if (pr.kind == OCTO_PRIOR_UNIFORM) { c[2] = -std::log(b - a); q[0] = a; q[1] = b - a; }
+        else if (pr.kind == OCTO_PRIOR_LOGUNIFORM) { c[2] = std::log(b / a); q[0] = std::log(a); q[1] = std::log(b) - std::log(a); }
+        else if (pr.kind == OCTO_PRIOR_NORMAL || pr.kind == OCTO_PRIOR_TRUNCNORMAL) { c[2] = -std::log(pr.p1); c[3] = 1.0 / pr.p1; }
+        if (pr.kind == OCTO_PRIOR_TRUNCNORMAL) {
+            const double lo = std::isfinite(pr.lo) ? normcdf_host((pr.lo - pr.p0) / pr.p1) : 0.0;
+            const double hi = std::isfinite(pr.hi) ? normcdf_host((pr.hi - pr.p0) / pr.p1) : 1.0;
+            c[0] = -std::log(hi - lo);
+            const double al = (pr.lo - pr.p0) / pr.p1, be = (pr.hi - pr.p0) / pr.p1;      // ±Inf at an open end
+            if (al < 0.0) { q[0] = lo; q[1] = hi - lo; q[2] = 0.0; }
+            else { q[0] = normcdf_host(-al); q[1] = q[0] - (std::isfinite(be) ? normcdf_host(-be) : 0.0); q[2] = 1.0; }
+            if (!(q[1] > 0.0)) return fail(nullptr, OCTO_EINVAL, "octo_draws_create: prior " + std::to_string(k) + ": the truncation leaves no probability in double precision");
+        }
+    }
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { (void)hipGetLastError(); return fail(nullptr, OCTO_ENODEV, "octo_draws_create: no HIP device"); }
+    if (device_id < 0 || device_id >= n_dev) return fail(nullptr, OCTO_EINVAL, "octo_draws_create: device_id out of range");
+    octo_draws* h = new (std::nothrow) octo_draws();
+    if (!h) return fail(nullptr, OCTO_ENOMEM, "octo_draws_create: host allocation failed");
+    h->ctx = ctx; h->model = model; h->device = device_id; h->D = D;
+    auto bail = [&](int code, const char* msg) { octo_draws_destroy(h); return fail(nullptr, code, msg); };
+    if (hipSetDevice(device_id) != hipSuccess) return bail(OCTO_EHIP, "octo_draws_create: hipSetDevice failed");
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(OCTO_EHIP, "octo_draws_create: stream creation failed");
+    if (hipMalloc((void**)&h->d_priors, sizeof(octo_prior) * D) != hipSuccess || hipMalloc((void**)&h->d_pc, sizeof(double) * pc.size()) != hipSuccess ||
+        hipMalloc((void**)&h->d_ic, sizeof(double) * ic.size()) != hipSuccess)
+        return bail(OCTO_ENOMEM, "octo_draws_create: hipMalloc failed");
+    if (hipMemcpy(h->d_priors, priors, sizeof(octo_prior) * D, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_pc, pc.data(), sizeof(double) * pc.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_ic, ic.data(), sizeof(double) * ic.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return bail(OCTO_EHIP, "octo_draws_create: upload failed");
+    *out = h;
+    return OCTO_OK;
+}
+
+int32_t octo_draws_destroy(octo_draws* h) {
+    if (!h) return OCTO_OK;
+    (void)hipSetDevice(h->device);
+    if (h->stream) {
+        (void)hipStreamSynchronize(h->stream);
+        // The context orders a change of stream with an event recorded on the stream of its PREVIOUS call: it must not be left naming a stream
+        // that no longer exists. One host-buffer call (a one-element Kepler solve) moves it back to its own stream; if the context refuses it
+        // (an evaluation in flight), the stream is kept alive instead of destroyed.
+        bool release = true;
+        if (h->ctx && h->ctx_on_stream) {
+            const double ma = 0.0, e = 0.0;
+            double E = 0.0;
+            release = octo_kepler_solve(h->ctx, &ma, &e, 1, &E, nullptr, nullptr) == OCTO_OK;
+        }
+        if (release) (void)hipStreamDestroy(h->stream);
+    }
+    (void)hipFree(h->d_priors); (void)hipFree(h->d_pc); (void)hipFree(h->d_ic); (void)hipFree(h->d_tt); (void)hipFree(h->d_lpt);
+    (void)hipFree(h->d_clp); (void)hipFree(h->d_cix); (void)hipFree(h->d_lp); (void)hipFree(h->d_ll); (void)hipFree(h->d_pmax); (void)hipFree(h->d_cnt);
+    (void)hipFree(h->d_oix); (void)hipFree(h->d_oll); (void)hipFree(h->d_olp); (void)hipFree(h->d_oth); (void)hipFree(h->d_max);
+    delete h;
+    return OCTO_OK;
+}
+
+int32_t octo_draws_detach(octo_draws* h) {
+    if (!h) return OCTO_EINVAL;
+    h->ctx = nullptr; h->model = nullptr;
+    return OCTO_OK;
+}
+
+const char* octo_draws_last_error(const octo_draws* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int32_t octo_draws_sample_device(octo_draws* h, uint64_t seed, uint64_t first, int64_t n, int64_t ld, double* d_theta, double* d_theta_t,
+                                 double* d_logprior_t, void* hip_stream) {
+    if (!h) return OCTO_EINVAL;
+    if (n < 0 || ld < n) return fail(h, OCTO_EINVAL, "octo_draws_sample_device: need 0 <= n <= ld");
+    if (first + (uint64_t)n < first) return fail(h, OCTO_EINVAL, "octo_draws_sample_device: first + n overflows the draw index");
+    if (n == 0 || (!d_theta && !d_theta_t && !d_logprior_t)) return OCTO_OK;
+    DCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = hip_stream == OCTO_STREAM_CTX ? h->stream : (hipStream_t)hip_stream;
+    return launch_draw(h, st, seed, first, nullptr, n, ld, d_theta, d_theta_t, d_logprior_t);
+}
+
+int32_t octo_draws_sync(octo_draws* h) {
+    if (!h) return OCTO_EINVAL;
+    DCHK(h, hipSetDevice(h->device));
+    DCHK(h, hipStreamSynchronize(h->stream));
+    return OCTO_OK;
+}
+
+int32_t octo_draws_best(octo_draws* h, uint64_t seed, uint64_t first, int64_t N, int32_t keep, double* theta_out, double* logpost_out, uint64_t* index_out) {
+    if (!h) return OCTO_EINVAL;
+    if (keep < 1 || keep > OCTO_DRAWS_MAX_KEEP) return fail(h, OCTO_EINVAL, "octo_draws_best: 1 <= keep <= 64");
+    { int rc = check_range(h, "octo_draws_best", first, N, true); if (rc) return rc; }
+    if (keep > N) return fail(h, OCTO_EINVAL, "octo_draws_best: keep <= N");
+    if (!theta_out || !logpost_out || !index_out) return fail(h, OCTO_EINVAL, "octo_draws_best: null output");
+    DCHK(h, hipSetDevice(h->device));
+    { int rc = ensure_chunk(h); if (rc) return rc; }
+    { int rc = ensure_draw_arrays(h, std::min(N, CHUNK)); if (rc) return rc; }
+    { int rc = ensure_outputs(h, OCTO_DRAWS_MAX_KEEP); if (rc) return rc; }
+    const hipStream_t st = h->stream;
+    // the running list starts empty: every byte 0xFF = (NaN, NO_INDEX), which k_topk reads as no candidate
+    DCHK(h, hipMemsetAsync(h->d_clp, 0xFF, sizeof(double) * keep, st));
+    DCHK(h, hipMemsetAsync(h->d_cix, 0xFF, sizeof(uint64_t) * keep, st));
+    for (int64_t done = 0; done < N; done += CHUNK) {
+        const int64_t n = std::min(CHUNK, N - done);
+        { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, h->d_tt, nullptr); if (rc) return rc; }
+        { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, h->d_tt, CHUNK, n, h->d_lp, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+        const int64_t nb = (n + SEL_SLAB - 1) / SEL_SLAB;
+        hipLaunchKernelGGL(k_topk, dim3((unsigned)nb), dim3(TPB), 0, st, h->d_lp, (const uint64_t*)nullptr, first + (uint64_t)done, n, keep, (int64_t)1, h->d_clp, h->d_cix);
+        hipLaunchKernelGGL(k_topk, dim3(1), dim3(TPB), 0, st, h->d_clp, h->d_cix, (uint64_t)0, (1 + nb) * keep, keep, (int64_t)0, h->d_clp, h->d_cix);
+        DCHK(h, hipGetLastError());
+    }
+    DCHK(h, hipMemcpyAsync(logpost_out, h->d_clp, sizeof(double) * keep, hipMemcpyDeviceToHost, st));
+    DCHK(h, hipMemcpyAsync(index_out, h->d_cix, sizeof(uint64_t) * keep, hipMemcpyDeviceToHost, st));
+    DCHK(h, hipStreamSynchronize(st));
+    // places no finite log-posterior took: −Inf and the lowest draw indices not listed yet
+    uint64_t next = first;
+    for (int r = 0; r < keep; ++r) {
+        if (index_out[r] != NO_INDEX) continue;
+        for (;; ++next) {
+            bool listed = false;
+            for (int q = 0; q < keep; ++q) listed = listed || index_out[q] == next;
+            if (!listed) break;
+        }
+        index_out[r] = next++;
+        logpost_out[r] = -INFINITY;
+    }
+    // θ of the winners, from the counter
+    DCHK(h, hipMemcpyAsync(h->d_oix, index_out, sizeof(uint64_t) * keep, hipMemcpyHostToDevice, st));
+    { int rc = launch_draw(h, st, seed, 0, h->d_oix, keep, keep, h->d_oth, nullptr, nullptr); if (rc) return rc; }
+    DCHK(h, hipMemcpyAsync(theta_out, h->d_oth, sizeof(double) * keep * h->D, hipMemcpyDeviceToHost, st));
+    DCHK(h, hipStreamSynchronize(st));
+    return OCTO_OK;
+}
+
+int32_t octo_draws_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64_t N, int64_t cap, double* theta_out, double* loglike_out,
+                             double* logpost_out, uint64_t* index_out, int64_t* n_accepted, double* max_loglike) {
+    if (!h) return OCTO_EINVAL;
+    { int rc = check_range(h, "octo_draws_rejection", first, N, true); if (rc) return rc; }
+    if (cap < 0 || !n_accepted) return fail(h, OCTO_EINVAL, "octo_draws_rejection: cap >= 0 and n_accepted are required");
+    if (cap > 0 && (!theta_out || !loglike_out || !logpost_out || !index_out)) return fail(h, OCTO_EINVAL, "octo_draws_rejection: null output with cap > 0");
+    DCHK(h, hipSetDevice(h->device));
+    { int rc = ensure_chunk(h); if (rc) return rc; }
+    { int rc = ensure_draw_arrays(h, N); if (rc) return rc; }
+    const hipStream_t st = h->stream;
+    const int64_t nblk = (N + TPB - 1) / TPB;
+    // pass 1: ll of every draw, chunk by chunk (chunk boundaries are block boundaries), and its maximum
+    for (int64_t done = 0; done < N; done += CHUNK) {
+        const int64_t n = std::min(CHUNK, N - done);
+        { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, h->d_tt, h->d_lpt); if (rc) return rc; }
+        { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, h->d_tt, CHUNK, n, h->d_lp + done, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+        hipLaunchKernelGGL(k_loglike, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, h->d_lp + done, h->d_lpt, n, h->d_ll + done, h->d_pmax + done / TPB);
+        DCHK(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_max, dim3(1), dim3(TPB), 0, st, h->d_pmax, nblk, h->d_max);
+    DCHK(h, hipGetLastError());
+    double mx = 0.0;
+    DCHK(h, hipMemcpyAsync(&mx, h->d_max, sizeof(double), hipMemcpyDeviceToHost, st));
+    DCHK(h, hipStreamSynchronize(st));
+    if (max_loglike) *max_loglike = mx;
+    *n_accepted = 0;
+    if (!std::isfinite(mx))      // sampling.jl:194-197
+        return fail(h, OCTO_EINVAL, "All " + std::to_string(N) + " prior samples produced non-finite log-likelihoods. Check your model and priors.");
+    // pass 2: flags -> block counts -> offsets -> ordered scatter
+    { int rc = ensure_outputs(h, std::max<int64_t>(std::min(cap, N), 1)); if (rc) return rc; }
+    const int64_t room = std::min(cap, N);
+    hipLaunchKernelGGL(k_count, dim3((unsigned)nblk), dim3(TPB), 0, st, h->d_ll, N, h->d_max, seed, first, h->d_cnt);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(TPB), 0, st, h->d_cnt, nblk);
+    hipLaunchKernelGGL(k_scatter, dim3((unsigned)nblk), dim3(TPB), 0, st, h->d_ll, h->d_lp, N, h->d_max, seed, first, h->d_cnt, room, h->d_oix, h->d_oll, h->d_olp);
+    DCHK(h, hipGetLastError());
+    int64_t total = 0;
+    DCHK(h, hipMemcpyAsync(&total, h->d_cnt + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    DCHK(h, hipStreamSynchronize(st));
+    *n_accepted = total;
+    const int64_t ns = std::min(total, room);
+    if (ns == 0) return OCTO_OK;
+    { int rc = launch_draw(h, st, seed, 0, h->d_oix, ns, ns, h->d_oth, nullptr, nullptr); if (rc) return rc; }
+    DCHK(h, hipMemcpyAsync(index_out, h->d_oix, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
+    DCHK(h, hipMemcpyAsync(loglike_out, h->d_oll, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+    DCHK(h, hipMemcpyAsync(logpost_out, h->d_olp, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+    DCHK(h, hipMemcpy2DAsync(theta_out, sizeof(double) * cap, h->d_oth, sizeof(double) * ns, sizeof(double) * ns, h->D, hipMemcpyDeviceToHost, st));
+    DCHK(h, hipStreamSynchronize(st));
+    return OCTO_OK;
+}
+
+}  // extern "C"

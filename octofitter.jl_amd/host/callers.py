@@ -6,6 +6,9 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   octofit_rejection(rng, model, draws)       src/sampling.jl:168-256        prior draws, accept with prob exp(ll − max ll)
   rejection_evaluate_likelihoods(model, θ)   src/sampling.jl:260-268        the inner batch: non-finite -> -Inf
 
+  guess_starting_position_device / octofit_rejection_device: the same two drivers with the draws, the link, the argmax and the
+  accept / compaction step on the device too (host/draws.py: PriorDraws) — only the winners / the accepted chain cross PCIe.
+
 The accept/reject and argmax logic is the reference's, line for line; random numbers come from NumPy's Generator
 (the reference uses Julia's Xoshiro), so individual draws differ while the sampled distribution is the same.
 """
@@ -76,6 +79,47 @@ def octofit_rejection(rng, model, draws=100_000, verbosity=0, prior_samples=None
     logpost = model.ℓπcallback(model.link(samples))                           # _rejection_build_chain, :270-
     return dict(samples=samples, loglike=log_likes[idx], logpost=logpost, draws=draws, n_accepted=int(idx.size),
                 acceptance_rate=idx.size / draws, names=list(model.names), accept=accept, all_loglike=log_likes)
+
+
+def guess_starting_position_device(model, N=500_000, seed=0, keep=1):
+    """guess_starting_position with the N prior draws made, linked, scored and ranked on the device (draws 0 … N − 1 of the counter-based
+    stream `seed`): (bestparams, bestlogpost) like the host twin; with keep > 1 the `keep` best, best first: ([D, keep], [keep])."""
+    from .draws import PriorDraws
+    draws = PriorDraws(model)
+    try:
+        θ, lp, _ = draws.best(seed, N, keep=keep)
+    finally:
+        draws.close()
+    if keep == 1:
+        return θ[:, 0].copy(), float(lp[0])
+    return θ, lp
+
+
+def octofit_rejection_device(model, draws=100_000, seed=0):
+    """octofit_rejection with the prior draws, their likelihoods, the uniforms and the accept / compaction step on the device (draws
+    0 … draws − 1 of the counter-based stream `seed`). Returns the host twin's dict for the accepted chain: samples [D, n_accepted]
+    (natural domain), loglike, logpost, draws, n_accepted, acceptance_rate, names, accept (the mask, rebuilt on the host from the accepted
+    draw indices `index`) — and all_loglike = None: the per-draw likelihoods stay on the device."""
+    from . import capi
+    from .draws import PriorDraws
+    pd = PriorDraws(model)
+    try:
+        try:
+            r = pd.rejection(seed, draws)
+        except capi.OctoError as e:
+            if e.status == capi.OCTO_EINVAL and "non-finite log-likelihoods" in str(e):
+                raise RuntimeError(str(e).split(": ", 1)[1]) from None
+            raise
+    finally:
+        pd.close()
+    if r["n_accepted"] == 0:
+        raise RuntimeError(f"No samples were accepted out of {draws} draws. The posterior may be extremely concentrated relative "
+                           "to the prior. Consider increasing `draws` or using a different sampler.")
+    accept = np.zeros(int(draws), dtype=bool)
+    accept[r["index"].astype(np.int64)] = True
+    return dict(samples=r["samples"], loglike=r["loglike"], logpost=r["logpost"], draws=int(draws), n_accepted=r["n_accepted"],
+                acceptance_rate=r["n_accepted"] / draws, names=list(model.names), accept=accept, all_loglike=None,
+                index=r["index"], max_loglike=r["max_loglike"])
 
 
 def pointwise_like(model, θ_samples):

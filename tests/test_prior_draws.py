@@ -1,0 +1,441 @@
+"""
+Prior draws on the device (include/octofitter_hip_draws.h, host/draws.py): the counter-based generator, the inverse CDFs, the link and
+the density, and the two drivers built on them — octo_draws_best (guess_starting_position, src/initialization.jl:14-66) and
+octo_draws_rejection (octofit_rejection, src/sampling.jl:168-268).
+
+The generator is restated here in integers (philox_int) and pinned to numpy.random.Philox; everything the device draws is a
+deterministic function of uniforms this restatement reproduces, so every check below is against an independent value: the bits of
+the uniforms, scipy.stats CDFs and densities, host/priors.py's link, the oracle's callback on the same draws.
+
+Tolerances: 1e-11 relative to max(1, |ref|) is the bar the callers' parity test uses (tests/test_model.py:423-425); the rejection
+log-likelihood is a difference lp − logprior_t of numbers that cancel, held to 1e-8 of the largest of them; the Kolmogorov-Smirnov
+bar 1.95/√n is the 0.1 % critical value.
+"""
+import math
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+
+M64 = (1 << 64) - 1
+PHILOX_M0, PHILOX_M1 = 0xD2E7470EE14C6C93, 0xCA5A826395121157
+PHILOX_W0, PHILOX_W1 = 0x9E3779B97F4A7C15, 0xBB67AE8584CAA73B
+KEY1 = 0x6F63746F64726177
+
+
+# ---------------------------------------------------------------------------------------------------- the generator, restated
+def philox_int(key, ctr):
+    """Philox4x64-10 on Python integers: key (k0, k1), counter (c0, c1, c2, c3) -> four 64-bit words."""
+    k0, k1 = key
+    c0, c1, c2, c3 = ctr
+    for _ in range(10):
+        p0, p1 = PHILOX_M0 * c0, PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> 64) ^ c1 ^ k0, p1 & M64, (p0 >> 64) ^ c3 ^ k1, p0 & M64
+        k0, k1 = (k0 + PHILOX_W0) & M64, (k1 + PHILOX_W1) & M64
+    return c0, c1, c2, c3
+
+
+def _mulhilo(a, b):
+    """(high, low) 64-bit halves of a·b: a a Python integer constant, b a uint64 array."""
+    a0, a1 = np.uint64(a & 0xFFFFFFFF), np.uint64(a >> 32)
+    m32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    b0, b1 = b & m32, b >> s32
+    p00, p01, p10, p11 = a0 * b0, a0 * b1, a1 * b0, a1 * b1
+    mid = (p00 >> s32) + (p01 & m32) + (p10 & m32)
+    hi = p11 + (p01 >> s32) + (p10 >> s32) + (mid >> s32)
+    lo = (mid << s32) | (p00 & m32)
+    return hi, lo
+
+
+def philox_vec(key, c0, c1, c2, c3):
+    """The same rounds on uint64 arrays (one counter per element)."""
+    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, dtype=np.uint64) for c in (c0, c1, c2, c3)])
+    k0, k1 = key
+    with np.errstate(over="ignore"):
+        for _ in range(10):
+            hi0, lo0 = _mulhilo(PHILOX_M0, c0)
+            hi1, lo1 = _mulhilo(PHILOX_M1, c2)
+            c0, c1, c2, c3 = hi1 ^ c1 ^ np.uint64(k0), lo1, hi0 ^ c3 ^ np.uint64(k1), lo0
+            k0, k1 = (k0 + PHILOX_W0) & M64, (k1 + PHILOX_W1) & M64
+    return c0, c1, c2, c3
+
+
+def u01(x):
+    """(2·(x >> 12) + 1)·2⁻⁵³"""
+    return ((x >> np.uint64(12)) * np.uint64(2) + np.uint64(1)).astype(np.float64) * 2.0 ** -53
+
+
+def prior_uniforms(seed, idx, D):
+    """u[d][k] of draw idx[k]: counter (i, d // 4, 0, 0), word d % 4."""
+    idx = np.asarray(idx, dtype=np.uint64)
+    out = np.empty((D, idx.size))
+    for j in range((D + 3) // 4):
+        words = philox_vec((seed, KEY1), idx, j, 0, 0)
+        for q in range(4):
+            if 4 * j + q < D:
+                out[4 * j + q] = u01(words[q])
+    return out
+
+
+def rejection_uniforms(seed, idx):
+    """counter (i, 0, 1, 0), word 0"""
+    return u01(philox_vec((seed, KEY1), np.asarray(idx, dtype=np.uint64), 0, 1, 0)[0])
+
+
+def test_philox_restatement_is_numpy_philox():
+    """numpy.random.Philox(counter=c, key=k) hands out the block of counter c + 1 first (it increments before it generates)."""
+    cases = [((0, 0), (0, 0, 0, 0)), ((1, KEY1), (41, 3, 0, 0)), ((0xDEADBEEFCAFEF00D, KEY1), (M64, 5, 1, 0)),      # a counter word at 2⁶⁴ − 1: the carry
+             ((M64, M64), (M64 - 1, M64, M64, 7)), ((20240607, KEY1), ((1 << 40) + 3, 2, 0, 0))]
+    for key, ctr in cases:
+        raw = np.random.Philox(counter=np.array(ctr, dtype=np.uint64), key=np.array(key, dtype=np.uint64)).random_raw(4)
+        n = sum(c << (64 * k) for k, c in enumerate(ctr)) + 1
+        nxt = tuple((n >> (64 * k)) & M64 for k in range(4))
+        assert tuple(int(x) for x in raw) == philox_int(key, nxt), (key, ctr)
+        vec = philox_vec(key, *[np.array([c], dtype=np.uint64) for c in nxt])
+        assert tuple(int(v[0]) for v in vec) == philox_int(key, nxt), (key, ctr)
+    u = u01(np.array([0, M64, 1 << 12], dtype=np.uint64))
+    assert u[0] == 2.0 ** -53 and u[1] == 1.0 - 2.0 ** -53 and u[2] == 3 * 2.0 ** -53
+
+
+# ---------------------------------------------------------------------------------------------------- distributions
+def ks_statistic(x, cdf):
+    """One-sample Kolmogorov-Smirnov D_n."""
+    F = np.sort(cdf(np.asarray(x)))
+    n = F.size
+    k = np.arange(1, n + 1)
+    return max(np.max(k / n - F), np.max(F - (k - 1) / n))
+
+
+def ks_cases(pkg):
+    """(prior of host/priors.py, scipy CDF, scipy quantile, support)"""
+    import scipy.stats as ss
+    tn = lambda mu, sig, lo, hi: ss.truncnorm((lo - mu) / sig, (hi - mu) / sig, mu, sig)      # noqa: E731
+    d = [(pkg.Uniform(-3, 7), ss.uniform(-3, 10), (-3.0, 7.0)),
+         (pkg.LogUniform(0.1, 1000), ss.loguniform(0.1, 1000), (0.1, 1000.0)),
+         (pkg.Normal(1.2, 0.05), ss.norm(1.2, 0.05), (-np.inf, np.inf)),
+         (pkg.truncated(pkg.Normal(50, 0.1), lower=0.1), tn(50, 0.1, 0.1, np.inf), (0.1, np.inf)),
+         (pkg.truncated(pkg.Normal(0, 1), lower=3), tn(0, 1, 3, np.inf), (3.0, np.inf)),
+         (pkg.truncated(pkg.Normal(0, 1), lower=-0.5, upper=0.2), tn(0, 1, -0.5, 0.2), (-0.5, 0.2))]
+    out = [(p, s.cdf, s.ppf, s.logpdf, sup) for p, s, sup in d]
+    out.append((pkg.Sine(), lambda x: (1 - np.cos(x)) / 2, lambda u: np.arccos(1 - 2 * u), lambda x: np.log(np.sin(x) / 2), (0.0, math.pi)))
+    return out
+
+
+KS_N = 1 << 20
+KS_BAR = 1.95 / math.sqrt(KS_N)
+KS_SEEDS = (11, 12)
+
+
+def test_ks_seeds_pass_on_the_cpu(pkg):
+    """The condition on the seeds of test_gpu_distributions, from the restatement alone: its uniforms pushed through the scipy quantiles
+    stay under the bar for every prior (so a failure on the device is the device's)."""
+    cases = ks_cases(pkg)
+    for seed in KS_SEEDS:
+        u = prior_uniforms(seed, np.arange(KS_N, dtype=np.uint64), len(cases))
+        for d, (_p, cdf, ppf, _l, _s) in enumerate(cases):
+            stat = ks_statistic(ppf(u[d]), cdf)
+            print(f"seed {seed} prior {d}: CPU D_n = {stat:.3e} (bar {KS_BAR:.3e})")
+            assert stat < KS_BAR, (seed, d, stat)
+
+
+# ---------------------------------------------------------------------------------------------------- GPU
+def _log_jacobian(lo, hi, y):
+    """log|dx/dy| of the bijector of the support (lo, hi) at the linked value y — as tests/test_third_party_pins.py spells it."""
+    if math.isfinite(lo) and math.isfinite(hi):
+        sg = 1.0 / (1.0 + np.exp(-y))
+        return math.log(hi - lo) + np.log(sg) + np.log1p(-sg)
+    if math.isfinite(lo) or math.isfinite(hi):
+        return y
+    return np.zeros_like(y)
+
+
+@pytest.fixture(scope="module")
+def draws_mod(pkg):
+    from octofitter_jl_amd.host import draws
+    draws.load_library()
+    return draws
+
+
+@pytest.mark.gpu
+def test_gpu_uniform_bits(pkg, draws_mod):
+    """All priors Uniform(0, 1): θ[d][i] is the restatement's uniform, bit for bit."""
+    for D in (1, 4, 5, 11, 64):
+        pd = draws_mod.PriorDraws(priors=[pkg.Uniform(0, 1)] * D)
+        for first in (0, (1 << 40) + 3):
+            for seed in (0, 0x9E3779B97F4A7C15):
+                n = 1000
+                th, _, _ = pd.sample(seed, first, n, theta_t=False, logprior_t=False)
+                ref = prior_uniforms(seed, first + np.arange(n, dtype=np.uint64), D)
+                assert np.array_equal(th.cpu().numpy(), ref), (D, first, seed)
+        pd.close()
+
+
+@pytest.mark.gpu
+def test_gpu_call_invariance(pkg, draws_mod):
+    """Draws [0, N) in one call = [0, n1) then [n1, N) with another leading dimension, bitwise: θ, θ_t and logprior_t."""
+    import torch
+    priors = [c[0] for c in ks_cases(pkg)] * 2
+    pd = draws_mod.PriorDraws(priors=priors)
+    N, n1, seed, first = 5000, 1237, 5, 77
+    th, tt, lp = [x.cpu().numpy() for x in pd.sample(seed, first, N)]
+    D = len(priors)
+    dev = torch.device("cuda", 0)
+    parts = []
+    for lo, n, ld in ((0, n1, n1 + 19), (n1, N - n1, N)):
+        bufs = [torch.full((D, ld), float("nan"), dtype=torch.float64, device=dev) for _ in range(2)] + [torch.empty(n, dtype=torch.float64, device=dev)]
+        import ctypes as C
+        st = pd.lib.octo_draws_sample_device(pd._h, seed, first + lo, n, ld, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(),
+                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        assert st == 0
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(bufs[0][:, n:]).all()) and bool(torch.isnan(bufs[1][:, n:]).all())      # nothing written beyond column n
+        parts.append([bufs[0][:, :n].cpu().numpy(), bufs[1][:, :n].cpu().numpy(), bufs[2].cpu().numpy()])
+    assert np.array_equal(np.concatenate([parts[0][0], parts[1][0]], axis=1), th)
+    assert np.array_equal(np.concatenate([parts[0][1], parts[1][1]], axis=1), tt)
+    assert np.array_equal(np.concatenate([parts[0][2], parts[1][2]]), lp)
+    pd.close()
+
+
+@pytest.mark.gpu
+def test_gpu_distributions(pkg, draws_mod):
+    """2²⁰ draws per prior against the scipy CDF; every draw strictly inside the support, every θ_t finite."""
+    cases = ks_cases(pkg)
+    pd = draws_mod.PriorDraws(priors=[c[0] for c in cases])
+    for seed in KS_SEEDS:
+        th, tt, _ = pd.sample(seed, 0, KS_N, logprior_t=False)
+        th, tt = th.cpu().numpy(), tt.cpu().numpy()
+        assert np.all(np.isfinite(tt))
+        for d, (_p, cdf, _ppf, _l, (lo, hi)) in enumerate(cases):
+            assert np.all(th[d] > lo) and np.all(th[d] < hi), (seed, d)
+            stat = ks_statistic(th[d], cdf)
+            print(f"seed {seed} prior {d}: D_n = {stat:.3e} (bar {KS_BAR:.3e})")
+            assert stat < KS_BAR, (seed, d, stat)
+    pd.close()
+
+
+@pytest.mark.gpu
+def test_gpu_link_and_density(pkg, draws_mod):
+    """θ_t against Prior.link(θ); logprior_t against Σ scipy logpdf + log-Jacobian. Bar 1e-11 relative to max(1, |ref|)."""
+    cases = ks_cases(pkg)
+    pd = draws_mod.PriorDraws(priors=[c[0] for c in cases])
+    th, tt, lp = [x.cpu().numpy() for x in pd.sample(3, 0, 200_000)]
+    ref_lp = np.zeros(th.shape[1])
+    worst_t = 0.0
+    for d, (p, _c, _q, logpdf, _s) in enumerate(cases):
+        ref_t = p.link(th[d])
+        err = np.max(np.abs(tt[d] - ref_t) / np.maximum(1.0, np.abs(ref_t)))
+        worst_t = max(worst_t, err)
+        assert err <= 1e-11, (d, err)
+        a, b = p.bounds()
+        ref_lp += logpdf(th[d]) + _log_jacobian(a, b, tt[d])
+    worst_lp = np.max(np.abs(lp - ref_lp) / np.maximum(1.0, np.abs(ref_lp)))
+    print(f"link: max rel err {worst_t:.3e}; logprior_t: max rel err {worst_lp:.3e}")
+    assert worst_lp <= 1e-11, worst_lp
+    pd.close()
+
+
+def callers_model(pkg, e_prior=None, sigma_scale=1.0):
+    """The model of tests/test_model.py::test_gpu_batched_callers_vs_oracle: RA/Dec + absolute RV, every prior kind.
+    sigma_scale: the same data with every quoted uncertainty multiplied by it (a wider posterior: more draws accepted)."""
+    import synth
+    rng = np.random.default_rng(17)
+    t = 50000.0 + 90.0 * np.arange(10)
+    ra, dec = synth.truth_radec(t)
+    table = dict(epoch=t, ra=ra + rng.normal(0, 60.0, 10), dec=dec + rng.normal(0, 60.0, 10), σ_ra=np.full(10, 60.0 * sigma_scale),
+                 σ_dec=np.full(10, 60.0 * sigma_scale))
+    rvt = dict(epoch=t + 7.0, rv=rng.normal(0, 30, 10), σ_rv=np.full(10, 8.0 * sigma_scale))
+    astrom = pkg.PlanetRelAstromObs(table, name="sim", variables=pkg.variables(jitter=pkg.LogUniform(0.1, 30.0)))
+    rv = pkg.StarAbsoluteRVObs(rvt, name="rv", variables=pkg.variables(offset=pkg.Normal(0, 20), jitter=pkg.LogUniform(0.1, 20.0)))
+    b = pkg.Planet(name="b", basis="Visual{KepOrbit}", observations=[astrom],
+                   variables=pkg.variables(a=pkg.LogUniform(5, 20), e=e_prior or pkg.Uniform(0.0, 0.6), i=pkg.Sine(), ω=pkg.UniformCircular(),
+                                           Ω=pkg.UniformCircular(), θ=pkg.UniformCircular(), tp=pkg.θ_at_epoch_to_tperi("θ", 50000),
+                                           mass=pkg.LogUniform(1.0, 50.0)))
+    sys_ = pkg.System(name="sim", companions=[b], observations=[rv],
+                      variables=pkg.variables(M=pkg.truncated(pkg.Normal(1.2, 0.05), lower=0.1), plx=pkg.truncated(pkg.Normal(50.0, 0.1), lower=0.1)))
+    return pkg.LogDensityModel(sys_)
+
+
+def oracle_logpost(oracle, model, θ):
+    fn = model.ln_like
+    lp, _ = oracle.oracle_model_logpost(fn.obs_tables, fn.planet_desc, model._c_priors, model._c_esrc, model._c_nsrc, model.link(θ), grad=False, n_threads=0)
+    return lp
+
+
+def top_k(lp, k, first):
+    """(indices, values) of the k highest finite lp: lp descending, index ascending."""
+    idx = np.nonzero(np.isfinite(lp))[0]
+    order = idx[np.lexsort((idx, -lp[idx]))][:k]
+    return order.astype(np.uint64) + np.uint64(first), lp[order]
+
+
+BEST_N, BEST_KEEP = 600_000, 8
+BEST_RUNS = ((4, 0), (4, 250_001))      # (seed, first)
+
+
+@pytest.mark.gpu
+def test_gpu_starting_points(pkg, oracle, draws_mod):
+    """octo_draws_best against the oracle's callback on all N draws: the same eight indices in order, θ bit-equal to sample's columns,
+    log-posteriors within 1e-11; bitwise equal to octo_model_logpost under OCTO_OPT_BATCH_INVARIANT."""
+    model = callers_model(pkg)
+    pd = draws_mod.PriorDraws(model)
+    for seed, first in BEST_RUNS:
+        θ = pd.sample(seed, first, BEST_N, theta_t=False, logprior_t=False)[0].cpu().numpy()
+        lp_o = oracle_logpost(oracle, model, θ)
+        ix_o, top_o = top_k(lp_o, BEST_KEEP + 1, first)
+        gaps = -np.diff(top_o)
+        print(f"seed {seed} first {first}: oracle top {BEST_KEEP + 1} = {top_o}, smallest gap {gaps.min():.3e}")
+        assert gaps.min() > 1e-6, "condition on the seed: the nine highest oracle log-posteriors are more than 1e-6 apart"
+        th_b, lp_b, ix_b = pd.best(seed, BEST_N, keep=BEST_KEEP, first=first)
+        assert np.array_equal(ix_b, ix_o[:BEST_KEEP]), (ix_b, ix_o)
+        assert np.array_equal(th_b, θ[:, (ix_b - np.uint64(first)).astype(np.int64)])
+        err = np.max(np.abs(lp_b - top_o[:BEST_KEEP]) / np.abs(top_o[:BEST_KEEP]))
+        print(f"  log-posterior of the winners: max rel err {err:.3e}")
+        assert err <= 1e-11
+        one_th, one_lp, one_ix = pd.best(seed, BEST_N, keep=1, first=first)
+        assert one_ix[0] == ix_b[0] and one_lp[0] == lp_b[0] and np.array_equal(one_th[:, 0], th_b[:, 0])
+    # bitwise against the callback itself
+    fn = model.ln_like
+    fn._check(fn.lib.octo_ctx_set_option(fn._ctx, pkg.capi.OPT_BATCH_INVARIANT, 1), "octo_ctx_set_option")
+    seed, first = BEST_RUNS[0]
+    th_b, lp_b, ix_b = pd.best(seed, BEST_N, keep=BEST_KEEP, first=first)
+    tt = np.stack([pd.sample(seed, int(i), 1, theta=False, logprior_t=False)[1].cpu().numpy()[:, 0] for i in ix_b], axis=1)
+    assert np.array_equal(model.ℓπcallback(tt), lp_b)
+    pd.close()
+    model.close()
+
+
+@pytest.mark.gpu
+def test_gpu_starting_points_nothing_finite(pkg, draws_mod):
+    """e ~ Uniform(1.5, 2): every orbit is invalid, every log-posterior −Inf. The first `keep` draws and −Inf come back (the reference
+    returns a prior draw and −Inf); the rejection driver reports the reference's error."""
+    model = callers_model(pkg, e_prior=pkg.Uniform(1.5, 2.0))
+    pd = draws_mod.PriorDraws(model)
+    first = 1000
+    th, lp, ix = pd.best(2, 5000, keep=3, first=first)
+    assert np.all(lp == -np.inf) and np.array_equal(ix, np.uint64(first) + np.arange(3, dtype=np.uint64))
+    assert np.array_equal(th, pd.sample(2, first, 3)[0].cpu().numpy())
+    with pytest.raises(pkg.capi.OctoError, match="All 5000 prior samples produced non-finite log-likelihoods"):
+        pd.rejection(2, 5000)
+    with pytest.raises(RuntimeError, match="All 5000 prior samples produced non-finite log-likelihoods"):
+        pkg.octofit_rejection_device(model, draws=5000, seed=2)
+    pd.close()
+    model.close()
+
+
+REJ_N = 100_000
+# (every quoted σ of the tables times this, seed). The model as it stands accepts one to five of 1e5 prior draws whatever the seed (seeds 1 … 1152
+# tried with the oracle on the CPU: Σ exp(ll − max) is 1 … 3.4, five accepted at best — seed 386), so "between 10 and 10 000 accepted" cannot be
+# met by choosing a seed for it. Both are run: the model as it stands with its best seed, every check but that count; and the same data with ten
+# times the quoted uncertainties, where 37 draws are accepted and the count condition holds and is asserted.
+REJ_CASES = ((1.0, 386, 2), (10.0, 4, 10))      # (sigma_scale, seed, least number accepted)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sigma_scale,REJ_SEED,least", REJ_CASES)
+def test_gpu_rejection(pkg, oracle, draws_mod, sigma_scale, REJ_SEED, least):
+    """octo_draws_rejection against octofit_rejection fed the same draws and uniforms with the oracle's likelihood: the same accepted
+    indices in order, log-likelihoods within 1e-8 of the largest of |ll|, |lp|, |logprior_t|, the same maximum; `cap` below the count."""
+    from octofitter_jl_amd.host.callers import _unit_length_terms
+    model = callers_model(pkg, sigma_scale=sigma_scale)
+    fn = model.ln_like
+    pd = draws_mod.PriorDraws(model)
+    θ, _, lpt = pd.sample(REJ_SEED, 0, REJ_N, theta_t=False)
+    θ, lpt = θ.cpu().numpy(), lpt.cpu().numpy()
+    u = rejection_uniforms(REJ_SEED, np.arange(REJ_N, dtype=np.uint64))
+    elems, nuis = model.kernel_inputs(θ)
+    ll_o, _, _ = oracle.oracle_eval(fn.obs_tables, fn.planet_desc, elems, nuis, grad=False, n_threads=0)
+    ll_o = ll_o + _unit_length_terms(model, θ)
+    ll_o = np.where(np.isfinite(ll_o), ll_o, -np.inf)
+    with np.errstate(over="ignore"):
+        p_o = np.exp(ll_o - ll_o.max())
+    acc_o = (ll_o != -np.inf) & (u < p_o)
+    print(f"oracle: {int(acc_o.sum())} accepted of {REJ_N}, max ll {ll_o.max():.6f}, closest |u − p| {np.min(np.abs(u - p_o)):.3e}")
+    assert np.min(np.abs(u - p_o)) >= 1e-9 and least <= acc_o.sum() <= 10_000, "condition on the seed"
+    lp_o = oracle_logpost(oracle, model, θ)
+    r = pd.rejection(REJ_SEED, REJ_N)
+    idx_o = np.nonzero(acc_o)[0]
+    assert r["n_accepted"] == idx_o.size and np.array_equal(r["index"], idx_o.astype(np.uint64))
+    assert np.array_equal(r["samples"], θ[:, idx_o])
+    scale = np.maximum(np.maximum(np.abs(ll_o[idx_o]), np.abs(lp_o[idx_o])), np.abs(lpt[idx_o]))
+    err = np.max(np.abs(r["loglike"] - ll_o[idx_o]) / scale)
+    err_lp = np.max(np.abs(r["logpost"] - lp_o[idx_o]) / np.abs(lp_o[idx_o]))
+    k = int(np.argmax(ll_o))
+    err_mx = abs(r["max_loglike"] - ll_o[k]) / max(abs(ll_o[k]), abs(lp_o[k]), abs(lpt[k]))
+    print(f"loglike: max err {err:.3e} of the scale; logpost: max rel err {err_lp:.3e}; max_loglike: {err_mx:.3e}")
+    assert err <= 1e-8 and err_lp <= 1e-11 and err_mx <= 1e-8
+    # the same chain through the reference-shaped driver fed these draws and uniforms
+    chain = pkg.octofit_rejection(None, model, prior_samples=θ, uniforms=u)
+    assert np.array_equal(np.nonzero(chain["accept"])[0], idx_o) and np.array_equal(chain["samples"], r["samples"])
+    # cap below the count: the full count, exactly cap rows, the first cap of the chain
+    cap = idx_o.size // 2
+    rc = pd.rejection(REJ_SEED, REJ_N, cap=cap)
+    assert rc["n_accepted"] == idx_o.size and rc["samples"].shape == (model.D, cap) and rc["index"].size == cap
+    assert np.array_equal(rc["index"], r["index"][:cap]) and np.array_equal(rc["samples"], r["samples"][:, :cap])
+    assert np.array_equal(rc["loglike"], r["loglike"][:cap]) and np.array_equal(rc["logpost"], r["logpost"][:cap])
+    # a window of the stream: draws [first, first + n) of a longer run are the same draws
+    sub = pd.rejection(REJ_SEED, 40_000, first=30_000)
+    assert np.all(sub["index"] >= 30_000) and np.all(sub["index"] < 70_000)
+    pd.close()
+    model.close()
+
+
+@pytest.mark.gpu
+def test_gpu_host_callers(pkg, draws_mod):
+    """guess_starting_position_device / octofit_rejection_device: shapes and keys of the host twins, values of PriorDraws."""
+    model = callers_model(pkg)
+    pd = draws_mod.PriorDraws(model)
+    rng = np.random.default_rng(1)
+    N = 20_000
+    host_best, host_lp = pkg.guess_starting_position(rng, model, N)
+    best, lp = pkg.guess_starting_position_device(model, N=N, seed=9)
+    assert best.shape == host_best.shape == (model.D,) and isinstance(lp, float) and isinstance(host_lp, float)
+    th, lps, _ = pd.best(9, N, keep=1)
+    assert np.array_equal(best, th[:, 0]) and lp == lps[0]
+    many, lp_many = pkg.guess_starting_position_device(model, N=N, seed=9, keep=5)
+    assert many.shape == (model.D, 5) and lp_many.shape == (5,) and np.all(np.diff(lp_many) <= 0) and lp_many[0] == lp
+    host_chain = pkg.octofit_rejection(rng, model, draws=N)
+    chain = pkg.octofit_rejection_device(model, draws=N, seed=9)
+    assert set(host_chain) <= set(chain)
+    r = pd.rejection(9, N)
+    assert np.array_equal(chain["samples"], r["samples"]) and np.array_equal(chain["loglike"], r["loglike"]) and np.array_equal(chain["logpost"], r["logpost"])
+    n = chain["n_accepted"]
+    assert n == r["n_accepted"] >= 1 and chain["samples"].shape == (model.D, n) and chain["loglike"].shape == chain["logpost"].shape == (n,)
+    assert chain["draws"] == N and chain["acceptance_rate"] == n / N and chain["names"] == host_chain["names"]
+    assert chain["accept"].shape == host_chain["accept"].shape and chain["accept"].dtype == bool and int(chain["accept"].sum()) == n
+    # the chain is a posterior sample: its log-posteriors are the callback's at the accepted draws
+    lp_cb = model.ℓπcallback(model.link(chain["samples"]))
+    assert np.all(np.abs(lp_cb - chain["logpost"]) <= 1e-11 * np.abs(lp_cb))
+    pd.close()
+    model.close()
+
+
+@pytest.mark.gpu
+def test_gpu_argument_checks(pkg, draws_mod):
+    import ctypes as C
+    model = callers_model(pkg)
+    pd = draws_mod.PriorDraws(model)
+    lib, EINVAL = pd.lib, pkg.capi.OCTO_EINVAL
+    th, lp, ix = np.empty((model.D, 64)), np.empty(64), np.empty(64, dtype=np.uint64)
+    args = (pkg.capi._dptr(th), pkg.capi._dptr(lp), draws_mod._u64ptr(ix))
+    assert lib.octo_draws_best(None, 0, 0, 100, 1, *args) == EINVAL
+    for keep in (0, 65):
+        assert lib.octo_draws_best(pd._h, 0, 0, 100, keep, *args) == EINVAL
+    assert lib.octo_draws_best(pd._h, 0, 0, 0, 1, *args) == EINVAL
+    assert lib.octo_draws_best(pd._h, 0, (1 << 64) - 5, 100, 1, *args) == EINVAL
+    assert b"overflows" in lib.octo_draws_last_error(pd._h)
+    n_acc, mx = C.c_int64(), C.c_double()
+    assert lib.octo_draws_rejection(pd._h, 0, (1 << 64) - 5, 100, 0, None, None, None, None, C.byref(n_acc), C.byref(mx)) == EINVAL
+    nomodel = draws_mod.PriorDraws(priors=[pkg.Uniform(0, 1)])
+    assert lib.octo_draws_best(nomodel._h, 0, 0, 100, 1, *args) == EINVAL
+    h = C.c_void_p()
+    fn = model.ln_like
+    for D in (0, 65):
+        assert lib.octo_draws_create(fn._ctx, model._m, model._c_priors, D, 0, C.byref(h)) == EINVAL
+    nomodel.close()
+    # a handle that outlives its model: closed after it, it must not touch the context that is gone
+    pd.best(0, 1000, keep=1)
+    model.close()
+    pd.close()
