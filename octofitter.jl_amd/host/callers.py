@@ -9,6 +9,9 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   guess_starting_position_device / octofit_rejection_device: the same two drivers with the draws, the link, the argmax and the
   accept / compaction step on the device too (host/draws.py: PriorDraws) — only the winners / the accepted chain cross PCIe.
 
+  simulate_tables / posterior_predictive: the back end of the workflow — the tables' model values (`simulate!`) and the orbit / RV curves
+  of posterior draws over a time grid, computed or reduced to a band on the device (host/predict.py: Predictor).
+
 The accept/reject and argmax logic is the reference's, line for line; random numbers come from NumPy's Generator
 (the reference uses Julia's Xoshiro), so individual draws differ while the sampled distribution is the same.
 """
@@ -147,3 +150,64 @@ def pointwise_like(model, θ_samples):
             one.close()
         names.append(key)
     return out, names
+
+
+def simulate_tables(obs_tables, planets, elems, nuis=None, device=0, consts=None):
+    """`simulate!` of every observation table for a batch of parameter sets (relative-astrometry.jl:104-142, rv-absolute.jl:135-158,
+    rv-absolute-margin.jl:106-126, rv-relative.jl:121-164), on the device: one Predictor per table at the table's own epochs, with the
+    channels its kind needs and the RV offset / trend coefficient wired from `nuis`.
+    obs_tables / planets: as given to capi.pack_obs / pack_planets; elems [P*9, W]; nuis [n_obs*3, W] or None (the defaults).
+    Returns one dict per table of [n_epochs, W] arrays: RADEC / ONEIL_RADEC -> ra, dec; SEPPA / ONEIL_SEPPA -> pa, sep (the wrapped
+    table's model); RV_ABS, RV_ABS_MARG (no offset), RV_REL -> rv. The platescale and northangle nuisances act on the data, not on these.
+    An HGCA table raises OctoError(OCTO_ENOTSUP): its model values are not on the device path."""
+    from . import capi, predict
+    elems = np.ascontiguousarray(elems, dtype=np.float64)
+    nu = None if nuis is None else np.ascontiguousarray(nuis, dtype=np.float64)
+    out = []
+    for io, t in enumerate(obs_tables):
+        kind, ip = int(t["kind"]), int(t["planet"])
+        if kind == capi.HGCA:
+            raise capi.OctoError(capi.OCTO_ENOTSUP, f"simulate_tables: table {io} is an HGCA table: its model values are not on the device path")
+        basis = add0 = add1 = None
+        if kind in (capi.ASTROM_RADEC, capi.ONEIL_RADEC):
+            names, channels = ("ra", "dec"), [(predict.ASTROM_RA, ip), (predict.ASTROM_DEC, ip)]
+        elif kind in (capi.ASTROM_SEPPA, capi.ONEIL_SEPPA):
+            names, channels = ("pa", "sep"), [(predict.ASTROM_PA, ip), (predict.ASTROM_SEP, ip)]
+        elif kind in (capi.RV_ABS, capi.RV_ABS_MARG, capi.RV_REL):
+            names, channels = ("rv",), [(predict.RV_REL, ip) if kind == capi.RV_REL else (predict.RV_STAR, -1)]
+            extra = t.get("extra")
+            if nu is not None:
+                rows = nu[io * capi.N_NUIS:(io + 1) * capi.N_NUIS]
+                if kind != capi.RV_ABS_MARG:
+                    add0 = rows[capi.NU_RV_OFFSET:capi.NU_RV_OFFSET + 1]
+                if extra is not None and len(extra) == len(t["epoch"]):      # the trend applies only to a table uploaded with a basis column
+                    basis, add1 = extra, rows[capi.NU_RV_TREND:capi.NU_RV_TREND + 1]
+        else:
+            raise capi.OctoError(capi.OCTO_EINVAL, f"simulate_tables: table {io} has an unknown kind {kind}")
+        if len(t["epoch"]) == 0:
+            out.append({n: np.empty((0, elems.shape[1])) for n in names})
+            continue
+        pr = predict.Predictor(planets, t["epoch"], channels, basis=basis, device=device, consts=consts)
+        try:
+            cube = pr.values(elems, add0=add0, add1=add1)
+        finally:
+            pr.close()
+        out.append({n: cube[k] for k, n in enumerate(names)})
+    return out
+
+
+def posterior_predictive(planets, elems, epochs, channels, summary=True, basis=None, add0=None, add1=None, device=0, consts=None):
+    """The model curves of posterior draws over a time grid: `channels` [(quantity, planet)] (host/predict.py) of every draw in `elems`
+    [P*9, W] at `epochs` [T]. summary=True: dict(n_valid, mean, sd, min, max), each [C, T], reduced over the draws on the device (the
+    cube is never stored); summary=False: the cube [C, T, W]. NumPy or device (torch) elements, as Predictor takes them."""
+    from . import predict
+    pr = predict.Predictor(planets, epochs, channels, basis=basis, device=device, consts=consts)
+    try:
+        res = pr.summary(elems, add0=add0, add1=add1) if summary else pr.values(elems, add0=add0, add1=add1)
+        pr.sync()
+        if not isinstance(res, (dict, np.ndarray)) or (isinstance(res, dict) and not isinstance(res["mean"], np.ndarray)):
+            import torch
+            torch.cuda.synchronize()      # device inputs ran on torch's current stream: the handle is destroyed below
+        return res
+    finally:
+        pr.close()
