@@ -9,6 +9,10 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   guess_starting_position_device / octofit_rejection_device: the same two drivers with the draws, the link, the argmax and the
   accept / compaction step on the device too (host/draws.py: PriorDraws) — only the winners / the accepted chain cross PCIe.
 
+  pointwise_like_rows / waic: the pointwise log-likelihood at the grain model comparison needs — one column per DATUM (table row), not per
+  table — and its WAIC / importance-sampling LOO sums, computed (and for waic reduced over the samples) on the device
+  (host/pointwise.py: Pointwise).
+
   simulate_tables / posterior_predictive: the back end of the workflow — the tables' model values (`simulate!`) and the orbit / RV curves
   of posterior draws over a time grid, computed or reduced to a band on the device (host/predict.py: Predictor).
 
@@ -150,6 +154,53 @@ def pointwise_like(model, θ_samples):
             one.close()
         names.append(key)
     return out, names
+
+
+def _pointwise_handle(model):
+    """The Pointwise handle of a model's tables and their labels [(table name, row index)] in the matrix's row order. A model that holds a
+    table whose value is no sum over its rows (marginalised RV, HGCA, the O'Neil prior) raises OctoError(OCTO_ENOTSUP)."""
+    from .pointwise import Pointwise
+    fn = model.ln_like
+    pw = Pointwise(fn.obs_tables, fn.planet_desc, device=fn.device_index)
+    labels = [(key, j) for (_obs, _ip, _pl, key), t in zip(fn.obs_entries, fn.obs_tables) for j in range(len(t["epoch"]))]
+    return pw, labels
+
+
+def pointwise_like_rows(model, θ_samples):
+    """`Octofitter.pointwise_like` (src/cross-validation.jl:17-46) per DATUM: LL[n_samples, R], the log-likelihood of every posterior sample
+    under each table ROW alone (what a one-row table scores, constant terms included), in ONE device call — the matrix WAIC, IS-LOO and
+    PSIS-LOO consume (PSIS smoothing stays with the caller's tool). θ_samples: [D, n] natural domain.
+    Returns (LL, labels) with labels[r] = (table name, row index). The rows of a table sum to its column of pointwise_like."""
+    θ_samples = np.asarray(θ_samples, dtype=np.float64).reshape(model.D, -1)
+    elems, nuis = model.kernel_inputs(θ_samples)
+    pw, labels = _pointwise_handle(model)
+    try:
+        LL = pw.values(elems, nuis)
+    finally:
+        pw.close()
+    return np.ascontiguousarray(LL.T), labels
+
+
+def waic(model, θ_samples):
+    """WAIC and importance-sampling LOO of a model from posterior samples θ_samples [D, n] (natural domain), reduced over the samples on the
+    device: the matrix of pointwise_like_rows is never stored. Per row r, over the samples with a finite value:
+        lppd[r] = log mean exp(ll),  p_waic[r] = sample variance of ll,  elpd_waic[r] = lppd[r] − p_waic[r],  elpd_is_loo[r] = −log mean exp(−ll).
+    Returns dict(lppd, p_waic, elpd_waic, elpd_is_loo: [R] arrays; <name>_total: their sums over the rows; <name>_se = √(R · var over the
+    rows): the totals' standard errors; n_valid [R]; n_samples; labels [(table name, row index)])."""
+    θ_samples = np.asarray(θ_samples, dtype=np.float64).reshape(model.D, -1)
+    elems, nuis = model.kernel_inputs(θ_samples)
+    pw, labels = _pointwise_handle(model)
+    try:
+        s = pw.summary(elems, nuis)
+    finally:
+        pw.close()
+    out = dict(lppd=s["lppd"], p_waic=s["var"], elpd_waic=s["lppd"] - s["var"], elpd_is_loo=s["elpd_is_loo"])
+    R = len(labels)
+    for k in ("lppd", "p_waic", "elpd_waic", "elpd_is_loo"):
+        out[k + "_total"] = float(np.sum(out[k]))
+        out[k + "_se"] = float(np.sqrt(R * np.var(out[k], ddof=1))) if R > 1 else float("nan")
+    out.update(n_valid=s["n"], n_samples=int(θ_samples.shape[1]), labels=labels)
+    return out
 
 
 def simulate_tables(obs_tables, planets, elems, nuis=None, device=0, consts=None):
