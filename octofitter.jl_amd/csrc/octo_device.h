@@ -95,12 +95,26 @@ struct KSol { double sE, cE, invD, dt, E; };
 // e -> 1 − 1e-9: D-weighted error of (sin E, cos E) 3.9e-16 below 1e-3, 2.2e-16 below 1e-4). Where it does not (a fast orbit near the periastron
 // of a high-e walker) the wave falls back to the Markley starter for that row — WAVE-UNIFORMLY (one ballot, one scalar branch: the loop stays
 // divergence-free), and the root is unique, so the result is the same E to rounding either way.
-// The test is a priori and one compare: x³/D² < tol  <=>  1/D < thr with thr = (tol / ΔM³)^(1/5) per lane, from the TABLE's largest
-// 2π Δt (DevObs::dm_max; exact for a uniform cadence, conservative otherwise). A wave starts warm only where every lane's thr >= WARM_MIN_THR, i.e.
-// ΔM_max <= (tol/32)^(1/3) = 0.0315, so a pass bounds |x| = ΔM/D < ΔM_max · thr = tol^(1/5) ΔM_max^(2/5) <= 0.063 and |dE| < 0.066:
+// The test is a priori and one compare per lane: 1/D of the previous row < thr, thr = warm_thr(e, |ΔM|) below, from the TABLE's step bound
+// (DevObs::dm_ladder; exact for a uniform cadence, conservative otherwise). thr is the larger of two sufficient conditions:
+//   (a) x³/D² < WARM_TOL  <=>  1/D < (WARM_TOL / ΔM³)^(1/5) — the crude bound on the third derivative above, blind to e; and
+//   (b) |x| < min(c(e), WARM_X_CAP)  <=>  1/D < min(c(e), WARM_X_CAP)/ΔM — the predictor's third-order term itself, (x³/6)(3β² − α) with β = e sin E/D,
+//       α = e cos E/D. With v = 1/D, e² sin²E = e² − (1 − D)² and e cos E = 1 − D give β² = 2v − 1 − (1 − e²)v² and α = v − 1, so the term is
+//       (x³/6) q(v), q(v) = 7v − 4 − 3(1 − e²)v² <= q_cap(e) = max of q on [1, 1/(1 − e)] = 49/(12(1 − e²)) − 4 where the vertex 7/(6(1 − e²)) lies
+//       inside (e > 1/6), q(1/(1 − e)) = e/(1 − e) — the periastron — otherwise. c(e) = (6·WARM_C3/q_cap)^(1/3) keeps the term below WARM_C3.
+// (a) was calibrated at e -> 1 and rejects a lane with e = 0.5 at v = 2 for a term 24x below it (3.7x at e = 0.95): a third of config 3's walkers
+// (0.6 < e < 0.9) were rejected near their periastra for nothing. Taking the maximum never rejects a row (a) admits.
+// Calibrated (tests/warm_bound_model.py restates the step and the bound in float64, tests/test_warm_bound.py holds it; 80-bit Newton reference, 2e5
+// samples of (e, E, ΔM), e to 1 − 1e-9, half within |E| < 0.6, |ΔM| 1e-7 … 0.0314 both signs): the rows (b) admits beyond (a) carry a D-weighted error
+// of (sin E, cos E) of at most 2.4e-16 at WARM_C3 = 2.5e-4 (2.5e-16 on the device) — the same rounding level as the bulk of (a)'s rows; the worst rows are (a)'s own corner
+// (e > 0.9, ΔM > 0.012 at the very edge of the bound: the fourth-order correction's truncation, 0.2 ε⁴ at ε = 3.6e-4 — 4e-15). Above WARM_E_MAX = 0.99 (b) is
+// dropped rather than tightened: the predictor's FOURTH-order term grows like v³ there and is no longer small against the third-order one the constant prices,
+// an FP32 1 − e² loses its digits, and no prior puts a useful share of walkers there. Config 3's cold wave-rows: 7.7 % -> 4.4 % (tools/warm_rates.py).
+// A wave starts warm only where every lane's ΔM <= WARM_DM_VETO, i.e. (a) >= WARM_MIN_THR — (b) is below 2 wherever ΔM > 0.03, so the veto is (a)'s as
+// before — and a pass bounds |x| = ΔM/D < max(tol^(1/5) ΔM_max^(2/5), WARM_X_CAP) <= 0.063 and |dE| < 0.066:
 // the rotation's polynomials (sin to dE⁷, cos to dE⁸) are exact to 1e-16 there. tol = 1e-3 with the FOURTH-order correction of the warm rows
-// (kepler_correct): its truncation is ~2e-16 there (tools/kepler_warm_proto.py: D-weighted maximum 1.1e-15 at 4e-4 and at 1e-3 — the rounding
-// level of the cold solve — 3.4e-15 at 2e-3); config 3 falls back on 8 % of its wave-rows at 1e-3, on 12.5 % at 4e-4.
+// (kepler_correct): its truncation is ~2e-16 there (tools/kepler_warm_proto.py: D-weighted maximum 1.1e-15 at 4e-4 and at 1e-3 over config 3's walkers — the rounding
+// level of the cold solve — 3.4e-15 at 2e-3).
 // What the chain gives up: E and M never appear, so the solve of row j starts from the SOLUTION of row j−1 and its rounding (~1e-16 in M per
 // row) accumulates until the next cold row — at most a wave's chunk of rows (tens to a few hundred: < 1e-13 in M, the size of the
 // rounding of (t − tp)/P itself for a walker a few orbits from tp; the prototype measures 8e-15 after 72 rows).
@@ -116,8 +130,22 @@ struct KWarm { double sE, cE, invD; };
 constexpr double WARM_TOL = 1.0e-3;
 constexpr double WARM_MIN_THR = 2.0;      // a wave takes the warm loop only if every lane passes at least wherever D >= 1/2
 constexpr float WARM_DM_VETO = 0.0314f;   // (WARM_TOL/32)^(1/3) = 0.03150, less the 2^-18 stretch and the float roundings: thr >= WARM_MIN_THR
+constexpr float WARM_C3 = 2.5e-4f;        // bound (b): the predictor's third-order term stays below this
+constexpr float WARM_X_CAP = 0.06f;       // bound (b): |x| the rotation's polynomials are exact for (|dE| < 0.066)
+constexpr float WARM_E_MAX = 0.99f;       // above: bound (a) alone
 constexpr int WARM_LADDER = 8;            // candidate step bounds per table (DevObs::dm_ladder)
 constexpr int WARM_RESTART = 256;         // every WARM_RESTART-th row of a table starts cold
+
+// The lane's bound on 1/D of the previous row (KWarm above): e the eccentricity, dm = |ΔM| of the wave's step bound. FP32 (v_log_f32 / v_exp_f32 are base 2),
+// once per lane per task. The ONE copy of the formula: k_main (warm_init, warm_last_init), the test hook k_kepler_warm and k_tile_sort's closed-form failure
+// share all call it. A NaN step gives a NaN bound (passes: an invalid walker's sums are discarded); an invalid or NaN e leaves bound (a) as it was.
+__device__ __forceinline__ float warm_thr(float e, float dm) {
+    const float a = __builtin_amdgcn_exp2f(0.2f * (__builtin_amdgcn_logf((float)WARM_TOL) - 3.0f * __builtin_amdgcn_logf(dm)));
+    const float q = e > (1.0f / 6.0f) ? fmaf(49.0f / 12.0f, __builtin_amdgcn_rcpf(fmaf(-e, e, 1.0f)), -4.0f) : e * __builtin_amdgcn_rcpf(1.0f - e);
+    const float c = __builtin_amdgcn_exp2f((1.0f / 3.0f) * (__builtin_amdgcn_logf(6.0f * WARM_C3) - __builtin_amdgcn_logf(q)));      // e = 0: +Inf
+    const float xc = (e >= 0.0f && e < WARM_E_MAX) ? fminf(c, WARM_X_CAP) : 0.0f;
+    return fmaxf(a, xc * __builtin_amdgcn_rcpf(dm));
+}
 
 __device__ __forceinline__ void load_pc(PC& pc, const double* __restrict__ wc, int64_t ldw, int p, int64_t w) {
     const double* b = wc + (int64_t)p * NWC * ldw + w;

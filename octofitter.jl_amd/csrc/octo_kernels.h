@@ -417,7 +417,7 @@ static __global__ __launch_bounds__(256) void k_kepler_warm(const double* __rest
     const KSol s0 = kepler_solve<2, true>(MA[i], pc, tab);
     KWarm st{s0.sE, s0.cE, s0.invD};
     const float dmx = fabsf((float)dMa[i]);
-    double thr = (double)__builtin_amdgcn_exp2f(0.2f * (__builtin_amdgcn_logf((float)WARM_TOL) - 3.0f * __builtin_amdgcn_logf(dmx)));
+    double thr = (double)warm_thr((float)e, dmx);
     if (thr < WARM_MIN_THR) thr = 0.0;      // k_main's veto (warm_init): a bound below WARM_MIN_THR never starts warm — the routine's polynomials count on |dE| < 0.066
     const bool warm = __builtin_amdgcn_ballot_w64(st.invD >= thr) == 0;
     // dm = 2π·Δt with 1/P = 1/2π: ΔM = dMa[i]; t = MA + dM so that the cold fallback solves the same row
@@ -1002,15 +1002,14 @@ __device__ __forceinline__ float warm_last_init(WarmState<P>& ws, const PC& pc, 
     }
     ws.key_hi = (uint32_t)__builtin_amdgcn_readfirstlane(__double2hiint((double)bound));
     const float dmx = fabsf(bound * (1.0f + 0x1p-18f) * (float)pc.invP);
-    const float th = __builtin_amdgcn_exp2f(0.2f * (__builtin_amdgcn_logf((float)WARM_TOL) - 3.0f * __builtin_amdgcn_logf(dmx)));
-    ws.thr[P - 1] = (double)th;
+    ws.thr[P - 1] = (double)warm_thr(pc.ef, dmx);
     ws.st[P - 1].sE = 0.0; ws.st[P - 1].cE = 1.0; ws.st[P - 1].invD = __builtin_huge_val();
     return bound;
 }
 
 // The wave's step bound: the first entry of the table's ladder (DevObs::dm_ladder, preferred first) that no lane vetoes, a veto being
-// ΔM = bound/P > WARM_DM_VETO (thr would fall below WARM_MIN_THR; a NaN — an invalid walker — does not veto). thr = (tol / ΔM³)^(1/5) per lane from
-// that bound (v_log_f32 / v_exp_f32 are base 2). No entry passes: the wave runs the cold loop. The first row of a wave is cold.
+// ΔM = bound/P > WARM_DM_VETO (thr would fall below WARM_MIN_THR; a NaN — an invalid walker — does not veto). thr = warm_thr(e, ΔM) per lane from
+// that bound (octo_device.h). No entry passes: the wave runs the cold loop. The first row of a wave is cold.
 template <int P>
 __device__ __forceinline__ float warm_init(WarmState<P>& ws, const PC (&pc)[P], const DevObs& ob, bool enabled) {
     float bound = 0.0f;
@@ -1028,8 +1027,7 @@ __device__ __forceinline__ float warm_init(WarmState<P>& ws, const PC (&pc)[P], 
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         const float dmx = fabsf(bs * (float)pc[p].invP);
-        const float th = __builtin_amdgcn_exp2f(0.2f * (__builtin_amdgcn_logf((float)WARM_TOL) - 3.0f * __builtin_amdgcn_logf(dmx)));
-        ws.thr[p] = (double)th;
+        ws.thr[p] = (double)warm_thr(pc[p].ef, dmx);
         ws.st[p].sE = 0.0; ws.st[p].cE = 1.0; ws.st[p].invD = __builtin_huge_val();
     }
     ws.row_ok = true;

@@ -86,7 +86,7 @@ static __global__ __launch_bounds__(TILE_TPB) void k_tile_sort(TileArgs a) {
             b = 25 + (x >= 0.0f ? (x < 6.0f ? (int)x : 6) : (x < 0.0f ? 0 : 6));
             p = 1.0f;
         } else {
-            const float thr = __builtin_amdgcn_exp2f(0.2f * (__builtin_amdgcn_logf((float)WARM_TOL) - 3.0f * __builtin_amdgcn_logf(dM)));
+            const float thr = warm_thr(e, dM);      // the bound k_main tests against: >= 2 here (dM <= WARM_DM_VETO)
             const float g = 1.0f - __builtin_amdgcn_rcpf(thr);
             if (e <= g) { b = 0; p = 0.0f; }
             else {

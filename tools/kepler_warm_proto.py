@@ -12,12 +12,16 @@ with a WAVE-UNIFORM fallback to the Markley starter whenever any lane of the wav
 own walkers and epochs: (1) the accuracy of the warm chain against an 80-bit solve, including the drift of a chain that never sees E
 or M as numbers; (2) the fallback rate per wave-row for a given bound, by eccentricity bin; (3) the issue-time model's estimate of the
 step time. Development aid; not shipped, not imported by tests.
-    python tools/kepler_warm_proto.py [rows_per_wave] [tol]"""
+    python tools/kepler_warm_proto.py [rows_per_wave] [tol] [order] [parent]
+The bound is the device's (octo_device.h: warm_thr, restated in tests/warm_bound_model.py: the larger of x³/D² < tol and the eccentricity-aware
+|x| < min(c(e), 0.06)); a fourth argument `parent` gives the e-blind form alone. The one-step calibration of the bound over the whole elliptic
+domain (not only config 3's walkers) is tests/test_warm_bound.py."""
 import sys
 import numpy as np
 sys.path.insert(0, "tests"); sys.path.insert(0, "tools")
 import synth
 from kepler_proto import starter32, refine_device, truth
+import warm_bound_model as wm
 
 TWO_PI = 2 * np.pi
 
@@ -76,6 +80,7 @@ def main():
     rows_per_wave = int(sys.argv[1]) if len(sys.argv) > 1 else 74
     tol = float(sys.argv[2]) if len(sys.argv) > 2 else 1e-3
     order = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+    parent = len(sys.argv) > 4 and sys.argv[4] == "parent"
     n_rows = rows_per_wave * 12
     cfg = synth.config_astrom(n_epochs=10_000, n_walkers=10_000, cfg=3)
     el = cfg["elems"]; W = el.shape[1]
@@ -116,6 +121,8 @@ def main():
             # a-priori bound, per lane: first-order step x = ΔM/D and the predictor's relative error scale
             bound = np.abs(x) ** 3 * state[2] ** 2 if order == 2 else np.abs(x) ** 4 * state[2] ** 3
             ok_lane = (np.abs(x) < XMAX) & (bound < tol)
+            if order == 2 and not parent:      # the device's bound: (a) above or (b) |x| < min(c(e), X_CAP), e < WARM_E_MAX
+                ok_lane |= state[2] < wm.warm_thr(e, dM, c3=wm.WARM_C3 * tol / wm.WARM_TOL)
             okp = np.concatenate([ok_lane, np.ones(pad, bool)]).reshape(tiles, 64)
             wave_ok = okp.all(axis=1)
             lane_wave_ok = np.repeat(wave_ok, 64)[:W]
