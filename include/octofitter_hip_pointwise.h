@@ -4,7 +4,7 @@
  * WAIC and importance-sampling LOO are made from.
  *
  * In the reference this is `pointwise_like` (src/cross-validation.jl:17-46: one system per epoch, threaded over the samples):
- * the matrix that WAIC, IS-LOO and PSIS-LOO consume. PSIS smoothing stays with the caller's tool; the matrix is what it takes.
+ * the matrix that WAIC, IS-LOO and PSIS-LOO consume. PSIS smoothing of it on the device: include/octofitter_hip_psis.h.
  *
  * A companion of include/octofitter_hip.h in a shared object of its own (liboctofitter_hip_pointwise.so): it adds nothing to
  * the main header or library, and needs no octo_ctx. Same conventions: `extern "C"`, the int32 status codes of the main

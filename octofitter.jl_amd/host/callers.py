@@ -169,7 +169,7 @@ def _pointwise_handle(model):
 def pointwise_like_rows(model, θ_samples):
     """`Octofitter.pointwise_like` (src/cross-validation.jl:17-46) per DATUM: LL[n_samples, R], the log-likelihood of every posterior sample
     under each table ROW alone (what a one-row table scores, constant terms included), in ONE device call — the matrix WAIC, IS-LOO and
-    PSIS-LOO consume (PSIS smoothing stays with the caller's tool). θ_samples: [D, n] natural domain.
+    PSIS-LOO consume (PSIS smoothing on the device: include/octofitter_hip_psis.h, `loo`). θ_samples: [D, n] natural domain.
     Returns (LL, labels) with labels[r] = (table name, row index). The rows of a table sum to its column of pointwise_like."""
     θ_samples = np.asarray(θ_samples, dtype=np.float64).reshape(model.D, -1)
     elems, nuis = model.kernel_inputs(θ_samples)
@@ -200,6 +200,46 @@ def waic(model, θ_samples):
         out[k + "_total"] = float(np.sum(out[k]))
         out[k + "_se"] = float(np.sqrt(R * np.var(out[k], ddof=1))) if R > 1 else float("nan")
     out.update(n_valid=s["n"], n_samples=int(θ_samples.shape[1]), labels=labels)
+    return out
+
+
+def loo(model, θ_samples, weights=False):
+    """PSIS-LOO (Pareto-smoothed importance-sampling leave-one-out; Vehtari, Gelman & Gabry 2017) of a model from posterior samples θ_samples
+    [D, n] (natural domain), on the device: the matrix of pointwise_like_rows is formed there by the Pointwise handle and smoothed there by
+    Psis (include/octofitter_hip_psis.h states the algorithm), so it never crosses PCIe. It is STORED on the device: R·n·8 bytes of HBM (plus as
+    much again for the log-weights when asked). Per row r, over the samples with a finite value:
+        pareto_k[r] = the fitted Pareto shape k̂ (> 0.7: do not trust this row; +Inf: no fit was made),  elpd_loo[r] = logsumexp(ll + lw),
+        lppd[r] = log mean exp(ll),  p_loo[r] = lppd[r] − elpd_loo[r],  ess[r] = 1/Σ exp(2·lw).
+    Returns dict(elpd_loo, pareto_k, lppd, p_loo, ess, n_valid, tail_len: [R] arrays; <name>_total and <name>_se = √(R · var over the rows) for
+    elpd_loo and p_loo, as waic() forms them; n_bad_k = count(pareto_k > 0.7); n_samples; labels [(table name, row index)]; and, with
+    weights=True, log_weights [R, n]: the smoothed normalised log-weights). A model with a marginalised-RV, HGCA or O'Neil table raises
+    OctoError(OCTO_ENOTSUP), as waic() does."""
+    import torch
+    from .psis import Psis
+    θ_samples = np.asarray(θ_samples, dtype=np.float64).reshape(model.D, -1)
+    elems, nuis = model.kernel_inputs(θ_samples)
+    pw, labels = _pointwise_handle(model)
+    ps = None
+    try:
+        dev = torch.device("cuda", pw.device_index)
+        ps = Psis(device=pw.device_index)
+        d_el = torch.from_numpy(np.ascontiguousarray(elems, dtype=np.float64)).to(dev)
+        d_nu = None if nuis is None else torch.from_numpy(np.ascontiguousarray(nuis, dtype=np.float64)).to(dev)
+        s = ps.loo(pw.values(d_el, d_nu), weights=weights)
+        s = {k: v.cpu().numpy() for k, v in s.items()}      # the copy waits for the stream both calls ran on
+    finally:
+        if ps is not None:
+            ps.close()
+        pw.close()
+    out = dict(elpd_loo=s["elpd_loo"], pareto_k=s["pareto_k"], lppd=s["lppd"], p_loo=s["lppd"] - s["elpd_loo"], ess=s["ess"],
+               n_valid=s["n"], tail_len=s["tail_len"])
+    R = len(labels)
+    for k in ("elpd_loo", "p_loo"):
+        out[k + "_total"] = float(np.sum(out[k]))
+        out[k + "_se"] = float(np.sqrt(R * np.var(out[k], ddof=1))) if R > 1 else float("nan")
+    out.update(n_bad_k=int(np.count_nonzero(out["pareto_k"] > 0.7)), n_samples=int(θ_samples.shape[1]), labels=labels)
+    if weights:
+        out["log_weights"] = s["log_weights"]
     return out
 
 
