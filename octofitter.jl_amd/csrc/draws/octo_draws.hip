@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "octo_companion_host.h"
 #include "octo_model.h"
 #include "octofitter_hip_draws.h"
 
@@ -296,15 +297,12 @@ __global__ __launch_bounds__(TPB) void k_scatter(const double* __restrict__ ll, 
     if (f && pos < cap) { o_idx[pos] = first + (uint64_t)k; o_ll[pos] = v; o_lp[pos] = lp[k]; }
 }
 
-thread_local std::string g_create_error;
-
 }  // namespace
 
-struct octo_draws {
+struct octo_draws : CompanionBase {
     octo_ctx* ctx = nullptr;
     octo_model* model = nullptr;
-    int device = 0, D = 0;
-    hipStream_t stream = nullptr;
+    int D = 0;
     bool ctx_on_stream = false;      // the context was handed `stream` (octo_model_logpost_device) and may still name it as its last stream
     octo_prior* d_priors = nullptr;
     double *d_pc = nullptr, *d_ic = nullptr;
@@ -319,21 +317,9 @@ struct octo_draws {
     uint64_t* d_oix = nullptr; double *d_oll = nullptr, *d_olp = nullptr, *d_oth = nullptr;
     int64_t cap_o = 0;
     double* d_max = nullptr;
-    std::string err;
 };
 
 namespace {
-
-int fail(octo_draws* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_create_error = msg;
-    return code;
-}
-
-#define DCHK(h, expr)                                                                                                   \
-    do {                                                                                                                \
-        const hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return fail(h, e_ == hipErrorOutOfMemory ? OCTO_ENOMEM : OCTO_EHIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
 
 int main_call(octo_draws* h, int rc, const char* what) {
     h->ctx_on_stream = true;
@@ -344,8 +330,8 @@ int main_call(octo_draws* h, int rc, const char* what) {
 
 template <class T>
 int regrow(octo_draws* h, T*& p, int64_t n) {
-    if (p) { DCHK(h, hipFree(p)); p = nullptr; }
-    DCHK(h, hipMalloc((void**)&p, sizeof(T) * (size_t)n));
+    if (p) { OCHK(h, hipFree(p)); p = nullptr; }
+    OCHK(h, hipMalloc((void**)&p, sizeof(T) * (size_t)n));
     return OCTO_OK;
 }
 
@@ -361,7 +347,7 @@ int ensure_chunk(octo_draws* h) {
 
 int ensure_draw_arrays(octo_draws* h, int64_t n) {
     if (n <= h->cap_n) return OCTO_OK;
-    DCHK(h, hipStreamSynchronize(h->stream));
+    OCHK(h, hipStreamSynchronize(h->stream));
     h->cap_n = 0;
     int rc;
     if ((rc = regrow(h, h->d_lp, n))) return rc;
@@ -374,7 +360,7 @@ int ensure_draw_arrays(octo_draws* h, int64_t n) {
 
 int ensure_outputs(octo_draws* h, int64_t n) {
     if (n <= h->cap_o) return OCTO_OK;
-    DCHK(h, hipStreamSynchronize(h->stream));
+    OCHK(h, hipStreamSynchronize(h->stream));
     h->cap_o = 0;
     int rc;
     if ((rc = regrow(h, h->d_oix, n))) return rc;
@@ -399,7 +385,7 @@ int launch_draw(octo_draws* h, hipStream_t st, uint64_t seed, uint64_t first, co
         a.theta = d_theta ? d_theta + o : nullptr; a.theta_t = d_theta_t ? d_theta_t + o : nullptr; a.lpt = d_lpt ? d_lpt + o : nullptr;
         for (a.d0 = 0; a.d0 < h->D; a.d0 += 4) hipLaunchKernelGGL(k_draw, dim3((unsigned)((a.n + TPB - 1) / TPB)), dim3(TPB), 0, st, a);
     }
-    DCHK(h, hipGetLastError());
+    OCHK(h, hipGetLastError());
     return OCTO_OK;
 }
 
@@ -455,15 +441,10 @@ int32_t octo_draws_create(octo_ctx* ctx, octo_model* model, const octo_prior* pr
             if (!(q[1] > 0.0)) return fail(nullptr, OCTO_EINVAL, "octo_draws_create: prior " + std::to_string(k) + ": the truncation leaves no probability in double precision");
         }
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { (void)hipGetLastError(); return fail(nullptr, OCTO_ENODEV, "octo_draws_create: no HIP device"); }
-    if (device_id < 0 || device_id >= n_dev) return fail(nullptr, OCTO_EINVAL, "octo_draws_create: device_id out of range");
-    octo_draws* h = new (std::nothrow) octo_draws();
-    if (!h) return fail(nullptr, OCTO_ENOMEM, "octo_draws_create: host allocation failed");
-    h->ctx = ctx; h->model = model; h->device = device_id; h->D = D;
+    octo_draws* h;
+    { int rc = open_device(device_id, "octo_draws_create: ", h); if (rc) return rc; }
+    h->ctx = ctx; h->model = model; h->D = D;
     auto bail = [&](int code, const char* msg) { octo_draws_destroy(h); return fail(nullptr, code, msg); };
-    if (hipSetDevice(device_id) != hipSuccess) return bail(OCTO_EHIP, "octo_draws_create: hipSetDevice failed");
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(OCTO_EHIP, "octo_draws_create: stream creation failed");
     if (hipMalloc((void**)&h->d_priors, sizeof(octo_prior) * D) != hipSuccess || hipMalloc((void**)&h->d_pc, sizeof(double) * pc.size()) != hipSuccess ||
         hipMalloc((void**)&h->d_ic, sizeof(double) * ic.size()) != hipSuccess)
         return bail(OCTO_ENOMEM, "octo_draws_create: hipMalloc failed");
@@ -504,7 +485,7 @@ int32_t octo_draws_detach(octo_draws* h) {
     return OCTO_OK;
 }
 
-const char* octo_draws_last_error(const octo_draws* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* octo_draws_last_error(const octo_draws* h) { return last_error(h); }
 
 int32_t octo_draws_sample_device(octo_draws* h, uint64_t seed, uint64_t first, int64_t n, int64_t ld, double* d_theta, double* d_theta_t,
                                  double* d_logprior_t, void* hip_stream) {
@@ -512,17 +493,12 @@ int32_t octo_draws_sample_device(octo_draws* h, uint64_t seed, uint64_t first, i
     if (n < 0 || ld < n) return fail(h, OCTO_EINVAL, "octo_draws_sample_device: need 0 <= n <= ld");
     if (first + (uint64_t)n < first) return fail(h, OCTO_EINVAL, "octo_draws_sample_device: first + n overflows the draw index");
     if (n == 0 || (!d_theta && !d_theta_t && !d_logprior_t)) return OCTO_OK;
-    DCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = hip_stream == OCTO_STREAM_CTX ? h->stream : (hipStream_t)hip_stream;
+    OCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream_of(h, hip_stream);
     return launch_draw(h, st, seed, first, nullptr, n, ld, d_theta, d_theta_t, d_logprior_t);
 }
 
-int32_t octo_draws_sync(octo_draws* h) {
-    if (!h) return OCTO_EINVAL;
-    DCHK(h, hipSetDevice(h->device));
-    DCHK(h, hipStreamSynchronize(h->stream));
-    return OCTO_OK;
-}
+int32_t octo_draws_sync(octo_draws* h) { return sync_handle(h); }
 
 int32_t octo_draws_best(octo_draws* h, uint64_t seed, uint64_t first, int64_t N, int32_t keep, double* theta_out, double* logpost_out, uint64_t* index_out) {
     if (!h) return OCTO_EINVAL;
@@ -530,14 +506,14 @@ int32_t octo_draws_best(octo_draws* h, uint64_t seed, uint64_t first, int64_t N,
     { int rc = check_range(h, "octo_draws_best", first, N, true); if (rc) return rc; }
     if (keep > N) return fail(h, OCTO_EINVAL, "octo_draws_best: keep <= N");
     if (!theta_out || !logpost_out || !index_out) return fail(h, OCTO_EINVAL, "octo_draws_best: null output");
-    DCHK(h, hipSetDevice(h->device));
+    OCHK(h, hipSetDevice(h->device));
     { int rc = ensure_chunk(h); if (rc) return rc; }
     { int rc = ensure_draw_arrays(h, std::min(N, CHUNK)); if (rc) return rc; }
     { int rc = ensure_outputs(h, OCTO_DRAWS_MAX_KEEP); if (rc) return rc; }
     const hipStream_t st = h->stream;
     // the running list starts empty: every byte 0xFF = (NaN, NO_INDEX), which k_topk reads as no candidate
-    DCHK(h, hipMemsetAsync(h->d_clp, 0xFF, sizeof(double) * keep, st));
-    DCHK(h, hipMemsetAsync(h->d_cix, 0xFF, sizeof(uint64_t) * keep, st));
+    OCHK(h, hipMemsetAsync(h->d_clp, 0xFF, sizeof(double) * keep, st));
+    OCHK(h, hipMemsetAsync(h->d_cix, 0xFF, sizeof(uint64_t) * keep, st));
     for (int64_t done = 0; done < N; done += CHUNK) {
         const int64_t n = std::min(CHUNK, N - done);
         { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, h->d_tt, nullptr); if (rc) return rc; }
@@ -545,11 +521,11 @@ int32_t octo_draws_best(octo_draws* h, uint64_t seed, uint64_t first, int64_t N,
         const int64_t nb = (n + SEL_SLAB - 1) / SEL_SLAB;
         hipLaunchKernelGGL(k_topk, dim3((unsigned)nb), dim3(TPB), 0, st, h->d_lp, (const uint64_t*)nullptr, first + (uint64_t)done, n, keep, (int64_t)1, h->d_clp, h->d_cix);
         hipLaunchKernelGGL(k_topk, dim3(1), dim3(TPB), 0, st, h->d_clp, h->d_cix, (uint64_t)0, (1 + nb) * keep, keep, (int64_t)0, h->d_clp, h->d_cix);
-        DCHK(h, hipGetLastError());
+        OCHK(h, hipGetLastError());
     }
-    DCHK(h, hipMemcpyAsync(logpost_out, h->d_clp, sizeof(double) * keep, hipMemcpyDeviceToHost, st));
-    DCHK(h, hipMemcpyAsync(index_out, h->d_cix, sizeof(uint64_t) * keep, hipMemcpyDeviceToHost, st));
-    DCHK(h, hipStreamSynchronize(st));
+    OCHK(h, hipMemcpyAsync(logpost_out, h->d_clp, sizeof(double) * keep, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(index_out, h->d_cix, sizeof(uint64_t) * keep, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipStreamSynchronize(st));
     // places no finite log-posterior took: −Inf and the lowest draw indices not listed yet
     uint64_t next = first;
     for (int r = 0; r < keep; ++r) {
@@ -563,10 +539,10 @@ int32_t octo_draws_best(octo_draws* h, uint64_t seed, uint64_t first, int64_t N,
         logpost_out[r] = -INFINITY;
     }
     // θ of the winners, from the counter
-    DCHK(h, hipMemcpyAsync(h->d_oix, index_out, sizeof(uint64_t) * keep, hipMemcpyHostToDevice, st));
+    OCHK(h, hipMemcpyAsync(h->d_oix, index_out, sizeof(uint64_t) * keep, hipMemcpyHostToDevice, st));
     { int rc = launch_draw(h, st, seed, 0, h->d_oix, keep, keep, h->d_oth, nullptr, nullptr); if (rc) return rc; }
-    DCHK(h, hipMemcpyAsync(theta_out, h->d_oth, sizeof(double) * keep * h->D, hipMemcpyDeviceToHost, st));
-    DCHK(h, hipStreamSynchronize(st));
+    OCHK(h, hipMemcpyAsync(theta_out, h->d_oth, sizeof(double) * keep * h->D, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipStreamSynchronize(st));
     return OCTO_OK;
 }
 
@@ -576,7 +552,7 @@ int32_t octo_draws_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64
     { int rc = check_range(h, "octo_draws_rejection", first, N, true); if (rc) return rc; }
     if (cap < 0 || !n_accepted) return fail(h, OCTO_EINVAL, "octo_draws_rejection: cap >= 0 and n_accepted are required");
     if (cap > 0 && (!theta_out || !loglike_out || !logpost_out || !index_out)) return fail(h, OCTO_EINVAL, "octo_draws_rejection: null output with cap > 0");
-    DCHK(h, hipSetDevice(h->device));
+    OCHK(h, hipSetDevice(h->device));
     { int rc = ensure_chunk(h); if (rc) return rc; }
     { int rc = ensure_draw_arrays(h, N); if (rc) return rc; }
     const hipStream_t st = h->stream;
@@ -587,13 +563,13 @@ int32_t octo_draws_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64
         { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, h->d_tt, h->d_lpt); if (rc) return rc; }
         { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, h->d_tt, CHUNK, n, h->d_lp + done, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
         hipLaunchKernelGGL(k_loglike, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, h->d_lp + done, h->d_lpt, n, h->d_ll + done, h->d_pmax + done / TPB);
-        DCHK(h, hipGetLastError());
+        OCHK(h, hipGetLastError());
     }
     hipLaunchKernelGGL(k_max, dim3(1), dim3(TPB), 0, st, h->d_pmax, nblk, h->d_max);
-    DCHK(h, hipGetLastError());
+    OCHK(h, hipGetLastError());
     double mx = 0.0;
-    DCHK(h, hipMemcpyAsync(&mx, h->d_max, sizeof(double), hipMemcpyDeviceToHost, st));
-    DCHK(h, hipStreamSynchronize(st));
+    OCHK(h, hipMemcpyAsync(&mx, h->d_max, sizeof(double), hipMemcpyDeviceToHost, st));
+    OCHK(h, hipStreamSynchronize(st));
     if (max_loglike) *max_loglike = mx;
     *n_accepted = 0;
     if (!std::isfinite(mx))      // sampling.jl:194-197
@@ -604,19 +580,19 @@ int32_t octo_draws_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64
     hipLaunchKernelGGL(k_count, dim3((unsigned)nblk), dim3(TPB), 0, st, h->d_ll, N, h->d_max, seed, first, h->d_cnt);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(TPB), 0, st, h->d_cnt, nblk);
     hipLaunchKernelGGL(k_scatter, dim3((unsigned)nblk), dim3(TPB), 0, st, h->d_ll, h->d_lp, N, h->d_max, seed, first, h->d_cnt, room, h->d_oix, h->d_oll, h->d_olp);
-    DCHK(h, hipGetLastError());
+    OCHK(h, hipGetLastError());
     int64_t total = 0;
-    DCHK(h, hipMemcpyAsync(&total, h->d_cnt + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    DCHK(h, hipStreamSynchronize(st));
+    OCHK(h, hipMemcpyAsync(&total, h->d_cnt + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    OCHK(h, hipStreamSynchronize(st));
     *n_accepted = total;
     const int64_t ns = std::min(total, room);
     if (ns == 0) return OCTO_OK;
     { int rc = launch_draw(h, st, seed, 0, h->d_oix, ns, ns, h->d_oth, nullptr, nullptr); if (rc) return rc; }
-    DCHK(h, hipMemcpyAsync(index_out, h->d_oix, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
-    DCHK(h, hipMemcpyAsync(loglike_out, h->d_oll, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
-    DCHK(h, hipMemcpyAsync(logpost_out, h->d_olp, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
-    DCHK(h, hipMemcpy2DAsync(theta_out, sizeof(double) * cap, h->d_oth, sizeof(double) * ns, sizeof(double) * ns, h->D, hipMemcpyDeviceToHost, st));
-    DCHK(h, hipStreamSynchronize(st));
+    OCHK(h, hipMemcpyAsync(index_out, h->d_oix, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(loglike_out, h->d_oll, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(logpost_out, h->d_olp, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpy2DAsync(theta_out, sizeof(double) * cap, h->d_oth, sizeof(double) * ns, sizeof(double) * ns, h->D, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipStreamSynchronize(st));
     return OCTO_OK;
 }
 

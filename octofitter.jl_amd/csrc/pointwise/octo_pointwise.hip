@@ -3,9 +3,10 @@
 // Of the main library's sources it INCLUDES the device routines the likelihood kernels run — setup_planet_vals / setup_valid (orbit
 // constructors and validity, octo_kernels.h), load_pc / set_starter / the cold kepler_solve / atan2_fast / rem_2pi_trunc / rcp_nr / rsqrt_nr
 // (octo_device.h), sincos_reduced — so a row is scored from the constants the likelihood was made from. It calls one symbol of the main
-// library, octo_consts_default. Restated here because it is a host function of octo_api.hip, not reachable by inclusion: dev_consts
-// (octo_consts -> DevConsts). The DENSITY is written here: astrom_row / rv_row (octo_kernels.h) only accumulate Σ rᵀΣ⁻¹r and Π|Σ|
-// over a table's rows; row_density() below follows their rules term by term and closes each row with its own −log 2π − ½ log|Σ|.
+// library, octo_consts_default. What it shares with the model-value library (walker_setup, planet_prims, wave_sum, dev_consts) is in
+// companion/octo_companion_device.h, the host scaffold of every companion in companion/octo_companion_host.h. The DENSITY is written
+// here: astrom_row / rv_row (octo_kernels.h) only accumulate Σ rᵀΣ⁻¹r and Π|Σ| over a table's rows; row_density() below follows their
+// rules term by term and closes each row with its own −log 2π − ½ log|Σ|.
 //
 //   k_pointwise<P, SUM>      lane = walker, block = 256 walkers × one chunk of 32 rows of ONE table. Prologue: the orbit constructors of the
 //                            block's walkers (constants in registers), the table's three nuisances and each planet's coefficient in the
@@ -30,7 +31,8 @@
 #include <string>
 #include <vector>
 
-#include "octo_kernels.h"
+#include "octo_companion_device.h"
+#include "octo_companion_host.h"
 #include "octofitter_hip_pointwise.h"
 
 namespace {
@@ -40,7 +42,6 @@ constexpr int TPB = 256;               // lanes per block of the templated kerne
 constexpr int RPB = 32;                // rows per block: the summary kernels hold a chunk's values in LDS (RPB × 256 doubles = 64 KB); the prologue's ~350 FP64 instructions per planet are < 10 % of the chunk's
 constexpr int NSTAT = OCTO_POINTWISE_N_STATS;
 constexpr int ROW_N = 8;               // doubles per row record (64 bytes: one line of the scalar cache)
-constexpr int NEED_AST = 1, NEED_RV = 2;
 constexpr int FLAG_COR = 1, FLAG_BASIS = 2;
 
 // rows [r0, r1) of one table: what a block's blockIdx.y selects. Wave-uniform: read by scalar loads.
@@ -110,22 +111,6 @@ struct LdsSys {
     __device__ __forceinline__ double mu(int p) const { return wc[(p * NWC + WC_MU) * WAVE]; }
     __device__ __forceinline__ double K(int p) const { return wc[(p * NWC + WC_K) * WAVE]; }
 };
-
-// The three primitives of one planet at epoch t, the arithmetic of astrom_row / rv_row (octo_kernels.h) on the cold solve:
-//   raoff = cB·cosE + cG·β·sinE − cB·e, decoff likewise; V = cos(ν + ω) + e·cos ω, radvel = K·V.
-__device__ __forceinline__ void planet_prims(const PC& pc, double t, int need, double& ra, double& de, double& V) {
-    const KSol s = kepler_solve<2, false>(t, pc);
-    ra = 0.0; de = 0.0; V = 0.0;
-    if (need & NEED_AST) {
-        ra = fma(pc.cB, s.cE, fma(pc.cGb, s.sE, -pc.cBe));
-        de = fma(pc.cA, s.cE, fma(pc.cFb, s.sE, -pc.cAe));
-    }
-    if (need & NEED_RV) {
-        const double cnu = (s.cE - pc.e) * s.invD;
-        const double snu = pc.beta * s.sE * s.invD;
-        V = fma(cnu + pc.e, pc.cw, -(snu * pc.sw));
-    }
-}
 
 __host__ __device__ __forceinline__ bool is_astrom_kind(int kind) { return kind == OCTO_ASTROM_RADEC || kind == OCTO_ASTROM_SEPPA; }
 
@@ -234,18 +219,6 @@ __device__ __forceinline__ double row_density(const TabCoef& co, int kind, int f
     return fma(-0.5, q, fma(-0.5, log(det), -LOG2PI));
 }
 
-// the orbit constructor of (walker wl, planet p): constants into v[NWC], validity returned — setup_planet_vals<true>, what k_setup runs
-__device__ __forceinline__ bool walker_setup(const PwArgs& a, int p, int64_t wl, double (&v)[NWC]) {
-    const double* el = a.elems + (int64_t)p * OCTO_N_EL * a.ld + wl;
-    double elv[OCTO_N_EL];
-#pragma unroll
-    for (int k = 0; k < OCTO_N_EL; ++k) elv[k] = el[(int64_t)k * a.ld];
-    const SetupOut so = setup_planet_vals<true>(elv, a.c, a.orbit_kind[p], a.has_mass[p]);
-#pragma unroll
-    for (int k = 0; k < NWC; ++k) v[k] = so.v[k];
-    return so.ok;
-}
-
 // ---- the reduction over the walkers ------------------------------------------------------------------------------------------------------
 struct PStat { double n, mx, s1, mn, s2, mean, m2; };      // s1 = Σ exp(ll − mx), s2 = Σ exp(mn − ll)
 
@@ -264,12 +237,6 @@ __device__ __forceinline__ void stat_merge(PStat& s, const PStat& b) {
     s.mean = fma(d, wb, s.mean);
     s.m2 = s.m2 + b.m2 + d * d * (s.n * wb);
     s.n = nt;
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int m = WAVE / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, WAVE);      // x_i + x_{i^m} on both partners: every lane ends with the same bits
-    return x;
 }
 
 // the wave's 64 values: every lane ends with the same seven numbers
@@ -467,67 +434,26 @@ __global__ __launch_bounds__(TPB) void k_pointwise_merge(const double* __restric
     out[OCTO_POINTWISE_MAX * R + r] = none ? NAN : s.mx;
 }
 
-thread_local std::string g_create_error;
-
 }  // namespace
 
-struct octo_pointwise {
-    int device = 0, P = 0, n_obs = 0;
+struct octo_pointwise : CompanionStaged {
+    int P = 0, n_obs = 0;
     int64_t R = 0;
     int32_t n_chunks = 0;
-    hipStream_t stream = nullptr;
     PwArgs base;                            // everything of a launch that the handle fixes
     std::vector<int32_t> row_table;
     double* d_rows = nullptr;
     RowChunk* d_chunks = nullptr;
     // summary: block partials (grown on demand)
     double* d_part = nullptr; int64_t cap_part = 0;
-    // host-buffer calls: inputs, matrix chunk, summary result, pinned staging (grown on demand)
+    // host-buffer calls: inputs, matrix chunk, summary result (grown on demand)
     double* d_in = nullptr; int64_t cap_in = 0;
     double* d_mat = nullptr; int64_t cap_mat = 0;
     double* d_sum = nullptr;
-    double* h_stage = nullptr; int64_t cap_stage = 0;
-    int64_t mat_bytes = (int64_t)64 << 20, stage_bytes = (int64_t)16 << 20;
-    std::string err;
+    int64_t mat_bytes = (int64_t)64 << 20;
 };
 
 namespace {
-
-int fail(octo_pointwise* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_create_error = msg;
-    return code;
-}
-
-#define PCHK(h, expr)                                                                                                   \
-    do {                                                                                                                \
-        const hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return fail(h, e_ == hipErrorOutOfMemory ? OCTO_ENOMEM : OCTO_EHIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-// octo_api.hip: dev_consts (a host function of the main library's C ABI translation unit; see the head of this file)
-DevConsts dev_consts(const octo_consts& c) {
-    DevConsts d;
-    d.k_yr = c.kepler_year_to_julian_day; d.yd = c.year2day_julian; d.au2m = c.au2m; d.sec2yr = c.sec2year_julian;
-    d.mas_per_au_per_plx = c.rad2as / c.pc2au;      // cart2angle = plx · rad2as/pc2au   (parameterizations.jl:215-216)
-    d.mjup2msol = c.mjup2msol;
-    return d;
-}
-
-int grow(octo_pointwise* h, double*& p, int64_t& cap, int64_t need) {
-    if (need <= cap) return OCTO_OK;
-    PCHK(h, hipStreamSynchronize(h->stream));
-    if (p) { PCHK(h, hipFree(p)); p = nullptr; cap = 0; }
-    PCHK(h, hipMalloc((void**)&p, sizeof(double) * (size_t)need));
-    cap = need;
-    return OCTO_OK;
-}
-
-int64_t env_bytes(const char* name, int64_t dflt) {
-    const char* s = std::getenv(name);
-    if (!s || !*s) return dflt;
-    const long long v = std::atoll(s);
-    return v > 0 ? (int64_t)v : dflt;
-}
 
 int check_batch(octo_pointwise* h, const char* who, const void* elems, const void* out, int64_t ld, int64_t W, int64_t w_min) {
     if (W < w_min || ld < W) return fail(h, OCTO_EINVAL, std::string(who) + ": need " + std::to_string(w_min) + " <= W <= ld");
@@ -666,18 +592,13 @@ static int32_t pointwise_create(int32_t device_id, const octo_consts* consts, co
         r_at += d.n_epochs;
     }
 
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { (void)hipGetLastError(); return fail(nullptr, OCTO_ENODEV, fn + "no HIP device"); }
-    if (device_id < 0 || device_id >= n_dev) return fail(nullptr, OCTO_EINVAL, fn + "device_id out of range");
-    octo_pointwise* h = new (std::nothrow) octo_pointwise();
-    if (!h) return fail(nullptr, OCTO_ENOMEM, fn + "host allocation failed");
-    h->device = device_id; h->P = n_planets; h->n_obs = n_obs; h->R = R; h->n_chunks = (int32_t)chunks.size();
+    octo_pointwise* h;
+    { int rc = open_device(device_id, fn, h); if (rc) return rc; }
+    h->P = n_planets; h->n_obs = n_obs; h->R = R; h->n_chunks = (int32_t)chunks.size();
     h->row_table = std::move(row_table);
     h->mat_bytes = env_bytes("OCTO_POINTWISE_MATRIX_BYTES", h->mat_bytes);
     h->stage_bytes = env_bytes("OCTO_POINTWISE_STAGE_BYTES", h->stage_bytes);
     auto bail = [&](int code, const std::string& msg) { octo_pointwise_destroy(h); return fail(nullptr, code, msg); };
-    if (hipSetDevice(device_id) != hipSuccess) return bail(OCTO_EHIP, fn + "hipSetDevice failed");
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(OCTO_EHIP, fn + "stream creation failed");
     const size_t n_ch = std::max<size_t>(chunks.size(), 1);
     if (hipMalloc((void**)&h->d_rows, sizeof(double) * rows.size()) != hipSuccess || hipMalloc((void**)&h->d_chunks, sizeof(RowChunk) * n_ch) != hipSuccess ||
         hipMalloc((void**)&h->d_sum, sizeof(double) * NSTAT * (size_t)std::max<int64_t>(R, 1)) != hipSuccess)
@@ -704,14 +625,9 @@ int32_t octo_pointwise_destroy(octo_pointwise* h) {
     return OCTO_OK;
 }
 
-const char* octo_pointwise_last_error(const octo_pointwise* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* octo_pointwise_last_error(const octo_pointwise* h) { return last_error(h); }
 
-int32_t octo_pointwise_sync(octo_pointwise* h) {
-    if (!h) return OCTO_EINVAL;
-    PCHK(h, hipSetDevice(h->device));
-    PCHK(h, hipStreamSynchronize(h->stream));
-    return OCTO_OK;
-}
+int32_t octo_pointwise_sync(octo_pointwise* h) { return sync_handle(h); }
 
 int64_t octo_pointwise_n_rows(const octo_pointwise* h) { return h ? h->R : -1; }
 
@@ -728,12 +644,12 @@ int32_t octo_pointwise_eval_device(octo_pointwise* h, const double* d_elems, int
     { int rc = check_batch(h, "octo_pointwise_eval_device", d_elems, d_out, ld, W, 0); if (rc) return rc; }
     if (ld_out < W) return fail(h, OCTO_EINVAL, "octo_pointwise_eval_device: need W <= ld_out");
     if (W == 0 || h->R == 0) return OCTO_OK;
-    PCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = hip_stream == OCTO_STREAM_CTX ? h->stream : (hipStream_t)hip_stream;
+    OCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream_of(h, hip_stream);
     PwArgs a = h->base;
     a.elems = d_elems; a.nuis = d_nuis; a.ld = ld; a.W = W; a.out = d_out; a.ld_out = ld_out;
     launch_rows<false>(h, a, st);
-    PCHK(h, hipGetLastError());
+    OCHK(h, hipGetLastError());
     return OCTO_OK;
 }
 
@@ -742,15 +658,15 @@ int32_t octo_pointwise_summary_device(octo_pointwise* h, const double* d_elems, 
     if (!h) return OCTO_EINVAL;
     { int rc = check_batch(h, "octo_pointwise_summary_device", d_elems, d_out, ld, W, 1); if (rc) return rc; }
     if (h->R == 0) return OCTO_OK;
-    PCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = hip_stream == OCTO_STREAM_CTX ? h->stream : (hipStream_t)hip_stream;
+    OCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream_of(h, hip_stream);
     const int64_t tiles = summary_tiles(h, W);
     { int rc = grow(h, h->d_part, h->cap_part, tiles * NSTAT * h->R); if (rc) return rc; }
     PwArgs a = h->base;
     a.elems = d_elems; a.nuis = d_nuis; a.ld = ld; a.W = W; a.out = h->d_part; a.ld_out = 0;
     launch_rows<true>(h, a, st);
     hipLaunchKernelGGL(k_pointwise_merge, dim3((unsigned)((h->R + TPB - 1) / TPB)), dim3(TPB), 0, st, (const double*)h->d_part, tiles, h->R, d_out);
-    PCHK(h, hipGetLastError());
+    OCHK(h, hipGetLastError());
     return OCTO_OK;
 }
 
@@ -759,10 +675,10 @@ static int upload_inputs(octo_pointwise* h, const double* elems, int64_t ld, int
     const int64_t n_el = (int64_t)h->P * OCTO_N_EL, n_nu = (int64_t)h->n_obs * OCTO_N_NUIS;
     { int rc = grow(h, h->d_in, h->cap_in, (n_el + n_nu) * W); if (rc) return rc; }
     double* p = h->d_in;
-    PCHK(h, hipMemcpy2DAsync(p, sizeof(double) * W, elems, sizeof(double) * ld, sizeof(double) * W, n_el, hipMemcpyHostToDevice, h->stream));
+    OCHK(h, hipMemcpy2DAsync(p, sizeof(double) * W, elems, sizeof(double) * ld, sizeof(double) * W, n_el, hipMemcpyHostToDevice, h->stream));
     *d_elems = p; p += n_el * W;
     *d_nuis = nullptr;
-    if (nuis && n_nu > 0) { PCHK(h, hipMemcpy2DAsync(p, sizeof(double) * W, nuis, sizeof(double) * ld, sizeof(double) * W, n_nu, hipMemcpyHostToDevice, h->stream)); *d_nuis = p; }
+    if (nuis && n_nu > 0) { OCHK(h, hipMemcpy2DAsync(p, sizeof(double) * W, nuis, sizeof(double) * ld, sizeof(double) * W, n_nu, hipMemcpyHostToDevice, h->stream)); *d_nuis = p; }
     return OCTO_OK;
 }
 
@@ -771,7 +687,7 @@ int32_t octo_pointwise_eval(octo_pointwise* h, const double* elems, int64_t ld, 
     { int rc = check_batch(h, "octo_pointwise_eval", elems, out, ld, W, 0); if (rc) return rc; }
     if (ld_out < W) return fail(h, OCTO_EINVAL, "octo_pointwise_eval: need W <= ld_out");
     if (W == 0 || h->R == 0) return OCTO_OK;
-    PCHK(h, hipSetDevice(h->device));
+    OCHK(h, hipSetDevice(h->device));
     const double *d_elems, *d_nuis;
     { int rc = upload_inputs(h, elems, ld, W, nuis, &d_elems, &d_nuis); if (rc) return rc; }
     const int64_t rows = h->R;
@@ -779,20 +695,15 @@ int32_t octo_pointwise_eval(octo_pointwise* h, const double* elems, int64_t ld, 
     int64_t Wc = std::min(h->mat_bytes / (int64_t)(sizeof(double) * rows), h->stage_bytes / (int64_t)sizeof(double));
     Wc = std::max<int64_t>(std::min(Wc, W), 1);
     { int rc = grow(h, h->d_mat, h->cap_mat, rows * Wc); if (rc) return rc; }
-    const int64_t want_stage = std::max<int64_t>(h->stage_bytes / (int64_t)sizeof(double), 1);
-    if (h->cap_stage < want_stage) {
-        if (h->h_stage) { PCHK(h, hipHostFree(h->h_stage)); h->h_stage = nullptr; h->cap_stage = 0; }
-        PCHK(h, hipHostMalloc((void**)&h->h_stage, sizeof(double) * (size_t)want_stage, hipHostMallocDefault));
-        h->cap_stage = want_stage;
-    }
+    { int rc = ensure_stage(h, std::max<int64_t>(h->stage_bytes / (int64_t)sizeof(double), 1)); if (rc) return rc; }
     for (int64_t w0 = 0; w0 < W; w0 += Wc) {
         const int64_t n = std::min(Wc, W - w0);
         { int rc = octo_pointwise_eval_device(h, d_elems + w0, W, n, d_nuis ? d_nuis + w0 : nullptr, h->d_mat, Wc, OCTO_STREAM_CTX); if (rc) return rc; }
         const int64_t rps = std::max<int64_t>(h->cap_stage / n, 1);      // rows per staging pass
         for (int64_t r0 = 0; r0 < rows; r0 += rps) {
             const int64_t nr = std::min(rps, rows - r0);
-            PCHK(h, hipMemcpy2DAsync(h->h_stage, sizeof(double) * n, h->d_mat + r0 * Wc, sizeof(double) * Wc, sizeof(double) * n, nr, hipMemcpyDeviceToHost, h->stream));
-            PCHK(h, hipStreamSynchronize(h->stream));
+            OCHK(h, hipMemcpy2DAsync(h->h_stage, sizeof(double) * n, h->d_mat + r0 * Wc, sizeof(double) * Wc, sizeof(double) * n, nr, hipMemcpyDeviceToHost, h->stream));
+            OCHK(h, hipStreamSynchronize(h->stream));
             for (int64_t r = 0; r < nr; ++r) std::memcpy(out + (r0 + r) * ld_out + w0, h->h_stage + r * n, sizeof(double) * n);
         }
     }
@@ -803,12 +714,12 @@ int32_t octo_pointwise_summary(octo_pointwise* h, const double* elems, int64_t l
     if (!h) return OCTO_EINVAL;
     { int rc = check_batch(h, "octo_pointwise_summary", elems, out, ld, W, 1); if (rc) return rc; }
     if (h->R == 0) return OCTO_OK;
-    PCHK(h, hipSetDevice(h->device));
+    OCHK(h, hipSetDevice(h->device));
     const double *d_elems, *d_nuis;
     { int rc = upload_inputs(h, elems, ld, W, nuis, &d_elems, &d_nuis); if (rc) return rc; }
     { int rc = octo_pointwise_summary_device(h, d_elems, W, W, d_nuis, h->d_sum, OCTO_STREAM_CTX); if (rc) return rc; }
-    PCHK(h, hipMemcpyAsync(out, h->d_sum, sizeof(double) * NSTAT * h->R, hipMemcpyDeviceToHost, h->stream));
-    PCHK(h, hipStreamSynchronize(h->stream));
+    OCHK(h, hipMemcpyAsync(out, h->d_sum, sizeof(double) * NSTAT * h->R, hipMemcpyDeviceToHost, h->stream));
+    OCHK(h, hipStreamSynchronize(h->stream));
     return OCTO_OK;
 }
 

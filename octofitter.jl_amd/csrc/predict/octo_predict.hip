@@ -2,8 +2,8 @@
 // Of the main library's sources it INCLUDES the device routines the likelihood kernels run — setup_planet_vals / setup_valid (orbit
 // constructors and validity, octo_kernels.h), load_pc / set_starter / the cold kepler_solve / atan2_fast (octo_device.h), sqrt_fast — so a
 // prediction is made from the constants the likelihood was made from. It calls one symbol of the main library, octo_consts_default.
-// Restated here because it is a host function of octo_api.hip, not reachable by inclusion: dev_consts (octo_consts -> DevConsts, five
-// assignments and one quotient); tests/test_predict.py pins it to the oracle through every offset and velocity.
+// What it shares with the pointwise library (walker_setup, planet_prims, wave_sum, dev_consts) is in companion/octo_companion_device.h, the
+// host scaffold of every companion (handle base, fail, OCHK, open_device, grow, ensure_stage) in companion/octo_companion_host.h.
 //
 //   k_predict_cube<P, WPL>   lane = walker (WPL adjacent walkers per lane), block = 256 lanes × one chunk of epochs. Prologue: the orbit
 //                            constructors of the block's walkers, constants in registers. Epoch loop: the epoch (and basis) are wave-uniform
@@ -24,7 +24,8 @@
 #include <string>
 #include <vector>
 
-#include "octo_kernels.h"
+#include "octo_companion_device.h"
+#include "octo_companion_host.h"
 #include "octofitter_hip_predict.h"
 
 namespace {
@@ -34,7 +35,6 @@ constexpr int TPB = 256;               // lanes per block of the templated kerne
 constexpr int EPB = 32;                // epochs per block (at least): the prologue's ~350 FP64 instructions per planet are < 10 % of the chunk's
 constexpr int MAXC = OCTO_PREDICT_MAX_CHANNELS;
 constexpr int NSTAT = 5;               // n_valid, mean, sd | M2, min, max
-constexpr int NEED_AST = 1, NEED_RV = 2;
 
 struct Chan8 { int8_t q, p; };
 
@@ -80,22 +80,6 @@ struct LdsSys {
     __device__ __forceinline__ double de(int p) const { return prim[(p * LDS_PRIM + 1) * WAVE]; }
     __device__ __forceinline__ double V(int p) const { return prim[(p * LDS_PRIM + 2) * WAVE]; }
 };
-
-// The three primitives of one planet at epoch t, the arithmetic of astrom_row / rv_row (octo_kernels.h) on the cold solve:
-//   raoff = cB·cosE + cG·β·sinE − cB·e, decoff likewise; V = cos(ν + ω) + e·cos ω, radvel = K·V.
-__device__ __forceinline__ void planet_prims(const PC& pc, double t, int need, double& ra, double& de, double& V) {
-    const KSol s = kepler_solve<2, false>(t, pc);
-    ra = 0.0; de = 0.0; V = 0.0;
-    if (need & NEED_AST) {
-        ra = fma(pc.cB, s.cE, fma(pc.cGb, s.sE, -pc.cBe));
-        de = fma(pc.cA, s.cE, fma(pc.cFb, s.sE, -pc.cAe));
-    }
-    if (need & NEED_RV) {
-        const double cnu = (s.cE - pc.e) * s.invD;
-        const double snu = pc.beta * s.sE * s.invD;
-        V = fma(cnu + pc.e, pc.cw, -(snu * pc.sw));
-    }
-}
 
 // THE value of channel (q, pl) from a system's primitives: every entry point's numbers come from this routine.
 //   RV quantities: rv_row's model — fma(add1, basis, add0), then one fma(g_p·K_p, V_p, ·) per planet in planet order, g_p = 1 for the channel's
@@ -143,18 +127,6 @@ __device__ __forceinline__ void channel_add(const PredictArgs& a, int c, int q, 
         if (a.add0) add0 = a.add0[(int64_t)c * a.ld + wl];
         if (a.add1 && a.basis) add1 = a.add1[(int64_t)c * a.ld + wl];
     }
-}
-
-// the orbit constructor of (walker wl, planet p): constants into v[NWC], validity returned — setup_planet_vals<true>, what k_setup runs
-__device__ __forceinline__ bool walker_setup(const PredictArgs& a, int p, int64_t wl, double (&v)[NWC]) {
-    const double* el = a.elems + (int64_t)p * OCTO_N_EL * a.ld + wl;
-    double elv[OCTO_N_EL];
-#pragma unroll
-    for (int k = 0; k < OCTO_N_EL; ++k) elv[k] = el[(int64_t)k * a.ld];
-    const SetupOut so = setup_planet_vals<true>(elv, a.c, a.orbit_kind[p], a.has_mass[p]);
-#pragma unroll
-    for (int k = 0; k < NWC; ++k) v[k] = so.v[k];
-    return so.ok;
 }
 
 template <int P, int WPL>
@@ -276,12 +248,6 @@ __device__ __forceinline__ void stat_merge(Stat& s, const Stat& b) {
     s.mn = fmin(s.mn, b.mn); s.mx = fmax(s.mx, b.mx);
 }
 
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int m = WAVE / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, WAVE);      // x_i + x_{i^m} on both partners: every lane ends with the same bits
-    return x;
-}
-
 // the wave's 64 values, exactly: two passes over registers
 __device__ __forceinline__ Stat wave_stat(double x, bool valid) {
     Stat s;
@@ -382,64 +348,23 @@ __global__ __launch_bounds__(TPB) void k_predict_merge(const double* __restrict_
     out[4 * CT + k] = none ? NAN : s.mx;
 }
 
-thread_local std::string g_create_error;
-
 }  // namespace
 
-struct octo_predict {
-    int device = 0, P = 0, C = 0, need = 0, variant = 0;
+struct octo_predict : CompanionStaged {
+    int P = 0, C = 0, need = 0, variant = 0;
     int64_t T = 0;
-    hipStream_t stream = nullptr;
     PredictArgs base;                       // everything of a launch that the handle fixes
     double *d_epochs = nullptr, *d_basis = nullptr;
     // summary: block partials (grown on demand)
     double* d_part = nullptr; int64_t cap_part = 0;
-    // host-buffer calls: inputs, cube chunk, summary result, pinned staging (grown on demand)
+    // host-buffer calls: inputs, cube chunk, summary result (grown on demand)
     double* d_in = nullptr; int64_t cap_in = 0;
     double* d_cube = nullptr; int64_t cap_cube = 0;
     double* d_sum = nullptr;
-    double* h_stage = nullptr; int64_t cap_stage = 0;
-    int64_t cube_bytes = (int64_t)64 << 20, stage_bytes = (int64_t)16 << 20;
-    std::string err;
+    int64_t cube_bytes = (int64_t)64 << 20;
 };
 
 namespace {
-
-int fail(octo_predict* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_create_error = msg;
-    return code;
-}
-
-#define PCHK(h, expr)                                                                                                   \
-    do {                                                                                                                \
-        const hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return fail(h, e_ == hipErrorOutOfMemory ? OCTO_ENOMEM : OCTO_EHIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-// octo_api.hip: dev_consts (a host function of the main library's C ABI translation unit; see the head of this file)
-DevConsts dev_consts(const octo_consts& c) {
-    DevConsts d;
-    d.k_yr = c.kepler_year_to_julian_day; d.yd = c.year2day_julian; d.au2m = c.au2m; d.sec2yr = c.sec2year_julian;
-    d.mas_per_au_per_plx = c.rad2as / c.pc2au;      // cart2angle = plx · rad2as/pc2au   (parameterizations.jl:215-216)
-    d.mjup2msol = c.mjup2msol;
-    return d;
-}
-
-int grow(octo_predict* h, double*& p, int64_t& cap, int64_t need) {
-    if (need <= cap) return OCTO_OK;
-    PCHK(h, hipStreamSynchronize(h->stream));
-    if (p) { PCHK(h, hipFree(p)); p = nullptr; cap = 0; }
-    PCHK(h, hipMalloc((void**)&p, sizeof(double) * (size_t)need));
-    cap = need;
-    return OCTO_OK;
-}
-
-int64_t env_bytes(const char* name, int64_t dflt) {
-    const char* s = std::getenv(name);
-    if (!s || !*s) return dflt;
-    const long long v = std::atoll(s);
-    return v > 0 ? (int64_t)v : dflt;
-}
 
 int check_batch(octo_predict* h, const char* who, const void* elems, const void* out, int64_t ld, int64_t W, int64_t w_min) {
     if (W < w_min || ld < W) return fail(h, OCTO_EINVAL, std::string(who) + ": need " + std::to_string(w_min) + " <= W <= ld");
@@ -509,17 +434,12 @@ int32_t octo_predict_create(int32_t device_id, const octo_consts* consts, const 
     if (consts) cst = *consts;
     else if (octo_consts_default(&cst) != OCTO_OK) return fail(nullptr, OCTO_EINVAL, "octo_predict_create: octo_consts_default failed");
 
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { (void)hipGetLastError(); return fail(nullptr, OCTO_ENODEV, "octo_predict_create: no HIP device"); }
-    if (device_id < 0 || device_id >= n_dev) return fail(nullptr, OCTO_EINVAL, "octo_predict_create: device_id out of range");
-    octo_predict* h = new (std::nothrow) octo_predict();
-    if (!h) return fail(nullptr, OCTO_ENOMEM, "octo_predict_create: host allocation failed");
-    h->device = device_id; h->P = n_planets; h->C = n_channels; h->T = T; h->need = need;
+    octo_predict* h;
+    { int rc = open_device(device_id, "octo_predict_create: ", h); if (rc) return rc; }
+    h->P = n_planets; h->C = n_channels; h->T = T; h->need = need;
     h->cube_bytes = env_bytes("OCTO_PREDICT_CUBE_BYTES", h->cube_bytes);
     h->stage_bytes = env_bytes("OCTO_PREDICT_STAGE_BYTES", h->stage_bytes);
     auto bail = [&](int code, const char* msg) { octo_predict_destroy(h); return fail(nullptr, code, msg); };
-    if (hipSetDevice(device_id) != hipSuccess) return bail(OCTO_EHIP, "octo_predict_create: hipSetDevice failed");
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(OCTO_EHIP, "octo_predict_create: stream creation failed");
     if (hipMalloc((void**)&h->d_epochs, sizeof(double) * T) != hipSuccess || (basis && hipMalloc((void**)&h->d_basis, sizeof(double) * T) != hipSuccess) ||
         hipMalloc((void**)&h->d_sum, sizeof(double) * NSTAT * n_channels * T) != hipSuccess)
         return bail(OCTO_ENOMEM, "octo_predict_create: hipMalloc failed");
@@ -546,14 +466,9 @@ int32_t octo_predict_destroy(octo_predict* h) {
     return OCTO_OK;
 }
 
-const char* octo_predict_last_error(const octo_predict* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* octo_predict_last_error(const octo_predict* h) { return last_error(h); }
 
-int32_t octo_predict_sync(octo_predict* h) {
-    if (!h) return OCTO_EINVAL;
-    PCHK(h, hipSetDevice(h->device));
-    PCHK(h, hipStreamSynchronize(h->stream));
-    return OCTO_OK;
-}
+int32_t octo_predict_sync(octo_predict* h) { return sync_handle(h); }
 
 int32_t octo_predict_set_variant(octo_predict* h, int32_t variant) {
     if (!h) return OCTO_EINVAL;
@@ -568,8 +483,8 @@ int32_t octo_predict_eval_device(octo_predict* h, const double* d_elems, int64_t
     { int rc = check_batch(h, "octo_predict_eval_device", d_elems, d_out, ld, W, 0); if (rc) return rc; }
     if (ld_out < W) return fail(h, OCTO_EINVAL, "octo_predict_eval_device: need W <= ld_out");
     if (W == 0) return OCTO_OK;
-    PCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = hip_stream == OCTO_STREAM_CTX ? h->stream : (hipStream_t)hip_stream;
+    OCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream_of(h, hip_stream);
     PredictArgs a = h->base;
     a.elems = d_elems; a.add0 = d_add0; a.add1 = d_add1; a.ld = ld; a.W = W; a.out = d_out; a.ld_out = ld_out;
     if (h->P > MAXP_T) {
@@ -580,7 +495,7 @@ int32_t octo_predict_eval_device(octo_predict* h, const double* d_elems, int64_t
         const bool wide = can_wide && (h->variant == 2 || (h->variant == 0 && h->P == 1));
         launch_cube(a, st, wide);
     }
-    PCHK(h, hipGetLastError());
+    OCHK(h, hipGetLastError());
     return OCTO_OK;
 }
 
@@ -588,8 +503,8 @@ int32_t octo_predict_summary_device(octo_predict* h, const double* d_elems, int6
                                     double* d_out, void* hip_stream) {
     if (!h) return OCTO_EINVAL;
     { int rc = check_batch(h, "octo_predict_summary_device", d_elems, d_out, ld, W, 1); if (rc) return rc; }
-    PCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = hip_stream == OCTO_STREAM_CTX ? h->stream : (hipStream_t)hip_stream;
+    OCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream_of(h, hip_stream);
     const int64_t tiles = summary_tiles(h, W), CT = (int64_t)h->C * h->T;
     { int rc = grow(h, h->d_part, h->cap_part, tiles * NSTAT * CT); if (rc) return rc; }
     PredictArgs a = h->base;
@@ -603,7 +518,7 @@ int32_t octo_predict_summary_device(octo_predict* h, const double* d_elems, int6
     default: hipLaunchKernelGGL(k_predict_part_n, grid, dim3(WAVE), 0, st, a); break;
     }
     hipLaunchKernelGGL(k_predict_merge, dim3((unsigned)((CT + TPB - 1) / TPB)), dim3(TPB), 0, st, (const double*)h->d_part, tiles, CT, d_out);
-    PCHK(h, hipGetLastError());
+    OCHK(h, hipGetLastError());
     return OCTO_OK;
 }
 
@@ -613,12 +528,12 @@ static int upload_inputs(octo_predict* h, const double* elems, int64_t ld, int64
     const int64_t n_el = (int64_t)h->P * OCTO_N_EL, Wp = W + (W & 1);      // an even leading dimension: every row starts 16-byte aligned
     { int rc = grow(h, h->d_in, h->cap_in, (n_el + 2 * h->C) * Wp); if (rc) return rc; }
     double* p = h->d_in;
-    PCHK(h, hipMemcpy2DAsync(p, sizeof(double) * Wp, elems, sizeof(double) * ld, sizeof(double) * W, n_el, hipMemcpyHostToDevice, h->stream));
+    OCHK(h, hipMemcpy2DAsync(p, sizeof(double) * Wp, elems, sizeof(double) * ld, sizeof(double) * W, n_el, hipMemcpyHostToDevice, h->stream));
     *d_elems = p; p += n_el * Wp;
     *d_add0 = nullptr; *d_add1 = nullptr;
-    if (add0) { PCHK(h, hipMemcpy2DAsync(p, sizeof(double) * Wp, add0, sizeof(double) * ld, sizeof(double) * W, h->C, hipMemcpyHostToDevice, h->stream)); *d_add0 = p; }
+    if (add0) { OCHK(h, hipMemcpy2DAsync(p, sizeof(double) * Wp, add0, sizeof(double) * ld, sizeof(double) * W, h->C, hipMemcpyHostToDevice, h->stream)); *d_add0 = p; }
     p += (int64_t)h->C * Wp;
-    if (add1) { PCHK(h, hipMemcpy2DAsync(p, sizeof(double) * Wp, add1, sizeof(double) * ld, sizeof(double) * W, h->C, hipMemcpyHostToDevice, h->stream)); *d_add1 = p; }
+    if (add1) { OCHK(h, hipMemcpy2DAsync(p, sizeof(double) * Wp, add1, sizeof(double) * ld, sizeof(double) * W, h->C, hipMemcpyHostToDevice, h->stream)); *d_add1 = p; }
     return OCTO_OK;
 }
 
@@ -627,7 +542,7 @@ int32_t octo_predict_eval(octo_predict* h, const double* elems, int64_t ld, int6
     { int rc = check_batch(h, "octo_predict_eval", elems, out, ld, W, 0); if (rc) return rc; }
     if (ld_out < W) return fail(h, OCTO_EINVAL, "octo_predict_eval: need W <= ld_out");
     if (W == 0) return OCTO_OK;
-    PCHK(h, hipSetDevice(h->device));
+    OCHK(h, hipSetDevice(h->device));
     const double *d_elems, *d_add0, *d_add1;
     { int rc = upload_inputs(h, elems, ld, W, add0, add1, &d_elems, &d_add0, &d_add1); if (rc) return rc; }
     const int64_t Wp = W + (W & 1), rows = (int64_t)h->C * h->T;
@@ -637,19 +552,15 @@ int32_t octo_predict_eval(octo_predict* h, const double* elems, int64_t ld, int6
     if (Wc >= 2) Wc &= ~(int64_t)1;
     const int64_t ldc = Wc + (Wc & 1);
     { int rc = grow(h, h->d_cube, h->cap_cube, rows * ldc); if (rc) return rc; }
-    if (h->cap_stage < h->stage_bytes / (int64_t)sizeof(double)) {
-        if (h->h_stage) { PCHK(h, hipHostFree(h->h_stage)); h->h_stage = nullptr; h->cap_stage = 0; }
-        PCHK(h, hipHostMalloc((void**)&h->h_stage, (size_t)h->stage_bytes, hipHostMallocDefault));
-        h->cap_stage = h->stage_bytes / (int64_t)sizeof(double);
-    }
+    { int rc = ensure_stage(h, h->stage_bytes / (int64_t)sizeof(double)); if (rc) return rc; }
     for (int64_t w0 = 0; w0 < W; w0 += Wc) {
         const int64_t n = std::min(Wc, W - w0);
         { int rc = octo_predict_eval_device(h, d_elems + w0, Wp, n, d_add0 ? d_add0 + w0 : nullptr, d_add1 ? d_add1 + w0 : nullptr, h->d_cube, ldc, OCTO_STREAM_CTX); if (rc) return rc; }
         const int64_t rps = std::max<int64_t>(h->cap_stage / n, 1);      // rows per staging pass
         for (int64_t r0 = 0; r0 < rows; r0 += rps) {
             const int64_t nr = std::min(rps, rows - r0);
-            PCHK(h, hipMemcpy2DAsync(h->h_stage, sizeof(double) * n, h->d_cube + r0 * ldc, sizeof(double) * ldc, sizeof(double) * n, nr, hipMemcpyDeviceToHost, h->stream));
-            PCHK(h, hipStreamSynchronize(h->stream));
+            OCHK(h, hipMemcpy2DAsync(h->h_stage, sizeof(double) * n, h->d_cube + r0 * ldc, sizeof(double) * ldc, sizeof(double) * n, nr, hipMemcpyDeviceToHost, h->stream));
+            OCHK(h, hipStreamSynchronize(h->stream));
             for (int64_t r = 0; r < nr; ++r) std::memcpy(out + (r0 + r) * ld_out + w0, h->h_stage + r * n, sizeof(double) * n);
         }
     }
@@ -659,12 +570,12 @@ int32_t octo_predict_eval(octo_predict* h, const double* elems, int64_t ld, int6
 int32_t octo_predict_summary(octo_predict* h, const double* elems, int64_t ld, int64_t W, const double* add0, const double* add1, double* out) {
     if (!h) return OCTO_EINVAL;
     { int rc = check_batch(h, "octo_predict_summary", elems, out, ld, W, 1); if (rc) return rc; }
-    PCHK(h, hipSetDevice(h->device));
+    OCHK(h, hipSetDevice(h->device));
     const double *d_elems, *d_add0, *d_add1;
     { int rc = upload_inputs(h, elems, ld, W, add0, add1, &d_elems, &d_add0, &d_add1); if (rc) return rc; }
     { int rc = octo_predict_summary_device(h, d_elems, W + (W & 1), W, d_add0, d_add1, h->d_sum, OCTO_STREAM_CTX); if (rc) return rc; }
-    PCHK(h, hipMemcpyAsync(out, h->d_sum, sizeof(double) * NSTAT * h->C * h->T, hipMemcpyDeviceToHost, h->stream));
-    PCHK(h, hipStreamSynchronize(h->stream));
+    OCHK(h, hipMemcpyAsync(out, h->d_sum, sizeof(double) * NSTAT * h->C * h->T, hipMemcpyDeviceToHost, h->stream));
+    OCHK(h, hipStreamSynchronize(h->stream));
     return OCTO_OK;
 }
 

@@ -23,11 +23,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
 
+#include "octo_companion_host.h"
 #include "octofitter_hip_psis.h"
 
 namespace {
@@ -344,50 +344,17 @@ __global__ __launch_bounds__(TPB) void k_psis(const double* __restrict__ ll, int
     }
 }
 
-thread_local std::string g_create_error;
-
 }  // namespace
 
-struct octo_psis {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    // host-buffer call: matrix chunk, weights chunk, result chunk, pinned staging (grown on demand)
+struct octo_psis : CompanionStaged {
+    // host-buffer call: matrix chunk, weights chunk, result chunk (grown on demand)
     double* d_mat = nullptr; int64_t cap_mat = 0;
     double* d_lw = nullptr; int64_t cap_lw = 0;
     double* d_out = nullptr; int64_t cap_out = 0;
-    double* h_stage = nullptr; int64_t cap_stage = 0;
-    int64_t mat_bytes = (int64_t)64 << 20, stage_bytes = (int64_t)16 << 20;
-    std::string err;
+    int64_t mat_bytes = (int64_t)64 << 20;
 };
 
 namespace {
-
-int fail(octo_psis* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_create_error = msg;
-    return code;
-}
-
-#define SCHK(h, expr)                                                                                                   \
-    do {                                                                                                                \
-        const hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return fail(h, e_ == hipErrorOutOfMemory ? OCTO_ENOMEM : OCTO_EHIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-int grow(octo_psis* h, double*& p, int64_t& cap, int64_t need) {
-    if (need <= cap) return OCTO_OK;
-    SCHK(h, hipStreamSynchronize(h->stream));
-    if (p) { SCHK(h, hipFree(p)); p = nullptr; cap = 0; }
-    SCHK(h, hipMalloc((void**)&p, sizeof(double) * (size_t)need));
-    cap = need;
-    return OCTO_OK;
-}
-
-int64_t env_bytes(const char* name, int64_t dflt) {
-    const char* s = std::getenv(name);
-    if (!s || !*s) return dflt;
-    const long long v = std::atoll(s);
-    return v > 0 ? (int64_t)v : dflt;
-}
 
 int check_args(octo_psis* h, const char* who, const void* ll, int64_t ld, int64_t R, int64_t S, const void* out, const void* lw, int64_t ld_w) {
     if (R < 0 || S < 1 || ld < S) return fail(h, OCTO_EINVAL, std::string(who) + ": need R >= 0 and 1 <= S <= ld");
@@ -410,9 +377,9 @@ int staged_rows(octo_psis* h, double* host, int64_t ld_h, double* dev, int64_t n
             const int64_t w = std::min(piece, S - at);
             if (to_device)
                 for (int64_t r = 0; r < k; ++r) std::memcpy(h->h_stage + r * w, host + (r0 + r) * ld_h + at, sizeof(double) * (size_t)w);
-            if (w == S) SCHK(h, hipMemcpyAsync(to_device ? dev + r0 * S : h->h_stage, to_device ? h->h_stage : dev + r0 * S, sizeof(double) * (size_t)(k * S), kind, h->stream));
-            else SCHK(h, hipMemcpyAsync(to_device ? dev + r0 * S + at : h->h_stage, to_device ? h->h_stage : dev + r0 * S + at, sizeof(double) * (size_t)w, kind, h->stream));
-            SCHK(h, hipStreamSynchronize(h->stream));
+            if (w == S) OCHK(h, hipMemcpyAsync(to_device ? dev + r0 * S : h->h_stage, to_device ? h->h_stage : dev + r0 * S, sizeof(double) * (size_t)(k * S), kind, h->stream));
+            else OCHK(h, hipMemcpyAsync(to_device ? dev + r0 * S + at : h->h_stage, to_device ? h->h_stage : dev + r0 * S + at, sizeof(double) * (size_t)w, kind, h->stream));
+            OCHK(h, hipStreamSynchronize(h->stream));
             if (!to_device)
                 for (int64_t r = 0; r < k; ++r) std::memcpy(host + (r0 + r) * ld_h + at, h->h_stage + r * w, sizeof(double) * (size_t)w);
         }
@@ -439,16 +406,10 @@ int32_t octo_psis_create(int32_t device_id, octo_psis** out) {
     const std::string fn = "octo_psis_create: ";
     if (!out) return fail(nullptr, OCTO_EINVAL, fn + "null out pointer");
     *out = nullptr;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { (void)hipGetLastError(); return fail(nullptr, OCTO_ENODEV, fn + "no HIP device"); }
-    if (device_id < 0 || device_id >= n_dev) return fail(nullptr, OCTO_EINVAL, fn + "device_id out of range");
-    octo_psis* h = new (std::nothrow) octo_psis();
-    if (!h) return fail(nullptr, OCTO_ENOMEM, fn + "host allocation failed");
-    h->device = device_id;
+    octo_psis* h;
+    { int rc = open_device(device_id, fn, h); if (rc) return rc; }
     h->mat_bytes = env_bytes("OCTO_PSIS_MATRIX_BYTES", h->mat_bytes);
     h->stage_bytes = env_bytes("OCTO_PSIS_STAGE_BYTES", h->stage_bytes);
-    if (hipSetDevice(device_id) != hipSuccess) { octo_psis_destroy(h); return fail(nullptr, OCTO_EHIP, fn + "hipSetDevice failed"); }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { h->stream = nullptr; octo_psis_destroy(h); return fail(nullptr, OCTO_EHIP, fn + "stream creation failed"); }
     *out = h;
     return OCTO_OK;
 }
@@ -463,24 +424,19 @@ int32_t octo_psis_destroy(octo_psis* h) {
     return OCTO_OK;
 }
 
-const char* octo_psis_last_error(const octo_psis* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* octo_psis_last_error(const octo_psis* h) { return last_error(h); }
 
-int32_t octo_psis_sync(octo_psis* h) {
-    if (!h) return OCTO_EINVAL;
-    SCHK(h, hipSetDevice(h->device));
-    SCHK(h, hipStreamSynchronize(h->stream));
-    return OCTO_OK;
-}
+int32_t octo_psis_sync(octo_psis* h) { return sync_handle(h); }
 
 int32_t octo_psis_loo_device(octo_psis* h, const double* d_ll, int64_t ld, int64_t R, int64_t S, double* d_out, double* d_lw, int64_t ld_w,
                              void* hip_stream) {
     if (!h) return OCTO_EINVAL;
     { int rc = check_args(h, "octo_psis_loo_device", d_ll, ld, R, S, d_out, d_lw, ld_w); if (rc) return rc; }
     if (R == 0) return OCTO_OK;
-    SCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = hip_stream == OCTO_STREAM_CTX ? h->stream : (hipStream_t)hip_stream;
+    OCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream_of(h, hip_stream);
     hipLaunchKernelGGL(k_psis, dim3((unsigned)R), dim3(TPB), 0, st, d_ll, ld, S, R, d_out, d_lw, ld_w);
-    SCHK(h, hipGetLastError());
+    OCHK(h, hipGetLastError());
     return OCTO_OK;
 }
 
@@ -492,17 +448,12 @@ int32_t octo_psis_loo(octo_psis* h, const double* ll, int64_t ld, int64_t R, int
     if (cap_rows < 1)
         return fail(h, OCTO_ENOMEM, "octo_psis_loo: one row of S = " + std::to_string(S) + " samples (" + std::to_string(S * 8) + " bytes) is larger than the device buffer of " +
                                         std::to_string(h->mat_bytes) + " bytes (OCTO_PSIS_MATRIX_BYTES)");
-    SCHK(h, hipSetDevice(h->device));
+    OCHK(h, hipSetDevice(h->device));
     const int64_t Rc = std::min(cap_rows, R);      // rows per chunk
     { int rc = grow(h, h->d_mat, h->cap_mat, Rc * S); if (rc) return rc; }
     if (lw) { int rc = grow(h, h->d_lw, h->cap_lw, Rc * S); if (rc) return rc; }
     { int rc = grow(h, h->d_out, h->cap_out, Rc * NSTAT); if (rc) return rc; }
-    const int64_t want_stage = std::max<int64_t>(h->stage_bytes / (int64_t)sizeof(double), NSTAT);
-    if (h->cap_stage < want_stage) {
-        if (h->h_stage) { SCHK(h, hipHostFree(h->h_stage)); h->h_stage = nullptr; h->cap_stage = 0; }
-        SCHK(h, hipHostMalloc((void**)&h->h_stage, sizeof(double) * (size_t)want_stage, hipHostMallocDefault));
-        h->cap_stage = want_stage;
-    }
+    { int rc = ensure_stage(h, std::max<int64_t>(h->stage_bytes / (int64_t)sizeof(double), NSTAT)); if (rc) return rc; }
     for (int64_t r0 = 0; r0 < R; r0 += Rc) {
         const int64_t nr = std::min(Rc, R - r0);
         { int rc = staged_rows(h, const_cast<double*>(ll) + r0 * ld, ld, h->d_mat, nr, S, true); if (rc) return rc; }

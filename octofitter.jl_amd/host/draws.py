@@ -13,12 +13,9 @@ has not been built: the draws have no NumPy fallback here (host/callers.py keeps
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
-
 import numpy as np
 
-from . import capi
+from . import capi, companion
 
 DRAWS_LIB_PATH = capi.PKG_DIR / "lib" / "liboctofitter_hip_draws.so"
 MAX_KEEP = 64                      # OCTO_DRAWS_MAX_KEEP
@@ -41,50 +38,33 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
-_lib = None
-
-
 def load_library(path=None):
     """Load liboctofitter_hip_draws.so (after the main library it links against). Raises if it has not been built."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    capi.load_library()
-    p = Path(path or os.environ.get("OCTOFITTER_HIP_DRAWS_LIB", DRAWS_LIB_PATH))
-    if not p.exists():
-        raise FileNotFoundError(
-            f"{p} not found: build the companion library first (python -c 'import __graft_entry__ as g; g.build()'). "
-            "Prior draws on the device have no CPU fallback.")
-    lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if path is None:
-        _lib = lib
-    return lib
+    return companion.load_library(path, DRAWS_LIB_PATH, "OCTOFITTER_HIP_DRAWS_LIB", _SIGS, needs_main=True,
+                                  no_fallback="Prior draws on the device have no CPU fallback.")
 
 
 def _u64ptr(a):
     return a.ctypes.data_as(c_uint64_p)
 
 
-class PriorDraws:
+class PriorDraws(companion.Handle):
     """The handle of octo_draws_create. PriorDraws(model): for one LogDensityModel — its priors, its device model, its context.
     PriorDraws(priors=[…], device=0): a list of host/priors.py priors and a context of its own — sampling only (no best / rejection)."""
+
+    PREFIX = "octo_draws"
 
     def __init__(self, model=None, priors=None, device=0):
         if (model is None) == (priors is None):
             raise ValueError("PriorDraws takes a LogDensityModel or a list of priors")
-        self.lib = load_library()
         self.model = model
         self._own_ctx = None
-        self._h = C.c_void_p()
+        self._open(load_library(), model.ln_like.device_index if model is not None else device)
         if model is not None:
-            self.D, self.device_index = int(model.D), int(model.ln_like.device_index)
+            self.D = int(model.D)
             ctx, m, self._c_priors = model.ln_like._ctx, model._m, model._c_priors
         else:
-            self.D, self.device_index = len(priors), int(device)
+            self.D = len(priors)
             self._c_priors = (capi.OctoPrior * max(self.D, 1))()
             for k, p in enumerate(priors):
                 self._c_priors[k].kind = p.kind
@@ -95,15 +75,7 @@ class PriorDraws:
             if st != capi.OCTO_OK:
                 raise capi.OctoError(st, "octo_ctx_create")
             self._own_ctx = ctx
-        st = self.lib.octo_draws_create(ctx, m, self._c_priors, self.D, self.device_index, C.byref(self._h))
-        if st != capi.OCTO_OK:
-            self._h = None
-            self.close()
-            raise capi.OctoError(st, (self.lib.octo_draws_last_error(None) or b"").decode())
-
-    def _check(self, status):
-        if status != capi.OCTO_OK:
-            raise capi.OctoError(status, (self.lib.octo_draws_last_error(self._h) or b"").decode())
+        self._created(self.lib.octo_draws_create(ctx, m, self._c_priors, self.D, self.device_index, C.byref(self._h)))
 
     def sample(self, seed, first, n, theta=True, theta_t=True, logprior_t=True, stream=None):
         """Draws first … first + n − 1 of stream `seed` as torch float64 tensors on the model's device: (θ [D, n] natural domain,
@@ -114,10 +86,8 @@ class PriorDraws:
         th = torch.empty((self.D, n), dtype=torch.float64, device=dev) if theta else None
         tt = torch.empty((self.D, n), dtype=torch.float64, device=dev) if theta_t else None
         lp = torch.empty(n, dtype=torch.float64, device=dev) if logprior_t else None
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
         ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
-        self._check(self.lib.octo_draws_sample_device(self._h, int(seed), int(first), n, n, ptr(th), ptr(tt), ptr(lp), C.c_void_p(stream)))
+        self._check(self.lib.octo_draws_sample_device(self._h, int(seed), int(first), n, n, ptr(th), ptr(tt), ptr(lp), self._stream(stream, dev)))
         return th, tt, lp
 
     def best(self, seed, N, keep=1, first=0):
@@ -149,21 +119,10 @@ class PriorDraws:
         return dict(samples=np.ascontiguousarray(th[:, :ns]), loglike=ll[:ns].copy(), logpost=lp[:ns].copy(), index=ix[:ns].copy(),
                     n_accepted=int(n_acc.value), max_loglike=float(mx.value))
 
-    def sync(self):
-        self._check(self.lib.octo_draws_sync(self._h))
-
     def close(self):
-        if getattr(self, "_h", None):
-            if self.model is not None and not getattr(self.model.ln_like, "_ctx", None):
-                self.lib.octo_draws_detach(self._h)      # the model was closed first: its context is gone
-            self.lib.octo_draws_destroy(self._h)
-            self._h = None
+        if getattr(self, "_h", None) and self.model is not None and not getattr(self.model.ln_like, "_ctx", None):
+            self.lib.octo_draws_detach(self._h)      # the model was closed first: its context is gone
+        super().close()
         if getattr(self, "_own_ctx", None):
             capi.load_library().octo_ctx_destroy(self._own_ctx)
             self._own_ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

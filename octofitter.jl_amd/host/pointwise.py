@@ -16,12 +16,9 @@ no NumPy fallback.
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
-
 import numpy as np
 
-from . import capi
+from . import capi, companion
 
 POINTWISE_LIB_PATH = capi.PKG_DIR / "lib" / "liboctofitter_hip_pointwise.so"
 MAX_TABLES = 1024      # OCTO_POINTWISE_MAX_TABLES
@@ -45,58 +42,29 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
-_lib = None
-
-
 def load_library(path=None):
     """Load liboctofitter_hip_pointwise.so (after the main library it links against). Raises if it has not been built."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    capi.load_library()
-    p = Path(path or os.environ.get("OCTOFITTER_HIP_POINTWISE_LIB", POINTWISE_LIB_PATH))
-    if not p.exists():
-        raise FileNotFoundError(
-            f"{p} not found: build the companion library first (python -c 'import __graft_entry__ as g; g.build()'). "
-            "The pointwise log-likelihood on the device has no CPU fallback.")
-    lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if path is None:
-        _lib = lib
-    return lib
+    return companion.load_library(path, POINTWISE_LIB_PATH, "OCTOFITTER_HIP_POINTWISE_LIB", _SIGS, needs_main=True,
+                                  no_fallback="The pointwise log-likelihood on the device has no CPU fallback.")
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
-
-
-class Pointwise:
+class Pointwise(companion.Handle):
     """The handle of octo_pointwise_create: the observation tables (dicts of kind, planet and NumPy columns, as capi.pack_obs takes them)
     and the planet list of a system. Kinds served: ASTROM_RADEC, ASTROM_SEPPA, RV_ABS, RV_REL; any other raises OctoError(OCTO_ENOTSUP)."""
 
+    PREFIX = "octo_pointwise"
+
     def __init__(self, obs_tables, planets, device=0, consts=None):
-        self.lib = load_library()
+        self._open(load_library(), device)
         self.n_obs, self.n_planets = len(obs_tables), len(planets)
-        self.device_index = int(device)
         obs_arr, keep = capi.pack_obs(obs_tables)
-        self._h = C.c_void_p()
         st = self.lib.octo_pointwise_create(self.device_index, None if consts is None else C.byref(consts), obs_arr, self.n_obs,
                                             capi.pack_planets(planets), self.n_planets, C.byref(self._h))
         del keep
-        if st != capi.OCTO_OK:
-            self._h = None
-            raise capi.OctoError(st, (self.lib.octo_pointwise_last_error(None) or b"").decode())
+        self._created(st)
         self.n_rows = int(self.lib.octo_pointwise_n_rows(self._h))
         self.row_table = np.zeros(self.n_rows, dtype=np.int32)
         self._check(self.lib.octo_pointwise_row_table(self._h, self.row_table.ctypes.data_as(C.POINTER(C.c_int32))))
-        self._keep = None
-
-    def _check(self, status):
-        if status != capi.OCTO_OK:
-            raise capi.OctoError(status, (self.lib.octo_pointwise_last_error(self._h) or b"").decode())
 
     def _host_inputs(self, elems, nuis):
         elems = np.ascontiguousarray(elems, dtype=np.float64)
@@ -126,15 +94,13 @@ class Pointwise:
     def values(self, elems, nuis=None, stream=None):
         """The matrix [R, W]. NumPy inputs: the blocking host-buffer call, NumPy out. A torch tensor on the handle's device: the device
         call, asynchronous on `stream` (default: torch's current stream), a torch tensor out."""
-        if _is_torch(elems) and elems.is_cuda:
+        if companion.is_torch(elems) and elems.is_cuda:
             import torch
             W, ld, nu = self._device_inputs(elems, nuis)
             out = torch.empty((self.n_rows, W), dtype=torch.float64, device=elems.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(elems.device).cuda_stream
             self._keep = (elems, nu)
             self._check(self.lib.octo_pointwise_eval_device(self._h, elems.data_ptr(), ld, W, None if nu is None else nu.data_ptr(),
-                                                            out.data_ptr(), max(W, 1), C.c_void_p(stream)))
+                                                            out.data_ptr(), max(W, 1), self._stream(stream, elems.device)))
             return out
         elems, nuis, W = self._host_inputs(elems, nuis)
         out = np.empty((self.n_rows, W))
@@ -144,32 +110,15 @@ class Pointwise:
     def summary(self, elems, nuis=None, stream=None):
         """The reduction over the walkers with a finite value, the matrix never stored: dict(n, lppd, mean, var, elpd_is_loo, min, max),
         each [R] (NumPy for NumPy inputs, torch tensors for device inputs). var is the sample variance (n − 1): NaN for n = 1."""
-        if _is_torch(elems) and elems.is_cuda:
+        if companion.is_torch(elems) and elems.is_cuda:
             import torch
             W, ld, nu = self._device_inputs(elems, nuis)
             out = torch.empty((N_STATS, self.n_rows), dtype=torch.float64, device=elems.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(elems.device).cuda_stream
             self._keep = (elems, nu)
             self._check(self.lib.octo_pointwise_summary_device(self._h, elems.data_ptr(), ld, W, None if nu is None else nu.data_ptr(),
-                                                               out.data_ptr(), C.c_void_p(stream)))
+                                                               out.data_ptr(), self._stream(stream, elems.device)))
             return dict(zip(SUMMARY_FIELDS, out))
         elems, nuis, W = self._host_inputs(elems, nuis)
         out = np.empty((N_STATS, self.n_rows))
         self._check(self.lib.octo_pointwise_summary(self._h, capi._dptr(elems), W, W, capi._dptr(nuis), capi._dptr(out)))
         return dict(zip(SUMMARY_FIELDS, out))
-
-    def sync(self):
-        self._check(self.lib.octo_pointwise_sync(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.octo_pointwise_destroy(self._h)
-            self._h = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

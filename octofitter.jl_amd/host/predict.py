@@ -14,12 +14,9 @@ built: there is no NumPy fallback.
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
-
 import numpy as np
 
-from . import capi
+from . import capi, companion
 
 PREDICT_LIB_PATH = capi.PKG_DIR / "lib" / "liboctofitter_hip_predict.so"
 MAX_CHANNELS = 32      # OCTO_PREDICT_MAX_CHANNELS
@@ -49,28 +46,10 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
-_lib = None
-
-
 def load_library(path=None):
     """Load liboctofitter_hip_predict.so (after the main library it links against). Raises if it has not been built."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    capi.load_library()
-    p = Path(path or os.environ.get("OCTOFITTER_HIP_PREDICT_LIB", PREDICT_LIB_PATH))
-    if not p.exists():
-        raise FileNotFoundError(
-            f"{p} not found: build the companion library first (python -c 'import __graft_entry__ as g; g.build()'). "
-            "Model values on the device have no CPU fallback.")
-    lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if path is None:
-        _lib = lib
-    return lib
+    return companion.load_library(path, PREDICT_LIB_PATH, "OCTOFITTER_HIP_PREDICT_LIB", _SIGS, needs_main=True,
+                                  no_fallback="Model values on the device have no CPU fallback.")
 
 
 def pack_channels(channels):
@@ -82,33 +61,23 @@ def pack_channels(channels):
     return arr
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
-
-
-class Predictor:
+class Predictor(companion.Handle):
     """The handle of octo_predict_create: a planet list, an epoch grid [T] (MJD, any order), up to 32 channels (quantity, planet) and an
     optional basis column [T] that an RV channel's add1 multiplies."""
 
+    PREFIX = "octo_predict"
+
     def __init__(self, planets, epochs, channels, basis=None, device=0, consts=None):
-        self.lib = load_library()
         self.epochs = np.ascontiguousarray(epochs, dtype=np.float64).reshape(-1)
         self.basis = None if basis is None else np.ascontiguousarray(basis, dtype=np.float64).reshape(-1)
         if self.basis is not None and self.basis.shape != self.epochs.shape:
             raise ValueError("Predictor: the basis column has one value per epoch")
         self.channels = [(QUANTITY_NAMES.index(q) if isinstance(q, str) else int(q), int(p)) for q, p in channels]
         self.n_planets, self.T, self.C = len(planets), int(self.epochs.size), len(self.channels)
-        self.device_index = int(device)
-        self._h = C.c_void_p()
+        self._open(load_library(), device)
         st = self.lib.octo_predict_create(self.device_index, None if consts is None else C.byref(consts), capi.pack_planets(planets), self.n_planets,
                                           capi._dptr(self.epochs), self.T, capi._dptr(self.basis), pack_channels(self.channels), self.C, C.byref(self._h))
-        if st != capi.OCTO_OK:
-            self._h = None
-            raise capi.OctoError(st, (self.lib.octo_predict_last_error(None) or b"").decode())
-
-    def _check(self, status):
-        if status != capi.OCTO_OK:
-            raise capi.OctoError(status, (self.lib.octo_predict_last_error(self._h) or b"").decode())
+        self._created(st)
 
     def _host_inputs(self, elems, add0, add1):
         elems = np.ascontiguousarray(elems, dtype=np.float64)
@@ -144,16 +113,14 @@ class Predictor:
     def values(self, elems, add0=None, add1=None, stream=None):
         """The cube [C, T, W]. NumPy inputs: the blocking host-buffer call, NumPy out. A torch tensor on the handle's device: the device
         call, asynchronous on `stream` (default: torch's current stream), a torch tensor out."""
-        if _is_torch(elems) and elems.is_cuda:
+        if companion.is_torch(elems) and elems.is_cuda:
             import torch
             W, ld, a0, a1 = self._device_inputs(elems, add0, add1)
             ldo = W + (W & 1)      # an even leading dimension: 16-byte stores
             buf = torch.empty((self.C * self.T, ldo), dtype=torch.float64, device=elems.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(elems.device).cuda_stream
             self._keep = (elems, a0, a1)
             self._check(self.lib.octo_predict_eval_device(self._h, elems.data_ptr(), ld, W, None if a0 is None else a0.data_ptr(),
-                                                          None if a1 is None else a1.data_ptr(), buf.data_ptr(), ldo, C.c_void_p(stream)))
+                                                          None if a1 is None else a1.data_ptr(), buf.data_ptr(), ldo, self._stream(stream, elems.device)))
             return buf[:, :W].reshape(self.C, self.T, W)
         elems, add0, add1, W = self._host_inputs(elems, add0, add1)
         out = np.empty((self.C, self.T, W))
@@ -163,15 +130,13 @@ class Predictor:
     def summary(self, elems, add0=None, add1=None, stream=None):
         """Statistics over the valid walkers for every (channel, epoch), the cube never stored: dict(n_valid, mean, sd, min, max), each [C, T]
         (NumPy for NumPy inputs, torch tensors for device inputs). sd is the sample standard deviation (n − 1): NaN for one valid walker."""
-        if _is_torch(elems) and elems.is_cuda:
+        if companion.is_torch(elems) and elems.is_cuda:
             import torch
             W, ld, a0, a1 = self._device_inputs(elems, add0, add1)
             out = torch.empty((len(SUMMARY_FIELDS), self.C, self.T), dtype=torch.float64, device=elems.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(elems.device).cuda_stream
             self._keep = (elems, a0, a1)
             self._check(self.lib.octo_predict_summary_device(self._h, elems.data_ptr(), ld, W, None if a0 is None else a0.data_ptr(),
-                                                             None if a1 is None else a1.data_ptr(), out.data_ptr(), C.c_void_p(stream)))
+                                                             None if a1 is None else a1.data_ptr(), out.data_ptr(), self._stream(stream, elems.device)))
             return dict(zip(SUMMARY_FIELDS, out))
         elems, add0, add1, W = self._host_inputs(elems, add0, add1)
         out = np.empty((len(SUMMARY_FIELDS), self.C, self.T))
@@ -181,18 +146,3 @@ class Predictor:
     def set_variant(self, variant):
         """Measurement hook: the cube kernel's store width (0 / 2: two walkers per lane and 16-byte stores where the output allows, 1: 8-byte)."""
         self._check(self.lib.octo_predict_set_variant(self._h, int(variant)))
-
-    def sync(self):
-        self._check(self.lib.octo_predict_sync(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.octo_predict_destroy(self._h)
-            self._h = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -14,12 +14,9 @@ and torch tensors out. Like capi.py this is plumbing that FAILS LOUDLY when the 
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
-
 import numpy as np
 
-from . import capi
+from . import capi, companion
 
 PSIS_LIB_PATH = capi.PKG_DIR / "lib" / "liboctofitter_hip_psis.so"
 STAT_FIELDS = ("n", "tail_len", "pareto_k", "elpd_loo", "lppd", "ess")      # OCTO_PSIS_N … OCTO_PSIS_ESS
@@ -39,56 +36,27 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
-_lib = None
-
-
 def load_library(path=None):
     """Load liboctofitter_hip_psis.so (it links nothing of the main library). Raises if it has not been built."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = Path(path or os.environ.get("OCTOFITTER_HIP_PSIS_LIB", PSIS_LIB_PATH))
-    if not p.exists():
-        raise FileNotFoundError(
-            f"{p} not found: build the companion library first (python -c 'import __graft_entry__ as g; g.build()'). "
-            "PSIS-LOO on the device has no CPU fallback.")
-    lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if path is None:
-        _lib = lib
-    return lib
+    return companion.load_library(path, PSIS_LIB_PATH, "OCTOFITTER_HIP_PSIS_LIB", _SIGS, needs_main=False,
+                                  no_fallback="PSIS-LOO on the device has no CPU fallback.")
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
-
-
-class Psis:
+class Psis(companion.Handle):
     """The handle of octo_psis_create: a stream and the buffers of the host-buffer call."""
 
-    def __init__(self, device=0):
-        self.lib = load_library()
-        self.device_index = int(device)
-        self._h = C.c_void_p()
-        st = self.lib.octo_psis_create(self.device_index, C.byref(self._h))
-        if st != capi.OCTO_OK:
-            self._h = None
-            raise capi.OctoError(st, (self.lib.octo_psis_last_error(None) or b"").decode())
-        self._keep = None
+    PREFIX = "octo_psis"
 
-    def _check(self, status):
-        if status != capi.OCTO_OK:
-            raise capi.OctoError(status, (self.lib.octo_psis_last_error(self._h) or b"").decode())
+    def __init__(self, device=0):
+        self._open(load_library(), device)
+        self._created(self.lib.octo_psis_create(self.device_index, C.byref(self._h)))
 
     def loo(self, ll, weights=False, stream=None):
         """dict(n, tail_len, pareto_k, elpd_loo, lppd, ess), each [R], of the matrix ll [R, S]; with weights=True also log_weights [R, S], the
         smoothed normalised log-weights (−Inf where ll is not finite). NumPy input: the blocking host-buffer call, NumPy out. A torch
         tensor on the handle's device (sample index fastest; the row stride is the leading dimension): the device call, asynchronous on
         `stream` (default: torch's current stream), torch tensors out."""
-        if _is_torch(ll) and ll.is_cuda:
+        if companion.is_torch(ll) and ll.is_cuda:
             import torch
             if ll.dtype != torch.float64 or ll.dim() != 2 or (ll.shape[1] > 1 and ll.stride(1) != 1):
                 raise ValueError("ll must be a float64 tensor [R, S] with the sample index fastest")
@@ -98,11 +66,9 @@ class Psis:
             ld = max(int(ll.stride(0)), S) if R > 1 else S
             out = torch.empty((N_STATS, R), dtype=torch.float64, device=ll.device)
             lw = torch.empty((R, S), dtype=torch.float64, device=ll.device) if weights else None
-            if stream is None:
-                stream = torch.cuda.current_stream(ll.device).cuda_stream
             self._keep = ll
             self._check(self.lib.octo_psis_loo_device(self._h, ll.data_ptr(), ld, R, S, out.data_ptr(), None if lw is None else lw.data_ptr(),
-                                                      max(S, 1), C.c_void_p(stream)))
+                                                      max(S, 1), self._stream(stream, ll.device)))
             res = dict(zip(STAT_FIELDS, out))
         else:
             ll = np.ascontiguousarray(ll, dtype=np.float64)
@@ -116,18 +82,3 @@ class Psis:
         if weights:
             res["log_weights"] = lw
         return res
-
-    def sync(self):
-        self._check(self.lib.octo_psis_sync(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.octo_psis_destroy(self._h)
-            self._h = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,23 +1,20 @@
 """
-Build checks of the companion library liboctofitter_hip_pointwise.so (include/octofitter_hip_pointwise.h, csrc/pointwise/): what it exports
-against what its header declares and host/pointwise.py binds, that the main library's symbol set and sources did not move, the argument
-checks that need no device, and the compiled kernels' resources read from the code objects (tools/kernel_resources.py). CPU suite: hipcc
-cross-compiles.
+Build checks of the companion library liboctofitter_hip_pointwise.so (include/octofitter_hip_pointwise.h, csrc/pointwise/): what it exports against
+what its header declares and host/pointwise.py binds, that the main library's sources did not move, the argument checks that need no device,
+and the compiled kernels' resources read from the code objects (tools/kernel_resources.py). The bodies every companion library shares are
+in tests/companion_checks.py; linkage and the main library's symbol set are checked for all four in tests/test_companion_libraries.py.
+CPU suite: hipcc cross-compiles.
 """
 import ctypes as C
 import re
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT / "tools"))
-HEADER = ROOT / "include" / "octofitter_hip_pointwise.h"
-MAIN_LIB = ROOT / "octofitter.jl_amd" / "lib" / "liboctofitter_hip.so"
-POINTWISE_BUILD = ROOT / "octofitter.jl_amd" / "csrc" / "pointwise" / "build"
+import companion_checks as cc
+
+FUNCTIONS = {"octo_pointwise_create", "octo_pointwise_destroy", "octo_pointwise_eval", "octo_pointwise_eval_device", "octo_pointwise_last_error",
+             "octo_pointwise_n_rows", "octo_pointwise_row_table", "octo_pointwise_summary", "octo_pointwise_summary_device", "octo_pointwise_sync"}
 
 
 @pytest.fixture(scope="module")
@@ -27,78 +24,16 @@ def pointwise_lib():
     return build_pointwise()
 
 
-def declared_functions():
-    """{name: number of parameters} of every function the header declares."""
-    text = re.sub(r"/\*.*?\*/", " ", HEADER.read_text(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(octo_pointwise_\w+)\s*\(([^()]*)\)\s*;", text):
-        params = m.group(2).strip()
-        out[m.group(1)] = 0 if params in ("", "void") else params.count(",") + 1
-    return out
-
-
-def dynamic_symbols(lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True, check=True).stdout
-    return {line.split()[-1] for line in out.splitlines() if line.strip()}
-
-
 def test_header_library_and_binding_agree(pkg, pointwise_lib):
     pw = pkg.pointwise
-    decl = declared_functions()
-    assert {"octo_pointwise_create", "octo_pointwise_destroy", "octo_pointwise_last_error", "octo_pointwise_sync", "octo_pointwise_n_rows",
-            "octo_pointwise_row_table", "octo_pointwise_eval_device", "octo_pointwise_eval", "octo_pointwise_summary_device",
-            "octo_pointwise_summary"} == set(decl)
-    exported = {s for s in dynamic_symbols(pointwise_lib) if s.startswith("octo_")}
-    assert exported == set(decl), (sorted(exported), sorted(decl))
-    assert set(pw.EXPORTED_SYMBOLS) == set(decl)
-    lib = pw.load_library()
-    for name, n_params in decl.items():
-        assert len(pw._SIGS[name][1]) == n_params, name
-        assert getattr(lib, name).argtypes is not None
+    text = cc.check_header_library_and_binding_agree("pointwise", pw, pointwise_lib, FUNCTIONS, exact=True)
     # the constants of the binding are those of the header
-    text = HEADER.read_text()
     for k, name in enumerate(pw.SUMMARY_FIELDS):
         assert re.search(rf"#define OCTO_POINTWISE_{name.upper()}\s+{k}\b", text), name
     assert re.search(rf"#define OCTO_POINTWISE_N_STATS\s+{pw.N_STATS}\b", text) and pw.N_STATS == len(pw.SUMMARY_FIELDS)
     assert re.search(rf"#define OCTO_POINTWISE_MAX_TABLES\s+{pw.MAX_TABLES}\b", text)
     # … and the package exports the class and the two callers
     assert pkg.Pointwise is pw.Pointwise and callable(pkg.pointwise_like_rows) and callable(pkg.waic)
-
-
-def test_main_library_exports_no_pointwise_symbol(pointwise_lib):
-    syms = dynamic_symbols(MAIN_LIB)
-    assert any(s.startswith("octo_") for s in syms)
-    assert not [s for s in syms if s.startswith("octo_pointwise")]
-
-
-def test_companion_links_the_main_library_by_origin(pointwise_lib):
-    dyn = subprocess.run(["readelf", "-d", str(pointwise_lib)], capture_output=True, text=True, check=True).stdout
-    assert "liboctofitter_hip.so" in dyn and "$ORIGIN" in dyn
-
-
-def _git(*args):
-    return subprocess.run(["git", "-C", str(ROOT), *args], capture_output=True, text=True)
-
-
-def test_main_library_sources_untouched():
-    """The pointwise library came with no change to a file directly under csrc/ (kernel_source_hash() covers exactly those, and the committed
-    counter evidence is keyed to it): neither the commit that added include/octofitter_hip_pointwise.h nor, while that header is still
-    uncommitted, the working tree differs from its parent there."""
-    if _git("rev-parse", "--is-inside-work-tree").stdout.strip() != "true":
-        pytest.skip("not a git checkout")
-    files = [":(glob)octofitter.jl_amd/csrc/*.h", ":(glob)octofitter.jl_amd/csrc/*.hip"]      # directly under csrc/: `*` stops at a slash
-    added = _git("log", "--diff-filter=A", "--format=%H", "--", "include/octofitter_hip_pointwise.h").stdout.split()
-    if not added:      # the header is not committed yet: the working tree against HEAD
-        r = _git("diff", "--quiet", "HEAD", "--", *files)
-        assert r.returncode == 0, _git("diff", "--stat", "HEAD", "--", *files).stdout
-        untracked = _git("ls-files", "--others", "--exclude-standard", "--", *files).stdout.split()
-        assert not untracked, untracked
-        return
-    commit = added[-1]
-    if _git("rev-parse", "--verify", "--quiet", commit + "~").returncode != 0:
-        pytest.skip("the parent of the commit that added the header is not in this (shallow) checkout")
-    r = _git("diff", "--quiet", commit + "~", commit, "--", *files)
-    assert r.returncode == 0, _git("diff", "--stat", commit + "~", commit, "--", *files).stdout
 
 
 def _table(capi, kind, planet=0, n=3, **over):
@@ -110,6 +45,11 @@ def _table(capi, kind, planet=0, n=3, **over):
         tab.update(planet=-1, y1=np.zeros(n), y2=np.zeros(n), s1=None, s2=None, extra=np.tile([1.0, 1.0, 0.1, 0.1, 0.0], 3))
     tab.update(over)
     return tab
+
+
+def test_main_library_sources_untouched():
+    """The pointwise library came with no change to a file directly under csrc/."""
+    cc.check_main_library_sources_untouched("include/octofitter_hip_pointwise.h")
 
 
 def test_argument_checks_that_need_no_device(pkg, pointwise_lib):
@@ -187,13 +127,8 @@ def test_argument_checks_that_need_no_device(pkg, pointwise_lib):
 
 
 def test_pointwise_kernels_have_no_scratch(pointwise_lib):
-    import kernel_resources as kr
-    rows = kr.resources(build_dir=POINTWISE_BUILD)
-    names = {r["name"].split("(")[0].split("<")[0].replace("void ", "") for r in rows}
+    rows, names = cc.check_kernels_have_no_scratch("pointwise", sgpr_too=True)
     assert {"k_pointwise", "k_pointwise_n", "k_pointwise_merge"} <= names, names
-    bad = [(r["name"], r["vgpr_spill_count"], r["sgpr_spill_count"], r["scratch_instructions"], r["private_segment_fixed_size"]) for r in rows
-           if r["vgpr_spill_count"] or r["sgpr_spill_count"] or r["scratch_instructions"] or r["private_segment_fixed_size"]]
-    assert not bad, bad
     # the single-planet matrix kernel is held to the registers of four waves per SIMD (128 of the 512 per lane)
     one = [r for r in rows if "k_pointwise<1, false>" in r["name"]]
     assert len(one) == 1 and one[0]["vgpr_count"] + one[0]["agpr_count"] <= 128, [(r["name"], r["vgpr_count"], r["agpr_count"]) for r in one]
