@@ -1,6 +1,6 @@
 /*
  * octofitter_hip_draws.h — companion C ABI: IID prior draws made ON the device, and the two reference drivers that
- * consume a whole batch of them.
+ * consume a whole batch of them, and a tempered HMC explorer for batches of chains (below).
  *
  *   octo_draws_best       <- guess_starting_position, src/initialization.jl:14-66: score N prior draws, keep the best.
  *   octo_draws_rejection  <- octofit_rejection, src/sampling.jl:168-268: accept draw i with probability exp(ll_i − max ll).
@@ -20,6 +20,13 @@
  * Each coordinate is the prior's inverse CDF of its uniform (a result that rounds onto a bound of the support is moved one
  * ulp inside), then Bijectors' link of it; the densities and Jacobians are the device routines of the model callback.
  *
+ * The third driver is an explorer: one tempered HMC step of every chain of a batch (octo_draws_hmc_step_device), the piece between the
+ * batched log-posterior with its gradient and the swap step of parallel tempering (octo_pt_step_device). Its two streams add
+ *   purpose 2: the momentum of chain c at `step`, counter (c, d / 4, 2, step), coordinate d takes word d % 4
+ *   purpose 3: the acceptance uniform of chain c at `step`, counter (c, 0, 3, step), word 0
+ * Purposes 0 and 1 keep counter word 3 = 0. The step is stated in full at its declaration, so that a restatement elsewhere (tests/hmc_reference.py)
+ * and the device compute the same function.
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -35,6 +42,8 @@ extern "C" {
 #define OCTO_DRAWS_MAX_KEEP 64
 #define OCTO_DRAWS_PURPOSE_PRIOR   0
 #define OCTO_DRAWS_PURPOSE_UNIFORM 1
+#define OCTO_DRAWS_PURPOSE_MOMENTUM 2
+#define OCTO_DRAWS_PURPOSE_ACCEPT   3
 
 typedef struct octo_draws octo_draws;
 
@@ -76,6 +85,56 @@ int32_t octo_draws_best(octo_draws* h, uint64_t seed, uint64_t first, int64_t N,
 int32_t octo_draws_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64_t N, int64_t cap,
                              double* theta_out /*[D][cap]*/, double* loglike_out /*[cap]*/, double* logpost_out /*[cap]*/,
                              uint64_t* index_out /*[cap]*/, int64_t* n_accepted, double* max_loglike);
+
+/* ---- The tempered HMC explorer. Chain c = chain0 + w (w < W) at `step`; D, the priors and (if any) the model are the handle's.
+ *
+ * Momentum   z_d = normcdfinv(uniform of word d % 4 of Philox(key, counter (c, d / 4, 2, step))), p_d = z_d / sqrt(inv_mass_d).
+ * Target     E(θ_t) = ℓprior_t + β·(ℓπ − ℓprior_t) and ∇E = β·∇ℓπ + (1 − β)·∇ℓprior_t, with
+ *              ℓπ, ∇ℓπ     octo_model_logpost_device;
+ *              ℓprior_t    Σ_d logpdf_with_trans in declaration order — octo_draws_sample_device's d_logprior_t, the same routine, the
+ *                          same order, the same sentinel −DBL_MAX when a term is non-finite (the healed prior of the model callback);
+ *              ∇ℓprior_t   the derivative of the same routine; 0 in every coordinate when the prior was healed.
+ *            β = 1 takes ∇E = ∇ℓπ bit for bit. β = 0 takes E = ℓprior_t and ∇E = ∇ℓprior_t and never consults ℓπ (a −Inf likelihood is
+ *            no NaN there).
+ * Trajectory n_leapfrog >= 1 leapfrog steps of size ε_w with the diagonal inverse mass: p += (ε/2)∇E, then n_leapfrog times
+ *            { θ_t += ε·inv_mass·p;  p += ε∇E (the last time: (ε/2)∇E) }. K = ½ Σ_d inv_mass_d p_d², summed in index order. The start point
+ *            is always evaluated (n_leapfrog + 1 log-posterior calls a step); nothing is kept from the previous step.
+ * Decision   H = −E + K. A state is dead if E is not finite, if ℓprior_t is the sentinel, or if β > 0 and ℓπ is not finite.
+ *            Accepted iff the end state is alive and (the start is dead or log u < H₀ − H₁), u the uniform of word 0 of counter
+ *            (c, 0, 3, step). NaN runs through the trajectory and ends as a rejection; there is no other special case. A rejected chain
+ *            keeps its θ_t bit for bit.
+ * ℓ = ℓπ − ℓprior_t (not finite -> −Inf, as octo_draws_rejection defines it) is what octo_pt_step_device gathers.
+ *
+ * octo_draws_momentum_device: the momenta alone, d_p [D][ld], of chains chain0 … chain0 + n − 1; d_inv_mass [D] or NULL = 1.
+ * OCTO_EINVAL: NULL handle, n < 0, ld < n, n > 2^30. */
+int32_t octo_draws_momentum_device(octo_draws* h, uint64_t seed, uint64_t step, uint64_t chain0, int64_t n, int64_t ld,
+                                   const double* d_inv_mass, double* d_p, void* hip_stream);
+
+/* One step of W chains on DEVICE buffers, asynchronous on hip_stream: no host synchronisation, no allocation once the handle's work
+ * arrays hold (4·D + 4)·ld doubles (they grow behind the handle's own stream), no graph capture. The decision is made on the device.
+ *   d_theta_t    [D][ld]  in/out: the states; an accepted chain receives its proposal, a rejected one is not written
+ *   d_beta       [W]      or NULL: β = 1
+ *   d_eps        [W]      or NULL: the scalar eps for every chain
+ *   d_inv_mass   [D]      or NULL: 1
+ *   d_theta_prop [D][ld]  or NULL: the end point of the trajectory, whatever the decision
+ *   d_logpost    [W]      or NULL: ℓπ of the returned state
+ *   d_loglike    [W]      or NULL: ℓ of the returned state
+ *   d_dH         [W]      or NULL: H₀ − H₁
+ *   d_accepted   [W]      int32 0 / 1
+ * A handle without a model (created with model = NULL, or detached) explores the prior: β = 0 for every chain, d_beta is ignored,
+ * d_logpost and d_loglike must be NULL.
+ * OCTO_EINVAL: NULL handle; n_leapfrog < 1; W < 0, ld < W, W > 2^30; eps not finite or <= 0 with d_eps NULL; d_logpost or d_loglike on a
+ * handle without a model; NULL d_theta_t or d_accepted with W > 0. */
+int32_t octo_draws_hmc_step_device(octo_draws* h, uint64_t seed, uint64_t step, uint64_t chain0, int64_t W, int64_t ld,
+                                   double* d_theta_t, const double* d_beta, const double* d_eps, double eps, int32_t n_leapfrog,
+                                   const double* d_inv_mass, double* d_theta_prop, double* d_logpost, double* d_loglike,
+                                   double* d_dH, int32_t* d_accepted, void* hip_stream);
+
+/* The same step on HOST arrays of the same shapes, blocking, staged through the handle on its own stream: the same bits. */
+int32_t octo_draws_hmc_step(octo_draws* h, uint64_t seed, uint64_t step, uint64_t chain0, int64_t W, int64_t ld,
+                            double* theta_t, const double* beta, const double* eps_w, double eps, int32_t n_leapfrog,
+                            const double* inv_mass, double* theta_prop, double* logpost, double* loglike,
+                            double* dH, int32_t* accepted);
 
 #ifdef __cplusplus
 }

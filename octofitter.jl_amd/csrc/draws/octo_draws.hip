@@ -11,90 +11,23 @@
 //               and the running list. No atomics.
 //   k_loglike   ll = lp − logprior_t (non-finite -> −Inf) and the per-block maximum; k_max the maximum of those.
 //   k_count / k_scan / k_scatter   accept flags (recomputed, never stored), per-block counts, their exclusive scan, ordered scatter.
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "octo_companion_host.h"
-#include "octo_model.h"
-#include "octofitter_hip_draws.h"
+// The handle, the counter generator and the prior helpers are in octo_draws_common.h, shared with the explorer (octo_draws_hmc.hip).
+#include "octo_draws_common.h"
 
 namespace {
-using namespace octo;
 
-constexpr uint64_t PHILOX_M0 = 0xD2E7470EE14C6C93ull, PHILOX_M1 = 0xCA5A826395121157ull;
-constexpr uint64_t PHILOX_W0 = 0x9E3779B97F4A7C15ull, PHILOX_W1 = 0xBB67AE8584CAA73Bull;
-constexpr uint64_t KEY1 = 0x6f63746f64726177ull;      // "octodraw"
-constexpr int TPB = 256;
 constexpr int64_t CHUNK = 1 << 18;                    // draws per log-posterior call (a multiple of TPB)
 constexpr int SEL_EPT = 17;                           // candidates per thread of k_topk
 constexpr int64_t SEL_SLAB = (int64_t)TPB * SEL_EPT;  // 4352 per block: 61 blocks per chunk, and (61 + 1)·64 candidates fit the merging block
 constexpr int64_t SEL_BLOCKS = (CHUNK + SEL_SLAB - 1) / SEL_SLAB;
 constexpr uint64_t NO_INDEX = ~0ull;
-constexpr int IC_N = 4;                               // inverse-CDF constants per prior
 static_assert((SEL_BLOCKS + 1) * OCTO_DRAWS_MAX_KEEP <= SEL_SLAB, "the merging block must hold every partial list and the running list");
 static_assert(CHUNK % TPB == 0, "chunk boundaries are block boundaries of the rejection pass");
-
-// Philox4x64-10 (Salmon et al. 2011), the variant NumPy ships: ten rounds, the key bumped after each.
-__device__ __forceinline__ void philox4x64(uint64_t k0, uint64_t k1, uint64_t c0, uint64_t c1, uint64_t c2, uint64_t c3, uint64_t (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t hi0 = __umul64hi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
-        const uint64_t hi1 = __umul64hi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += PHILOX_W0; k1 += PHILOX_W1;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
-// (2·(x >> 12) + 1)·2⁻⁵³: an odd multiple of 2⁻⁵³ below 1 — exact, never 0 or 1
-__device__ __forceinline__ double u01(uint64_t x) { return (double)(2 * (x >> 12) + 1) * 0x1p-53; }
 
 __device__ __forceinline__ double rejection_uniform(uint64_t seed, uint64_t i) {
     uint64_t r[4];
     philox4x64(seed, KEY1, i, 0, OCTO_DRAWS_PURPOSE_UNIFORM, 0, r);
     return u01(r[0]);
-}
-
-// Quantile of the prior at u, strictly inside the support the bijector assumes (prior_bounds). ic: constants made at octo_draws_create —
-//   Uniform {a, b − a} · LogUniform {log a, log b − log a} · truncated Normal {P0, ΔP, mirrored} with α = (lo − μ)/σ, β = (hi − μ)/σ:
-//   α < 0: z = Φ⁻¹(Φ(α) + u(Φ(β) − Φ(α))) · α >= 0 (a tail): z = −Φ⁻¹(Φ(−α) − u(Φ(−α) − Φ(−β))), so that the tail keeps its digits.
-// The coordinate d is the same for every lane, so the branch on the kind is wave-uniform.
-__device__ __forceinline__ double prior_quantile(const octo_prior& pr, const PriorBounds& B, const double* __restrict__ ic, double u) {
-    double x;
-    switch (pr.kind) {
-    case OCTO_PRIOR_UNIFORM: x = ic[0] + ic[1] * u; break;
-    case OCTO_PRIOR_LOGUNIFORM: x = exp(ic[0] + u * ic[1]); break;
-    case OCTO_PRIOR_NORMAL: x = pr.p0 + pr.p1 * normcdfinv(u); break;
-    case OCTO_PRIOR_TRUNCNORMAL: {
-        const bool mirrored = ic[2] != 0.0;
-        double p = mirrored ? ic[0] - u * ic[1] : ic[0] + u * ic[1];
-        p = fmin(fmax(p, 2.2250738585072014e-308), 1.0 - 0x1p-53);      // a probability that rounded onto 0 or 1 has no finite quantile
-        const double z = normcdfinv(p);
-        x = pr.p0 + pr.p1 * (mirrored ? -z : z);
-        break;
-    }
-    default: x = acos(1.0 - 2.0 * u); break;                              // Sine: distributions.jl:39
-    }
-    if (B.fa && !(x > B.a)) x = nextafter(B.a, INFINITY);
-    if (B.fb && !(x < B.b)) x = nextafter(B.b, -INFINITY);
-    return x;
-}
-
-// Bijectors.link (TruncatedBijector), the inverse of prior_link_lanes; host/priors.py: Prior.link is its executable statement
-__device__ __forceinline__ double prior_link_forward(const PriorBounds& B, double x) {
-    if (B.both) {
-        double u = (x - B.a) / (B.b - B.a);
-        u = fmin(fmax(u, 2.2250738585072014e-308), 1.0 - 0x1p-53);        // x is inside (a, b); the quotient may still round onto 1
-        return log(u) - log1p(-u);
-    }
-    if (B.fa) return log(x - B.a);
-    if (B.fb) return log(B.b - x);
-    return x;
 }
 
 struct DrawArgs {
@@ -297,44 +230,6 @@ __global__ __launch_bounds__(TPB) void k_scatter(const double* __restrict__ ll, 
     if (f && pos < cap) { o_idx[pos] = first + (uint64_t)k; o_ll[pos] = v; o_lp[pos] = lp[k]; }
 }
 
-}  // namespace
-
-struct octo_draws : CompanionBase {
-    octo_ctx* ctx = nullptr;
-    octo_model* model = nullptr;
-    int D = 0;
-    bool ctx_on_stream = false;      // the context was handed `stream` (octo_model_logpost_device) and may still name it as its last stream
-    octo_prior* d_priors = nullptr;
-    double *d_pc = nullptr, *d_ic = nullptr;
-    // chunk buffers
-    double *d_tt = nullptr, *d_lpt = nullptr;      // [D][CHUNK], [CHUNK]
-    // selection: candidate lists [(1 + SEL_BLOCKS)·keep], list 0 = the running list
-    double* d_clp = nullptr; uint64_t* d_cix = nullptr;
-    // per-draw arrays of a call (grown on demand): lp | ll, the block maxima, the block counts (+1)
-    double *d_lp = nullptr, *d_ll = nullptr, *d_pmax = nullptr; int64_t* d_cnt = nullptr;
-    int64_t cap_n = 0;
-    // outputs before they go to the host (grown on demand): index, ll, lp, θ [D][n]
-    uint64_t* d_oix = nullptr; double *d_oll = nullptr, *d_olp = nullptr, *d_oth = nullptr;
-    int64_t cap_o = 0;
-    double* d_max = nullptr;
-};
-
-namespace {
-
-int main_call(octo_draws* h, int rc, const char* what) {
-    h->ctx_on_stream = true;
-    if (rc == OCTO_OK) return rc;
-    const char* m = octo_last_error(h->ctx);
-    return fail(h, rc, std::string(what) + ": " + (m ? m : ""));
-}
-
-template <class T>
-int regrow(octo_draws* h, T*& p, int64_t n) {
-    if (p) { OCHK(h, hipFree(p)); p = nullptr; }
-    OCHK(h, hipMalloc((void**)&p, sizeof(T) * (size_t)n));
-    return OCTO_OK;
-}
-
 int ensure_chunk(octo_draws* h) {
     if (h->d_tt) return OCTO_OK;
     int rc;
@@ -475,6 +370,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
     (void)hipFree(h->d_priors); (void)hipFree(h->d_pc); (void)hipFree(h->d_ic); (void)hipFree(h->d_tt); (void)hipFree(h->d_lpt);
     (void)hipFree(h->d_clp); (void)hipFree(h->d_cix); (void)hipFree(h->d_lp); (void)hipFree(h->d_ll); (void)hipFree(h->d_pmax); (void)hipFree(h->d_cnt);
     (void)hipFree(h->d_oix); (void)hipFree(h->d_oll); (void)hipFree(h->d_olp); (void)hipFree(h->d_oth); (void)hipFree(h->d_max);
+    (void)hipFree(h->d_hmc); (void)hipFree(h->d_hst);
     delete h;
     return OCTO_OK;
 }

@@ -9,6 +9,9 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   guess_starting_position_device / octofit_rejection_device: the same two drivers with the draws, the link, the argmax and the
   accept / compaction step on the device too (host/draws.py: PriorDraws) — only the winners / the accepted chain cross PCIe.
 
+  octofit_pt_device: parallel tempering with a tempered HMC explorer, fresh prior draws at β = 0 and the swap step all on the device
+  (PriorDraws.hmc_step, host/tempering.py: TemperedSwap) — the device-resident twin of julia/OctofitterHIP.jl: octofit_pigeons_hip.
+
   pointwise_like_rows / waic: the pointwise log-likelihood at the grain model comparison needs — one column per DATUM (table row), not per
   table — and its WAIC / importance-sampling LOO sums, computed (and for waic reduced over the samples) on the device
   (host/pointwise.py: Pointwise).
@@ -127,6 +130,87 @@ def octofit_rejection_device(model, draws=100_000, seed=0):
     return dict(samples=r["samples"], loglike=r["loglike"], logpost=r["logpost"], draws=int(draws), n_accepted=r["n_accepted"],
                 acceptance_rate=r["n_accepted"] / draws, names=list(model.names), accept=accept, all_loglike=None,
                 index=r["index"], max_loglike=r["max_loglike"])
+
+
+def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None, betas=None, inv_mass=None, seed=0, n_adapt=None):
+    """Parallel tempering with every piece on the device — the device-resident twin of julia/OctofitterHIP.jl: octofit_pigeons_hip, with a
+    gradient-based explorer in place of its random walk: n_chains independent PT chains of n_temps replicas each (replica r of chain c is
+    walker r·n_chains + c, the layout of TemperedSwap), θ_t never leaving the device during a round. Single rank.
+
+    Initial states are prior draws 0 … n_temps·n_chains − 1 of the counter stream `seed`; inv_mass defaults to the per-coordinate variance of
+    prior draws 0 … 4095 in θ_t. A round is, in order:
+      1. β and ε of every replica from slot2rep (indexing only);
+      2. one PriorDraws.hmc_step over all n_temps·n_chains replicas (chain index = walker index, step = round);
+      3. the replicas at β = 0 replaced by fresh IID prior draws (Pigeons' sample_iid!, OctofitterPigeonsExt.jl:42-50) — the draw indices go on
+         from where the initial states stopped, n_chains a round — with ℓ of the new states from one forward log-posterior call;
+      4. TemperedSwap.swap_step on ℓ.
+    During the first n_adapt rounds (default: half of them) ε of every temperature follows log ε_t += (acc_t − 0.8)/√(round + 1), acc_t that
+    temperature's mean acceptance of the round. eps: the starting ε, a number or one per temperature (default 0.1).
+
+    Returns dict(samples [n_rounds, D, n_chains] natural domain, samples_t the same as θ_t, logpost [n_rounds, n_chains] — the β = 1 replica of
+    every chain after the exploration of each round —, hmc_acceptance [n_temps], swap_acceptance [n_temps − 1], eps [n_temps], betas, names,
+    and state = dict(theta_t [D, n_temps·n_chains], slot2rep, refreshed (walker indices the last round redrew), refreshed_first (their first
+    draw index)) for a driver that goes on, all NumPy)."""
+    import torch
+    from .draws import PriorDraws
+    from .tempering import TemperedSwap
+    T, Cn, R = int(n_temps), int(n_chains), int(n_rounds)
+    if T < 2 or Cn < 1 or R < 1:
+        raise ValueError("octofit_pt_device: n_temps >= 2, n_chains >= 1, n_rounds >= 1")
+    n_adapt = R // 2 if n_adapt is None else int(n_adapt)
+    fn = model.ln_like
+    dev = torch.device("cuda", fn.device_index)
+    W, D = T * Cn, int(model.D)
+    pd = PriorDraws(model)
+    try:
+        swap = TemperedSwap(fn, T, Cn, device=dev, seed=seed, betas=betas)
+        cold_last = float(swap.beta[-1]) == 0.0      # the ladder ends at the prior: its replicas are redrawn IID every round
+        if inv_mass is None:
+            inv_mass = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1)
+        inv_mass = torch.as_tensor(inv_mass, dtype=torch.float64, device=dev).contiguous()
+        log_eps = torch.log(torch.as_tensor(0.1 if eps is None else eps, dtype=torch.float64, device=dev).expand(T).clone())
+        theta_t = pd.sample(seed, 0, W, theta=False, logprior_t=False)[1]
+        next_draw = W
+        slots = torch.arange(T, dtype=torch.int32, device=dev).repeat(Cn, 1)
+        chains = torch.arange(Cn, device=dev)
+        acc_sum = torch.zeros(T, dtype=torch.float64, device=dev)
+        rec_t = torch.empty((R, D, Cn), dtype=torch.float64, device=dev)
+        rec_lp = torch.empty((R, Cn), dtype=torch.float64, device=dev)
+        refreshed = None
+        for r in range(R):
+            rep2slot = torch.empty_like(swap.slot2rep)
+            rep2slot.scatter_(1, swap.slot2rep.long(), slots)
+            slot_w = rep2slot.t().contiguous().reshape(-1).long()                     # the ladder slot of walker r·n_chains + c
+            lp, ll, _dH, acc = pd.hmc_step(theta_t, beta=swap.beta[slot_w], eps=torch.exp(log_eps)[slot_w], n_leapfrog=n_leapfrog,
+                                           inv_mass=inv_mass, seed=seed, step=r)
+            if cold_last:
+                refreshed = swap.slot2rep[:, T - 1].long() * Cn + chains
+                _, fresh, lpt = pd.sample(seed, next_draw, Cn, theta=False)
+                lp_f, _ = model.logpost_device(fresh, grad=False)
+                ll_f = lp_f - lpt
+                theta_t[:, refreshed] = fresh
+                lp[refreshed] = lp_f
+                ll[refreshed] = torch.where(torch.isfinite(ll_f), ll_f, torch.full_like(ll_f, -float("inf")))
+                next_draw += Cn
+            acc_t = torch.zeros(T, dtype=torch.float64, device=dev).index_add_(0, slot_w, acc.double()) / Cn
+            acc_sum += acc_t
+            if r < n_adapt:
+                log_eps += (acc_t - 0.8) / (r + 1) ** 0.5
+            target = swap.slot2rep[:, 0].long() * Cn + chains
+            rec_t[r] = theta_t[:, target]
+            rec_lp[r] = lp[target]
+            swap.swap_step(ll, r)
+        torch.cuda.synchronize(dev)
+        pairs = np.arange(T - 1)
+        attempts = np.array([(R + 1 - (t % 2)) // 2 for t in pairs]) * Cn            # pair (t, t + 1) is tried in the rounds of parity t % 2
+        samples_t = rec_t.cpu().numpy()
+        return dict(samples=np.stack([model.invlink(x) for x in samples_t]), samples_t=samples_t, logpost=rec_lp.cpu().numpy(),
+                    hmc_acceptance=(acc_sum / R).cpu().numpy(), swap_acceptance=swap.accepted.cpu().numpy()[:T - 1] / np.maximum(attempts, 1),
+                    eps=torch.exp(log_eps).cpu().numpy(), betas=swap.beta.cpu().numpy(), names=list(model.names),
+                    state=dict(theta_t=theta_t.cpu().numpy(), slot2rep=swap.slot2rep.cpu().numpy(),
+                               refreshed=None if refreshed is None else refreshed.cpu().numpy(), refreshed_first=next_draw - Cn if cold_last else None))
+    finally:
+        pd.close()
 
 
 def pointwise_like(model, θ_samples):

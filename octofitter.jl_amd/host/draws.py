@@ -5,6 +5,8 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     θ, θ_t, logprior_t = draws.sample(seed, first, n)       # torch tensors on the model's device: [D, n], [D, n], [n]
     θ, logpost, index = draws.best(seed, N, keep=8)         # NumPy: [D, keep], [keep], [keep]
     chain = draws.rejection(seed, N)                        # dict: samples [D, n_accepted], loglike, logpost, index, …
+    p = draws.momentum(seed, step, n)                       # torch [D, n]: the momenta of chains 0 … n − 1 at `step`
+    lp, ll, dH, acc = draws.hmc_step(θ_t, beta, eps=0.1, n_leapfrog=4, seed=seed, step=step)      # one tempered HMC step, θ_t updated in place
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -20,7 +22,7 @@ from . import capi, companion
 DRAWS_LIB_PATH = capi.PKG_DIR / "lib" / "liboctofitter_hip_draws.so"
 MAX_KEEP = 64                      # OCTO_DRAWS_MAX_KEEP
 PHILOX_KEY1 = 0x6F63746F64726177   # second key word; the first is the seed
-PURPOSE_PRIOR, PURPOSE_UNIFORM = 0, 1
+PURPOSE_PRIOR, PURPOSE_UNIFORM, PURPOSE_MOMENTUM, PURPOSE_ACCEPT = 0, 1, 2, 3
 
 c_uint64_p = C.POINTER(C.c_uint64)
 
@@ -34,6 +36,12 @@ _SIGS = {
     "octo_draws_best": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, capi.c_double_p, capi.c_double_p, c_uint64_p]),
     "octo_draws_rejection": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, capi.c_double_p, capi.c_double_p, capi.c_double_p,
                                          c_uint64_p, C.POINTER(C.c_int64), capi.c_double_p]),
+    "octo_draws_momentum_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_hmc_step_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_hmc_step": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, capi.c_double_p, capi.c_double_p,
+                                        capi.c_double_p, C.c_double, C.c_int32, capi.c_double_p, capi.c_double_p, capi.c_double_p, capi.c_double_p,
+                                        capi.c_double_p, C.POINTER(C.c_int32)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -118,6 +126,59 @@ class PriorDraws(companion.Handle):
         ns = min(int(n_acc.value), cap)
         return dict(samples=np.ascontiguousarray(th[:, :ns]), loglike=ll[:ns].copy(), logpost=lp[:ns].copy(), index=ix[:ns].copy(),
                     n_accepted=int(n_acc.value), max_loglike=float(mx.value))
+
+    def _device_vector(self, x, n, dev, what):
+        """None, or a float64 tensor of n elements on `dev` (a scalar is broadcast, host values are uploaded)."""
+        import torch
+        if x is None:
+            return None
+        t = torch.as_tensor(x, dtype=torch.float64, device=dev)
+        t = t.expand(n).contiguous() if t.ndim == 0 else t.contiguous()
+        if t.shape != (n,):
+            raise ValueError(f"{what}: expected {n} values, got a tensor of shape {tuple(t.shape)}")
+        return t
+
+    def momentum(self, seed, step, n, inv_mass=None, chain0=0, stream=None):
+        """The momenta p [D, n] of chains chain0 … chain0 + n − 1 at `step`: standard normals of the counter generator over √inv_mass."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        n = int(n)
+        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
+        p = torch.empty((self.D, n), dtype=torch.float64, device=dev)
+        self._check(self.lib.octo_draws_momentum_device(self._h, int(seed), int(step), int(chain0), n, n, None if im is None else im.data_ptr(),
+                                                        p.data_ptr(), self._stream(stream, dev)))
+        self._keep = (im,)
+        return p
+
+    def hmc_step(self, theta_t, beta=None, eps=None, n_leapfrog=4, inv_mass=None, seed=0, step=0, chain0=0, want_proposal=False, stream=None):
+        """One tempered HMC step of the W chains in theta_t (torch float64 [D, W] on the handle's device, rows contiguous; updated in
+        place where a chain accepts). beta: [W] or None (β = 1); eps: a number or [W]; inv_mass: [D] or None (1). A handle made from priors
+        alone explores the prior (β = 0) and returns None for logpost and loglike.
+        Returns (logpost [W], loglike [W], dH [W], accepted int32 [W][, proposal [D, W]]). Asynchronous on `stream`."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        if theta_t.dtype != torch.float64 or theta_t.ndim != 2 or theta_t.shape[0] != self.D or theta_t.device != dev or (theta_t.shape[1] and theta_t.stride(1) != 1):
+            raise ValueError(f"hmc_step: theta_t must be a float64 [D = {self.D}, W] tensor on {dev} with contiguous rows")
+        W = int(theta_t.shape[1])
+        ld = int(theta_t.stride(0)) if self.D > 1 and W else W
+        if eps is None:
+            raise ValueError("hmc_step: eps is required (a number, or one value per chain)")
+        per_chain = torch.is_tensor(eps) or np.ndim(eps) > 0
+        eps_w = self._device_vector(eps, W, dev, "eps") if per_chain else None
+        be = self._device_vector(beta, W, dev, "beta")
+        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
+        has_model = self.model is not None
+        lp = torch.empty(W, dtype=torch.float64, device=dev) if has_model else None
+        ll = torch.empty(W, dtype=torch.float64, device=dev) if has_model else None
+        dH = torch.empty(W, dtype=torch.float64, device=dev)
+        acc = torch.empty(W, dtype=torch.int32, device=dev)
+        prop = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev) if want_proposal else None
+        ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
+        self._check(self.lib.octo_draws_hmc_step_device(self._h, int(seed), int(step), int(chain0), W, ld, theta_t.data_ptr(), ptr(be), ptr(eps_w),
+                                                        0.0 if per_chain else float(eps), int(n_leapfrog), ptr(im), ptr(prop), ptr(lp), ptr(ll),
+                                                        dH.data_ptr(), acc.data_ptr(), self._stream(stream, dev)))
+        self._keep = (theta_t, be, eps_w, im)
+        return (lp, ll, dH, acc, prop) if want_proposal else (lp, ll, dH, acc)
 
     def close(self):
         if getattr(self, "_h", None) and self.model is not None and not getattr(self.model.ln_like, "_ctx", None):
