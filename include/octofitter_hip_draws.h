@@ -27,6 +27,9 @@
  * Purposes 0 and 1 keep counter word 3 = 0. The step is stated in full at its declaration, so that a restatement elsewhere (tests/hmc_reference.py)
  * and the device compute the same function.
  *
+ * The fourth is an optimiser: a batched L-BFGS that takes W chains from starting points (octo_draws_best's, say) to local optima of ℓπ
+ * (octo_draws_lbfgs_device), also stated in full at its declaration (tests/lbfgs_reference.py restates it). It draws no random number.
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -135,6 +138,70 @@ int32_t octo_draws_hmc_step(octo_draws* h, uint64_t seed, uint64_t step, uint64_
                             double* theta_t, const double* beta, const double* eps_w, double eps, int32_t n_leapfrog,
                             const double* inv_mass, double* theta_prop, double* logpost, double* loglike,
                             double* dH, int32_t* accepted);
+
+/* ---- Multi-start L-BFGS: W chains minimise f = −ℓπ over θ_t independently and in lockstep (stage 2 of the reference's initialisation,
+ * src/initialization.jl:188-289: optimise from the best prior draws). D, the priors and the model are the handle's; ℓπ and ∇ℓπ come from
+ * octo_model_logpost_device. Deterministic: no random number. The function is stated in full so that a restatement elsewhere
+ * (tests/lbfgs_reference.py) and the device compute the same thing.
+ *
+ * Scaling    v = d_inv_mass [D], a variance per coordinate with the meaning it has in the HMC step (NULL: v = 1). It defines the metric
+ *            ⟨a,b⟩_v = Σ_d v_d a_d b_d and ⟨a,b⟩_{1/v} = Σ_d a_d b_d / v_d. Every sum over d runs in index order.
+ * Open       f, g at x = θ_t. The chain is DEAD if f or any g_d is not finite (its θ_t is never written). Otherwise d = −v⊙g, gd = gᵀd,
+ *            t = min(1, 1/√⟨g,g⟩_v), trial = x + t·d; the ring is empty, the diagonal α = v, iters = 0, evals = 1.
+ * Round      one log-posterior call at the trial points of all W chains (evals += 1 of every ACTIVE chain), then per chain:
+ *   accept   iff f_t and every g_t,d are finite and f_t <= f + c1·t·gd, c1 = 1e-4. Then
+ *            1. s = trial − x, y = g_t − g; x, f, g take the trial values; iters += 1; the backtrack count returns to 0.
+ *            2. the pair (s, y, sᵀy) goes into a ring of m slots (over the oldest when full) iff sᵀy > 1e-10·√(⟨s,s⟩_{1/v}·⟨y,y⟩_v);
+ *            3. with a stored pair the Pathfinder diagonal: a = ⟨y,y⟩_α, b = sᵀy, c = ⟨s,s⟩_{1/α} (all with the α before the update),
+ *               α_d <- 1 / (a/(b·α_d) + y_d²/b − a·s_d²/(b·c·α_d²)) — the diagonal of the BFGS update of (a/b)·diag(1/α);
+ *            4. max_d |g_d|·√v_d <= gtol: status GTOL. Otherwise ftol > 0 and |f_old − f| <= ftol·max(1, |f|): status FTOL.
+ *            5. otherwise the new direction by the two-loop recursion over the stored pairs, newest first:
+ *                 q = g; for each pair: c_k = sᵀq / sᵀy, q −= c_k·y;  r = γ·v⊙q, γ = sᵀy/⟨y,y⟩_v of the newest pair (1 with none);
+ *                 for each pair, oldest first: r += (c_k − yᵀr / sᵀy)·s;  d = −r.
+ *               gd = gᵀd; if gd is not < 0 the ring is emptied and d = −v⊙g. t = 1, trial = x + t·d.
+ *   reject   t <- t/2, one more backtrack; more than 30 in a row: status LINESEARCH, the chain stays at x. Otherwise trial = x + t·d.
+ * A chain whose status is not ACTIVE is frozen: its trial point is x, the result there is ignored, and its θ_t and every output keep their
+ * bits for the rest of the call and across `resume`. */
+#define OCTO_DRAWS_LBFGS_MAX_M 8
+#define OCTO_DRAWS_LBFGS_ACTIVE     0
+#define OCTO_DRAWS_LBFGS_GTOL       1
+#define OCTO_DRAWS_LBFGS_FTOL       2
+#define OCTO_DRAWS_LBFGS_LINESEARCH 3
+#define OCTO_DRAWS_LBFGS_DEAD       4
+
+/* The two-loop recursion alone (step 5 without the descent test), a pure function of its inputs, for callers who keep their own history;
+ * the optimiser's kernel calls the same device routine. Asynchronous on hip_stream; the handle needs no model.
+ *   d_cnt  [W] int32   stored pairs of the chain, 0 … m (clamped)
+ *   d_head [W] int32   the slot the NEXT pair would take: the newest pair is in slot (head − 1) mod m, the one before it in (head − 2) mod m …
+ *   d_S, d_Y [m][D][ld]  slot-major; sᵀy of a slot is summed from them in index order
+ *   d_g [D][ld], d_inv_mass [D] or NULL = 1, d_dir [D][ld] out
+ * OCTO_EINVAL: NULL handle; m outside 1 … OCTO_DRAWS_LBFGS_MAX_M; W < 0, ld < W, W > 2^30; a NULL array other than d_inv_mass with W > 0. */
+int32_t octo_draws_lbfgs_direction_device(octo_draws* h, int64_t W, int64_t ld, int32_t m, const int32_t* d_cnt, const int32_t* d_head,
+                                          const double* d_S, const double* d_Y, const double* d_g, const double* d_inv_mass,
+                                          double* d_dir, void* hip_stream);
+
+/* The optimiser on DEVICE buffers, asynchronous on hip_stream: no host synchronisation, and no allocation once the handle's work arrays
+ * hold ((5 + 2m)·D + 2m + 11)·ld doubles (they grow behind the handle's own stream). resume = 0 opens and makes n_rounds rounds:
+ * n_rounds + 1 log-posterior calls. resume = 1 continues the state the handle holds with n_rounds more rounds: the same W, ld and m as the
+ * call before it, and d_theta_t as that call left it. Two calls of a and b rounds give the bits of one call of a + b.
+ *   d_theta_t       [D][ld]  in/out: x of every chain; a DEAD chain's column is never written
+ *   d_inv_mass      [D]      or NULL: v = 1
+ *   d_logpost       [W]      ℓπ at the returned θ_t (of a DEAD chain: what the callback gave)
+ *   d_gnorm         [W]      max_d |g_d|·√v_d there (of a DEAD chain: NaN)
+ *   d_status        [W]      int32 OCTO_DRAWS_LBFGS_*
+ *   d_iters, d_evals [W]     int32: accepted steps, log-posterior evaluations while the chain was ACTIVE (the opening one included)
+ *   d_inv_hess_diag [D][ld]  or NULL: α
+ * OCTO_EINVAL: NULL handle; a handle without a model (created with model = NULL, or detached); m outside 1 … OCTO_DRAWS_LBFGS_MAX_M;
+ * n_rounds < 0; W < 0, ld < W, W > 2^30; gtol or ftol not finite or < 0; resume without a previous call or with another W, ld or m; a NULL
+ * array other than d_inv_mass and d_inv_hess_diag with W > 0. */
+int32_t octo_draws_lbfgs_device(octo_draws* h, int64_t W, int64_t ld, double* d_theta_t, const double* d_inv_mass, int32_t m,
+                                int32_t n_rounds, double gtol, double ftol, int32_t resume, double* d_logpost, double* d_gnorm,
+                                int32_t* d_status, int32_t* d_iters, int32_t* d_evals, double* d_inv_hess_diag, void* hip_stream);
+
+/* The same optimisation (resume = 0) on HOST arrays of the same shapes, blocking, staged through the handle on its own stream: the same bits. */
+int32_t octo_draws_lbfgs(octo_draws* h, int64_t W, int64_t ld, double* theta_t, const double* inv_mass, int32_t m, int32_t n_rounds,
+                         double gtol, double ftol, double* logpost, double* gnorm, int32_t* status, int32_t* iters, int32_t* evals,
+                         double* inv_hess_diag);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // octo_draws_common.h — what the translation units of liboctofitter_hip_draws.so share: the handle, the counter generator and the prior
 // helpers on top of octo_model.h's device routines. octo_draws.hip (the draws and the two drivers that consume a batch of them) and
-// octo_draws_hmc.hip (the tempered HMC explorer) include it; everything but the handle lives in an unnamed namespace, one copy per unit.
+// octo_draws_hmc.hip (the tempered HMC explorer) and octo_draws_lbfgs.hip (the multi-start L-BFGS) include it; everything but the handle lives in an unnamed namespace, one copy per unit.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
 
@@ -100,6 +100,11 @@ struct octo_draws : CompanionBase {
     // the explorer (octo_draws_hmc.hip), grown on demand: its work arrays in one allocation, and the device side of the host-buffer call
     double* d_hmc = nullptr; int64_t cap_hmc = 0;
     double* d_hst = nullptr; int64_t cap_hst = 0;
+    // the L-BFGS (octo_draws_lbfgs.hip), grown on demand: the chains' state in one allocation with the shape it was opened for (lbf_m = 0:
+    // nothing to resume), and the coefficients of the direction call
+    double* d_lbf = nullptr; int64_t cap_lbf = 0;
+    int64_t lbf_W = 0, lbf_ld = 0; int32_t lbf_m = 0;
+    double* d_lbd = nullptr; int64_t cap_lbd = 0;
 };
 
 namespace {

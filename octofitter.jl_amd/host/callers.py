@@ -12,6 +12,9 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   octofit_pt_device: parallel tempering with a tempered HMC explorer, fresh prior draws at β = 0 and the swap step all on the device
   (PriorDraws.hmc_step, host/tempering.py: TemperedSwap) — the device-resident twin of julia/OctofitterHIP.jl: octofit_pigeons_hip.
 
+  optimize_starting_points_device: stage 2 of the reference's initialisation (src/initialization.jl:188-289) — a batched L-BFGS from the best
+  prior draws, every chain on the device (PriorDraws.lbfgs); the host reads one status vector a segment.
+
   pointwise_like_rows / waic: the pointwise log-likelihood at the grain model comparison needs — one column per DATUM (table row), not per
   table — and its WAIC / importance-sampling LOO sums, computed (and for waic reduced over the samples) on the device
   (host/pointwise.py: Pointwise).
@@ -209,6 +212,43 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
                     eps=torch.exp(log_eps).cpu().numpy(), betas=swap.beta.cpu().numpy(), names=list(model.names),
                     state=dict(theta_t=theta_t.cpu().numpy(), slot2rep=swap.slot2rep.cpu().numpy(),
                                refreshed=None if refreshed is None else refreshed.cpu().numpy(), refreshed_first=next_draw - Cn if cold_last else None))
+    finally:
+        pd.close()
+
+
+def optimize_starting_points_device(model, N=500_000, n_starts=64, seed=0, m=6, gtol=1e-6, ftol=0.0, max_rounds=1000, rounds_per_call=50, inv_mass=None):
+    """MAP candidates from the best prior draws: the n_starts (<= 64) best of draws 0 … N − 1 of the counter stream `seed` (PriorDraws.best),
+    each optimised by the batched L-BFGS of include/octofitter_hip_draws.h in θ_t, all chains in lockstep on the device. inv_mass, the
+    scaling of the optimiser, defaults to the per-coordinate variance of prior draws 0 … 4095 in θ_t (the default of octofit_pt_device). The
+    optimiser runs in segments of rounds_per_call rounds; the host reads the status between them and stops when no chain is active or after
+    max_rounds rounds.
+
+    Returns a dict in start order (best start first), NumPy: theta [D, n] natural domain, theta_t, logpost, start_logpost, status (LBFGS_* of
+    host/draws.py), gnorm, iters, evals, inv_hess_diag [D, n] (the Pathfinder diagonal in θ_t: a natural inv_mass for hmc_step), best (the index of
+    the highest ℓπ), names."""
+    import torch
+    from .draws import LBFGS_ACTIVE, PriorDraws
+    if max_rounds < 1 or rounds_per_call < 1:
+        raise ValueError("optimize_starting_points_device: max_rounds >= 1, rounds_per_call >= 1")
+    dev = torch.device("cuda", model.ln_like.device_index)
+    pd = PriorDraws(model)
+    try:
+        θ0, lp0, _ = pd.best(seed, N, keep=n_starts)
+        if inv_mass is None:
+            inv_mass = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1)
+        inv_mass = torch.as_tensor(inv_mass, dtype=torch.float64, device=dev).contiguous()
+        theta_t = torch.as_tensor(model.link(θ0), dtype=torch.float64, device=dev).contiguous()
+        done, r = 0, None
+        while done < max_rounds:
+            n = min(int(rounds_per_call), int(max_rounds) - done)
+            r = pd.lbfgs(theta_t, inv_mass=inv_mass, m=m, n_rounds=n, gtol=gtol, ftol=ftol, resume=done > 0, want_inv_hess_diag=True)
+            done += n
+            if not bool((r["status"] == LBFGS_ACTIVE).any()):      # the one read of a segment
+                break
+        tt = theta_t.cpu().numpy()
+        out = {k: v.cpu().numpy() for k, v in r.items()}
+        return dict(theta=model.invlink(tt), theta_t=tt, start_logpost=lp0, best=int(np.argmax(np.where(np.isfinite(out["logpost"]), out["logpost"], -np.inf))),
+                    names=list(model.names), **out)
     finally:
         pd.close()
 

@@ -7,6 +7,7 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     chain = draws.rejection(seed, N)                        # dict: samples [D, n_accepted], loglike, logpost, index, …
     p = draws.momentum(seed, step, n)                       # torch [D, n]: the momenta of chains 0 … n − 1 at `step`
     lp, ll, dH, acc = draws.hmc_step(θ_t, beta, eps=0.1, n_leapfrog=4, seed=seed, step=step)      # one tempered HMC step, θ_t updated in place
+    r = draws.lbfgs(θ_t, inv_mass=v, n_rounds=50)           # 50 rounds of L-BFGS on every column, θ_t updated in place: dict of device tensors
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -23,6 +24,8 @@ DRAWS_LIB_PATH = capi.PKG_DIR / "lib" / "liboctofitter_hip_draws.so"
 MAX_KEEP = 64                      # OCTO_DRAWS_MAX_KEEP
 PHILOX_KEY1 = 0x6F63746F64726177   # second key word; the first is the seed
 PURPOSE_PRIOR, PURPOSE_UNIFORM, PURPOSE_MOMENTUM, PURPOSE_ACCEPT = 0, 1, 2, 3
+LBFGS_MAX_M = 8                    # OCTO_DRAWS_LBFGS_MAX_M
+LBFGS_ACTIVE, LBFGS_GTOL, LBFGS_FTOL, LBFGS_LINESEARCH, LBFGS_DEAD = 0, 1, 2, 3, 4      # OCTO_DRAWS_LBFGS_*
 
 c_uint64_p = C.POINTER(C.c_uint64)
 
@@ -42,6 +45,12 @@ _SIGS = {
     "octo_draws_hmc_step": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, capi.c_double_p, capi.c_double_p,
                                         capi.c_double_p, C.c_double, C.c_int32, capi.c_double_p, capi.c_double_p, capi.c_double_p, capi.c_double_p,
                                         capi.c_double_p, C.POINTER(C.c_int32)]),
+    "octo_draws_lbfgs_direction_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_lbfgs_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_lbfgs": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, capi.c_double_p, capi.c_double_p, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                     capi.c_double_p, capi.c_double_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), capi.c_double_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -179,6 +188,60 @@ class PriorDraws(companion.Handle):
                                                         dH.data_ptr(), acc.data_ptr(), self._stream(stream, dev)))
         self._keep = (theta_t, be, eps_w, im)
         return (lp, ll, dH, acc, prop) if want_proposal else (lp, ll, dH, acc)
+
+    def _chain_matrix(self, x, what, name="theta_t"):
+        """(W, ld) of a float64 [D, W] tensor on the handle's device with contiguous rows."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        if x.dtype != torch.float64 or x.ndim != 2 or x.shape[0] != self.D or x.device != dev or (x.shape[1] and x.stride(1) != 1):
+            raise ValueError(f"{what}: {name} must be a float64 [D = {self.D}, W] tensor on {dev} with contiguous rows")
+        W = int(x.shape[1])
+        return W, (int(x.stride(0)) if self.D > 1 and W else W)
+
+    def lbfgs_direction(self, cnt, head, S, Y, g, inv_mass=None, stream=None):
+        """The two-loop recursion of every chain on its own history: d [D, W] = −H·g with H₀ = γ·diag(inv_mass). cnt, head: int32 [W] (stored
+        pairs; the slot the next pair would take); S, Y: float64 [m, D, W], slot-major, rows contiguous and of g's leading dimension; g: [D, W]. Asynchronous."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        W, ld = self._chain_matrix(g, "lbfgs_direction", "g")
+        m = int(S.shape[0]) if S.ndim == 3 else 0
+        if self.D == 1 and m > 1:
+            ld = int(S.stride(0))      # a single row: only the slots' distance says what the leading dimension is
+        for x, what in ((S, "S"), (Y, "Y")):
+            ok = x.dtype == torch.float64 and x.device == dev and tuple(x.shape) == (m, self.D, W)
+            if ok and W:
+                ok = x.stride(2) == 1 and (self.D == 1 or x.stride(1) == ld) and (m == 1 or x.stride(0) == self.D * ld)
+            if not ok:
+                raise ValueError(f"lbfgs_direction: {what} must be a float64 [m, D = {self.D}, W = {W}] tensor on {dev} with g's leading dimension")
+        cnt = torch.as_tensor(cnt, dtype=torch.int32, device=dev).contiguous()
+        head = torch.as_tensor(head, dtype=torch.int32, device=dev).contiguous()
+        if cnt.shape != (W,) or head.shape != (W,):
+            raise ValueError(f"lbfgs_direction: cnt and head take {W} values each")
+        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
+        out = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev)
+        self._check(self.lib.octo_draws_lbfgs_direction_device(self._h, W, ld, m, cnt.data_ptr(), head.data_ptr(), S.data_ptr(), Y.data_ptr(), g.data_ptr(),
+                                                               None if im is None else im.data_ptr(), out.data_ptr(), self._stream(stream, dev)))
+        self._keep = (cnt, head, S, Y, g, im)
+        return out
+
+    def lbfgs(self, theta_t, inv_mass=None, m=6, n_rounds=50, gtol=1e-6, ftol=0.0, resume=False, want_inv_hess_diag=False, stream=None):
+        """n_rounds rounds of the batched L-BFGS (include/octofitter_hip_draws.h states it) on the W chains in theta_t (torch float64 [D, W] on
+        the handle's device, rows contiguous; updated in place where a chain accepts). inv_mass: the scaling v, [D] or None (1). resume=True
+        goes on from the state the handle holds: the same theta_t, W and m as the call before.
+        Returns dict(logpost [W], gnorm [W], status int32 [W] (LBFGS_*), iters, evals int32 [W], inv_hess_diag [D, W] or None), device tensors.
+        Asynchronous on `stream`."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        W, ld = self._chain_matrix(theta_t, "lbfgs")
+        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
+        lp, gn = (torch.empty(W, dtype=torch.float64, device=dev) for _ in range(2))
+        status, iters, evals = (torch.empty(W, dtype=torch.int32, device=dev) for _ in range(3))
+        ihd = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev) if want_inv_hess_diag else None
+        self._check(self.lib.octo_draws_lbfgs_device(self._h, W, ld, theta_t.data_ptr(), None if im is None else im.data_ptr(), int(m), int(n_rounds),
+                                                     float(gtol), float(ftol), 1 if resume else 0, lp.data_ptr(), gn.data_ptr(), status.data_ptr(),
+                                                     iters.data_ptr(), evals.data_ptr(), None if ihd is None else ihd.data_ptr(), self._stream(stream, dev)))
+        self._keep = (theta_t, im)
+        return dict(logpost=lp, gnorm=gn, status=status, iters=iters, evals=evals, inv_hess_diag=ihd)
 
     def close(self):
         if getattr(self, "_h", None) and self.model is not None and not getattr(self.model.ln_like, "_ctx", None):
