@@ -30,6 +30,11 @@
  * The fourth is an optimiser: a batched L-BFGS that takes W chains from starting points (octo_draws_best's, say) to local optima of ℓπ
  * (octo_draws_lbfgs_device), also stated in full at its declaration (tests/lbfgs_reference.py restates it). It draws no random number.
  *
+ * The fifth is Pathfinder on those paths (octo_draws_pathfinder_device): a normal approximation at every accepted iterate, an ELBO estimate
+ * of each from a few draws, the best one kept, and draws from it (tests/pathfinder_reference.py restates it). Its two streams add
+ *   purpose 4: ELBO draw k of chain c at its iterate number it, counter (c, d / 4, 4, it·32 + k), coordinate d takes word d % 4
+ *   purpose 5: final draw j of chain c, counter (c, d / 4, 5, j)
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -47,6 +52,8 @@ extern "C" {
 #define OCTO_DRAWS_PURPOSE_UNIFORM 1
 #define OCTO_DRAWS_PURPOSE_MOMENTUM 2
 #define OCTO_DRAWS_PURPOSE_ACCEPT   3
+#define OCTO_DRAWS_PURPOSE_ELBO       4
+#define OCTO_DRAWS_PURPOSE_PATHFINDER 5
 
 typedef struct octo_draws octo_draws;
 
@@ -202,6 +209,75 @@ int32_t octo_draws_lbfgs_device(octo_draws* h, int64_t W, int64_t ld, double* d_
 int32_t octo_draws_lbfgs(octo_draws* h, int64_t W, int64_t ld, double* theta_t, const double* inv_mass, int32_t m, int32_t n_rounds,
                          double gtol, double ftol, double* logpost, double* gnorm, int32_t* status, int32_t* iters, int32_t* evals,
                          double* inv_hess_diag);
+
+/* ---- Pathfinder (Zhang, Carpenter, Gelman & Vehtari 2022) on the L-BFGS paths: stage 3 of the reference's initialisation. At every accepted
+ * iterate of a chain the L-BFGS state defines a normal approximation N(μ, Σ) of the posterior in θ_t; an ELBO estimate from a few draws scores
+ * it; the chain keeps the best; octo_draws_pathfinder_draw_device draws from the kept one. The function is stated in full so that a
+ * restatement elsewhere (tests/pathfinder_reference.py) and the device compute the same thing. D <= OCTO_DRAWS_PF_MAX_D.
+ *
+ * Write g = ∇f = −∇ℓπ at x, α the Pathfinder diagonal, and the chain's cnt stored pairs oldest first: pair k = 0 … cnt − 1 sits in slot
+ * (head − cnt + k) mod m. Every sum over a coordinate or a pair runs in index order.
+ * Fit        in the scaled space s̃ = s/√α, ỹ = y·√α, from H̃ = I; for each pair, oldest first:
+ *              w = H̃ỹ, ρ = 1/(s̃ᵀỹ), H̃_ij <- H̃_ij − ρ·(s̃_i·w_j + w_i·s̃_j) + ρ·(1 + ρ·ỹᵀw)·(s̃_i·s̃_j)      (the inverse-BFGS update).
+ *            Σ = diag(√α)·H̃·diag(√α) is the L-BFGS inverse Hessian with H₀ = diag(α): the matrix of the paper's compact form
+ *            diag(α) + [αY, S]·γ·[αY, S]ᵀ, dense because D <= 64 (2·cnt can exceed D, and a Cholesky factor is unique).
+ *            μ = x − √α ⊙ (H̃(√α ⊙ g)). L̃ is the lower Cholesky factor of H̃, row by row from the left: the pivot of column j is
+ *            H̃_jj − Σ_{k<j} L̃_jk², the entry below it (H̃_ij − Σ_{k<j} L̃_ik·L̃_jk)/L̃_jj. logdet Σ = Σ_d log α_d + 2·Σ_d log L̃_dd.
+ *            The fit fails (ok = 0) if an α_d or a pivot is not finite and > 0; a failed fit is no candidate. With cnt = 0, Σ = diag(α).
+ * Draw       φ = μ + √α ⊙ (L̃z), log q(φ) = −½(D·log 2π + logdet Σ + zᵀz). z_d = normcdfinv(uniform of word d % 4 of Philox(key, counter
+ *            (chain0 + c, d / 4, purpose, t))): purpose 4 and t = iters_c·32 + k for ELBO draw k of the chain's iterate number iters_c,
+ *            purpose 5 and t = j for final draw j. The counter depends on the chain and its own iterate count, never on the round or the batch.
+ * ELBO       (1/K)·Σ_k (ℓπ(φ_k) − log q(φ_k)), K = n_elbo; a draw with a non-finite ℓπ makes it −Inf.
+ * Selection  a chain keeps the fit with the greatest ELBO over its accepted iterates (those that ended an L-BFGS round with iters advanced;
+ *            one that reaches GTOL or FTOL included; the opening point is not fitted). The comparison is strict: the earliest fit wins a
+ *            tie, −Inf never wins. The fit uses x, g, α and the ring as they stand after the round. DEAD chains and chains that never
+ *            accept have no fit. n_fits counts the candidates (fits with ok = 1). */
+#define OCTO_DRAWS_PF_MAX_D 64
+#define OCTO_DRAWS_PF_MAX_ELBO_DRAWS 32
+
+/* The fit alone, a pure function of a caller's history (the twin of octo_draws_lbfgs_direction_device: the same d_cnt, d_head, d_S, d_Y; the
+ * Pathfinder kernel is the same kernel). Asynchronous on hip_stream; the handle needs no model.
+ *   d_x, d_g, d_alpha [D][ld]   in
+ *   d_mu     [D][ld]            μ
+ *   d_chol   [D(D+1)/2][ld]     L̃ packed row-major: L̃_ij (j <= i) in row i(i+1)/2 + j
+ *   d_logdet [W], d_ok [W] int32
+ *   n, d_z [n][D][ld] -> d_phi [n][D][ld]   the draw map applied to the caller's z (n = 0: both may be NULL); of a chain with ok = 0: undefined
+ * OCTO_ENOTSUP: D > OCTO_DRAWS_PF_MAX_D. OCTO_EINVAL: NULL handle; m outside 1 … OCTO_DRAWS_LBFGS_MAX_M; W < 0, ld < W, W > 2^30; n < 0,
+ * n·W > 2^30; a NULL array with W > 0 (d_z, d_phi: with n > 0). */
+int32_t octo_draws_pathfinder_fit_device(octo_draws* h, int64_t W, int64_t ld, int32_t m, const int32_t* d_cnt, const int32_t* d_head,
+                                         const double* d_S, const double* d_Y, const double* d_x, const double* d_g, const double* d_alpha,
+                                         double* d_mu, double* d_chol, double* d_logdet, int32_t* d_ok, int32_t n, const double* d_z,
+                                         double* d_phi, void* hip_stream);
+
+/* octo_draws_lbfgs_device with Pathfinder along the path: the arguments, the outputs and `resume` of that call (which it makes, one round at
+ * a time: d_theta_t and the L-BFGS outputs have the bits that call gives), and per round the fit of every chain whose iters advanced, n_elbo
+ * draws of each into a dense batch [D][n_elbo·W] (draw k of chain c in column k·W + c; a chain without a new fit sends its x and the
+ * result is ignored), ONE log-posterior call on the batch, the ELBO and the selection. n_rounds·2 + 1 log-posterior calls when resume = 0.
+ * Asynchronous on hip_stream, no host synchronisation, and no allocation once the work arrays hold (D² + 5D + 8)·ld doubles of fits (two per
+ * chain, the kept one and the candidate: promotion is a flag flip) and (D + 2)·n_elbo·W of the batch, besides those of the L-BFGS.
+ * resume = 1 continues the previous octo_draws_pathfinder_device call of the handle (no octo_draws_lbfgs_device call of the handle's in
+ * between, other than a resumed one); n_elbo may differ. A chain's outputs do not depend on W, ld or its position: only on chain0 + c.
+ *   d_elbo      [W]        the ELBO of the kept fit, −Inf without one
+ *   d_elbo_iter [W] int32  the iters of the kept fit, −1 without one
+ *   d_n_fits    [W] int32
+ * OCTO_ENOTSUP: D > OCTO_DRAWS_PF_MAX_D. OCTO_EINVAL: as octo_draws_lbfgs_device, W > 2^25, n_elbo outside 1 … OCTO_DRAWS_PF_MAX_ELBO_DRAWS,
+ * resume without a previous call of THIS function with the same W, ld and m, a NULL d_elbo, d_elbo_iter or d_n_fits with W > 0. */
+int32_t octo_draws_pathfinder_device(octo_draws* h, uint64_t seed, uint64_t chain0, int64_t W, int64_t ld, double* d_theta_t,
+                                     const double* d_inv_mass, int32_t m, int32_t n_rounds, double gtol, double ftol, int32_t n_elbo,
+                                     int32_t resume, double* d_logpost, double* d_gnorm, int32_t* d_status, int32_t* d_iters,
+                                     int32_t* d_evals, double* d_inv_hess_diag, double* d_elbo, int32_t* d_elbo_iter, int32_t* d_n_fits,
+                                     void* hip_stream);
+
+/* n_draws draws from the kept fit of every chain of the previous octo_draws_pathfinder_device call (the same W, ld, d_theta_t, chain0),
+ * and ONE log-posterior call on them. Asynchronous on hip_stream.
+ *   d_phi     [D][ld_out]  ld_out >= n_draws·W; draw j of chain c in column j·W + c
+ *   d_logq    [n_draws·W]  log q(φ)
+ *   d_logpost [n_draws·W]  ℓπ(φ)
+ * Of a chain without a fit: φ = its x, log q = NaN, ℓπ = −Inf.
+ * OCTO_ENOTSUP: D > OCTO_DRAWS_PF_MAX_D. OCTO_EINVAL: NULL handle; a handle without a model; n_draws < 1; W < 0, ld < W, n_draws·W > 2^30;
+ * ld_out < n_draws·W; no previous octo_draws_pathfinder_device call, or one with another W or ld; a NULL array with W > 0. */
+int32_t octo_draws_pathfinder_draw_device(octo_draws* h, uint64_t seed, uint64_t chain0, int64_t W, int64_t ld, const double* d_theta_t,
+                                          int32_t n_draws, int64_t ld_out, double* d_phi, double* d_logq, double* d_logpost, void* hip_stream);
 
 #ifdef __cplusplus
 }

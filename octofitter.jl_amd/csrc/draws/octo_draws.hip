@@ -370,7 +370,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
     (void)hipFree(h->d_priors); (void)hipFree(h->d_pc); (void)hipFree(h->d_ic); (void)hipFree(h->d_tt); (void)hipFree(h->d_lpt);
     (void)hipFree(h->d_clp); (void)hipFree(h->d_cix); (void)hipFree(h->d_lp); (void)hipFree(h->d_ll); (void)hipFree(h->d_pmax); (void)hipFree(h->d_cnt);
     (void)hipFree(h->d_oix); (void)hipFree(h->d_oll); (void)hipFree(h->d_olp); (void)hipFree(h->d_oth); (void)hipFree(h->d_max);
-    (void)hipFree(h->d_hmc); (void)hipFree(h->d_hst); (void)hipFree(h->d_lbf); (void)hipFree(h->d_lbd);
+    (void)hipFree(h->d_hmc); (void)hipFree(h->d_hst); (void)hipFree(h->d_lbf); (void)hipFree(h->d_lbd); (void)hipFree(h->d_pf); (void)hipFree(h->d_pfb);
     delete h;
     return OCTO_OK;
 }

@@ -1,6 +1,6 @@
 // octo_draws_common.h — what the translation units of liboctofitter_hip_draws.so share: the handle, the counter generator and the prior
 // helpers on top of octo_model.h's device routines. octo_draws.hip (the draws and the two drivers that consume a batch of them) and
-// octo_draws_hmc.hip (the tempered HMC explorer) and octo_draws_lbfgs.hip (the multi-start L-BFGS) include it; everything but the handle lives in an unnamed namespace, one copy per unit.
+// octo_draws_hmc.hip (the tempered HMC explorer), octo_draws_lbfgs.hip (the multi-start L-BFGS) and octo_draws_pathfinder.hip (Pathfinder on its paths) include it; everything but the handle lives in an unnamed namespace, one copy per unit.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
 
@@ -105,6 +105,11 @@ struct octo_draws : CompanionBase {
     double* d_lbf = nullptr; int64_t cap_lbf = 0;
     int64_t lbf_W = 0, lbf_ld = 0; int32_t lbf_m = 0;
     double* d_lbd = nullptr; int64_t cap_lbd = 0;
+    // Pathfinder (octo_draws_pathfinder.hip), grown on demand: the chains' fits in one allocation with the shape it was opened for (pf_W = 0:
+    // nothing to resume or to draw from), and the transient work of a call (the ELBO batch; √α of the fit call)
+    double* d_pf = nullptr; int64_t cap_pf = 0;
+    int64_t pf_W = 0, pf_ld = 0;
+    double* d_pfb = nullptr; int64_t cap_pfb = 0;
 };
 
 namespace {

@@ -15,6 +15,10 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   optimize_starting_points_device: stage 2 of the reference's initialisation (src/initialization.jl:188-289) — a batched L-BFGS from the best
   prior draws, every chain on the device (PriorDraws.lbfgs); the host reads one status vector a segment.
 
+  pathfinder_device: stage 3 — multi-path Pathfinder from the same starts (PriorDraws.pathfinder / pathfinder_draw): a normal fit at every
+  L-BFGS iterate, the one with the best ELBO kept per path, draws from every path's fit, and PSIS importance resampling of their union
+  (host/psis.py: Psis.loo on one row). Only the resampling is on the host.
+
   pointwise_like_rows / waic: the pointwise log-likelihood at the grain model comparison needs — one column per DATUM (table row), not per
   table — and its WAIC / importance-sampling LOO sums, computed (and for waic reduced over the samples) on the device
   (host/pointwise.py: Pointwise).
@@ -250,6 +254,64 @@ def optimize_starting_points_device(model, N=500_000, n_starts=64, seed=0, m=6, 
         return dict(theta=model.invlink(tt), theta_t=tt, start_logpost=lp0, best=int(np.argmax(np.where(np.isfinite(out["logpost"]), out["logpost"], -np.inf))),
                     names=list(model.names), **out)
     finally:
+        pd.close()
+
+
+def pathfinder_device(model, N=500_000, n_paths=64, n_draws=1000, n_draws_per_path=256, n_elbo=5, seed=0, m=6, gtol=1e-6, ftol=0.0, max_rounds=1000,
+                      rounds_per_call=50, inv_mass=None):
+    """Multi-path Pathfinder (Zhang et al. 2022; stage 3 of the reference's initialisation, src/initialization.jl:188-289) on the device:
+    the starts and the default inv_mass of optimize_starting_points_device (path p starts from the p-th best of draws 0 … N − 1 and owns
+    chain p of the counter stream `seed`), PriorDraws.pathfinder in segments of rounds_per_call rounds until no chain is active or after
+    max_rounds, then n_draws_per_path draws from every path's kept fit (PriorDraws.pathfinder_draw). The log ratios r = ℓπ − log q over the
+    union of the draws of paths with a fit (non-finite: −Inf) are Pareto-smoothed by Psis.loo on the one row ll = −r, and n_draws are
+    resampled with replacement from the smoothed weights on the host: NumPy Generator(Philox(key=seed)), inverse CDF.
+
+    Returns a dict, NumPy: theta [D, n_draws] natural domain, theta_t, logpost [n_draws], path [n_draws] (the start index of each draw),
+    pareto_k, log_ratios and log_weights (over the n_paths·n_draws_per_path draws, draw j of path p at j·n_paths + p), per path elbo,
+    elbo_iter, n_fits and the outputs of optimize_starting_points_device (path_theta, path_theta_t, path_logpost, start_logpost, status, gnorm,
+    iters, evals, inv_hess_diag, best), names. Raises RuntimeError if no path has a fit."""
+    import torch
+    from .draws import LBFGS_ACTIVE, PriorDraws
+    from .psis import Psis
+    if max_rounds < 1 or rounds_per_call < 1 or n_draws < 1 or n_draws_per_path < 1:
+        raise ValueError("pathfinder_device: max_rounds, rounds_per_call, n_draws, n_draws_per_path >= 1")
+    dev = torch.device("cuda", model.ln_like.device_index)
+    pd, ps = PriorDraws(model), None
+    try:
+        θ0, lp0, _ = pd.best(seed, N, keep=n_paths)
+        if inv_mass is None:
+            inv_mass = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1)
+        inv_mass = torch.as_tensor(inv_mass, dtype=torch.float64, device=dev).contiguous()
+        theta_t = torch.as_tensor(model.link(θ0), dtype=torch.float64, device=dev).contiguous()
+        done, r = 0, None
+        while done < max_rounds:
+            n = min(int(rounds_per_call), int(max_rounds) - done)
+            r = pd.pathfinder(theta_t, inv_mass=inv_mass, m=m, n_rounds=n, gtol=gtol, ftol=ftol, resume=done > 0, want_inv_hess_diag=True, seed=seed, n_elbo=n_elbo)
+            done += n
+            if not bool((r["status"] == LBFGS_ACTIVE).any()):      # the one read of a segment
+                break
+        if not bool((r["elbo_iter"] >= 0).any()):
+            raise RuntimeError("pathfinder_device: no path has a fit (every start is dead, never accepted a step, or has only non-finite ELBOs)")
+        phi, logq, lp = pd.pathfinder_draw(theta_t, n_draws_per_path, seed=seed)
+        ratio = lp - logq
+        ratio = torch.where(torch.isfinite(ratio), ratio, torch.full_like(ratio, -float("inf")))
+        ps = Psis(device=model.ln_like.device_index)
+        s = ps.loo((-ratio).reshape(1, -1), weights=True)      # its step 1 smooths r − max r
+        lw = s["log_weights"][0].cpu().numpy()
+        cdf = np.cumsum(np.exp(lw - lw.max()))
+        u = np.random.Generator(np.random.Philox(key=int(seed))).random(int(n_draws))
+        pick = np.minimum(np.searchsorted(cdf, u * cdf[-1], side="right"), cdf.size - 1)
+        W = theta_t.shape[1]
+        tt = phi[:, torch.as_tensor(pick, device=dev)].cpu().numpy()
+        path_tt = theta_t.cpu().numpy()
+        out = {k: v.cpu().numpy() for k, v in r.items()}
+        path_lp = out.pop("logpost")
+        return dict(theta=model.invlink(tt), theta_t=tt, logpost=lp.cpu().numpy()[pick], path=(pick % W).astype(np.int64), pareto_k=float(s["pareto_k"][0]),
+                    log_ratios=ratio.cpu().numpy(), log_weights=lw, path_theta=model.invlink(path_tt), path_theta_t=path_tt, path_logpost=path_lp,
+                    start_logpost=lp0, best=int(np.argmax(np.where(np.isfinite(path_lp), path_lp, -np.inf))), names=list(model.names), **out)
+    finally:
+        if ps is not None:
+            ps.close()
         pd.close()
 
 

@@ -8,6 +8,8 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     p = draws.momentum(seed, step, n)                       # torch [D, n]: the momenta of chains 0 … n − 1 at `step`
     lp, ll, dH, acc = draws.hmc_step(θ_t, beta, eps=0.1, n_leapfrog=4, seed=seed, step=step)      # one tempered HMC step, θ_t updated in place
     r = draws.lbfgs(θ_t, inv_mass=v, n_rounds=50)           # 50 rounds of L-BFGS on every column, θ_t updated in place: dict of device tensors
+    r = draws.pathfinder(θ_t, inv_mass=v, n_rounds=50, seed=seed)      # the same rounds with Pathfinder's fits along the path: also elbo, elbo_iter, n_fits
+    φ, logq, logpost = draws.pathfinder_draw(θ_t, 256, seed=seed)      # [D, 256·W], [256·W], [256·W]: draws from every chain's kept fit
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -23,9 +25,11 @@ from . import capi, companion
 DRAWS_LIB_PATH = capi.PKG_DIR / "lib" / "liboctofitter_hip_draws.so"
 MAX_KEEP = 64                      # OCTO_DRAWS_MAX_KEEP
 PHILOX_KEY1 = 0x6F63746F64726177   # second key word; the first is the seed
-PURPOSE_PRIOR, PURPOSE_UNIFORM, PURPOSE_MOMENTUM, PURPOSE_ACCEPT = 0, 1, 2, 3
+PURPOSE_PRIOR, PURPOSE_UNIFORM, PURPOSE_MOMENTUM, PURPOSE_ACCEPT, PURPOSE_ELBO, PURPOSE_PATHFINDER = 0, 1, 2, 3, 4, 5
 LBFGS_MAX_M = 8                    # OCTO_DRAWS_LBFGS_MAX_M
 LBFGS_ACTIVE, LBFGS_GTOL, LBFGS_FTOL, LBFGS_LINESEARCH, LBFGS_DEAD = 0, 1, 2, 3, 4      # OCTO_DRAWS_LBFGS_*
+PF_MAX_D = 64                      # OCTO_DRAWS_PF_MAX_D
+PF_MAX_ELBO_DRAWS = 32             # OCTO_DRAWS_PF_MAX_ELBO_DRAWS
 
 c_uint64_p = C.POINTER(C.c_uint64)
 
@@ -51,6 +55,11 @@ _SIGS = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "octo_draws_lbfgs": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, capi.c_double_p, capi.c_double_p, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                      capi.c_double_p, capi.c_double_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), capi.c_double_p]),
+    "octo_draws_pathfinder_fit_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 11 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_pathfinder_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
+                                                 C.c_double, C.c_int32, C.c_int32] + [C.c_void_p] * 10),
+    "octo_draws_pathfinder_draw_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -203,20 +212,7 @@ class PriorDraws(companion.Handle):
         pairs; the slot the next pair would take); S, Y: float64 [m, D, W], slot-major, rows contiguous and of g's leading dimension; g: [D, W]. Asynchronous."""
         import torch
         dev = torch.device("cuda", self.device_index)
-        W, ld = self._chain_matrix(g, "lbfgs_direction", "g")
-        m = int(S.shape[0]) if S.ndim == 3 else 0
-        if self.D == 1 and m > 1:
-            ld = int(S.stride(0))      # a single row: only the slots' distance says what the leading dimension is
-        for x, what in ((S, "S"), (Y, "Y")):
-            ok = x.dtype == torch.float64 and x.device == dev and tuple(x.shape) == (m, self.D, W)
-            if ok and W:
-                ok = x.stride(2) == 1 and (self.D == 1 or x.stride(1) == ld) and (m == 1 or x.stride(0) == self.D * ld)
-            if not ok:
-                raise ValueError(f"lbfgs_direction: {what} must be a float64 [m, D = {self.D}, W = {W}] tensor on {dev} with g's leading dimension")
-        cnt = torch.as_tensor(cnt, dtype=torch.int32, device=dev).contiguous()
-        head = torch.as_tensor(head, dtype=torch.int32, device=dev).contiguous()
-        if cnt.shape != (W,) or head.shape != (W,):
-            raise ValueError(f"lbfgs_direction: cnt and head take {W} values each")
+        W, ld, m, cnt, head = self._history("lbfgs_direction", cnt, head, S, Y, g)
         im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
         out = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev)
         self._check(self.lib.octo_draws_lbfgs_direction_device(self._h, W, ld, m, cnt.data_ptr(), head.data_ptr(), S.data_ptr(), Y.data_ptr(), g.data_ptr(),
@@ -242,6 +238,96 @@ class PriorDraws(companion.Handle):
                                                      iters.data_ptr(), evals.data_ptr(), None if ihd is None else ihd.data_ptr(), self._stream(stream, dev)))
         self._keep = (theta_t, im)
         return dict(logpost=lp, gnorm=gn, status=status, iters=iters, evals=evals, inv_hess_diag=ihd)
+
+    def _history(self, what, cnt, head, S, Y, g):
+        """(W, ld, m, cnt, head) of a caller's L-BFGS history: g [D, W], S and Y [m, D, W] slot-major with g's leading dimension."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        W, ld = self._chain_matrix(g, what, "g")
+        m = int(S.shape[0]) if S.ndim == 3 else 0
+        if self.D == 1 and m > 1:
+            ld = int(S.stride(0))      # a single row: only the slots' distance says what the leading dimension is
+        for x, name in ((S, "S"), (Y, "Y")):
+            ok = x.dtype == torch.float64 and x.device == dev and tuple(x.shape) == (m, self.D, W)
+            if ok and W:
+                ok = x.stride(2) == 1 and (self.D == 1 or x.stride(1) == ld) and (m == 1 or x.stride(0) == self.D * ld)
+            if not ok:
+                raise ValueError(f"{what}: {name} must be a float64 [m, D = {self.D}, W = {W}] tensor on {dev} with g's leading dimension")
+        cnt = torch.as_tensor(cnt, dtype=torch.int32, device=dev).contiguous()
+        head = torch.as_tensor(head, dtype=torch.int32, device=dev).contiguous()
+        if cnt.shape != (W,) or head.shape != (W,):
+            raise ValueError(f"{what}: cnt and head take {W} values each")
+        return W, ld, m, cnt, head
+
+    def pathfinder_fit(self, cnt, head, S, Y, x, g, alpha, z=None, stream=None):
+        """Pathfinder's normal fit of every chain on its own history (include/octofitter_hip_draws.h states it): cnt, head, S, Y as in
+        lbfgs_direction; x, g (= −∇ℓπ), alpha: float64 [D, W] of one leading dimension; z: None or [n, D, W] standard normals of the same
+        leading dimension. Returns dict(mu [D, W], chol [D(D+1)/2, W] (L̃ packed row-major), logdet [W], ok int32 [W], phi [n, D, W] or None):
+        Σ = diag(√α)·L̃L̃ᵀ·diag(√α), φ = μ + √α ⊙ (L̃z). Asynchronous."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        W, ld, m, cnt, head = self._history("pathfinder_fit", cnt, head, S, Y, g)
+        for t, name in ((x, "x"), (alpha, "alpha")):
+            if self._chain_matrix(t, "pathfinder_fit", name)[0] != W or (self.D > 1 and W and t.stride(0) != g.stride(0)):
+                raise ValueError(f"pathfinder_fit: {name} must have g's shape and leading dimension")
+        n = 0 if z is None else int(z.shape[0])
+        if self.D == 1 and m <= 1 and n > 1:
+            ld = int(z.stride(0))      # a single row and a single slot: only the draws' distance says what the leading dimension is
+        if z is not None:
+            ok = z.dtype == torch.float64 and z.device == dev and tuple(z.shape) == (n, self.D, W)
+            if ok and W:
+                ok = z.stride(2) == 1 and (self.D == 1 or z.stride(1) == ld) and (n == 1 or z.stride(0) == self.D * ld)
+            if not ok:
+                raise ValueError(f"pathfinder_fit: z must be a float64 [n, D = {self.D}, W = {W}] tensor on {dev} with g's leading dimension")
+        P = self.D * (self.D + 1) // 2
+        mu = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev)
+        chol = torch.empty_strided((P, W), (ld, 1), dtype=torch.float64, device=dev)
+        logdet = torch.empty(W, dtype=torch.float64, device=dev)
+        ok = torch.empty(W, dtype=torch.int32, device=dev)
+        phi = torch.empty_strided((n, self.D, W), (self.D * ld, ld, 1), dtype=torch.float64, device=dev) if n else None
+        self._check(self.lib.octo_draws_pathfinder_fit_device(self._h, W, ld, m, cnt.data_ptr(), head.data_ptr(), S.data_ptr(), Y.data_ptr(), x.data_ptr(),
+                                                              g.data_ptr(), alpha.data_ptr(), mu.data_ptr(), chol.data_ptr(), logdet.data_ptr(), ok.data_ptr(), n,
+                                                              None if z is None else z.data_ptr(), None if phi is None else phi.data_ptr(),
+                                                              self._stream(stream, dev)))
+        self._keep = (cnt, head, S, Y, x, g, alpha, z)
+        return dict(mu=mu, chol=chol, logdet=logdet, ok=ok, phi=phi)
+
+    def pathfinder(self, theta_t, inv_mass=None, m=6, n_rounds=50, gtol=1e-6, ftol=0.0, resume=False, want_inv_hess_diag=False, seed=0, chain0=0, n_elbo=5,
+                   stream=None):
+        """lbfgs (the same arguments, the same bits in theta_t and in its outputs) with Pathfinder along the path: after every round the
+        normal fit of each chain that accepted, its ELBO from n_elbo draws of the counter stream (seed, chain0 + c), and the best fit kept
+        on the handle for pathfinder_draw. resume=True goes on from the previous pathfinder call.
+        Returns lbfgs's dict plus elbo [W] (−Inf without a fit), elbo_iter int32 [W] (the iters of the kept fit, −1 without one), n_fits int32 [W].
+        Asynchronous on `stream`."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        W, ld = self._chain_matrix(theta_t, "pathfinder")
+        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
+        lp, gn, elbo = (torch.empty(W, dtype=torch.float64, device=dev) for _ in range(3))
+        status, iters, evals, elbo_iter, n_fits = (torch.empty(W, dtype=torch.int32, device=dev) for _ in range(5))
+        ihd = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev) if want_inv_hess_diag else None
+        self._check(self.lib.octo_draws_pathfinder_device(self._h, int(seed), int(chain0), W, ld, theta_t.data_ptr(), None if im is None else im.data_ptr(), int(m),
+                                                          int(n_rounds), float(gtol), float(ftol), int(n_elbo), 1 if resume else 0, lp.data_ptr(), gn.data_ptr(),
+                                                          status.data_ptr(), iters.data_ptr(), evals.data_ptr(), None if ihd is None else ihd.data_ptr(),
+                                                          elbo.data_ptr(), elbo_iter.data_ptr(), n_fits.data_ptr(), self._stream(stream, dev)))
+        self._keep = (theta_t, im)
+        return dict(logpost=lp, gnorm=gn, status=status, iters=iters, evals=evals, inv_hess_diag=ihd, elbo=elbo, elbo_iter=elbo_iter, n_fits=n_fits)
+
+    def pathfinder_draw(self, theta_t, n_draws, seed=0, chain0=0, stream=None):
+        """n_draws draws from the kept fit of every chain of the previous pathfinder call (theta_t as that call left it, the same chain0):
+        (φ [D, n_draws·W] in θ_t, draw j of chain c in column j·W + c; log q [n_draws·W]; ℓπ [n_draws·W]). A chain without a fit gives its
+        x, log q = NaN and ℓπ = −Inf. Asynchronous on `stream`."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        W, ld = self._chain_matrix(theta_t, "pathfinder_draw")
+        n = int(n_draws)
+        cols = max(n, 0) * W
+        phi = torch.empty((self.D, cols), dtype=torch.float64, device=dev)
+        logq, lp = (torch.empty(cols, dtype=torch.float64, device=dev) for _ in range(2))
+        self._check(self.lib.octo_draws_pathfinder_draw_device(self._h, int(seed), int(chain0), W, ld, theta_t.data_ptr(), n, cols, phi.data_ptr(), logq.data_ptr(),
+                                                               lp.data_ptr(), self._stream(stream, dev)))
+        self._keep = (theta_t,)
+        return phi, logq, lp
 
     def close(self):
         if getattr(self, "_h", None) and self.model is not None and not getattr(self.model.ln_like, "_ctx", None):
