@@ -11,7 +11,7 @@
 //               and the running list. No atomics.
 //   k_loglike   ll = lp − logprior_t (non-finite -> −Inf) and the per-block maximum; k_max the maximum of those.
 //   k_count / k_scan / k_scatter   accept flags (recomputed, never stored), per-block counts, their exclusive scan, ordered scatter.
-// The handle, the counter generator and the prior helpers are in octo_draws_common.h, shared with the explorer (octo_draws_hmc.hip).
+// The handle, the counter generator and the prior helpers are in octo_draws_common.h, shared with the other units.
 #include "octo_draws_common.h"
 
 namespace {
@@ -21,7 +21,8 @@ constexpr int SEL_EPT = 17;                           // candidates per thread o
 constexpr int64_t SEL_SLAB = (int64_t)TPB * SEL_EPT;  // 4352 per block: 61 blocks per chunk, and (61 + 1)·64 candidates fit the merging block
 constexpr int64_t SEL_BLOCKS = (CHUNK + SEL_SLAB - 1) / SEL_SLAB;
 constexpr uint64_t NO_INDEX = ~0ull;
-static_assert((SEL_BLOCKS + 1) * OCTO_DRAWS_MAX_KEEP <= SEL_SLAB, "the merging block must hold every partial list and the running list");
+constexpr int64_t SEL_LISTS = (1 + SEL_BLOCKS) * OCTO_DRAWS_MAX_KEEP;      // list 0 = the running list
+static_assert(SEL_LISTS <= SEL_SLAB, "the merging block must hold every partial list and the running list");
 static_assert(CHUNK % TPB == 0, "chunk boundaries are block boundaries of the rejection pass");
 
 __device__ __forceinline__ double rejection_uniform(uint64_t seed, uint64_t i) {
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(TPB) void k_draw(DrawArgs a) {
     const bool want_t = a.theta_t != nullptr || a.lpt != nullptr;
     double lp = 0.0;
     bool healed = false;
-    if (a.lpt && a.d0 > 0) { lp = a.lpt[tl]; healed = lp == -1.7976931348623157e308; }
+    if (a.lpt && a.d0 > 0) { lp = a.lpt[tl]; healed = lp == HEALED; }
     uint64_t r[4];
     philox4x64(a.seed, KEY1, i, (uint64_t)(a.d0 >> 2), OCTO_DRAWS_PURPOSE_PRIOR, 0, r);
 #pragma unroll
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(TPB) void k_draw(DrawArgs a) {
             lp += pv;
         }
     }
-    if (a.lpt && live) a.lpt[t] = healed ? -1.7976931348623157e308 : lp;
+    if (a.lpt && live) a.lpt[t] = healed ? HEALED : lp;
 }
 
 // ---- selection ---------------------------------------------------------------------------------------------------------------------------
@@ -230,41 +231,11 @@ __global__ __launch_bounds__(TPB) void k_scatter(const double* __restrict__ ll, 
     if (f && pos < cap) { o_idx[pos] = first + (uint64_t)k; o_ll[pos] = v; o_lp[pos] = lp[k]; }
 }
 
-int ensure_chunk(octo_draws* h) {
-    if (h->d_tt) return OCTO_OK;
-    int rc;
-    if ((rc = regrow(h, h->d_tt, (int64_t)h->D * CHUNK))) return rc;
-    if ((rc = regrow(h, h->d_lpt, CHUNK))) return rc;
-    if ((rc = regrow(h, h->d_clp, (1 + SEL_BLOCKS) * OCTO_DRAWS_MAX_KEEP))) return rc;
-    if ((rc = regrow(h, h->d_cix, (1 + SEL_BLOCKS) * OCTO_DRAWS_MAX_KEEP))) return rc;
-    return regrow(h, h->d_max, 1);
-}
-
-int ensure_draw_arrays(octo_draws* h, int64_t n) {
-    if (n <= h->cap_n) return OCTO_OK;
-    OCHK(h, hipStreamSynchronize(h->stream));
-    h->cap_n = 0;
-    int rc;
-    if ((rc = regrow(h, h->d_lp, n))) return rc;
-    if ((rc = regrow(h, h->d_ll, n))) return rc;
-    if ((rc = regrow(h, h->d_pmax, (n + TPB - 1) / TPB))) return rc;
-    if ((rc = regrow(h, h->d_cnt, (n + TPB - 1) / TPB + 1))) return rc;
-    h->cap_n = n;
-    return OCTO_OK;
-}
-
-int ensure_outputs(octo_draws* h, int64_t n) {
-    if (n <= h->cap_o) return OCTO_OK;
-    OCHK(h, hipStreamSynchronize(h->stream));
-    h->cap_o = 0;
-    int rc;
-    if ((rc = regrow(h, h->d_oix, n))) return rc;
-    if ((rc = regrow(h, h->d_oll, n))) return rc;
-    if ((rc = regrow(h, h->d_olp, n))) return rc;
-    if ((rc = regrow(h, h->d_oth, n * h->D))) return rc;
-    h->cap_o = n;
-    return OCTO_OK;
-}
+// The three groups of work arrays, each one allocation laid out by its function of octo_draws_layout.h and kept while it is large enough
+// (a failed growth leaves the group empty): the chunk buffers, the per-draw arrays of n draws, the outputs of n draws.
+int ensure_chunk(octo_draws* h, ChunkBufs& k) { return grow_to(h, h->d_chunk, h->cap_chunk, k, chunk_bufs, (int64_t)h->D, CHUNK, SEL_LISTS); }
+int ensure_draw_arrays(octo_draws* h, int64_t n, DrawArrays& a) { return grow_to(h, h->d_arr, h->cap_arr, a, draw_arrays, n, (n + TPB - 1) / TPB); }
+int ensure_outputs(octo_draws* h, int64_t n, Outputs& o) { return grow_to(h, h->d_out, h->cap_out, o, outputs, (int64_t)h->D, n); }
 
 // draws [first, first + n) or the listed ones, enqueued on st in launches of at most 2³⁰ draws
 int launch_draw(octo_draws* h, hipStream_t st, uint64_t seed, uint64_t first, const uint64_t* d_idx, int64_t n, int64_t ld,
@@ -278,7 +249,7 @@ int launch_draw(octo_draws* h, hipStream_t st, uint64_t seed, uint64_t first, co
         a.seed = seed; a.first = first + (uint64_t)o;
         a.n = std::min(PIECE, n - o); a.ld = ld;
         a.theta = d_theta ? d_theta + o : nullptr; a.theta_t = d_theta_t ? d_theta_t + o : nullptr; a.lpt = d_lpt ? d_lpt + o : nullptr;
-        for (a.d0 = 0; a.d0 < h->D; a.d0 += 4) hipLaunchKernelGGL(k_draw, dim3((unsigned)((a.n + TPB - 1) / TPB)), dim3(TPB), 0, st, a);
+        for (a.d0 = 0; a.d0 < h->D; a.d0 += 4) hipLaunchKernelGGL(k_draw, grid_of(a.n), dim3(TPB), 0, st, a);
     }
     OCHK(h, hipGetLastError());
     return OCTO_OK;
@@ -287,8 +258,7 @@ int launch_draw(octo_draws* h, hipStream_t st, uint64_t seed, uint64_t first, co
 int check_range(octo_draws* h, const char* who, uint64_t first, int64_t N, bool need_model) {
     if (N < 1) return fail(h, OCTO_EINVAL, std::string(who) + ": N >= 1");
     if (first + (uint64_t)N < first) return fail(h, OCTO_EINVAL, std::string(who) + ": first + N overflows the draw index");
-    if (need_model && (!h->model || !h->ctx)) return fail(h, OCTO_EINVAL, std::string(who) + ": the handle has no model (created without one, or detached)");
-    return OCTO_OK;
+    return need_model ? check_model(h, who) : OCTO_OK;
 }
 
 double normcdf_host(double z) { return 0.5 * std::erfc(-z * 0.70710678118654752440); }
@@ -367,10 +337,8 @@ int32_t octo_draws_destroy(octo_draws* h) {
         }
         if (release) (void)hipStreamDestroy(h->stream);
     }
-    (void)hipFree(h->d_priors); (void)hipFree(h->d_pc); (void)hipFree(h->d_ic); (void)hipFree(h->d_tt); (void)hipFree(h->d_lpt);
-    (void)hipFree(h->d_clp); (void)hipFree(h->d_cix); (void)hipFree(h->d_lp); (void)hipFree(h->d_ll); (void)hipFree(h->d_pmax); (void)hipFree(h->d_cnt);
-    (void)hipFree(h->d_oix); (void)hipFree(h->d_oll); (void)hipFree(h->d_olp); (void)hipFree(h->d_oth); (void)hipFree(h->d_max);
-    (void)hipFree(h->d_hmc); (void)hipFree(h->d_hst); (void)hipFree(h->d_lbf); (void)hipFree(h->d_lbd); (void)hipFree(h->d_pf); (void)hipFree(h->d_pfb);
+    for (void* p : std::initializer_list<void*>{h->d_priors, h->d_pc, h->d_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb})
+        (void)hipFree(p);
     delete h;
     return OCTO_OK;
 }
@@ -403,24 +371,25 @@ int32_t octo_draws_best(octo_draws* h, uint64_t seed, uint64_t first, int64_t N,
     if (keep > N) return fail(h, OCTO_EINVAL, "octo_draws_best: keep <= N");
     if (!theta_out || !logpost_out || !index_out) return fail(h, OCTO_EINVAL, "octo_draws_best: null output");
     OCHK(h, hipSetDevice(h->device));
-    { int rc = ensure_chunk(h); if (rc) return rc; }
-    { int rc = ensure_draw_arrays(h, std::min(N, CHUNK)); if (rc) return rc; }
-    { int rc = ensure_outputs(h, OCTO_DRAWS_MAX_KEEP); if (rc) return rc; }
+    ChunkBufs k; DrawArrays a; Outputs o;
+    { int rc = ensure_chunk(h, k); if (rc) return rc; }
+    { int rc = ensure_draw_arrays(h, std::min(N, CHUNK), a); if (rc) return rc; }
+    { int rc = ensure_outputs(h, OCTO_DRAWS_MAX_KEEP, o); if (rc) return rc; }
     const hipStream_t st = h->stream;
     // the running list starts empty: every byte 0xFF = (NaN, NO_INDEX), which k_topk reads as no candidate
-    OCHK(h, hipMemsetAsync(h->d_clp, 0xFF, sizeof(double) * keep, st));
-    OCHK(h, hipMemsetAsync(h->d_cix, 0xFF, sizeof(uint64_t) * keep, st));
+    OCHK(h, hipMemsetAsync(k.clp, 0xFF, sizeof(double) * keep, st));
+    OCHK(h, hipMemsetAsync(k.cix, 0xFF, sizeof(uint64_t) * keep, st));
     for (int64_t done = 0; done < N; done += CHUNK) {
         const int64_t n = std::min(CHUNK, N - done);
-        { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, h->d_tt, nullptr); if (rc) return rc; }
-        { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, h->d_tt, CHUNK, n, h->d_lp, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+        { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, k.tt, nullptr); if (rc) return rc; }
+        { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, k.tt, CHUNK, n, a.lp, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
         const int64_t nb = (n + SEL_SLAB - 1) / SEL_SLAB;
-        hipLaunchKernelGGL(k_topk, dim3((unsigned)nb), dim3(TPB), 0, st, h->d_lp, (const uint64_t*)nullptr, first + (uint64_t)done, n, keep, (int64_t)1, h->d_clp, h->d_cix);
-        hipLaunchKernelGGL(k_topk, dim3(1), dim3(TPB), 0, st, h->d_clp, h->d_cix, (uint64_t)0, (1 + nb) * keep, keep, (int64_t)0, h->d_clp, h->d_cix);
+        hipLaunchKernelGGL(k_topk, dim3((unsigned)nb), dim3(TPB), 0, st, a.lp, (const uint64_t*)nullptr, first + (uint64_t)done, n, keep, (int64_t)1, k.clp, k.cix);
+        hipLaunchKernelGGL(k_topk, dim3(1), dim3(TPB), 0, st, k.clp, k.cix, (uint64_t)0, (1 + nb) * keep, keep, (int64_t)0, k.clp, k.cix);
         OCHK(h, hipGetLastError());
     }
-    OCHK(h, hipMemcpyAsync(logpost_out, h->d_clp, sizeof(double) * keep, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpyAsync(index_out, h->d_cix, sizeof(uint64_t) * keep, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(logpost_out, k.clp, sizeof(double) * keep, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(index_out, k.cix, sizeof(uint64_t) * keep, hipMemcpyDeviceToHost, st));
     OCHK(h, hipStreamSynchronize(st));
     // places no finite log-posterior took: −Inf and the lowest draw indices not listed yet
     uint64_t next = first;
@@ -435,9 +404,9 @@ int32_t octo_draws_best(octo_draws* h, uint64_t seed, uint64_t first, int64_t N,
         logpost_out[r] = -INFINITY;
     }
     // θ of the winners, from the counter
-    OCHK(h, hipMemcpyAsync(h->d_oix, index_out, sizeof(uint64_t) * keep, hipMemcpyHostToDevice, st));
-    { int rc = launch_draw(h, st, seed, 0, h->d_oix, keep, keep, h->d_oth, nullptr, nullptr); if (rc) return rc; }
-    OCHK(h, hipMemcpyAsync(theta_out, h->d_oth, sizeof(double) * keep * h->D, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(o.ix, index_out, sizeof(uint64_t) * keep, hipMemcpyHostToDevice, st));
+    { int rc = launch_draw(h, st, seed, 0, o.ix, keep, keep, o.theta, nullptr, nullptr); if (rc) return rc; }
+    OCHK(h, hipMemcpyAsync(theta_out, o.theta, sizeof(double) * keep * h->D, hipMemcpyDeviceToHost, st));
     OCHK(h, hipStreamSynchronize(st));
     return OCTO_OK;
 }
@@ -449,45 +418,46 @@ int32_t octo_draws_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64
     if (cap < 0 || !n_accepted) return fail(h, OCTO_EINVAL, "octo_draws_rejection: cap >= 0 and n_accepted are required");
     if (cap > 0 && (!theta_out || !loglike_out || !logpost_out || !index_out)) return fail(h, OCTO_EINVAL, "octo_draws_rejection: null output with cap > 0");
     OCHK(h, hipSetDevice(h->device));
-    { int rc = ensure_chunk(h); if (rc) return rc; }
-    { int rc = ensure_draw_arrays(h, N); if (rc) return rc; }
+    ChunkBufs k; DrawArrays a; Outputs o;
+    { int rc = ensure_chunk(h, k); if (rc) return rc; }
+    { int rc = ensure_draw_arrays(h, N, a); if (rc) return rc; }
     const hipStream_t st = h->stream;
     const int64_t nblk = (N + TPB - 1) / TPB;
     // pass 1: ll of every draw, chunk by chunk (chunk boundaries are block boundaries), and its maximum
     for (int64_t done = 0; done < N; done += CHUNK) {
         const int64_t n = std::min(CHUNK, N - done);
-        { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, h->d_tt, h->d_lpt); if (rc) return rc; }
-        { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, h->d_tt, CHUNK, n, h->d_lp + done, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
-        hipLaunchKernelGGL(k_loglike, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, h->d_lp + done, h->d_lpt, n, h->d_ll + done, h->d_pmax + done / TPB);
+        { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, k.tt, k.lpt); if (rc) return rc; }
+        { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, k.tt, CHUNK, n, a.lp + done, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+        hipLaunchKernelGGL(k_loglike, grid_of(n), dim3(TPB), 0, st, a.lp + done, k.lpt, n, a.ll + done, a.pmax + done / TPB);
         OCHK(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_max, dim3(1), dim3(TPB), 0, st, h->d_pmax, nblk, h->d_max);
+    hipLaunchKernelGGL(k_max, dim3(1), dim3(TPB), 0, st, a.pmax, nblk, k.max);
     OCHK(h, hipGetLastError());
     double mx = 0.0;
-    OCHK(h, hipMemcpyAsync(&mx, h->d_max, sizeof(double), hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(&mx, k.max, sizeof(double), hipMemcpyDeviceToHost, st));
     OCHK(h, hipStreamSynchronize(st));
     if (max_loglike) *max_loglike = mx;
     *n_accepted = 0;
     if (!std::isfinite(mx))      // sampling.jl:194-197
         return fail(h, OCTO_EINVAL, "All " + std::to_string(N) + " prior samples produced non-finite log-likelihoods. Check your model and priors.");
     // pass 2: flags -> block counts -> offsets -> ordered scatter
-    { int rc = ensure_outputs(h, std::max<int64_t>(std::min(cap, N), 1)); if (rc) return rc; }
+    { int rc = ensure_outputs(h, std::max<int64_t>(std::min(cap, N), 1), o); if (rc) return rc; }
     const int64_t room = std::min(cap, N);
-    hipLaunchKernelGGL(k_count, dim3((unsigned)nblk), dim3(TPB), 0, st, h->d_ll, N, h->d_max, seed, first, h->d_cnt);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(TPB), 0, st, h->d_cnt, nblk);
-    hipLaunchKernelGGL(k_scatter, dim3((unsigned)nblk), dim3(TPB), 0, st, h->d_ll, h->d_lp, N, h->d_max, seed, first, h->d_cnt, room, h->d_oix, h->d_oll, h->d_olp);
+    hipLaunchKernelGGL(k_count, grid_of(N), dim3(TPB), 0, st, a.ll, N, k.max, seed, first, a.cnt);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(TPB), 0, st, a.cnt, nblk);
+    hipLaunchKernelGGL(k_scatter, grid_of(N), dim3(TPB), 0, st, a.ll, a.lp, N, k.max, seed, first, a.cnt, room, o.ix, o.ll, o.lp);
     OCHK(h, hipGetLastError());
     int64_t total = 0;
-    OCHK(h, hipMemcpyAsync(&total, h->d_cnt + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(&total, a.cnt + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     OCHK(h, hipStreamSynchronize(st));
     *n_accepted = total;
     const int64_t ns = std::min(total, room);
     if (ns == 0) return OCTO_OK;
-    { int rc = launch_draw(h, st, seed, 0, h->d_oix, ns, ns, h->d_oth, nullptr, nullptr); if (rc) return rc; }
-    OCHK(h, hipMemcpyAsync(index_out, h->d_oix, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpyAsync(loglike_out, h->d_oll, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpyAsync(logpost_out, h->d_olp, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpy2DAsync(theta_out, sizeof(double) * cap, h->d_oth, sizeof(double) * ns, sizeof(double) * ns, h->D, hipMemcpyDeviceToHost, st));
+    { int rc = launch_draw(h, st, seed, 0, o.ix, ns, ns, o.theta, nullptr, nullptr); if (rc) return rc; }
+    OCHK(h, hipMemcpyAsync(index_out, o.ix, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(loglike_out, o.ll, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(logpost_out, o.lp, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpy2DAsync(theta_out, sizeof(double) * cap, o.theta, sizeof(double) * ns, sizeof(double) * ns, h->D, hipMemcpyDeviceToHost, st));
     OCHK(h, hipStreamSynchronize(st));
     return OCTO_OK;
 }

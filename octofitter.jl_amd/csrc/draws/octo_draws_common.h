@@ -1,6 +1,8 @@
-// octo_draws_common.h — what the translation units of liboctofitter_hip_draws.so share: the handle, the counter generator and the prior
-// helpers on top of octo_model.h's device routines. octo_draws.hip (the draws and the two drivers that consume a batch of them) and
-// octo_draws_hmc.hip (the tempered HMC explorer), octo_draws_lbfgs.hip (the multi-start L-BFGS) and octo_draws_pathfinder.hip (Pathfinder on its paths) include it; everything but the handle lives in an unnamed namespace, one copy per unit.
+// octo_draws_common.h — what the translation units of liboctofitter_hip_draws.so share: the handle, the counter generator, the prior
+// helpers on top of octo_model.h's device routines, and the argument checks their functions repeat. Four units include it: octo_draws.hip
+// (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC explorer), octo_draws_lbfgs.hip (the
+// multi-start L-BFGS) and octo_draws_pathfinder.hip (Pathfinder on its paths). Everything but the handle lives in an unnamed namespace,
+// one copy per unit. How the handle's work allocations are cut into their parts is octo_draws_layout.h.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
 
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "octo_companion_host.h"
+#include "octo_draws_layout.h"
 #include "octo_model.h"
 #include "octofitter_hip_draws.h"
 
@@ -24,6 +27,8 @@ constexpr uint64_t PHILOX_W0 = 0x9E3779B97F4A7C15ull, PHILOX_W1 = 0xBB67AE8584CA
 constexpr uint64_t KEY1 = 0x6f63746f64726177ull;      // "octodraw"
 constexpr int TPB = 256;
 constexpr int IC_N = 4;                               // inverse-CDF constants per prior
+constexpr int64_t MAX_CHAINS = (int64_t)1 << 30;      // one launch: 2²² blocks
+constexpr double HEALED = -1.7976931348623157e308;    // the sentinel of a healed prior (k_model_fwd)
 
 // Philox4x64-10 (Salmon et al. 2011), the variant NumPy ships: ten rounds, the key bumped after each.
 __device__ __forceinline__ void philox4x64(uint64_t k0, uint64_t k1, uint64_t c0, uint64_t c1, uint64_t c2, uint64_t c3, uint64_t (&o)[4]) {
@@ -86,17 +91,11 @@ struct octo_draws : CompanionBase {
     bool ctx_on_stream = false;      // the context was handed a stream (octo_model_logpost_device) and may still name it as its last stream
     octo_prior* d_priors = nullptr;
     double *d_pc = nullptr, *d_ic = nullptr;
-    // chunk buffers
-    double *d_tt = nullptr, *d_lpt = nullptr;      // [D][CHUNK], [CHUNK]
-    // selection: candidate lists [(1 + SEL_BLOCKS)·keep], list 0 = the running list
-    double* d_clp = nullptr; uint64_t* d_cix = nullptr;
-    // per-draw arrays of a call (grown on demand): lp | ll, the block maxima, the block counts (+1)
-    double *d_lp = nullptr, *d_ll = nullptr, *d_pmax = nullptr; int64_t* d_cnt = nullptr;
-    int64_t cap_n = 0;
-    // outputs before they go to the host (grown on demand): index, ll, lp, θ [D][n]
-    uint64_t* d_oix = nullptr; double *d_oll = nullptr, *d_olp = nullptr, *d_oth = nullptr;
-    int64_t cap_o = 0;
-    double* d_max = nullptr;
+    // the drivers (octo_draws.hip), one allocation per group: the chunk buffers and candidate lists (fixed size), the per-draw arrays of a
+    // call and the outputs before they go to the host (both grown on demand)
+    double* d_chunk = nullptr; int64_t cap_chunk = 0;
+    double* d_arr = nullptr; int64_t cap_arr = 0;
+    double* d_out = nullptr; int64_t cap_out = 0;
     // the explorer (octo_draws_hmc.hip), grown on demand: its work arrays in one allocation, and the device side of the host-buffer call
     double* d_hmc = nullptr; int64_t cap_hmc = 0;
     double* d_hst = nullptr; int64_t cap_hst = 0;
@@ -121,11 +120,29 @@ inline int main_call(octo_draws* h, int rc, const char* what) {
     return fail(h, rc, std::string(what) + ": " + (m ? m : ""));
 }
 
-template <class T>
-int regrow(octo_draws* h, T*& p, int64_t n) {
-    if (p) { OCHK(h, hipFree(p)); p = nullptr; }
-    OCHK(h, hipMalloc((void**)&p, sizeof(T) * (size_t)n));
-    return OCTO_OK;
+inline dim3 grid_of(int64_t n) { return dim3((unsigned)((n + TPB - 1) / TPB)); }
+
+// the allocation (p, cap) grown to hold layout(args…), and its parts
+template <class S, class F, class... A>
+int grow_to(octo_draws* h, double*& p, int64_t& cap, S& parts, F layout, A... args) {
+    const int rc = grow(h, p, cap, carve_size(layout, args...));
+    parts = carve_at(p, layout, args...);
+    return rc;
+}
+
+// The argument checks the functions share: who = the function's name, the rest of the message is the same in each.
+inline int check_model(octo_draws* h, const char* who) {
+    return h->model && h->ctx ? OCTO_OK : fail(h, OCTO_EINVAL, std::string(who) + ": the handle has no model (created without one, or detached)");
+}
+inline int check_m(octo_draws* h, const char* who, int32_t m) {
+    return m >= 1 && m <= OCTO_DRAWS_LBFGS_MAX_M ? OCTO_OK : fail(h, OCTO_EINVAL, std::string(who) + ": m must be 1 ... OCTO_DRAWS_LBFGS_MAX_M");
+}
+inline int check_chains(octo_draws* h, const char* who, int64_t W, int64_t ld, int64_t limit, const char* limit_text) {      // "2^30": limit as the message spells it
+    return W >= 0 && ld >= W && W <= limit ? OCTO_OK : fail(h, OCTO_EINVAL, std::string(who) + ": need 0 <= W <= ld, W <= " + limit_text);
+}
+inline int check_tolerances(octo_draws* h, const char* who, double gtol, double ftol) {
+    if (!(std::isfinite(gtol) && gtol >= 0.0)) return fail(h, OCTO_EINVAL, std::string(who) + ": gtol must be finite and >= 0");
+    return std::isfinite(ftol) && ftol >= 0.0 ? OCTO_OK : fail(h, OCTO_EINVAL, std::string(who) + ": ftol must be finite and >= 0");
 }
 
 }  // namespace

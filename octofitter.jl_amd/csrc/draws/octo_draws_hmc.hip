@@ -12,7 +12,6 @@
 
 namespace {
 
-constexpr double HEALED = -1.7976931348623157e308;      // the sentinel of a healed prior (k_model_fwd, k_draw)
 enum { HMC_OPEN = 0, HMC_STEP = 1, HMC_LAST = 2 };
 
 struct MomentumArgs {
@@ -135,10 +134,8 @@ __global__ __launch_bounds__(TPB) void k_hmc_leap(HmcArgs a) {
 void launch_momentum(hipStream_t st, uint64_t seed, uint64_t step, uint64_t chain0, int64_t n, int64_t ld, int32_t D, const double* d_inv_mass, double* d_p) {
     MomentumArgs m;
     m.inv_mass = d_inv_mass; m.seed = seed; m.step = step; m.chain0 = chain0; m.n = n; m.ld = ld; m.D = D; m.p = d_p;
-    for (m.d0 = 0; m.d0 < D; m.d0 += 4) hipLaunchKernelGGL(k_hmc_momentum, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, m);
+    for (m.d0 = 0; m.d0 < D; m.d0 += 4) hipLaunchKernelGGL(k_hmc_momentum, grid_of(n), dim3(TPB), 0, st, m);
 }
-
-constexpr int64_t MAX_CHAINS = (int64_t)1 << 30;      // one launch: 2²² blocks
 
 }  // namespace
 
@@ -161,7 +158,7 @@ int32_t octo_draws_hmc_step_device(octo_draws* h, uint64_t seed, uint64_t step, 
                                    double* d_theta_prop, double* d_logpost, double* d_loglike, double* d_dH, int32_t* d_accepted, void* hip_stream) {
     if (!h) return OCTO_EINVAL;
     if (n_leapfrog < 1) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: n_leapfrog >= 1");
-    if (W < 0 || ld < W || W > MAX_CHAINS) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: need 0 <= W <= ld, W <= 2^30");
+    if (int rc = check_chains(h, "octo_draws_hmc_step_device", W, ld, MAX_CHAINS, "2^30")) return rc;
     if (!d_eps && !(eps > 0.0 && std::isfinite(eps))) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: eps must be finite and > 0 when d_eps is NULL");
     const bool has_model = h->model && h->ctx;
     if (!has_model && (d_logpost || d_loglike))
@@ -170,26 +167,23 @@ int32_t octo_draws_hmc_step_device(octo_draws* h, uint64_t seed, uint64_t step, 
     if (!d_theta_t || !d_accepted) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: d_theta_t and d_accepted are required");
     OCHK(h, hipSetDevice(h->device));
     const hipStream_t st = stream_of(h, hip_stream);
-    const int64_t D = h->D, plane = D * ld;
-    { int rc = grow(h, h->d_hmc, h->cap_hmc, 4 * plane + 4 * ld); if (rc) return rc; }
+    HmcWork w;
+    if (int rc = grow_to(h, h->d_hmc, h->cap_hmc, w, hmc_work, (int64_t)h->D, ld)) return rc;
     HmcArgs a;
     std::memset(&a, 0, sizeof(a));
     a.priors = h->d_priors; a.pc = h->d_pc; a.beta = d_beta; a.eps_w = d_eps; a.inv_mass = d_inv_mass; a.eps = eps;
     a.seed = seed; a.step = step; a.chain0 = chain0; a.W = W; a.ld = ld; a.D = h->D; a.has_model = has_model ? 1 : 0;
     a.theta_t = d_theta_t;
-    a.q = h->d_hmc; a.p = a.q + plane; a.gpr = a.p + plane;
-    double* glp = a.gpr + plane;
-    double* lp = glp + plane;
-    a.lp0 = lp + ld; a.lpt0 = a.lp0 + ld; a.K0 = a.lpt0 + ld;
-    if (has_model) { a.glp = glp; a.lp = lp; }
+    a.q = w.q; a.p = w.p; a.gpr = w.gpr; a.lp0 = w.lp0; a.lpt0 = w.lpt0; a.K0 = w.K0;
+    if (has_model) { a.glp = w.glp; a.lp = w.lp; }
     a.theta_prop = d_theta_prop; a.o_lp = d_logpost; a.o_ll = d_loglike; a.o_dH = d_dH; a.o_acc = d_accepted;
-    const dim3 grid((unsigned)((W + TPB - 1) / TPB)), block(TPB);
+    const dim3 grid = grid_of(W), block(TPB);
     launch_momentum(st, seed, step, chain0, W, ld, h->D, d_inv_mass, a.p);
     OCHK(h, hipGetLastError());
-    if (has_model) { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, d_theta_t, ld, W, lp, glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+    if (has_model) { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, d_theta_t, ld, W, w.lp, w.glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
     hipLaunchKernelGGL(k_hmc_leap<HMC_OPEN>, grid, block, 0, st, a);
     for (int s = 1; s <= n_leapfrog; ++s) {
-        if (has_model) { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, a.q, ld, W, lp, glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+        if (has_model) { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, a.q, ld, W, w.lp, w.glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
         if (s < n_leapfrog) hipLaunchKernelGGL(k_hmc_leap<HMC_STEP>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(k_hmc_leap<HMC_LAST>, grid, block, 0, st, a);
     }
@@ -208,33 +202,24 @@ int32_t octo_draws_hmc_step(octo_draws* h, uint64_t seed, uint64_t step, uint64_
     OCHK(h, hipSetDevice(h->device));
     const hipStream_t st = h->stream;
     const int64_t D = h->D, plane = D * ld;
-    // θ_t | proposal | β | ε | ℓπ | ℓ | dH | flags (int32, in a double's room each) | inv_mass
-    { int rc = grow(h, h->d_hst, h->cap_hst, 2 * plane + 6 * ld + D); if (rc) return rc; }
-    double* d_th = h->d_hst;
-    double* d_pr = d_th + plane;
-    double* d_be = d_pr + plane;
-    double* d_ep = d_be + ld;
-    double* d_lp = d_ep + ld;
-    double* d_ll = d_lp + ld;
-    double* d_dh = d_ll + ld;
-    int32_t* d_ac = (int32_t*)(d_dh + ld);
-    double* d_im = d_dh + 2 * ld;
-    OCHK(h, hipMemcpyAsync(d_th, theta_t, sizeof(double) * plane, hipMemcpyHostToDevice, st));
-    if (beta) OCHK(h, hipMemcpyAsync(d_be, beta, sizeof(double) * W, hipMemcpyHostToDevice, st));
-    if (eps_w) OCHK(h, hipMemcpyAsync(d_ep, eps_w, sizeof(double) * W, hipMemcpyHostToDevice, st));
-    if (inv_mass) OCHK(h, hipMemcpyAsync(d_im, inv_mass, sizeof(double) * D, hipMemcpyHostToDevice, st));
+    HmcStaging d;
+    if (int rc = grow_to(h, h->d_hst, h->cap_hst, d, hmc_staging, D, ld)) return rc;
+    OCHK(h, hipMemcpyAsync(d.theta_t, theta_t, sizeof(double) * plane, hipMemcpyHostToDevice, st));
+    if (beta) OCHK(h, hipMemcpyAsync(d.beta, beta, sizeof(double) * W, hipMemcpyHostToDevice, st));
+    if (eps_w) OCHK(h, hipMemcpyAsync(d.eps, eps_w, sizeof(double) * W, hipMemcpyHostToDevice, st));
+    if (inv_mass) OCHK(h, hipMemcpyAsync(d.inv_mass, inv_mass, sizeof(double) * D, hipMemcpyHostToDevice, st));
     {
-        int rc = octo_draws_hmc_step_device(h, seed, step, chain0, W, ld, d_th, beta ? d_be : nullptr, eps_w ? d_ep : nullptr, eps, n_leapfrog,
-                                            inv_mass ? d_im : nullptr, theta_prop ? d_pr : nullptr, logpost ? d_lp : nullptr, loglike ? d_ll : nullptr,
-                                            dH ? d_dh : nullptr, d_ac, OCTO_STREAM_CTX);
+        int rc = octo_draws_hmc_step_device(h, seed, step, chain0, W, ld, d.theta_t, beta ? d.beta : nullptr, eps_w ? d.eps : nullptr, eps, n_leapfrog,
+                                            inv_mass ? d.inv_mass : nullptr, theta_prop ? d.theta_prop : nullptr, logpost ? d.lp : nullptr, loglike ? d.ll : nullptr,
+                                            dH ? d.dH : nullptr, d.accepted, OCTO_STREAM_CTX);
         if (rc) return rc;
     }
-    OCHK(h, hipMemcpyAsync(theta_t, d_th, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
-    if (theta_prop) OCHK(h, hipMemcpyAsync(theta_prop, d_pr, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
-    if (logpost) OCHK(h, hipMemcpyAsync(logpost, d_lp, sizeof(double) * W, hipMemcpyDeviceToHost, st));
-    if (loglike) OCHK(h, hipMemcpyAsync(loglike, d_ll, sizeof(double) * W, hipMemcpyDeviceToHost, st));
-    if (dH) OCHK(h, hipMemcpyAsync(dH, d_dh, sizeof(double) * W, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpyAsync(accepted, d_ac, sizeof(int32_t) * W, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(theta_t, d.theta_t, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
+    if (theta_prop) OCHK(h, hipMemcpyAsync(theta_prop, d.theta_prop, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
+    if (logpost) OCHK(h, hipMemcpyAsync(logpost, d.lp, sizeof(double) * W, hipMemcpyDeviceToHost, st));
+    if (loglike) OCHK(h, hipMemcpyAsync(loglike, d.ll, sizeof(double) * W, hipMemcpyDeviceToHost, st));
+    if (dH) OCHK(h, hipMemcpyAsync(dH, d.dH, sizeof(double) * W, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(accepted, d.accepted, sizeof(int32_t) * W, hipMemcpyDeviceToHost, st));
     OCHK(h, hipStreamSynchronize(st));
     return OCTO_OK;
 }

@@ -1,0 +1,107 @@
+// octo_draws_layout.h — how every work allocation of liboctofitter_hip_draws.so is cut into its parts. One function per layout hands out
+// the parts from a Carve in the order its struct declares them; the same function sizes the allocation (a null base only counts) and
+// places the pointers, so the two cannot disagree, and a unit that reads another's state (Pathfinder, the L-BFGS's) calls that state's
+// function. Plain host C++ on <cstdint> alone: it compiles and is tested by itself (tests/test_draws_layout.py).
+#pragma once
+
+#include <cstdint>
+
+// Hands out consecutive parts of `base`, counted in doubles. A part of 4-byte elements takes a double's room per element — the rule
+// include/octofitter_hip_draws.h documents — so every part starts on an 8-byte boundary whatever precedes it.
+struct Carve {
+    double* base;          // null: size only
+    int64_t used = 0;      // doubles handed out so far
+    template <class T = double>
+    T* take(int64_t n) {
+        static_assert(sizeof(T) == 8 || sizeof(T) == 4, "a part holds 8-byte elements, or 4-byte ones in a double's room each");
+        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;      // no pointer is formed from a null base
+        used += n;
+        return p;
+    }
+};
+
+// the doubles of layout(c, args…) · its parts on base. The functions below return braced lists: their elements are evaluated in order.
+template <class F, class... A> int64_t carve_size(F layout, A... args) { Carve c{nullptr}; layout(c, args...); return c.used; }
+template <class F, class... A> auto carve_at(double* base, F layout, A... args) { Carve c{base}; return layout(c, args...); }
+
+// The L-BFGS state of one (ld, m), d_lbf: ((5 + 2m)·D + 2m + 11)·ld
+struct LbfgsState {
+    double *trial, *g, *dir, *alpha, *glp;                   // [D][ld]; glp = ∇ℓπ
+    double *S, *Y;                                           // [m][D][ld]
+    double *sy, *coef;                                       // [m][ld]
+    double *lp, *f, *t, *gd, *gn;                            // [ld]; lp = ℓπ
+    int32_t *status, *iters, *evals, *nbt, *cnt, *head;      // [ld]
+};
+inline LbfgsState lbfgs_state(Carve& c, int64_t D, int64_t ld, int64_t m) {
+    const int64_t plane = D * ld;
+    return {c.take(plane), c.take(plane), c.take(plane), c.take(plane), c.take(plane),
+            c.take(m * plane), c.take(m * plane),
+            c.take(m * ld), c.take(m * ld),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld)};
+}
+
+// sᵀy and the first loop's coefficients of the direction call, d_lbd: 2m·ld
+struct LbfgsCoef { double *sy, *coef; };      // [m][ld]
+inline LbfgsCoef lbfgs_coef(Carve& c, int64_t ld, int64_t m) { return {c.take(m * ld), c.take(m * ld)}; }
+
+// The Pathfinder state of one (ld), d_pf: (D² + 5D + 8)·ld. Two fits per chain — slot[c] names the kept one, the other receives the
+// candidate — and the scalars. The kernels take it by value (OpenArgs, ElboArgs): its members and their order are their argument layout.
+struct PfState {
+    double *mu, *sqa, *chol, *logdet, *elbo;      // μ, √α [2][D][ld] · L̃ packed [2][P][ld], P = D(D+1)/2 · logdet [2][ld] · ELBO [ld]
+    int32_t *slot, *elbo_iter, *n_fits, *prev_iters, *fresh;      // [ld]
+};
+inline PfState pf_state(Carve& c, int64_t D, int64_t ld) {
+    return {c.take(2 * D * ld), c.take(2 * D * ld), c.take(D * (D + 1) * ld), c.take(2 * ld), c.take(ld),
+            c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld)};
+}
+
+// Pathfinder's ELBO batch of KW = n_elbo·W draws, d_pfb: (D + 2)·KW
+struct PfBatch { double *phi, *lp, *logq; };      // φ [D][KW] · ℓπ, log q [KW]
+inline PfBatch pf_batch(Carve& c, int64_t D, int64_t KW) { return {c.take(D * KW), c.take(KW), c.take(KW)}; }
+
+// The explorer's work arrays, d_hmc: 4·D·ld + 4·ld. q, p, gpr, glp = ∇ℓπ [D][ld] · lp = ℓπ, lp0, lpt0, K0 [ld]
+struct HmcWork { double *q, *p, *gpr, *glp, *lp, *lp0, *lpt0, *K0; };
+inline HmcWork hmc_work(Carve& c, int64_t D, int64_t ld) {
+    return {c.take(D * ld), c.take(D * ld), c.take(D * ld), c.take(D * ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld)};
+}
+
+// The device side of the host-buffer twins, both on d_hst. octo_draws_lbfgs: 2·D·ld + 5·ld + D
+struct LbfgsStaging {
+    double *theta_t, *inv_hess_diag;      // [D][ld]
+    double *lp, *gn;                      // [ld]
+    int32_t *status, *iters, *evals;      // [ld]
+    double* inv_mass;                     // [D]
+};
+inline LbfgsStaging lbfgs_staging(Carve& c, int64_t D, int64_t ld) {
+    return {c.take(D * ld), c.take(D * ld), c.take(ld), c.take(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take(D)};
+}
+
+// octo_draws_hmc_step: 2·D·ld + 6·ld + D
+struct HmcStaging {
+    double *theta_t, *theta_prop;         // [D][ld]
+    double *beta, *eps, *lp, *ll, *dH;    // [ld]
+    int32_t* accepted;                    // [ld]
+    double* inv_mass;                     // [D]
+};
+inline HmcStaging hmc_staging(Carve& c, int64_t D, int64_t ld) {
+    return {c.take(D * ld), c.take(D * ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take<int32_t>(ld), c.take(D)};
+}
+
+// The three groups of the drivers (octo_draws.hip). The chunk buffers and the candidate lists, d_chunk: fixed for a handle
+struct ChunkBufs {
+    double *tt, *lpt;                     // θ_t [D][chunk], logprior_t [chunk]
+    double* clp; uint64_t* cix;           // [lists] the candidate lists, list 0 = the running list
+    double* max;                          // [1]
+};
+inline ChunkBufs chunk_bufs(Carve& c, int64_t D, int64_t chunk, int64_t lists) {
+    return {c.take(D * chunk), c.take(chunk), c.take(lists), c.take<uint64_t>(lists), c.take(1)};
+}
+
+// the per-draw arrays of a call of n draws, d_arr: lp, ll [n] · the block maxima [nblk] · the block counts and their total [nblk + 1]
+struct DrawArrays { double *lp, *ll, *pmax; int64_t* cnt; };
+inline DrawArrays draw_arrays(Carve& c, int64_t n, int64_t nblk) { return {c.take(n), c.take(n), c.take(nblk), c.take<int64_t>(nblk + 1)}; }
+
+// the outputs of a call before they go to the host, d_out: index, ll, lp [n] · θ [D][n]
+struct Outputs { uint64_t* ix; double *ll, *lp, *theta; };
+inline Outputs outputs(Carve& c, int64_t D, int64_t n) { return {c.take<uint64_t>(n), c.take(n), c.take(n), c.take(D * n)}; }

@@ -17,7 +17,6 @@ namespace {
 enum { LB_OPEN = 0, LB_ROUND = 1, LB_REPORT = 2 };
 constexpr double LB_C1 = 1e-4, LB_CURV = 1e-10;
 constexpr int LB_MAX_BACKTRACKS = 30;
-constexpr int64_t LB_MAX_CHAINS = (int64_t)1 << 30;      // one launch: 2²² blocks
 
 // The two-loop recursion of chain w over its cnt newest pairs, newest first; the pair k steps back from the newest sits in slot
 // (head − 1 − k) mod m. H₀ = γ·diag(v), γ = sᵀy/⟨y,y⟩_v of the newest pair (1 with none). q and r live in dir; coef [m][ld] holds the
@@ -220,9 +219,6 @@ __global__ __launch_bounds__(TPB) void k_lbfgs_advance(LbfgsArgs a) {
         for (int d = 0; d < a.D; ++d) a.o_ihd[(int64_t)d * a.ld + w] = a.alpha[(int64_t)d * a.ld + w];
 }
 
-// the handle's work arrays of one (ld, m): doubles, the int32 state in a double's room each
-inline int64_t lbfgs_doubles(int64_t D, int64_t ld, int64_t m) { return (5 + 2 * m) * D * ld + (2 * m + 5) * ld + 6 * ld; }
-
 }  // namespace
 
 extern "C" {
@@ -230,16 +226,17 @@ extern "C" {
 int32_t octo_draws_lbfgs_direction_device(octo_draws* h, int64_t W, int64_t ld, int32_t m, const int32_t* d_cnt, const int32_t* d_head, const double* d_S,
                                           const double* d_Y, const double* d_g, const double* d_inv_mass, double* d_dir, void* hip_stream) {
     if (!h) return OCTO_EINVAL;
-    if (m < 1 || m > OCTO_DRAWS_LBFGS_MAX_M) return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_direction_device: m must be 1 ... OCTO_DRAWS_LBFGS_MAX_M");
-    if (W < 0 || ld < W || W > LB_MAX_CHAINS) return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_direction_device: need 0 <= W <= ld, W <= 2^30");
+    if (int rc = check_m(h, "octo_draws_lbfgs_direction_device", m)) return rc;
+    if (int rc = check_chains(h, "octo_draws_lbfgs_direction_device", W, ld, MAX_CHAINS, "2^30")) return rc;
     if (W == 0) return OCTO_OK;
     if (!d_cnt || !d_head || !d_S || !d_Y || !d_g || !d_dir) return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_direction_device: only d_inv_mass may be NULL");
     OCHK(h, hipSetDevice(h->device));
-    { int rc = grow(h, h->d_lbd, h->cap_lbd, 2 * (int64_t)m * ld); if (rc) return rc; }
+    LbfgsCoef c;
+    if (int rc = grow_to(h, h->d_lbd, h->cap_lbd, c, lbfgs_coef, ld, (int64_t)m)) return rc;
     DirectionArgs a;
-    a.cnt = d_cnt; a.head = d_head; a.S = d_S; a.Y = d_Y; a.g = d_g; a.inv_mass = d_inv_mass; a.sy = h->d_lbd; a.coef = a.sy + (int64_t)m * ld;
+    a.cnt = d_cnt; a.head = d_head; a.S = d_S; a.Y = d_Y; a.g = d_g; a.inv_mass = d_inv_mass; a.sy = c.sy; a.coef = c.coef;
     a.dir = d_dir; a.W = W; a.ld = ld; a.D = h->D; a.m = m;
-    hipLaunchKernelGGL(k_lbfgs_direction, dim3((unsigned)((W + TPB - 1) / TPB)), dim3(TPB), 0, stream_of(h, hip_stream), a);
+    hipLaunchKernelGGL(k_lbfgs_direction, grid_of(W), dim3(TPB), 0, stream_of(h, hip_stream), a);
     OCHK(h, hipGetLastError());
     return OCTO_OK;
 }
@@ -248,12 +245,11 @@ int32_t octo_draws_lbfgs_device(octo_draws* h, int64_t W, int64_t ld, double* d_
                                 double ftol, int32_t resume, double* d_logpost, double* d_gnorm, int32_t* d_status, int32_t* d_iters, int32_t* d_evals,
                                 double* d_inv_hess_diag, void* hip_stream) {
     if (!h) return OCTO_EINVAL;
-    if (!(h->model && h->ctx)) return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_device: the handle has no model (created without one, or detached)");
-    if (m < 1 || m > OCTO_DRAWS_LBFGS_MAX_M) return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_device: m must be 1 ... OCTO_DRAWS_LBFGS_MAX_M");
+    if (int rc = check_model(h, "octo_draws_lbfgs_device")) return rc;
+    if (int rc = check_m(h, "octo_draws_lbfgs_device", m)) return rc;
     if (n_rounds < 0) return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_device: n_rounds >= 0");
-    if (W < 0 || ld < W || W > LB_MAX_CHAINS) return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_device: need 0 <= W <= ld, W <= 2^30");
-    if (!(std::isfinite(gtol) && gtol >= 0.0)) return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_device: gtol must be finite and >= 0");
-    if (!(std::isfinite(ftol) && ftol >= 0.0)) return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_device: ftol must be finite and >= 0");
+    if (int rc = check_chains(h, "octo_draws_lbfgs_device", W, ld, MAX_CHAINS, "2^30")) return rc;
+    if (int rc = check_tolerances(h, "octo_draws_lbfgs_device", gtol, ftol)) return rc;
     if (resume && (h->lbf_m == 0 || h->lbf_W != W || h->lbf_ld != ld || h->lbf_m != m))
         return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_device: resume needs a previous call with the same W, ld and m");
     if (W == 0) return OCTO_OK;
@@ -261,33 +257,27 @@ int32_t octo_draws_lbfgs_device(octo_draws* h, int64_t W, int64_t ld, double* d_
         return fail(h, OCTO_EINVAL, "octo_draws_lbfgs_device: only d_inv_mass and d_inv_hess_diag may be NULL");
     OCHK(h, hipSetDevice(h->device));
     const hipStream_t st = stream_of(h, hip_stream);
-    const int64_t D = h->D, plane = D * ld;
     if (!resume) {
         h->lbf_m = 0;      // a call that fails below leaves nothing to resume
-        int rc = grow(h, h->d_lbf, h->cap_lbf, lbfgs_doubles(D, ld, m)); if (rc) return rc;
+        int rc = grow(h, h->d_lbf, h->cap_lbf, carve_size(lbfgs_state, (int64_t)h->D, ld, (int64_t)m)); if (rc) return rc;
     }
+    const LbfgsState s = carve_at(h->d_lbf, lbfgs_state, (int64_t)h->D, ld, (int64_t)m);
     LbfgsArgs a;
     std::memset(&a, 0, sizeof(a));
     a.inv_mass = d_inv_mass; a.W = W; a.ld = ld; a.D = h->D; a.m = m; a.gtol = gtol; a.ftol = ftol;
     a.x = d_theta_t;
-    a.trial = h->d_lbf; a.g = a.trial + plane; a.dir = a.g + plane; a.alpha = a.dir + plane;
-    double* glp = a.alpha + plane;
-    a.S = glp + plane; a.Y = a.S + m * plane;
-    a.sy = a.Y + m * plane; a.coef = a.sy + (int64_t)m * ld;
-    double* lp = a.coef + (int64_t)m * ld;
-    a.f = lp + ld; a.t = a.f + ld; a.gd = a.t + ld; a.gn = a.gd + ld;
-    int32_t* ints = (int32_t*)(a.gn + ld);
-    a.status = ints; a.iters = ints + ld; a.evals = ints + 2 * ld; a.nbt = ints + 3 * ld; a.cnt = ints + 4 * ld; a.head = ints + 5 * ld;
-    a.glp = glp; a.lp = lp;
+    a.trial = s.trial; a.g = s.g; a.dir = s.dir; a.alpha = s.alpha; a.S = s.S; a.Y = s.Y; a.glp = s.glp; a.lp = s.lp; a.sy = s.sy; a.coef = s.coef;
+    a.f = s.f; a.t = s.t; a.gd = s.gd; a.gn = s.gn;
+    a.status = s.status; a.iters = s.iters; a.evals = s.evals; a.nbt = s.nbt; a.cnt = s.cnt; a.head = s.head;
     a.o_lp = d_logpost; a.o_gn = d_gnorm; a.o_ihd = d_inv_hess_diag; a.o_status = d_status; a.o_iters = d_iters; a.o_evals = d_evals;
-    const dim3 grid((unsigned)((W + TPB - 1) / TPB)), block(TPB);
+    const dim3 grid = grid_of(W), block(TPB);
     if (!resume) {
-        int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, d_theta_t, ld, W, lp, glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc;
+        int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, d_theta_t, ld, W, s.lp, s.glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc;
         a.write_out = n_rounds == 0;
         hipLaunchKernelGGL(k_lbfgs_advance<LB_OPEN>, grid, block, 0, st, a);
     }
     for (int r = 1; r <= n_rounds; ++r) {
-        int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, a.trial, ld, W, lp, glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc;
+        int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, a.trial, ld, W, s.lp, s.glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc;
         a.write_out = r == n_rounds;
         hipLaunchKernelGGL(k_lbfgs_advance<LB_ROUND>, grid, block, 0, st, a);
     }
@@ -309,31 +299,23 @@ int32_t octo_draws_lbfgs(octo_draws* h, int64_t W, int64_t ld, double* theta_t, 
     OCHK(h, hipSetDevice(h->device));
     const hipStream_t st = h->stream;
     const int64_t D = h->D, plane = D * ld;
-    // θ_t | inverse-Hessian diagonal | ℓπ | gnorm | status, iters, evals (int32, in a double's room each) | inv_mass
-    { int rc = grow(h, h->d_hst, h->cap_hst, 2 * plane + 5 * ld + D); if (rc) return rc; }
-    double* d_th = h->d_hst;
-    double* d_ih = d_th + plane;
-    double* d_lp = d_ih + plane;
-    double* d_gn = d_lp + ld;
-    int32_t* d_st = (int32_t*)(d_gn + ld);
-    int32_t* d_it = (int32_t*)(d_gn + 2 * ld);
-    int32_t* d_ev = (int32_t*)(d_gn + 3 * ld);
-    double* d_im = d_gn + 4 * ld;
-    if (W > 0) OCHK(h, hipMemcpyAsync(d_th, theta_t, sizeof(double) * plane, hipMemcpyHostToDevice, st));
-    if (inv_mass) OCHK(h, hipMemcpyAsync(d_im, inv_mass, sizeof(double) * D, hipMemcpyHostToDevice, st));
+    LbfgsStaging d;
+    if (int rc = grow_to(h, h->d_hst, h->cap_hst, d, lbfgs_staging, D, ld)) return rc;
+    if (W > 0) OCHK(h, hipMemcpyAsync(d.theta_t, theta_t, sizeof(double) * plane, hipMemcpyHostToDevice, st));
+    if (inv_mass) OCHK(h, hipMemcpyAsync(d.inv_mass, inv_mass, sizeof(double) * D, hipMemcpyHostToDevice, st));
     {
-        int rc = octo_draws_lbfgs_device(h, W, ld, d_th, inv_mass ? d_im : nullptr, m, n_rounds, gtol, ftol, 0, d_lp, d_gn, d_st, d_it, d_ev,
-                                         inv_hess_diag ? d_ih : nullptr, OCTO_STREAM_CTX);
+        int rc = octo_draws_lbfgs_device(h, W, ld, d.theta_t, inv_mass ? d.inv_mass : nullptr, m, n_rounds, gtol, ftol, 0, d.lp, d.gn, d.status, d.iters, d.evals,
+                                         inv_hess_diag ? d.inv_hess_diag : nullptr, OCTO_STREAM_CTX);
         if (rc) return rc;
     }
     if (W == 0) return OCTO_OK;
-    OCHK(h, hipMemcpyAsync(theta_t, d_th, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
-    if (inv_hess_diag) OCHK(h, hipMemcpyAsync(inv_hess_diag, d_ih, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpyAsync(logpost, d_lp, sizeof(double) * W, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpyAsync(gnorm, d_gn, sizeof(double) * W, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpyAsync(status, d_st, sizeof(int32_t) * W, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpyAsync(iters, d_it, sizeof(int32_t) * W, hipMemcpyDeviceToHost, st));
-    OCHK(h, hipMemcpyAsync(evals, d_ev, sizeof(int32_t) * W, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(theta_t, d.theta_t, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
+    if (inv_hess_diag) OCHK(h, hipMemcpyAsync(inv_hess_diag, d.inv_hess_diag, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(logpost, d.lp, sizeof(double) * W, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(gnorm, d.gn, sizeof(double) * W, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(status, d.status, sizeof(int32_t) * W, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(iters, d.iters, sizeof(int32_t) * W, hipMemcpyDeviceToHost, st));
+    OCHK(h, hipMemcpyAsync(evals, d.evals, sizeof(int32_t) * W, hipMemcpyDeviceToHost, st));
     OCHK(h, hipStreamSynchronize(st));
     return OCTO_OK;
 }

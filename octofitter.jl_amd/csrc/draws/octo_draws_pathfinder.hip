@@ -1,7 +1,8 @@
 // octo_draws_pathfinder.hip — Pathfinder on the L-BFGS paths of liboctofitter_hip_draws.so (include/octofitter_hip_draws.h states the
 // function): a normal approximation at every accepted iterate of every chain, an ELBO estimate of it from a few draws, the best one kept,
 // and draws from the kept one. The L-BFGS is octo_draws_lbfgs_device itself, called one round at a time with `resume`; this unit only READS
-// the state that call leaves in the handle (x is the caller's θ_t; g, α, the ring and the counters sit in h->d_lbf).
+// the state that call leaves in the handle (x is the caller's θ_t; g, α, the ring and the counters sit in h->d_lbf, found through the
+// optimiser's own layout function, lbfgs_state of octo_draws_layout.h; the Pathfinder state of h->d_pf is pf_state there).
 //
 //   k_pf_open     the chains' Pathfinder state at the start: no fit, ELBO −Inf.
 //   k_pf_fit      the fit: ONE WAVE PER CHAIN, lane i = row i of H̃, H̃ in LDS (D·(D|1) doubles: 33 KB at D = 64). A lane runs its row's
@@ -16,46 +17,8 @@
 
 namespace {
 
-constexpr int64_t PF_MAX_CHAINS = (int64_t)1 << 30;
 constexpr int PF_WAVE = 64;
 constexpr double PF_LOG_2PI = 1.8378770664093453;
-
-// The Pathfinder state of one (ld): two fits per chain — slot[c] names the kept one, the other receives the candidate — and the scalars.
-//   μ [2][D][ld] · √α [2][D][ld] · L̃ packed [2][P][ld], P = D(D+1)/2 · logdet [2][ld] · ELBO [ld] ·
-//   int32 in a double's room each: slot, elbo_iter, n_fits, prev_iters, fresh [ld]
-inline int64_t pf_doubles(int64_t D, int64_t ld) { return 2 * (2 * D + D * (D + 1) / 2) * ld + 2 * ld + ld + 5 * ld; }
-
-struct PfState {
-    double *mu, *sqa, *chol, *logdet, *elbo;
-    int32_t *slot, *elbo_iter, *n_fits, *prev_iters, *fresh;
-};
-
-inline PfState pf_state(double* base, int64_t D, int64_t ld) {
-    PfState s;
-    const int64_t plane = D * ld, P = D * (D + 1) / 2;
-    s.mu = base; s.sqa = s.mu + 2 * plane; s.chol = s.sqa + 2 * plane; s.logdet = s.chol + 2 * P * ld; s.elbo = s.logdet + 2 * ld;
-    double* ints = s.elbo + ld;
-    s.slot = (int32_t*)ints; s.elbo_iter = (int32_t*)(ints + ld); s.n_fits = (int32_t*)(ints + 2 * ld); s.prev_iters = (int32_t*)(ints + 3 * ld);
-    s.fresh = (int32_t*)(ints + 4 * ld);
-    return s;
-}
-
-// What octo_draws_lbfgs_device keeps in h->d_lbf, in its order (octo_draws_lbfgs.hip lays it out; this is a reader's view of it):
-//   trial, g, dir, α, ∇ℓπ [D][ld] · S, Y [m][D][ld] · sᵀy, coef [m][ld] · ℓπ, f, t, gd, gn [ld] · int32 status, iters, evals, nbt, cnt, head [ld]
-struct LbfgsView {
-    const double *g, *alpha, *S, *Y;
-    const int32_t *iters, *cnt, *head;
-};
-
-inline LbfgsView lbfgs_view(const octo_draws* h, int64_t D, int64_t ld, int64_t m) {
-    LbfgsView v;
-    const int64_t plane = D * ld;
-    const double* base = h->d_lbf;
-    v.g = base + plane; v.alpha = base + 3 * plane; v.S = base + 5 * plane; v.Y = v.S + m * plane;
-    const int32_t* ints = (const int32_t*)(v.Y + m * plane + 2 * m * ld + 5 * ld);
-    v.iters = ints + ld; v.cnt = ints + 4 * ld; v.head = ints + 5 * ld;
-    return v;
-}
 
 struct OpenArgs {
     PfState s;
@@ -287,7 +250,6 @@ __global__ __launch_bounds__(TPB) void k_pf_mask(MaskArgs a) {
     if (a.elbo_iter[t % a.W] < 0) a.lp[t] = -INFINITY;
 }
 
-inline dim3 grid_of(int64_t n) { return dim3((unsigned)((n + TPB - 1) / TPB)); }
 inline size_t fit_lds_bytes(int D) { return sizeof(double) * ((size_t)D * (D | 1) + 3 * PF_WAVE); }
 
 void launch_normals(hipStream_t st, NormalArgs n) {
@@ -303,9 +265,9 @@ int32_t octo_draws_pathfinder_fit_device(octo_draws* h, int64_t W, int64_t ld, i
                                          double* d_logdet, int32_t* d_ok, int32_t n, const double* d_z, double* d_phi, void* hip_stream) {
     if (!h) return OCTO_EINVAL;
     if (h->D > OCTO_DRAWS_PF_MAX_D) return fail(h, OCTO_ENOTSUP, "octo_draws_pathfinder_fit_device: D > OCTO_DRAWS_PF_MAX_D");
-    if (m < 1 || m > OCTO_DRAWS_LBFGS_MAX_M) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_fit_device: m must be 1 ... OCTO_DRAWS_LBFGS_MAX_M");
-    if (W < 0 || ld < W || W > PF_MAX_CHAINS) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_fit_device: need 0 <= W <= ld, W <= 2^30");
-    if (n < 0 || (int64_t)n * W > PF_MAX_CHAINS) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_fit_device: need n >= 0, n*W <= 2^30");
+    if (int rc = check_m(h, "octo_draws_pathfinder_fit_device", m)) return rc;
+    if (int rc = check_chains(h, "octo_draws_pathfinder_fit_device", W, ld, MAX_CHAINS, "2^30")) return rc;
+    if (n < 0 || (int64_t)n * W > MAX_CHAINS) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_fit_device: need n >= 0, n*W <= 2^30");
     if (W == 0) return OCTO_OK;
     if (!d_cnt || !d_head || !d_S || !d_Y || !d_x || !d_g || !d_alpha || !d_mu || !d_chol || !d_logdet || !d_ok || (n > 0 && (!d_z || !d_phi)))
         return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_fit_device: only d_z and d_phi may be NULL, with n = 0");
@@ -334,15 +296,13 @@ int32_t octo_draws_pathfinder_device(octo_draws* h, uint64_t seed, uint64_t chai
                                      double* d_gnorm, int32_t* d_status, int32_t* d_iters, int32_t* d_evals, double* d_inv_hess_diag, double* d_elbo,
                                      int32_t* d_elbo_iter, int32_t* d_n_fits, void* hip_stream) {
     if (!h) return OCTO_EINVAL;
-    if (!(h->model && h->ctx)) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_device: the handle has no model (created without one, or detached)");
+    if (int rc = check_model(h, "octo_draws_pathfinder_device")) return rc;
     if (h->D > OCTO_DRAWS_PF_MAX_D) return fail(h, OCTO_ENOTSUP, "octo_draws_pathfinder_device: D > OCTO_DRAWS_PF_MAX_D");
-    if (m < 1 || m > OCTO_DRAWS_LBFGS_MAX_M) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_device: m must be 1 ... OCTO_DRAWS_LBFGS_MAX_M");
+    if (int rc = check_m(h, "octo_draws_pathfinder_device", m)) return rc;
     if (n_rounds < 0) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_device: n_rounds >= 0");
     if (n_elbo < 1 || n_elbo > OCTO_DRAWS_PF_MAX_ELBO_DRAWS) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_device: n_elbo must be 1 ... OCTO_DRAWS_PF_MAX_ELBO_DRAWS");
-    if (W < 0 || ld < W || W > PF_MAX_CHAINS / OCTO_DRAWS_PF_MAX_ELBO_DRAWS)
-        return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_device: need 0 <= W <= ld, W <= 2^25");
-    if (!(std::isfinite(gtol) && gtol >= 0.0)) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_device: gtol must be finite and >= 0");
-    if (!(std::isfinite(ftol) && ftol >= 0.0)) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_device: ftol must be finite and >= 0");
+    if (int rc = check_chains(h, "octo_draws_pathfinder_device", W, ld, MAX_CHAINS / OCTO_DRAWS_PF_MAX_ELBO_DRAWS, "2^25")) return rc;
+    if (int rc = check_tolerances(h, "octo_draws_pathfinder_device", gtol, ftol)) return rc;
     if (resume && (h->pf_W == 0 || h->pf_W != W || h->pf_ld != ld || h->lbf_W != W || h->lbf_ld != ld || h->lbf_m != m))
         return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_device: resume needs a previous call with the same W, ld and m");
     if (W == 0) return OCTO_OK;
@@ -353,13 +313,11 @@ int32_t octo_draws_pathfinder_device(octo_draws* h, uint64_t seed, uint64_t chai
     const int64_t D = h->D, KW = (int64_t)n_elbo * W;
     if (!resume) {
         h->pf_W = 0;      // a call that fails below leaves nothing to resume or to draw from
-        int rc = grow(h, h->d_pf, h->cap_pf, pf_doubles(D, ld)); if (rc) return rc;
+        int rc = grow(h, h->d_pf, h->cap_pf, carve_size(pf_state, D, ld)); if (rc) return rc;
     }
-    { int rc = grow(h, h->d_pfb, h->cap_pfb, (D + 2) * KW); if (rc) return rc; }      // the ELBO batch φ [D][K·W] | ℓπ | log q
-    double* batch = h->d_pfb;
-    double* lp = batch + D * KW;
-    double* logq = lp + KW;
-    const PfState s = pf_state(h->d_pf, D, ld);
+    PfBatch b;
+    if (int rc = grow_to(h, h->d_pfb, h->cap_pfb, b, pf_batch, D, KW)) return rc;
+    const PfState s = carve_at(h->d_pf, pf_state, D, ld);
     // the opening evaluation (or, resumed, the outputs as they stand); every round below is the existing call with one round and resume
     {
         int rc = octo_draws_lbfgs_device(h, W, ld, d_theta_t, d_inv_mass, m, 0, gtol, ftol, resume, d_logpost, d_gnorm, d_status, d_iters, d_evals,
@@ -370,21 +328,21 @@ int32_t octo_draws_pathfinder_device(octo_draws* h, uint64_t seed, uint64_t chai
         OpenArgs o; o.s = s; o.W = W;
         hipLaunchKernelGGL(k_pf_open, grid_of(W), dim3(TPB), 0, st, o);
     }
-    const LbfgsView v = lbfgs_view(h, D, ld, m);
+    const LbfgsState v = carve_at(h->d_lbf, lbfgs_state, D, ld, (int64_t)m);      // as the call above left it
     FitArgs f;
     std::memset(&f, 0, sizeof(f));
     f.cnt = v.cnt; f.head = v.head; f.S = v.S; f.Y = v.Y; f.x = d_theta_t; f.g = v.g; f.alpha = v.alpha; f.iters = v.iters; f.prev_iters = s.prev_iters;
     f.slot = s.slot; f.mu = s.mu; f.sqa = s.sqa; f.chol = s.chol; f.logdet = s.logdet; f.ok = s.fresh; f.ld = ld; f.D = h->D; f.m = m;
     NormalArgs z;
     std::memset(&z, 0, sizeof(z));
-    z.seed = seed; z.chain0 = chain0; z.iters = v.iters; z.W = W; z.n = n_elbo; z.sj = W; z.sd = KW; z.D = h->D; z.z = batch;
+    z.seed = seed; z.chain0 = chain0; z.iters = v.iters; z.W = W; z.n = n_elbo; z.sj = W; z.sd = KW; z.D = h->D; z.z = b.phi;
     MapArgs p;
     std::memset(&p, 0, sizeof(p));
     p.mu = s.mu; p.sqa = s.sqa; p.chol = s.chol; p.logdet = s.logdet; p.slot = s.slot; p.flip = 1; p.use = s.fresh; p.use_min = 1; p.x = d_theta_t;
-    p.z = batch; p.phi = batch; p.logq = logq; p.W = W; p.n = n_elbo; p.ld = ld; p.sj = W; p.sd = KW; p.D = h->D;
+    p.z = b.phi; p.phi = b.phi; p.logq = b.logq; p.W = W; p.n = n_elbo; p.ld = ld; p.sj = W; p.sd = KW; p.D = h->D;
     ElboArgs e;
     std::memset(&e, 0, sizeof(e));
-    e.s = s; e.iters = v.iters; e.lp = lp; e.logq = logq; e.W = W; e.K = n_elbo; e.update = 1; e.o_elbo = d_elbo; e.o_iter = d_elbo_iter; e.o_nfits = d_n_fits;
+    e.s = s; e.iters = v.iters; e.lp = b.lp; e.logq = b.logq; e.W = W; e.K = n_elbo; e.update = 1; e.o_elbo = d_elbo; e.o_iter = d_elbo_iter; e.o_nfits = d_n_fits;
     for (int r = 1; r <= n_rounds; ++r) {
         int rc = octo_draws_lbfgs_device(h, W, ld, d_theta_t, d_inv_mass, m, 1, gtol, ftol, 1, d_logpost, d_gnorm, d_status, d_iters, d_evals,
                                          d_inv_hess_diag, hip_stream);
@@ -393,7 +351,7 @@ int32_t octo_draws_pathfinder_device(octo_draws* h, uint64_t seed, uint64_t chai
         launch_normals(st, z);
         hipLaunchKernelGGL(k_pf_map, grid_of(KW), dim3(TPB), 0, st, p);
         OCHK(h, hipGetLastError());
-        rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, batch, KW, KW, lp, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc;
+        rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, b.phi, KW, KW, b.lp, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc;
         hipLaunchKernelGGL(k_pf_elbo, grid_of(W), dim3(TPB), 0, st, e);
     }
     if (n_rounds == 0) {
@@ -408,10 +366,10 @@ int32_t octo_draws_pathfinder_device(octo_draws* h, uint64_t seed, uint64_t chai
 int32_t octo_draws_pathfinder_draw_device(octo_draws* h, uint64_t seed, uint64_t chain0, int64_t W, int64_t ld, const double* d_theta_t, int32_t n_draws,
                                           int64_t ld_out, double* d_phi, double* d_logq, double* d_logpost, void* hip_stream) {
     if (!h) return OCTO_EINVAL;
-    if (!(h->model && h->ctx)) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_draw_device: the handle has no model (created without one, or detached)");
+    if (int rc = check_model(h, "octo_draws_pathfinder_draw_device")) return rc;
     if (h->D > OCTO_DRAWS_PF_MAX_D) return fail(h, OCTO_ENOTSUP, "octo_draws_pathfinder_draw_device: D > OCTO_DRAWS_PF_MAX_D");
     if (n_draws < 1) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_draw_device: n_draws >= 1");
-    if (W < 0 || ld < W || (int64_t)n_draws * W > PF_MAX_CHAINS) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_draw_device: need 0 <= W <= ld, n_draws*W <= 2^30");
+    if (W < 0 || ld < W || (int64_t)n_draws * W > MAX_CHAINS) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_draw_device: need 0 <= W <= ld, n_draws*W <= 2^30");
     if (ld_out < (int64_t)n_draws * W) return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_draw_device: need ld_out >= n_draws*W");
     if (h->pf_W == 0 || h->pf_W != W || h->pf_ld != ld)
         return fail(h, OCTO_EINVAL, "octo_draws_pathfinder_draw_device: needs a previous octo_draws_pathfinder_device call with the same W and ld");
@@ -420,7 +378,7 @@ int32_t octo_draws_pathfinder_draw_device(octo_draws* h, uint64_t seed, uint64_t
     OCHK(h, hipSetDevice(h->device));
     const hipStream_t st = stream_of(h, hip_stream);
     const int64_t NW = (int64_t)n_draws * W;
-    const PfState s = pf_state(h->d_pf, h->D, ld);
+    const PfState s = carve_at(h->d_pf, pf_state, (int64_t)h->D, ld);
     NormalArgs z;
     std::memset(&z, 0, sizeof(z));
     z.seed = seed; z.chain0 = chain0; z.W = W; z.n = n_draws; z.sj = W; z.sd = ld_out; z.D = h->D; z.z = d_phi;

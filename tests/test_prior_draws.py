@@ -439,3 +439,96 @@ def test_gpu_argument_checks(pkg, draws_mod):
     pd.best(0, 1000, keep=1)
     model.close()
     pd.close()
+
+
+@pytest.mark.gpu
+def test_gpu_work_arrays_regrow_and_share(pkg, draws_mod):
+    """One handle through every call that grows, regrows or shares a work allocation, in an order that makes each of them happen: rejection
+    with N = 300, 3000 and 300 again (the per-draw arrays and the outputs grow, then serve a smaller call), best, the two host twins (one
+    staging allocation, cut differently by each), pathfinder_fit, pathfinder and pathfinder_draw (the fit's √α and the ELBO batch share an
+    allocation), and an L-BFGS resumed from the state the Pathfinder call left. W = 5 chains with leading dimension 7. Every output has the
+    bits of the same call on a handle created for that call alone (pathfinder_draw and the resumed L-BFGS after the pathfinder call they
+    continue): a pointer kept into a freed allocation, or two layouts colliding on a shared one, would show here."""
+    import ctypes as C
+    import torch
+    model = callers_model(pkg)
+    fn = model.ln_like
+    fn._check(fn.lib.octo_ctx_set_option(fn._ctx, pkg.capi.OPT_BATCH_INVARIANT, 1), "octo_ctx_set_option")
+    D, W, LD, M, nan = model.D, 5, 7, 3, float("nan")
+    dp, ip = pkg.capi._dptr, lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))      # noqa: E731
+    rng = np.random.default_rng(5)
+    src = draws_mod.PriorDraws(model)
+    start = np.ascontiguousarray(model.link(src.best(9, 3000, keep=W)[0]))      # W starts with a finite log-posterior
+    src.close()
+    beta, im = rng.uniform(0.2, 1.0, W), rng.uniform(0.5, 2.0, D)
+    S = rng.normal(size=(M, D, W))
+    Y, x, g, alpha, z = 2.0 * S + 0.1 * rng.normal(size=S.shape), rng.normal(size=(D, W)), rng.normal(size=(D, W)), rng.uniform(0.5, 2.0, (D, W)), rng.normal(size=(2, D, W))
+    cnt, head = torch.as_tensor([0, 1, 2, 3, 3], dtype=torch.int32), torch.as_tensor([0, 1, 2, 0, 1], dtype=torch.int32)
+
+    def padded(a):
+        buf = torch.full(tuple(a.shape[:-1]) + (LD,), nan, dtype=torch.float64, device="cuda")
+        buf[..., :W] = torch.as_tensor(a, device="cuda")
+        return buf[..., :W]
+
+    def host_matrix():
+        th = np.full((D, LD), nan)
+        th[:, :W] = start
+        return th
+
+    def rejection(N):
+        def call(h, tt):
+            r = h.rejection(9, N)
+            assert r["n_accepted"] >= 1
+            return [r[k] for k in ("samples", "loglike", "logpost", "index")] + [np.array([r["n_accepted"]]), np.array([r["max_loglike"]])]
+        return call
+
+    def hmc_twin(h, tt):
+        th, prop = host_matrix(), np.full((D, LD), nan)
+        lp, ll, dH, acc = np.empty(W), np.empty(W), np.empty(W), np.empty(W, dtype=np.int32)
+        h._check(h.lib.octo_draws_hmc_step(h._h, 3, 1, 0, W, LD, dp(th), dp(beta), None, 0.02, 3, dp(im), dp(prop), dp(lp), dp(ll), dp(dH), ip(acc)))
+        return [th, prop[:, :W], lp, ll, dH, acc]      # beyond column W the proposal is whatever the staging held
+
+    def lbfgs_twin(h, tt):
+        th, ihd = host_matrix(), np.full((D, LD), nan)
+        lp, gn = np.empty(W), np.empty(W)
+        status, iters, evals = (np.empty(W, dtype=np.int32) for _ in range(3))
+        h._check(h.lib.octo_draws_lbfgs(h._h, W, LD, dp(th), dp(im), M, 4, 1e-6, 0.0, dp(lp), dp(gn), ip(status), ip(iters), ip(evals), dp(ihd)))
+        return [th, ihd[:, :W], lp, gn, status, iters, evals]
+
+    def fit(h, tt):
+        out = h.pathfinder_fit(cnt, head, *[padded(a) for a in (S, Y, x, g, alpha, z)])
+        torch.cuda.synchronize()
+        assert bool((out["ok"] == 1).all())
+        return [out[k].cpu().numpy() for k in ("mu", "chol", "logdet", "ok", "phi")]
+
+    def device_outputs(r, tt):
+        torch.cuda.synchronize()
+        return [tt.cpu().numpy()] + [v.cpu().numpy() for _, v in sorted(r.items()) if v is not None]
+
+    def pathfinder(h, tt):
+        return device_outputs(h.pathfinder(tt, inv_mass=im, m=M, n_rounds=3, gtol=1e-6, want_inv_hess_diag=True, seed=7, n_elbo=4), tt)
+
+    def draw(h, tt):
+        return [t.cpu().numpy() for t in h.pathfinder_draw(tt, 2, seed=7)]
+
+    def resumed(h, tt):
+        return device_outputs(h.lbfgs(tt, inv_mass=im, m=M, n_rounds=2, gtol=1e-6, resume=True, want_inv_hess_diag=True), tt)
+
+    steps = [("rejection 300", rejection(300), ()), ("rejection 3000", rejection(3000), ()), ("rejection 300 again", rejection(300), ()),
+             ("best", lambda h, tt: list(h.best(9, 3000, keep=4)), ()), ("hmc host twin", hmc_twin, ()), ("lbfgs host twin", lbfgs_twin, ()),
+             ("pathfinder_fit", fit, ()), ("pathfinder", pathfinder, ()), ("pathfinder_draw", draw, (pathfinder,)), ("lbfgs resumed", resumed, (pathfinder,))]
+    one, tt_one = draws_mod.PriorDraws(model), padded(start)
+    try:
+        for name, call, before in steps:
+            got = call(one, tt_one)
+            alone, tt = draws_mod.PriorDraws(model), padded(start)
+            try:
+                for c in before:
+                    c(alone, tt)
+                want = call(alone, tt)
+            finally:
+                alone.close()
+            assert len(got) == len(want) and all(np.array_equal(a, b, equal_nan=True) for a, b in zip(got, want)), name
+    finally:
+        one.close()
+        model.close()
