@@ -35,6 +35,9 @@
  *   purpose 4: ELBO draw k of chain c at its iterate number it, counter (c, d / 4, 4, it·32 + k), coordinate d takes word d % 4
  *   purpose 5: final draw j of chain c, counter (c, d / 4, 5, j)
  *
+ * The sixth is the explorer's warm-up: grouped cross-chain moments, the diagonal metric they give, dual averaging of the step size and
+ * per-chain running moments (octo_draws_moments_device … octo_draws_chain_moments_device; tests/adapt_reference.py restates them). No random number.
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -278,6 +281,69 @@ int32_t octo_draws_pathfinder_device(octo_draws* h, uint64_t seed, uint64_t chai
  * ld_out < n_draws·W; no previous octo_draws_pathfinder_device call, or one with another W or ld; a NULL array with W > 0. */
 int32_t octo_draws_pathfinder_draw_device(octo_draws* h, uint64_t seed, uint64_t chain0, int64_t W, int64_t ld, const double* d_theta_t,
                                           int32_t n_draws, int64_t ld_out, double* d_phi, double* d_logq, double* d_logpost, void* hip_stream);
+
+/* ---- Warm-up of the explorer: what turns octo_draws_hmc_step_device into a sampler — the cross-chain statistics that give it d_inv_mass (the
+ * pooled variance of the chains) and d_eps (dual averaging on the mean acceptance probability), and the per-chain moments R̂ is made of. Five
+ * calls on DEVICE arrays, asynchronous on hip_stream, no host synchronisation, no allocation once the handle's work array holds
+ * ⌈W/256⌉·G·(2K + 1) doubles, no random number (no new Philox purpose), no model needed. Every sum runs in a fixed order — no floating-point
+ * atomic anywhere — so a call's outputs are the same bits from run to run, and they depend neither on ld, nor on what lies beyond column W, nor
+ * on the values of excluded chains. tests/adapt_reference.py restates the five. K, the rows of an array [K][ld], is an argument of its own
+ * (1 … 64), not the handle's D: the same call serves a [1][ld] array.
+ *
+ * Grouped moments. Chain w belongs to group d_group[w] (int32); d_group NULL: every chain in group 0, and G must be 1. A chain is EXCLUDED
+ * from every row if its id is outside 0 … G − 1 or if any of its K values is not finite. Over the remaining chains of group g:
+ *   d_count [G]     their number n, a double holding an exact integer
+ *   d_mean  [G][K]  (Σ x)/n
+ *   d_m2    [G][K]  Σ (x − mean)²
+ * Order: a block of 256 consecutive chains sums each row of a group by a butterfly over the 64 lanes of a wave and then over its four waves
+ * in wave order, takes the block's mean, and sums (x − that mean)² the same way; the blocks' triples (n, Σx, M2) are merged in block order,
+ * δ = Σx_b/n_b − Σx_a/n_a, M2 = M2_a + M2_b + δ²·n_a·n_b/(n_a + n_b); mean = Σx/n at the end.
+ * accumulate = 0 overwrites the three arrays; an empty group gives count 0, mean 0, M2 0. accumulate = 1 Chan-merges this call's block b into
+ * what they hold (a): n = n_a + n_b, δ = mean_b − mean_a, mean = mean_a + δ·n_b/n, M2 = M2_a + M2_b + δ²·n_a·n_b/n; a group empty in this call
+ * is left untouched, and a group whose held count is 0 takes this call's values.
+ * OCTO_EINVAL: NULL handle or array (d_group excepted, and d_x with W = 0); K or G outside 1 … OCTO_DRAWS_MAX_GROUPS; NULL d_group with G != 1 and W > 0; W < 0,
+ * ld < W, W > 2^24. */
+#define OCTO_DRAWS_MAX_GROUPS 64
+int32_t octo_draws_moments_device(octo_draws* h, int64_t W, int64_t ld, int32_t K, const double* d_x, const int32_t* d_group, int32_t G,
+                                  int32_t accumulate, double* d_count, double* d_mean, double* d_m2, void* hip_stream);
+
+/* One group's moments (d_count_g [1], d_mean_g [K] — not consulted, kept for symmetry —, d_m2_g [K]: rows of the arrays above) as a metric:
+ * var_d = M2_d/(n − 1); regularize = 0: v_d = var_d; regularize = 1, Stan's shrinkage: v_d = (n/(n + 5))·var_d + 1e-3·5/(n + 5).
+ * d_inv_mass[d] is written only where n >= 2 and v_d is finite and > 0; elsewhere it keeps its value.
+ * OCTO_EINVAL: NULL handle or array; K outside 1 … OCTO_DRAWS_MAX_GROUPS. */
+int32_t octo_draws_metric_device(octo_draws* h, int32_t K, const double* d_count_g, const double* d_mean_g, const double* d_m2_g,
+                                 int32_t regularize, double* d_inv_mass, void* hip_stream);
+
+/* Dual averaging of the step size (Hoffman & Gelman 2014, as Stan's stepsize_adaptation). d_state [G][4] = (x, x̄, H̄, μ) of group g, x = log ε.
+ * init: x = x̄ = log ε0_g, H̄ = 0, μ = log(10·ε0_g); ε0_g = d_eps0[g], or the scalar eps0 with d_eps0 NULL.
+ * OCTO_EINVAL: NULL handle or d_state; G outside 1 … OCTO_DRAWS_MAX_GROUPS; eps0 not finite or <= 0 with d_eps0 NULL. */
+int32_t octo_draws_hmc_adapt_init_device(octo_draws* h, int32_t G, const double* d_eps0, double eps0, double* d_state, void* hip_stream);
+
+/* Update number k >= 1 from the outputs d_dH, d_accepted of one octo_draws_hmc_step_device over W chains.
+ *   per chain   a_c = min(1, exp(dH_c)) where dH_c is not NaN; otherwise a_c = accepted_c ? 1 : 0 (defined whatever a dead state left in d_dH)
+ *   per group   a_g = the mean of a_c: the grouped reduction of octo_draws_moments_device on one row, the same exclusion by id (d_group NULL:
+ *               G must be 1). d_accept_stat [G] (may be NULL) receives it, NaN for an empty group.
+ *   update      η = 1/(k + t0); H̄ <- (1 − η)·H̄ + η·(δ − a_g); x <- μ − (√k/γ)·H̄; w = k^(−κ); x̄ <- w·x + (1 − w)·x̄.
+ *               An empty group keeps its state bit for bit.
+ *   d_eps_w [W] (may be NULL) receives exp(x_g) of the chain's group — with use_average = 1, exp(x̄_g) —, what d_eps of the step takes.
+ *               Excluded chains are not written.
+ * Stan's values: delta = 0.8, gamma = 0.05, t0 = 10, kappa = 0.75.
+ * OCTO_EINVAL: NULL handle, d_dH, d_accepted or d_state; G out of range; NULL d_group with G != 1 and W > 0; W < 0, W > 2^24; k < 1; delta, gamma, t0,
+ * kappa not finite or outside 0 < delta < 1, gamma > 0, t0 >= 0, kappa > 0. */
+int32_t octo_draws_hmc_adapt_device(octo_draws* h, int64_t W, const int32_t* d_group, int32_t G, const double* d_dH, const int32_t* d_accepted,
+                                    int64_t k, double delta, double gamma, double t0, double kappa, double* d_state, double* d_accept_stat,
+                                    int32_t use_average, double* d_eps_w, void* hip_stream);
+
+/* Per-chain running moments over time, lane = chain: d_cmean, d_cm2 [K][ld] of d_x [K][ld], k >= 1 the number of this sample.
+ * k = 1: mean = x, M2 = 0, whatever the arrays held. Otherwise Welford: δ = x − mean, mean += δ/k, M2 += δ·(x − mean). Non-finite values
+ * propagate. OCTO_EINVAL: NULL handle or array; K out of range; W < 0, ld < W, W > 2^24; k < 1.
+ *
+ * R̂ (Gelman & Rubin) of n samples per chain follows from these with no further function. Per coordinate d:
+ *   B/n  = M2/(count − 1) of octo_draws_moments_device(d_cmean): the variance of the chain means;
+ *   Wv   = the mean of octo_draws_moments_device(d_cm2), divided by n − 1: the mean within-chain variance;
+ *   R̂_d = √(((n − 1)/n·Wv + B/n)/Wv). */
+int32_t octo_draws_chain_moments_device(octo_draws* h, int64_t W, int64_t ld, int32_t K, int64_t k, const double* d_x, double* d_cmean,
+                                        double* d_cm2, void* hip_stream);
 
 #ifdef __cplusplus
 }

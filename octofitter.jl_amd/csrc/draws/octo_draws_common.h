@@ -1,7 +1,7 @@
 // octo_draws_common.h — what the translation units of liboctofitter_hip_draws.so share: the handle, the counter generator, the prior
-// helpers on top of octo_model.h's device routines, and the argument checks their functions repeat. Four units include it: octo_draws.hip
+// helpers on top of octo_model.h's device routines, and the argument checks their functions repeat. Five units include it: octo_draws.hip
 // (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC explorer), octo_draws_lbfgs.hip (the
-// multi-start L-BFGS) and octo_draws_pathfinder.hip (Pathfinder on its paths). Everything but the handle lives in an unnamed namespace,
+// multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder on its paths) and octo_draws_adapt.hip (the warm-up statistics of the explorer). Everything but the handle lives in an unnamed namespace,
 // one copy per unit. How the handle's work allocations are cut into their parts is octo_draws_layout.h.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
@@ -109,6 +109,8 @@ struct octo_draws : CompanionBase {
     double* d_pf = nullptr; int64_t cap_pf = 0;
     int64_t pf_W = 0, pf_ld = 0;
     double* d_pfb = nullptr; int64_t cap_pfb = 0;
+    // warm-up (octo_draws_adapt.hip), grown on demand: the block partials of the grouped moments
+    double* d_mom = nullptr; int64_t cap_mom = 0;
 };
 
 namespace {

@@ -66,6 +66,13 @@ inline HmcWork hmc_work(Carve& c, int64_t D, int64_t ld) {
     return {c.take(D * ld), c.take(D * ld), c.take(D * ld), c.take(D * ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld)};
 }
 
+// The block partials of the grouped moments (octo_draws_adapt.hip), d_mom: nblk·G·(2K + 1). Per block of 256 chains and group: the number
+// of chains it holds · per row their sum and Σ(x − the block's mean)². sum and m2 of a (block, group) with cnt = 0 are never written or read.
+struct MomentsPartials { double *cnt, *sum, *m2; };      // [nblk][G] · [nblk][G][K] · [nblk][G][K]
+inline MomentsPartials moments_partials(Carve& c, int64_t nblk, int64_t G, int64_t K) {
+    return {c.take(nblk * G), c.take(nblk * G * K), c.take(nblk * G * K)};
+}
+
 // The device side of the host-buffer twins, both on d_hst. octo_draws_lbfgs: 2·D·ld + 5·ld + D
 struct LbfgsStaging {
     double *theta_t, *inv_hess_diag;      // [D][ld]

@@ -12,6 +12,10 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   octofit_pt_device: parallel tempering with a tempered HMC explorer, fresh prior draws at β = 0 and the swap step all on the device
   (PriorDraws.hmc_step, host/tempering.py: TemperedSwap) — the device-resident twin of julia/OctofitterHIP.jl: octofit_pigeons_hip.
 
+  warmup_windows / hmc_warmup / octofit_hmc_device: the single-temperature sampler — Pathfinder starts, then HMC whose step size (dual
+  averaging on the mean acceptance probability) and diagonal metric (the pooled variance of the chains, Stan's windowed schedule) are adapted
+  from cross-chain reductions on the device (PriorDraws.moments / metric / adapt_init / adapt_step), with R̂ from per-chain running moments.
+
   optimize_starting_points_device: stage 2 of the reference's initialisation (src/initialization.jl:188-289) — a batched L-BFGS from the best
   prior draws, every chain on the device (PriorDraws.lbfgs); the host reads one status vector a segment.
 
@@ -139,7 +143,7 @@ def octofit_rejection_device(model, draws=100_000, seed=0):
                 index=r["index"], max_loglike=r["max_loglike"])
 
 
-def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None, betas=None, inv_mass=None, seed=0, n_adapt=None):
+def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None, betas=None, inv_mass=None, seed=0, n_adapt=None, adapt="host"):
     """Parallel tempering with every piece on the device — the device-resident twin of julia/OctofitterHIP.jl: octofit_pigeons_hip, with a
     gradient-based explorer in place of its random walk: n_chains independent PT chains of n_temps replicas each (replica r of chain c is
     walker r·n_chains + c, the layout of TemperedSwap), θ_t never leaving the device during a round. Single rank.
@@ -153,6 +157,9 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
       4. TemperedSwap.swap_step on ℓ.
     During the first n_adapt rounds (default: half of them) ε of every temperature follows log ε_t += (acc_t − 0.8)/√(round + 1), acc_t that
     temperature's mean acceptance of the round. eps: the starting ε, a number or one per temperature (default 0.1).
+    adapt="device" replaces that rule by dual averaging on the mean acceptance probability min(1, exp(dH)) of every temperature
+    (PriorDraws.adapt_init / adapt_step, group = ladder slot, update number = round + 1, Stan's constants); after the n_adapt rounds every
+    temperature runs at its averaged ε̄. The metric is the same in both.
 
     Returns dict(samples [n_rounds, D, n_chains] natural domain, samples_t the same as θ_t, logpost [n_rounds, n_chains] — the β = 1 replica of
     every chain after the exploration of each round —, hmc_acceptance [n_temps], swap_acceptance [n_temps − 1], eps [n_temps], betas, names,
@@ -165,6 +172,8 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
     if T < 2 or Cn < 1 or R < 1:
         raise ValueError("octofit_pt_device: n_temps >= 2, n_chains >= 1, n_rounds >= 1")
     n_adapt = R // 2 if n_adapt is None else int(n_adapt)
+    if adapt not in ("host", "device"):
+        raise ValueError('octofit_pt_device: adapt is "host" or "device"')
     fn = model.ln_like
     dev = torch.device("cuda", fn.device_index)
     W, D = T * Cn, int(model.D)
@@ -177,6 +186,10 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
         inv_mass = torch.as_tensor(inv_mass, dtype=torch.float64, device=dev).contiguous()
         log_eps = torch.log(torch.as_tensor(0.1 if eps is None else eps, dtype=torch.float64, device=dev).expand(T).clone())
         theta_t = pd.sample(seed, 0, W, theta=False, logprior_t=False)[1]
+        da_state = None
+        if adapt == "device":
+            da_state = pd.adapt_init(T, torch.as_tensor(0.1 if eps is None else eps, dtype=torch.float64, device=dev).expand(T).contiguous())
+            log_eps = da_state[:, 0].clone()
         next_draw = W
         slots = torch.arange(T, dtype=torch.int32, device=dev).repeat(Cn, 1)
         chains = torch.arange(Cn, device=dev)
@@ -201,7 +214,10 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
                 next_draw += Cn
             acc_t = torch.zeros(T, dtype=torch.float64, device=dev).index_add_(0, slot_w, acc.double()) / Cn
             acc_sum += acc_t
-            if r < n_adapt:
+            if r < n_adapt and da_state is not None:
+                pd.adapt_step(da_state, _dH, acc, r + 1, group=slot_w.int(), want_eps=False)
+                log_eps = da_state[:, 1 if r == n_adapt - 1 else 0].clone()      # the next round's slots differ: ε is gathered by slot there
+            elif r < n_adapt:
                 log_eps += (acc_t - 0.8) / (r + 1) ** 0.5
             target = swap.slot2rep[:, 0].long() * Cn + chains
             rec_t[r] = theta_t[:, target]
@@ -216,6 +232,144 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
                     eps=torch.exp(log_eps).cpu().numpy(), betas=swap.beta.cpu().numpy(), names=list(model.names),
                     state=dict(theta_t=theta_t.cpu().numpy(), slot2rep=swap.slot2rep.cpu().numpy(),
                                refreshed=None if refreshed is None else refreshed.cpu().numpy(), refreshed_first=next_draw - Cn if cold_last else None))
+    finally:
+        pd.close()
+
+
+def warmup_windows(n_warmup):
+    """Stan's windowed warm-up schedule, scaled to n_warmup rounds: (initial buffer, [slow window lengths], terminal buffer), which tile
+    rounds 0 … n_warmup − 1 in that order.
+      n_warmup < 20: (n_warmup, [], 0) — the step size alone adapts.
+      Otherwise the buffers are 75 and 50 rounds and the first window 25; if those 150 do not fit they are 15 % and 10 % of n_warmup (rounded
+      down) and the first window takes the rest. Each window is twice as long as the one before; a window after which the next one would not
+      fit in front of the terminal buffer is stretched to reach it. n_warmup = 1000: (75, [25, 50, 100, 200, 500], 50)."""
+    n = int(n_warmup)
+    if n < 0:
+        raise ValueError("warmup_windows: n_warmup >= 0")
+    if n < 20:
+        return n, [], 0
+    init, term, size = 75, 50, 25
+    if init + size + term > n:
+        init, term = 15 * n // 100, 10 * n // 100
+        size = n - init - term
+    windows, start, end = [], init, n - term
+    while start < end:
+        stop = start + size
+        if stop + 2 * size > end:
+            stop = end
+        windows.append(stop - start)
+        start, size = stop, 2 * size
+    return init, windows, term
+
+
+def hmc_warmup(pd, theta_t, n_warmup, n_leapfrog=8, eps=0.1, inv_mass=None, target_accept=0.8, seed=0, step=0, chain0=0, gamma=0.05, t0=10.0, kappa=0.75,
+               record=None):
+    """Warm-up of PriorDraws.hmc_step on the W chains of theta_t ([D, W] on the device, updated in place) at β = 1 — on a handle without a
+    model: on the prior. n_warmup rounds on the schedule of warmup_windows; round r is one hmc_step with step number step + r and then
+      * the dual-averaging update of ε from the round's mean acceptance probability (PriorDraws.adapt_step, one group, δ = target_accept);
+      * inside a slow window: the chains' states merged into the pooled moments (PriorDraws.moments, accumulate from the window's second round on);
+      * at a window's last round: inv_mass <- metric(regularize=True) of those moments, the moments restart with the next window, and the
+        dual averaging restarts from ε̄ (x = x̄ = log ε̄, H̄ = 0, μ = log 10ε̄, update number 1 next).
+    After the last round ε = ε̄. Nothing is read back: every statistic stays on the device.
+    record: a list that receives one dict a round with copies of what each call of the round read and wrote (dH, accepted, theta_t, the
+    dual-averaging state before and after, the moments before and after, inv_mass after), for a caller who follows the adaptation.
+    inv_mass: [D] (a copy is adapted) or None = 1. Returns dict(theta_t, eps (a [1] tensor), inv_mass [D], accept_stat [n_warmup], step (the
+    next step number)), device tensors."""
+    import torch
+    dev = theta_t.device
+    D, W = int(theta_t.shape[0]), int(theta_t.shape[1])
+    n = int(n_warmup)
+    init, windows, _term = warmup_windows(n)
+    first, last = set(), set()
+    at = init
+    for length in windows:
+        first.add(at)
+        at += length
+        last.add(at - 1)
+    inv_mass = torch.ones(D, dtype=torch.float64, device=dev) if inv_mass is None else torch.as_tensor(inv_mass, dtype=torch.float64, device=dev).clone().contiguous()
+    state = pd.adapt_init(1, eps)
+    eps_w = torch.exp(state[:, 0]).expand(W).contiguous()
+    accept_stat = torch.empty(n, dtype=torch.float64, device=dev)
+    mom, in_window, k = None, False, 0
+    for r in range(n):
+        _lp, _ll, dH, acc = pd.hmc_step(theta_t, eps=eps_w, n_leapfrog=n_leapfrog, inv_mass=inv_mass, seed=seed, step=step + r, chain0=chain0)
+        k += 1
+        rec = None if record is None else dict(round=r, k=k, dH=dH, accepted=acc, theta_t=theta_t.clone(), state_in=state.clone(), use_average=r == n - 1,
+                                               mom_in=None if mom is None else tuple(t.clone() for t in mom))
+        a, _ = pd.adapt_step(state, dH, acc, k, delta=target_accept, gamma=gamma, t0=t0, kappa=kappa, use_average=r == n - 1, eps_w=eps_w)
+        accept_stat[r:r + 1] = a
+        in_window = in_window or r in first
+        if in_window:
+            mom = pd.moments(theta_t, out=mom, accumulate=r not in first)
+        if rec is not None:
+            rec.update(state=state.clone(), accept_stat=a, eps_w=eps_w.clone(), in_window=in_window, first=r in first, last=r in last,
+                       mom=tuple(t.clone() for t in mom) if in_window else None, inv_mass_in=inv_mass.clone())
+            record.append(rec)
+        if r in last:
+            pd.metric(mom[0], mom[1][0], mom[2][0], inv_mass, regularize=True)
+            pd.adapt_init(1, torch.exp(state[:, 1]), state=state)
+            eps_w = torch.exp(state[:, 0]).expand(W).contiguous()
+            in_window, k = False, 0
+            if rec is not None:
+                rec.update(inv_mass=inv_mass.clone(), state_restart=state.clone())
+    return dict(theta_t=theta_t, eps=eps_w[:1].clone() if W else torch.exp(state[:, 1]), inv_mass=inv_mass, accept_stat=accept_stat, step=step + n)
+
+
+def rhat_from_chain_moments(pd, cmean, cm2, n):
+    """R̂ [K] of n samples per chain from their running moments (PriorDraws.chain_moments) by two PriorDraws.moments calls, as
+    include/octofitter_hip_draws.h states it. A device tensor."""
+    import torch
+    cnt, _, m2b = pd.moments(cmean)
+    _, mw, _ = pd.moments(cm2)
+    b_over_n = m2b[0] / (cnt[0] - 1.0)
+    wv = mw[0] / (n - 1.0)
+    return torch.sqrt(((n - 1.0) / n * wv + b_over_n) / wv)
+
+
+def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leapfrog=8, target_accept=0.8, init=None, eps=0.1, seed=0):
+    """The reference's main entry (octofit: Pathfinder start, then HMC with step-size and metric adaptation) with every piece on the device:
+    n_chains chains at β = 1, static trajectories of n_leapfrog steps, a diagonal metric.
+      starts    init [D, n_chains] in θ_t, or pathfinder_device(model, n_draws=n_chains, seed=seed)["theta_t"];
+      metric    starts at the per-coordinate variance of prior draws 0 … 4095 in θ_t (the default of the other drivers);
+      warm-up   hmc_warmup: n_warmup rounds, step numbers 0 … n_warmup − 1;
+      sampling  n_samples rounds with ε and the metric fixed, step numbers going on; every round is recorded and enters the per-chain
+                running moments (PriorDraws.chain_moments); R̂ from two PriorDraws.moments calls at the end.
+    Returns dict(samples [n_samples, D, n_chains] natural domain, samples_t the same as θ_t, logpost [n_samples, n_chains], accept_stat
+    [n_warmup + n_samples] (the mean of min(1, exp(dH)) of each round), eps, inv_mass [D], rhat [D], names, state = dict(theta_t, step)), NumPy."""
+    import torch
+    from .draws import PriorDraws
+    Cn, nw, ns = int(n_chains), int(n_warmup), int(n_samples)
+    if Cn < 2 or nw < 0 or ns < 1:
+        raise ValueError("octofit_hmc_device: n_chains >= 2, n_warmup >= 0, n_samples >= 1")
+    dev = torch.device("cuda", model.ln_like.device_index)
+    D = int(model.D)
+    if init is None:
+        init = pathfinder_device(model, n_draws=Cn, seed=seed)["theta_t"]
+    theta_t = torch.as_tensor(init, dtype=torch.float64, device=dev).clone().contiguous()
+    if tuple(theta_t.shape) != (D, Cn):
+        raise ValueError(f"octofit_hmc_device: init must be [D = {D}, n_chains = {Cn}] in θ_t")
+    pd = PriorDraws(model)
+    try:
+        inv_mass = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1)
+        wu = hmc_warmup(pd, theta_t, nw, n_leapfrog=n_leapfrog, eps=eps, inv_mass=inv_mass, target_accept=target_accept, seed=seed)
+        eps_w, inv_mass = wu["eps"].expand(Cn).contiguous(), wu["inv_mass"]
+        rec_t = torch.empty((ns, D, Cn), dtype=torch.float64, device=dev)
+        rec_lp = torch.empty((ns, Cn), dtype=torch.float64, device=dev)
+        acc_s = torch.empty(ns, dtype=torch.float64, device=dev)
+        cmean, cm2 = torch.empty_like(theta_t), torch.empty_like(theta_t)
+        state = pd.adapt_init(1, eps)      # never fed back: adapt_step is the reduction that gives the round's acceptance statistic
+        for r in range(ns):
+            lp, _ll, dH, acc = pd.hmc_step(theta_t, eps=eps_w, n_leapfrog=n_leapfrog, inv_mass=inv_mass, seed=seed, step=nw + r)
+            acc_s[r:r + 1] = pd.adapt_step(state, dH, acc, r + 1, delta=target_accept, want_eps=False)[0]
+            rec_t[r] = theta_t
+            rec_lp[r] = lp
+            pd.chain_moments(theta_t, r + 1, cmean, cm2)
+        rhat = rhat_from_chain_moments(pd, cmean, cm2, ns)
+        torch.cuda.synchronize(dev)
+        samples_t = rec_t.cpu().numpy()
+        return dict(samples=np.stack([model.invlink(x) for x in samples_t]), samples_t=samples_t, logpost=rec_lp.cpu().numpy(),
+                    accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
+                    rhat=rhat.cpu().numpy(), names=list(model.names), state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns))
     finally:
         pd.close()
 

@@ -10,6 +10,11 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     r = draws.lbfgs(θ_t, inv_mass=v, n_rounds=50)           # 50 rounds of L-BFGS on every column, θ_t updated in place: dict of device tensors
     r = draws.pathfinder(θ_t, inv_mass=v, n_rounds=50, seed=seed)      # the same rounds with Pathfinder's fits along the path: also elbo, elbo_iter, n_fits
     φ, logq, logpost = draws.pathfinder_draw(θ_t, 256, seed=seed)      # [D, 256·W], [256·W], [256·W]: draws from every chain's kept fit
+    count, mean, m2 = draws.moments(θ_t)                    # warm-up: pooled moments of the chains, [1], [1, D], [1, D] (or per group)
+    draws.metric(count[0:1], mean[0], m2[0], inv_mass)      # … the diagonal metric they give, written into inv_mass [D]
+    state = draws.adapt_init(1, 0.1)                        # … dual averaging of ε: the state [G, 4]
+    a, eps_w = draws.adapt_step(state, dH, acc, k)          # … update k from a step's dH and accepted: mean acceptance [G], ε per chain [W]
+    draws.chain_moments(θ_t, k, cmean, cm2)                 # per-chain running mean and M2 over time (R̂: include/octofitter_hip_draws.h)
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -30,6 +35,7 @@ LBFGS_MAX_M = 8                    # OCTO_DRAWS_LBFGS_MAX_M
 LBFGS_ACTIVE, LBFGS_GTOL, LBFGS_FTOL, LBFGS_LINESEARCH, LBFGS_DEAD = 0, 1, 2, 3, 4      # OCTO_DRAWS_LBFGS_*
 PF_MAX_D = 64                      # OCTO_DRAWS_PF_MAX_D
 PF_MAX_ELBO_DRAWS = 32             # OCTO_DRAWS_PF_MAX_ELBO_DRAWS
+MAX_GROUPS = 64                    # OCTO_DRAWS_MAX_GROUPS
 
 c_uint64_p = C.POINTER(C.c_uint64)
 
@@ -60,6 +66,13 @@ _SIGS = {
                                                  C.c_double, C.c_int32, C.c_int32] + [C.c_void_p] * 10),
     "octo_draws_pathfinder_draw_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_moments_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "octo_draws_metric_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "octo_draws_hmc_adapt_init_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "octo_draws_hmc_adapt_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "octo_draws_chain_moments_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -328,6 +341,113 @@ class PriorDraws(companion.Handle):
                                                                lp.data_ptr(), self._stream(stream, dev)))
         self._keep = (theta_t,)
         return phi, logq, lp
+
+    # ---- warm-up (include/octofitter_hip_draws.h, "Warm-up of the explorer"): K = the rows of x, not the handle's D
+    def _rows(self, x, what, name="x"):
+        """(K, W, ld) of a float64 [K, W] tensor on the handle's device with contiguous rows."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        if x.dtype != torch.float64 or x.ndim != 2 or x.device != dev or (x.shape[1] and x.stride(1) != 1):
+            raise ValueError(f"{what}: {name} must be a float64 [K, W] tensor on {dev} with contiguous rows")
+        K, W = int(x.shape[0]), int(x.shape[1])
+        return K, W, (int(x.stride(0)) if K > 1 and W else W)
+
+    def _groups(self, group, W, dev, what):
+        """None, or the int32 [W] group ids on `dev`."""
+        import torch
+        if group is None:
+            return None
+        g = torch.as_tensor(group, device=dev).to(torch.int32).contiguous()
+        if g.shape != (W,):
+            raise ValueError(f"{what}: group takes {W} ids")
+        return g
+
+    def moments(self, x, group=None, G=1, out=None, accumulate=False, stream=None):
+        """Cross-chain moments of x [K, W] per group (group: int32 [W] ids, None = one group; ids outside 0 … G − 1 and chains with a
+        non-finite value are excluded): (count [G], mean [G, K], m2 [G, K] = Σ(x − mean)²), device tensors. out=(count, mean, m2): write into these;
+        with accumulate=True Chan-merge this call's block into what they hold. Asynchronous on `stream`."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        K, W, ld = self._rows(x, "moments")
+        g = self._groups(group, W, dev, "moments")
+        G = int(G)
+        if accumulate and out is None:
+            raise ValueError("moments: accumulate=True needs out=(count, mean, m2)")
+        if out is None:
+            cnt = torch.empty(G, dtype=torch.float64, device=dev)
+            mean, m2 = (torch.empty((G, K), dtype=torch.float64, device=dev) for _ in range(2))
+        else:
+            cnt, mean, m2 = out
+            if cnt.shape != (G,) or mean.shape != (G, K) or m2.shape != (G, K) or not (cnt.is_contiguous() and mean.is_contiguous() and m2.is_contiguous()):
+                raise ValueError(f"moments: out must be contiguous (count [{G}], mean [{G}, {K}], m2 [{G}, {K}])")
+        self._check(self.lib.octo_draws_moments_device(self._h, W, ld, K, x.data_ptr(), None if g is None else g.data_ptr(), G, 1 if accumulate else 0,
+                                                       cnt.data_ptr(), mean.data_ptr(), m2.data_ptr(), self._stream(stream, dev)))
+        self._keep = (x, g)
+        return cnt, mean, m2
+
+    def metric(self, count, mean, m2, inv_mass, regularize=True, stream=None):
+        """inv_mass [K] (updated in place, returned) from ONE group's moments: count [1], mean [K], m2 [K] (rows of moments' outputs).
+        M2/(n − 1), with regularize Stan's shrinkage towards 1e-3; entries with n < 2 or a variance not finite and > 0 keep their value."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        K = int(m2.numel())
+        for t, n in ((count, 1), (mean, K), (m2, K), (inv_mass, K)):
+            if t.dtype != torch.float64 or t.device != dev or t.numel() != n or not t.is_contiguous():
+                raise ValueError("metric: count [1], mean [K], m2 [K] and inv_mass [K] must be contiguous float64 tensors on the handle's device")
+        self._check(self.lib.octo_draws_metric_device(self._h, K, count.data_ptr(), mean.data_ptr(), m2.data_ptr(), 1 if regularize else 0, inv_mass.data_ptr(),
+                                                      self._stream(stream, dev)))
+        self._keep = (count, mean, m2, inv_mass)
+        return inv_mass
+
+    def adapt_init(self, G, eps0, state=None, stream=None):
+        """The dual-averaging state [G, 4] = (log ε, log ε̄, H̄, μ) started at eps0 (a number, or one value per group); state: written in place."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        G = int(G)
+        per_group = torch.is_tensor(eps0) or np.ndim(eps0) > 0
+        e = self._device_vector(eps0, G, dev, "eps0") if per_group else None
+        if state is None:
+            state = torch.empty((G, 4), dtype=torch.float64, device=dev)
+        elif state.dtype != torch.float64 or state.device != dev or state.shape != (G, 4) or not state.is_contiguous():
+            raise ValueError(f"adapt_init: state must be a contiguous float64 [{G}, 4] tensor on {dev}")
+        self._check(self.lib.octo_draws_hmc_adapt_init_device(self._h, G, None if e is None else e.data_ptr(), 0.0 if per_group else float(eps0), state.data_ptr(),
+                                                              self._stream(stream, dev)))
+        self._keep = (e, state)
+        return state
+
+    def adapt_step(self, state, dH, accepted, k, group=None, delta=0.8, gamma=0.05, t0=10.0, kappa=0.75, use_average=False, eps_w=None, want_eps=True,
+                   stream=None):
+        """Dual-averaging update number k >= 1 of `state` [G, 4] (in place) from a step's dH [W] and accepted int32 [W]; group: int32 [W] ids or
+        None (G = 1). Returns (accept_stat [G], the mean of min(1, exp(dH)) per group, NaN for an empty one; eps_w [W], ε — with use_average
+        ε̄ — of every chain's group, what hmc_step takes as eps; None with want_eps=False). eps_w: written in place where a chain has a group."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        W, G = int(dH.numel()), int(state.shape[0])
+        if dH.dtype != torch.float64 or accepted.dtype != torch.int32 or accepted.numel() != W or not (dH.is_contiguous() and accepted.is_contiguous()) \
+                or state.dtype != torch.float64 or state.shape != (G, 4) or not state.is_contiguous() or dH.device != dev or accepted.device != dev or state.device != dev:
+            raise ValueError(f"adapt_step: dH float64 [W], accepted int32 [W] and state float64 [G, 4], contiguous on {dev}")
+        g = self._groups(group, W, dev, "adapt_step")
+        a = torch.empty(G, dtype=torch.float64, device=dev)
+        if eps_w is None and want_eps:
+            eps_w = torch.empty(W, dtype=torch.float64, device=dev)
+        self._check(self.lib.octo_draws_hmc_adapt_device(self._h, W, None if g is None else g.data_ptr(), G, dH.data_ptr(), accepted.data_ptr(), int(k), float(delta),
+                                                         float(gamma), float(t0), float(kappa), state.data_ptr(), a.data_ptr(), 1 if use_average else 0,
+                                                         None if eps_w is None else eps_w.data_ptr(), self._stream(stream, dev)))
+        self._keep = (state, dH, accepted, g, eps_w)
+        return a, eps_w
+
+    def chain_moments(self, x, k, cmean, cm2, stream=None):
+        """Sample number k >= 1 of every chain's running moments over time: cmean, cm2 [K, W] of x's shape and leading dimension, in place
+        (k = 1 starts them). R̂ follows from two moments calls on them (include/octofitter_hip_draws.h)."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        K, W, ld = self._rows(x, "chain_moments")
+        for t, name in ((cmean, "cmean"), (cm2, "cm2")):
+            if self._rows(t, "chain_moments", name) != (K, W, ld):
+                raise ValueError(f"chain_moments: {name} must have x's shape and leading dimension")
+        self._check(self.lib.octo_draws_chain_moments_device(self._h, W, ld, K, int(k), x.data_ptr(), cmean.data_ptr(), cm2.data_ptr(), self._stream(stream, dev)))
+        self._keep = (x, cmean, cm2)
+        return cmean, cm2
 
     def close(self):
         if getattr(self, "_h", None) and self.model is not None and not getattr(self.model.ln_like, "_ctx", None):
