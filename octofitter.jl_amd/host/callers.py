@@ -106,11 +106,8 @@ def guess_starting_position_device(model, N=500_000, seed=0, keep=1):
     """guess_starting_position with the N prior draws made, linked, scored and ranked on the device (draws 0 … N − 1 of the counter-based
     stream `seed`): (bestparams, bestlogpost) like the host twin; with keep > 1 the `keep` best, best first: ([D, keep], [keep])."""
     from .draws import PriorDraws
-    draws = PriorDraws(model)
-    try:
+    with PriorDraws(model) as draws:
         θ, lp, _ = draws.best(seed, N, keep=keep)
-    finally:
-        draws.close()
     if keep == 1:
         return θ[:, 0].copy(), float(lp[0])
     return θ, lp
@@ -123,16 +120,13 @@ def octofit_rejection_device(model, draws=100_000, seed=0):
     draw indices `index`) — and all_loglike = None: the per-draw likelihoods stay on the device."""
     from . import capi
     from .draws import PriorDraws
-    pd = PriorDraws(model)
-    try:
+    with PriorDraws(model) as pd:
         try:
             r = pd.rejection(seed, draws)
         except capi.OctoError as e:
             if e.status == capi.OCTO_EINVAL and "non-finite log-likelihoods" in str(e):
                 raise RuntimeError(str(e).split(": ", 1)[1]) from None
             raise
-    finally:
-        pd.close()
     if r["n_accepted"] == 0:
         raise RuntimeError(f"No samples were accepted out of {draws} draws. The posterior may be extremely concentrated relative "
                            "to the prior. Consider increasing `draws` or using a different sampler.")
@@ -141,6 +135,26 @@ def octofit_rejection_device(model, draws=100_000, seed=0):
     return dict(samples=r["samples"], loglike=r["loglike"], logpost=r["logpost"], draws=int(draws), n_accepted=r["n_accepted"],
                 acceptance_rate=r["n_accepted"] / draws, names=list(model.names), accept=accept, all_loglike=None,
                 index=r["index"], max_loglike=r["max_loglike"])
+
+
+def _default_metric(pd, seed, dev, inv_mass):
+    """inv_mass — by default the per-coordinate variance of prior draws 0 … 4095 in θ_t — as a contiguous float64 [D] tensor on dev."""
+    import torch
+    if inv_mass is None:
+        inv_mass = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1)
+    return torch.as_tensor(inv_mass, dtype=torch.float64, device=dev).contiguous()
+
+
+def _finite_or_neg_inf(x):
+    """x with −Inf in place of every non-finite value."""
+    import torch
+    return torch.where(torch.isfinite(x), x, torch.full_like(x, -float("inf")))
+
+
+def _recorded(model, rec_t, rec_lp):
+    """What a sampler returns of its recorded rounds rec_t [n, D, n_chains] (θ_t) and rec_lp [n, n_chains]: samples, samples_t, logpost."""
+    samples_t = rec_t.cpu().numpy()
+    return dict(samples=np.stack([model.invlink(x) for x in samples_t]), samples_t=samples_t, logpost=rec_lp.cpu().numpy())
 
 
 def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None, betas=None, inv_mass=None, seed=0, n_adapt=None, adapt="host"):
@@ -177,13 +191,10 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
     fn = model.ln_like
     dev = torch.device("cuda", fn.device_index)
     W, D = T * Cn, int(model.D)
-    pd = PriorDraws(model)
-    try:
+    with PriorDraws(model) as pd:
         swap = TemperedSwap(fn, T, Cn, device=dev, seed=seed, betas=betas)
         cold_last = float(swap.beta[-1]) == 0.0      # the ladder ends at the prior: its replicas are redrawn IID every round
-        if inv_mass is None:
-            inv_mass = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1)
-        inv_mass = torch.as_tensor(inv_mass, dtype=torch.float64, device=dev).contiguous()
+        inv_mass = _default_metric(pd, seed, dev, inv_mass)
         log_eps = torch.log(torch.as_tensor(0.1 if eps is None else eps, dtype=torch.float64, device=dev).expand(T).clone())
         theta_t = pd.sample(seed, 0, W, theta=False, logprior_t=False)[1]
         da_state = None
@@ -210,7 +221,7 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
                 ll_f = lp_f - lpt
                 theta_t[:, refreshed] = fresh
                 lp[refreshed] = lp_f
-                ll[refreshed] = torch.where(torch.isfinite(ll_f), ll_f, torch.full_like(ll_f, -float("inf")))
+                ll[refreshed] = _finite_or_neg_inf(ll_f)
                 next_draw += Cn
             acc_t = torch.zeros(T, dtype=torch.float64, device=dev).index_add_(0, slot_w, acc.double()) / Cn
             acc_sum += acc_t
@@ -226,14 +237,11 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
         torch.cuda.synchronize(dev)
         pairs = np.arange(T - 1)
         attempts = np.array([(R + 1 - (t % 2)) // 2 for t in pairs]) * Cn            # pair (t, t + 1) is tried in the rounds of parity t % 2
-        samples_t = rec_t.cpu().numpy()
-        return dict(samples=np.stack([model.invlink(x) for x in samples_t]), samples_t=samples_t, logpost=rec_lp.cpu().numpy(),
+        return dict(**_recorded(model, rec_t, rec_lp),
                     hmc_acceptance=(acc_sum / R).cpu().numpy(), swap_acceptance=swap.accepted.cpu().numpy()[:T - 1] / np.maximum(attempts, 1),
                     eps=torch.exp(log_eps).cpu().numpy(), betas=swap.beta.cpu().numpy(), names=list(model.names),
                     state=dict(theta_t=theta_t.cpu().numpy(), slot2rep=swap.slot2rep.cpu().numpy(),
                                refreshed=None if refreshed is None else refreshed.cpu().numpy(), refreshed_first=next_draw - Cn if cold_last else None))
-    finally:
-        pd.close()
 
 
 def warmup_windows(n_warmup):
@@ -348,9 +356,8 @@ def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leap
     theta_t = torch.as_tensor(init, dtype=torch.float64, device=dev).clone().contiguous()
     if tuple(theta_t.shape) != (D, Cn):
         raise ValueError(f"octofit_hmc_device: init must be [D = {D}, n_chains = {Cn}] in θ_t")
-    pd = PriorDraws(model)
-    try:
-        inv_mass = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1)
+    with PriorDraws(model) as pd:
+        inv_mass = _default_metric(pd, seed, dev, None)
         wu = hmc_warmup(pd, theta_t, nw, n_leapfrog=n_leapfrog, eps=eps, inv_mass=inv_mass, target_accept=target_accept, seed=seed)
         eps_w, inv_mass = wu["eps"].expand(Cn).contiguous(), wu["inv_mass"]
         rec_t = torch.empty((ns, D, Cn), dtype=torch.float64, device=dev)
@@ -366,12 +373,37 @@ def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leap
             pd.chain_moments(theta_t, r + 1, cmean, cm2)
         rhat = rhat_from_chain_moments(pd, cmean, cm2, ns)
         torch.cuda.synchronize(dev)
-        samples_t = rec_t.cpu().numpy()
-        return dict(samples=np.stack([model.invlink(x) for x in samples_t]), samples_t=samples_t, logpost=rec_lp.cpu().numpy(),
+        return dict(**_recorded(model, rec_t, rec_lp),
                     accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
                     rhat=rhat.cpu().numpy(), names=list(model.names), state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns))
-    finally:
-        pd.close()
+
+
+def _optimizer_starts(pd, model, N, n_starts, seed, dev, inv_mass):
+    """Where the two optimiser drivers start: (θ0 [D, n_starts] the best of prior draws 0 … N − 1, their ℓπ, inv_mass [D] on dev — by default
+    _default_metric —, theta_t = link(θ0) on dev)."""
+    import torch
+    θ0, lp0, _ = pd.best(seed, N, keep=n_starts)
+    inv_mass = _default_metric(pd, seed, dev, inv_mass)
+    return θ0, lp0, inv_mass, torch.as_tensor(model.link(θ0), dtype=torch.float64, device=dev).contiguous()
+
+
+def _run_segments(segment, max_rounds, rounds_per_call):
+    """segment(n_rounds, resume) -> result dict, in segments of rounds_per_call rounds until no chain is active or after max_rounds: the last result."""
+    from .draws import LBFGS_ACTIVE
+    done, r = 0, None
+    while done < max_rounds:
+        n = min(int(rounds_per_call), int(max_rounds) - done)
+        r = segment(n, done > 0)
+        done += n
+        if not bool((r["status"] == LBFGS_ACTIVE).any()):      # the one read of a segment
+            break
+    return r
+
+
+def _to_numpy_with_best(r):
+    """(an optimiser's result dict as NumPy, the index of its highest finite logpost)."""
+    out = {k: v.cpu().numpy() for k, v in r.items()}
+    return out, int(np.argmax(np.where(np.isfinite(out["logpost"]), out["logpost"], -np.inf)))
 
 
 def optimize_starting_points_device(model, N=500_000, n_starts=64, seed=0, m=6, gtol=1e-6, ftol=0.0, max_rounds=1000, rounds_per_call=50, inv_mass=None):
@@ -385,30 +417,17 @@ def optimize_starting_points_device(model, N=500_000, n_starts=64, seed=0, m=6, 
     host/draws.py), gnorm, iters, evals, inv_hess_diag [D, n] (the Pathfinder diagonal in θ_t: a natural inv_mass for hmc_step), best (the index of
     the highest ℓπ), names."""
     import torch
-    from .draws import LBFGS_ACTIVE, PriorDraws
+    from .draws import PriorDraws
     if max_rounds < 1 or rounds_per_call < 1:
         raise ValueError("optimize_starting_points_device: max_rounds >= 1, rounds_per_call >= 1")
     dev = torch.device("cuda", model.ln_like.device_index)
-    pd = PriorDraws(model)
-    try:
-        θ0, lp0, _ = pd.best(seed, N, keep=n_starts)
-        if inv_mass is None:
-            inv_mass = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1)
-        inv_mass = torch.as_tensor(inv_mass, dtype=torch.float64, device=dev).contiguous()
-        theta_t = torch.as_tensor(model.link(θ0), dtype=torch.float64, device=dev).contiguous()
-        done, r = 0, None
-        while done < max_rounds:
-            n = min(int(rounds_per_call), int(max_rounds) - done)
-            r = pd.lbfgs(theta_t, inv_mass=inv_mass, m=m, n_rounds=n, gtol=gtol, ftol=ftol, resume=done > 0, want_inv_hess_diag=True)
-            done += n
-            if not bool((r["status"] == LBFGS_ACTIVE).any()):      # the one read of a segment
-                break
+    with PriorDraws(model) as pd:
+        θ0, lp0, inv_mass, theta_t = _optimizer_starts(pd, model, N, n_starts, seed, dev, inv_mass)
+        r = _run_segments(lambda n, resume: pd.lbfgs(theta_t, inv_mass=inv_mass, m=m, n_rounds=n, gtol=gtol, ftol=ftol, resume=resume, want_inv_hess_diag=True),
+                          max_rounds, rounds_per_call)
         tt = theta_t.cpu().numpy()
-        out = {k: v.cpu().numpy() for k, v in r.items()}
-        return dict(theta=model.invlink(tt), theta_t=tt, start_logpost=lp0, best=int(np.argmax(np.where(np.isfinite(out["logpost"]), out["logpost"], -np.inf))),
-                    names=list(model.names), **out)
-    finally:
-        pd.close()
+        out, best = _to_numpy_with_best(r)
+        return dict(theta=model.invlink(tt), theta_t=tt, start_logpost=lp0, best=best, names=list(model.names), **out)
 
 
 def pathfinder_device(model, N=500_000, n_paths=64, n_draws=1000, n_draws_per_path=256, n_elbo=5, seed=0, m=6, gtol=1e-6, ftol=0.0, max_rounds=1000,
@@ -425,48 +444,33 @@ def pathfinder_device(model, N=500_000, n_paths=64, n_draws=1000, n_draws_per_pa
     elbo_iter, n_fits and the outputs of optimize_starting_points_device (path_theta, path_theta_t, path_logpost, start_logpost, status, gnorm,
     iters, evals, inv_hess_diag, best), names. Raises RuntimeError if no path has a fit."""
     import torch
-    from .draws import LBFGS_ACTIVE, PriorDraws
+    from .draws import PriorDraws
     from .psis import Psis
     if max_rounds < 1 or rounds_per_call < 1 or n_draws < 1 or n_draws_per_path < 1:
         raise ValueError("pathfinder_device: max_rounds, rounds_per_call, n_draws, n_draws_per_path >= 1")
     dev = torch.device("cuda", model.ln_like.device_index)
-    pd, ps = PriorDraws(model), None
-    try:
-        θ0, lp0, _ = pd.best(seed, N, keep=n_paths)
-        if inv_mass is None:
-            inv_mass = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1)
-        inv_mass = torch.as_tensor(inv_mass, dtype=torch.float64, device=dev).contiguous()
-        theta_t = torch.as_tensor(model.link(θ0), dtype=torch.float64, device=dev).contiguous()
-        done, r = 0, None
-        while done < max_rounds:
-            n = min(int(rounds_per_call), int(max_rounds) - done)
-            r = pd.pathfinder(theta_t, inv_mass=inv_mass, m=m, n_rounds=n, gtol=gtol, ftol=ftol, resume=done > 0, want_inv_hess_diag=True, seed=seed, n_elbo=n_elbo)
-            done += n
-            if not bool((r["status"] == LBFGS_ACTIVE).any()):      # the one read of a segment
-                break
+    with PriorDraws(model) as pd:
+        θ0, lp0, inv_mass, theta_t = _optimizer_starts(pd, model, N, n_paths, seed, dev, inv_mass)
+        r = _run_segments(lambda n, resume: pd.pathfinder(theta_t, inv_mass=inv_mass, m=m, n_rounds=n, gtol=gtol, ftol=ftol, resume=resume,
+                                                          want_inv_hess_diag=True, seed=seed, n_elbo=n_elbo), max_rounds, rounds_per_call)
         if not bool((r["elbo_iter"] >= 0).any()):
             raise RuntimeError("pathfinder_device: no path has a fit (every start is dead, never accepted a step, or has only non-finite ELBOs)")
         phi, logq, lp = pd.pathfinder_draw(theta_t, n_draws_per_path, seed=seed)
-        ratio = lp - logq
-        ratio = torch.where(torch.isfinite(ratio), ratio, torch.full_like(ratio, -float("inf")))
-        ps = Psis(device=model.ln_like.device_index)
-        s = ps.loo((-ratio).reshape(1, -1), weights=True)      # its step 1 smooths r − max r
-        lw = s["log_weights"][0].cpu().numpy()
-        cdf = np.cumsum(np.exp(lw - lw.max()))
-        u = np.random.Generator(np.random.Philox(key=int(seed))).random(int(n_draws))
-        pick = np.minimum(np.searchsorted(cdf, u * cdf[-1], side="right"), cdf.size - 1)
-        W = theta_t.shape[1]
-        tt = phi[:, torch.as_tensor(pick, device=dev)].cpu().numpy()
-        path_tt = theta_t.cpu().numpy()
-        out = {k: v.cpu().numpy() for k, v in r.items()}
-        path_lp = out.pop("logpost")
-        return dict(theta=model.invlink(tt), theta_t=tt, logpost=lp.cpu().numpy()[pick], path=(pick % W).astype(np.int64), pareto_k=float(s["pareto_k"][0]),
-                    log_ratios=ratio.cpu().numpy(), log_weights=lw, path_theta=model.invlink(path_tt), path_theta_t=path_tt, path_logpost=path_lp,
-                    start_logpost=lp0, best=int(np.argmax(np.where(np.isfinite(path_lp), path_lp, -np.inf))), names=list(model.names), **out)
-    finally:
-        if ps is not None:
-            ps.close()
-        pd.close()
+        ratio = _finite_or_neg_inf(lp - logq)
+        with Psis(device=model.ln_like.device_index) as ps:
+            s = ps.loo((-ratio).reshape(1, -1), weights=True)      # its step 1 smooths r − max r
+            lw = s["log_weights"][0].cpu().numpy()
+            cdf = np.cumsum(np.exp(lw - lw.max()))
+            u = np.random.Generator(np.random.Philox(key=int(seed))).random(int(n_draws))
+            pick = np.minimum(np.searchsorted(cdf, u * cdf[-1], side="right"), cdf.size - 1)
+            W = theta_t.shape[1]
+            tt = phi[:, torch.as_tensor(pick, device=dev)].cpu().numpy()
+            path_tt = theta_t.cpu().numpy()
+            out, best = _to_numpy_with_best(r)
+            path_lp = out.pop("logpost")
+            return dict(theta=model.invlink(tt), theta_t=tt, logpost=lp.cpu().numpy()[pick], path=(pick % W).astype(np.int64), pareto_k=float(s["pareto_k"][0]),
+                        log_ratios=ratio.cpu().numpy(), log_weights=lw, path_theta=model.invlink(path_tt), path_theta_t=path_tt, path_logpost=path_lp,
+                        start_logpost=lp0, best=best, names=list(model.names), **out)
 
 
 def pointwise_like(model, θ_samples):
@@ -514,11 +518,16 @@ def pointwise_like_rows(model, θ_samples):
     θ_samples = np.asarray(θ_samples, dtype=np.float64).reshape(model.D, -1)
     elems, nuis = model.kernel_inputs(θ_samples)
     pw, labels = _pointwise_handle(model)
-    try:
+    with pw:
         LL = pw.values(elems, nuis)
-    finally:
-        pw.close()
     return np.ascontiguousarray(LL.T), labels
+
+
+def _add_totals(out, keys, R):
+    """For each of the per-row arrays out[k], k in keys: out[k_total], the sum over the R rows, and out[k_se] = √(R · var over the rows)."""
+    for k in keys:
+        out[k + "_total"] = float(np.sum(out[k]))
+        out[k + "_se"] = float(np.sqrt(R * np.var(out[k], ddof=1))) if R > 1 else float("nan")
 
 
 def waic(model, θ_samples):
@@ -530,15 +539,10 @@ def waic(model, θ_samples):
     θ_samples = np.asarray(θ_samples, dtype=np.float64).reshape(model.D, -1)
     elems, nuis = model.kernel_inputs(θ_samples)
     pw, labels = _pointwise_handle(model)
-    try:
+    with pw:
         s = pw.summary(elems, nuis)
-    finally:
-        pw.close()
     out = dict(lppd=s["lppd"], p_waic=s["var"], elpd_waic=s["lppd"] - s["var"], elpd_is_loo=s["elpd_is_loo"])
-    R = len(labels)
-    for k in ("lppd", "p_waic", "elpd_waic", "elpd_is_loo"):
-        out[k + "_total"] = float(np.sum(out[k]))
-        out[k + "_se"] = float(np.sqrt(R * np.var(out[k], ddof=1))) if R > 1 else float("nan")
+    _add_totals(out, ("lppd", "p_waic", "elpd_waic", "elpd_is_loo"), len(labels))
     out.update(n_valid=s["n"], n_samples=int(θ_samples.shape[1]), labels=labels)
     return out
 
@@ -559,24 +563,15 @@ def loo(model, θ_samples, weights=False):
     θ_samples = np.asarray(θ_samples, dtype=np.float64).reshape(model.D, -1)
     elems, nuis = model.kernel_inputs(θ_samples)
     pw, labels = _pointwise_handle(model)
-    ps = None
-    try:
+    with pw, Psis(device=pw.device_index) as ps:
         dev = torch.device("cuda", pw.device_index)
-        ps = Psis(device=pw.device_index)
         d_el = torch.from_numpy(np.ascontiguousarray(elems, dtype=np.float64)).to(dev)
         d_nu = None if nuis is None else torch.from_numpy(np.ascontiguousarray(nuis, dtype=np.float64)).to(dev)
         s = ps.loo(pw.values(d_el, d_nu), weights=weights)
         s = {k: v.cpu().numpy() for k, v in s.items()}      # the copy waits for the stream both calls ran on
-    finally:
-        if ps is not None:
-            ps.close()
-        pw.close()
     out = dict(elpd_loo=s["elpd_loo"], pareto_k=s["pareto_k"], lppd=s["lppd"], p_loo=s["lppd"] - s["elpd_loo"], ess=s["ess"],
                n_valid=s["n"], tail_len=s["tail_len"])
-    R = len(labels)
-    for k in ("elpd_loo", "p_loo"):
-        out[k + "_total"] = float(np.sum(out[k]))
-        out[k + "_se"] = float(np.sqrt(R * np.var(out[k], ddof=1))) if R > 1 else float("nan")
+    _add_totals(out, ("elpd_loo", "p_loo"), len(labels))
     out.update(n_bad_k=int(np.count_nonzero(out["pareto_k"] > 0.7)), n_samples=int(θ_samples.shape[1]), labels=labels)
     if weights:
         out["log_weights"] = s["log_weights"]
@@ -618,11 +613,8 @@ def simulate_tables(obs_tables, planets, elems, nuis=None, device=0, consts=None
         if len(t["epoch"]) == 0:
             out.append({n: np.empty((0, elems.shape[1])) for n in names})
             continue
-        pr = predict.Predictor(planets, t["epoch"], channels, basis=basis, device=device, consts=consts)
-        try:
+        with predict.Predictor(planets, t["epoch"], channels, basis=basis, device=device, consts=consts) as pr:
             cube = pr.values(elems, add0=add0, add1=add1)
-        finally:
-            pr.close()
         out.append({n: cube[k] for k, n in enumerate(names)})
     return out
 
@@ -632,13 +624,10 @@ def posterior_predictive(planets, elems, epochs, channels, summary=True, basis=N
     [P*9, W] at `epochs` [T]. summary=True: dict(n_valid, mean, sd, min, max), each [C, T], reduced over the draws on the device (the
     cube is never stored); summary=False: the cube [C, T, W]. NumPy or device (torch) elements, as Predictor takes them."""
     from . import predict
-    pr = predict.Predictor(planets, epochs, channels, basis=basis, device=device, consts=consts)
-    try:
+    with predict.Predictor(planets, epochs, channels, basis=basis, device=device, consts=consts) as pr:
         res = pr.summary(elems, add0=add0, add1=add1) if summary else pr.values(elems, add0=add0, add1=add1)
         pr.sync()
         if not isinstance(res, (dict, np.ndarray)) or (isinstance(res, dict) and not isinstance(res["mean"], np.ndarray)):
             import torch
             torch.cuda.synchronize()      # device inputs ran on torch's current stream: the handle is destroyed below
         return res
-    finally:
-        pr.close()

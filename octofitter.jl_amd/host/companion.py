@@ -80,6 +80,12 @@ class Handle:
             self._h = None
         self._keep = None
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
     def __del__(self):
         try:
             self.close()

@@ -23,6 +23,7 @@ has not been built: the draws have no NumPy fallback here (host/callers.py keeps
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import numpy as np
 
 from . import capi, companion
@@ -87,6 +88,86 @@ def _u64ptr(a):
     return a.ctypes.data_as(c_uint64_p)
 
 
+# ---- the argument rules of the device calls. They only inspect their arguments; `dev` is the handle's torch.device.
+def ptr(x):
+    """The address of a tensor; None (a NULL pointer) for None: an input left at its default, an output switched off."""
+    return None if x is None else x.data_ptr()
+
+
+def chain_matrix(x, rows, dev, what, name="theta_t"):
+    """(K, W, ld) of a float64 [K, W] tensor on `dev` with contiguous rows. rows: the K it must have (the handle's D), None: any.
+    ld is the distance of two rows; a single row or empty rows have none, and ld = W."""
+    import torch
+    if x.dtype != torch.float64 or x.ndim != 2 or (rows is not None and x.shape[0] != rows) or x.device != dev or (x.shape[1] and x.stride(1) != 1):
+        shape = "[K, W]" if rows is None else f"[D = {rows}, W]"
+        raise ValueError(f"{what}: {name} must be a float64 {shape} tensor on {dev} with contiguous rows")
+    K, W = int(x.shape[0]), int(x.shape[1])
+    return K, W, (int(x.stride(0)) if K > 1 and W else W)
+
+
+def single_row_ld(ld, D, *stacks):
+    """The leading dimension of slot-major stacks [n, D, W] beside a matrix [D, W] of leading dimension ld. With D == 1 the matrix has no
+    second row to say it: only the slots' distance does, that of the first (stack, n) with more than one slot."""
+    if D == 1:
+        for x, n in stacks:
+            if n > 1:
+                return int(x.stride(0))
+    return ld
+
+
+def slot_stack(x, n, D, W, ld, dev, what, name, slots="m"):
+    """Refuses x unless it is a float64 [n, D, W] tensor on `dev`, slot-major: rows contiguous and ld apart, slots D·ld apart."""
+    import torch
+    ok = x.dtype == torch.float64 and x.device == dev and tuple(x.shape) == (n, D, W)
+    if ok and W:
+        ok = x.stride(2) == 1 and (D == 1 or x.stride(1) == ld) and (n == 1 or x.stride(0) == D * ld)
+    if not ok:
+        raise ValueError(f"{what}: {name} must be a float64 [{slots}, D = {D}, W = {W}] tensor on {dev} with g's leading dimension")
+
+
+def history(cnt, head, S, Y, g, D, dev, what):
+    """(W, ld, m, cnt, head) of a caller's L-BFGS history: g [D, W], S and Y [m, D, W] slot-major with g's leading dimension."""
+    import torch
+    _, W, ld = chain_matrix(g, D, dev, what, "g")
+    m = int(S.shape[0]) if S.ndim == 3 else 0
+    ld = single_row_ld(ld, D, (S, m))
+    slot_stack(S, m, D, W, ld, dev, what, "S")
+    slot_stack(Y, m, D, W, ld, dev, what, "Y")
+    cnt, head = (torch.as_tensor(t, dtype=torch.int32, device=dev).contiguous() for t in (cnt, head))
+    if cnt.shape != (W,) or head.shape != (W,):
+        raise ValueError(f"{what}: cnt and head take {W} values each")
+    return W, ld, m, cnt, head
+
+
+def device_vector(x, n, dev, what):
+    """None, or a float64 tensor of n elements on `dev` (a scalar is broadcast, host values are uploaded)."""
+    import torch
+    if x is None:
+        return None
+    t = torch.as_tensor(x, dtype=torch.float64, device=dev)
+    t = t.expand(n).contiguous() if t.ndim == 0 else t.contiguous()
+    if t.shape != (n,):
+        raise ValueError(f"{what}: expected {n} values, got a tensor of shape {tuple(t.shape)}")
+    return t
+
+
+def group_ids(group, W, dev, what):
+    """None, or the int32 [W] group ids on `dev`."""
+    import torch
+    if group is None:
+        return None
+    g = torch.as_tensor(group, device=dev).to(torch.int32).contiguous()
+    if g.shape != (W,):
+        raise ValueError(f"{what}: group takes {W} ids")
+    return g
+
+
+def is_adapt_state(state, G, dev):
+    """Whether `state` is a dual-averaging state: a contiguous float64 [G, 4] tensor on `dev`."""
+    import torch
+    return state.dtype == torch.float64 and state.device == dev and state.shape == (G, 4) and state.is_contiguous()
+
+
 class PriorDraws(companion.Handle):
     """The handle of octo_draws_create. PriorDraws(model): for one LogDensityModel — its priors, its device model, its context.
     PriorDraws(priors=[…], device=0): a list of host/priors.py priors and a context of its own — sampling only (no best / rejection)."""
@@ -116,17 +197,30 @@ class PriorDraws(companion.Handle):
             self._own_ctx = ctx
         self._created(self.lib.octo_draws_create(ctx, m, self._c_priors, self.D, self.device_index, C.byref(self._h)))
 
+    @functools.cached_property
+    def device(self):
+        """The torch.device every tensor of a device call lives on."""
+        import torch
+        return torch.device("cuda", self.device_index)
+
+    def _out(self, n, rows=None, ld=None, dtype=None):
+        """An uninitialised output on the handle's device: [n] of `dtype` (default float64), or float64 [rows, n] whose rows are ld apart
+        (default: contiguous)."""
+        import torch
+        if rows is None:
+            return torch.empty(n, dtype=dtype or torch.float64, device=self.device)
+        if ld is None:
+            return torch.empty((rows, n), dtype=torch.float64, device=self.device)
+        return torch.empty_strided((rows, n), (ld, 1), dtype=torch.float64, device=self.device)
+
     def sample(self, seed, first, n, theta=True, theta_t=True, logprior_t=True, stream=None):
         """Draws first … first + n − 1 of stream `seed` as torch float64 tensors on the model's device: (θ [D, n] natural domain,
         θ_t [D, n] linked, logprior_t [n]); None for an output switched off. Asynchronous on `stream` (default: torch's current stream)."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
         n = int(n)
-        th = torch.empty((self.D, n), dtype=torch.float64, device=dev) if theta else None
-        tt = torch.empty((self.D, n), dtype=torch.float64, device=dev) if theta_t else None
-        lp = torch.empty(n, dtype=torch.float64, device=dev) if logprior_t else None
-        ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
-        self._check(self.lib.octo_draws_sample_device(self._h, int(seed), int(first), n, n, ptr(th), ptr(tt), ptr(lp), self._stream(stream, dev)))
+        th = self._out(n, self.D) if theta else None
+        tt = self._out(n, self.D) if theta_t else None
+        lp = self._out(n) if logprior_t else None
+        self._check(self.lib.octo_draws_sample_device(self._h, int(seed), int(first), n, n, ptr(th), ptr(tt), ptr(lp), self._stream(stream, self.device)))
         return th, tt, lp
 
     def best(self, seed, N, keep=1, first=0):
@@ -158,26 +252,12 @@ class PriorDraws(companion.Handle):
         return dict(samples=np.ascontiguousarray(th[:, :ns]), loglike=ll[:ns].copy(), logpost=lp[:ns].copy(), index=ix[:ns].copy(),
                     n_accepted=int(n_acc.value), max_loglike=float(mx.value))
 
-    def _device_vector(self, x, n, dev, what):
-        """None, or a float64 tensor of n elements on `dev` (a scalar is broadcast, host values are uploaded)."""
-        import torch
-        if x is None:
-            return None
-        t = torch.as_tensor(x, dtype=torch.float64, device=dev)
-        t = t.expand(n).contiguous() if t.ndim == 0 else t.contiguous()
-        if t.shape != (n,):
-            raise ValueError(f"{what}: expected {n} values, got a tensor of shape {tuple(t.shape)}")
-        return t
-
     def momentum(self, seed, step, n, inv_mass=None, chain0=0, stream=None):
         """The momenta p [D, n] of chains chain0 … chain0 + n − 1 at `step`: standard normals of the counter generator over √inv_mass."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
         n = int(n)
-        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
-        p = torch.empty((self.D, n), dtype=torch.float64, device=dev)
-        self._check(self.lib.octo_draws_momentum_device(self._h, int(seed), int(step), int(chain0), n, n, None if im is None else im.data_ptr(),
-                                                        p.data_ptr(), self._stream(stream, dev)))
+        im = device_vector(inv_mass, self.D, self.device, "inv_mass")
+        p = self._out(n, self.D)
+        self._check(self.lib.octo_draws_momentum_device(self._h, int(seed), int(step), int(chain0), n, n, ptr(im), p.data_ptr(), self._stream(stream, self.device)))
         self._keep = (im,)
         return p
 
@@ -187,51 +267,43 @@ class PriorDraws(companion.Handle):
         alone explores the prior (β = 0) and returns None for logpost and loglike.
         Returns (logpost [W], loglike [W], dH [W], accepted int32 [W][, proposal [D, W]]). Asynchronous on `stream`."""
         import torch
-        dev = torch.device("cuda", self.device_index)
-        if theta_t.dtype != torch.float64 or theta_t.ndim != 2 or theta_t.shape[0] != self.D or theta_t.device != dev or (theta_t.shape[1] and theta_t.stride(1) != 1):
-            raise ValueError(f"hmc_step: theta_t must be a float64 [D = {self.D}, W] tensor on {dev} with contiguous rows")
-        W = int(theta_t.shape[1])
-        ld = int(theta_t.stride(0)) if self.D > 1 and W else W
+        dev = self.device
+        _, W, ld = chain_matrix(theta_t, self.D, dev, "hmc_step")
         if eps is None:
             raise ValueError("hmc_step: eps is required (a number, or one value per chain)")
         per_chain = torch.is_tensor(eps) or np.ndim(eps) > 0
-        eps_w = self._device_vector(eps, W, dev, "eps") if per_chain else None
-        be = self._device_vector(beta, W, dev, "beta")
-        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
-        has_model = self.model is not None
-        lp = torch.empty(W, dtype=torch.float64, device=dev) if has_model else None
-        ll = torch.empty(W, dtype=torch.float64, device=dev) if has_model else None
-        dH = torch.empty(W, dtype=torch.float64, device=dev)
-        acc = torch.empty(W, dtype=torch.int32, device=dev)
-        prop = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev) if want_proposal else None
-        ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
+        eps_w = device_vector(eps, W, dev, "eps") if per_chain else None
+        be = device_vector(beta, W, dev, "beta")
+        im = device_vector(inv_mass, self.D, dev, "inv_mass")
+        lp, ll = (self._out(W), self._out(W)) if self.model is not None else (None, None)
+        dH = self._out(W)
+        acc = self._out(W, dtype=torch.int32)
+        prop = self._out(W, self.D, ld) if want_proposal else None
         self._check(self.lib.octo_draws_hmc_step_device(self._h, int(seed), int(step), int(chain0), W, ld, theta_t.data_ptr(), ptr(be), ptr(eps_w),
                                                         0.0 if per_chain else float(eps), int(n_leapfrog), ptr(im), ptr(prop), ptr(lp), ptr(ll),
                                                         dH.data_ptr(), acc.data_ptr(), self._stream(stream, dev)))
         self._keep = (theta_t, be, eps_w, im)
         return (lp, ll, dH, acc, prop) if want_proposal else (lp, ll, dH, acc)
 
-    def _chain_matrix(self, x, what, name="theta_t"):
-        """(W, ld) of a float64 [D, W] tensor on the handle's device with contiguous rows."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
-        if x.dtype != torch.float64 or x.ndim != 2 or x.shape[0] != self.D or x.device != dev or (x.shape[1] and x.stride(1) != 1):
-            raise ValueError(f"{what}: {name} must be a float64 [D = {self.D}, W] tensor on {dev} with contiguous rows")
-        W = int(x.shape[1])
-        return W, (int(x.stride(0)) if self.D > 1 and W else W)
-
     def lbfgs_direction(self, cnt, head, S, Y, g, inv_mass=None, stream=None):
         """The two-loop recursion of every chain on its own history: d [D, W] = −H·g with H₀ = γ·diag(inv_mass). cnt, head: int32 [W] (stored
         pairs; the slot the next pair would take); S, Y: float64 [m, D, W], slot-major, rows contiguous and of g's leading dimension; g: [D, W]. Asynchronous."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
-        W, ld, m, cnt, head = self._history("lbfgs_direction", cnt, head, S, Y, g)
-        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
-        out = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev)
+        W, ld, m, cnt, head = history(cnt, head, S, Y, g, self.D, self.device, "lbfgs_direction")
+        im = device_vector(inv_mass, self.D, self.device, "inv_mass")
+        out = self._out(W, self.D, ld)
         self._check(self.lib.octo_draws_lbfgs_direction_device(self._h, W, ld, m, cnt.data_ptr(), head.data_ptr(), S.data_ptr(), Y.data_ptr(), g.data_ptr(),
-                                                               None if im is None else im.data_ptr(), out.data_ptr(), self._stream(stream, dev)))
+                                                               ptr(im), out.data_ptr(), self._stream(stream, self.device)))
         self._keep = (cnt, head, S, Y, g, im)
         return out
+
+    def _optimizer_outputs(self, what, theta_t, inv_mass, want_inv_hess_diag):
+        """What lbfgs and pathfinder share: (W, ld) of theta_t, inv_mass on the device, and the dict they return, its tensors allocated."""
+        import torch
+        _, W, ld = chain_matrix(theta_t, self.D, self.device, what)
+        im = device_vector(inv_mass, self.D, self.device, "inv_mass")
+        r = dict(logpost=self._out(W), gnorm=self._out(W), status=self._out(W, dtype=torch.int32), iters=self._out(W, dtype=torch.int32),
+                 evals=self._out(W, dtype=torch.int32), inv_hess_diag=self._out(W, self.D, ld) if want_inv_hess_diag else None)
+        return W, ld, im, r
 
     def lbfgs(self, theta_t, inv_mass=None, m=6, n_rounds=50, gtol=1e-6, ftol=0.0, resume=False, want_inv_hess_diag=False, stream=None):
         """n_rounds rounds of the batched L-BFGS (include/octofitter_hip_draws.h states it) on the W chains in theta_t (torch float64 [D, W] on
@@ -239,38 +311,11 @@ class PriorDraws(companion.Handle):
         goes on from the state the handle holds: the same theta_t, W and m as the call before.
         Returns dict(logpost [W], gnorm [W], status int32 [W] (LBFGS_*), iters, evals int32 [W], inv_hess_diag [D, W] or None), device tensors.
         Asynchronous on `stream`."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
-        W, ld = self._chain_matrix(theta_t, "lbfgs")
-        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
-        lp, gn = (torch.empty(W, dtype=torch.float64, device=dev) for _ in range(2))
-        status, iters, evals = (torch.empty(W, dtype=torch.int32, device=dev) for _ in range(3))
-        ihd = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev) if want_inv_hess_diag else None
-        self._check(self.lib.octo_draws_lbfgs_device(self._h, W, ld, theta_t.data_ptr(), None if im is None else im.data_ptr(), int(m), int(n_rounds),
-                                                     float(gtol), float(ftol), 1 if resume else 0, lp.data_ptr(), gn.data_ptr(), status.data_ptr(),
-                                                     iters.data_ptr(), evals.data_ptr(), None if ihd is None else ihd.data_ptr(), self._stream(stream, dev)))
+        W, ld, im, r = self._optimizer_outputs("lbfgs", theta_t, inv_mass, want_inv_hess_diag)
+        self._check(self.lib.octo_draws_lbfgs_device(self._h, W, ld, theta_t.data_ptr(), ptr(im), int(m), int(n_rounds), float(gtol), float(ftol),
+                                                     1 if resume else 0, *(ptr(t) for t in r.values()), self._stream(stream, self.device)))
         self._keep = (theta_t, im)
-        return dict(logpost=lp, gnorm=gn, status=status, iters=iters, evals=evals, inv_hess_diag=ihd)
-
-    def _history(self, what, cnt, head, S, Y, g):
-        """(W, ld, m, cnt, head) of a caller's L-BFGS history: g [D, W], S and Y [m, D, W] slot-major with g's leading dimension."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
-        W, ld = self._chain_matrix(g, what, "g")
-        m = int(S.shape[0]) if S.ndim == 3 else 0
-        if self.D == 1 and m > 1:
-            ld = int(S.stride(0))      # a single row: only the slots' distance says what the leading dimension is
-        for x, name in ((S, "S"), (Y, "Y")):
-            ok = x.dtype == torch.float64 and x.device == dev and tuple(x.shape) == (m, self.D, W)
-            if ok and W:
-                ok = x.stride(2) == 1 and (self.D == 1 or x.stride(1) == ld) and (m == 1 or x.stride(0) == self.D * ld)
-            if not ok:
-                raise ValueError(f"{what}: {name} must be a float64 [m, D = {self.D}, W = {W}] tensor on {dev} with g's leading dimension")
-        cnt = torch.as_tensor(cnt, dtype=torch.int32, device=dev).contiguous()
-        head = torch.as_tensor(head, dtype=torch.int32, device=dev).contiguous()
-        if cnt.shape != (W,) or head.shape != (W,):
-            raise ValueError(f"{what}: cnt and head take {W} values each")
-        return W, ld, m, cnt, head
+        return r
 
     def pathfinder_fit(self, cnt, head, S, Y, x, g, alpha, z=None, stream=None):
         """Pathfinder's normal fit of every chain on its own history (include/octofitter_hip_draws.h states it): cnt, head, S, Y as in
@@ -278,30 +323,24 @@ class PriorDraws(companion.Handle):
         leading dimension. Returns dict(mu [D, W], chol [D(D+1)/2, W] (L̃ packed row-major), logdet [W], ok int32 [W], phi [n, D, W] or None):
         Σ = diag(√α)·L̃L̃ᵀ·diag(√α), φ = μ + √α ⊙ (L̃z). Asynchronous."""
         import torch
-        dev = torch.device("cuda", self.device_index)
-        W, ld, m, cnt, head = self._history("pathfinder_fit", cnt, head, S, Y, g)
+        dev = self.device
+        W, ld, m, cnt, head = history(cnt, head, S, Y, g, self.D, dev, "pathfinder_fit")
+        like_g = chain_matrix(g, self.D, dev, "pathfinder_fit", "g")      # before the single-row rule: x and alpha are matrices, as g is
         for t, name in ((x, "x"), (alpha, "alpha")):
-            if self._chain_matrix(t, "pathfinder_fit", name)[0] != W or (self.D > 1 and W and t.stride(0) != g.stride(0)):
+            if chain_matrix(t, self.D, dev, "pathfinder_fit", name) != like_g:
                 raise ValueError(f"pathfinder_fit: {name} must have g's shape and leading dimension")
         n = 0 if z is None else int(z.shape[0])
-        if self.D == 1 and m <= 1 and n > 1:
-            ld = int(z.stride(0))      # a single row and a single slot: only the draws' distance says what the leading dimension is
+        ld = single_row_ld(ld, self.D, (S, m), (z, n))
         if z is not None:
-            ok = z.dtype == torch.float64 and z.device == dev and tuple(z.shape) == (n, self.D, W)
-            if ok and W:
-                ok = z.stride(2) == 1 and (self.D == 1 or z.stride(1) == ld) and (n == 1 or z.stride(0) == self.D * ld)
-            if not ok:
-                raise ValueError(f"pathfinder_fit: z must be a float64 [n, D = {self.D}, W = {W}] tensor on {dev} with g's leading dimension")
-        P = self.D * (self.D + 1) // 2
-        mu = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev)
-        chol = torch.empty_strided((P, W), (ld, 1), dtype=torch.float64, device=dev)
-        logdet = torch.empty(W, dtype=torch.float64, device=dev)
-        ok = torch.empty(W, dtype=torch.int32, device=dev)
+            slot_stack(z, n, self.D, W, ld, dev, "pathfinder_fit", "z", slots="n")
+        mu = self._out(W, self.D, ld)
+        chol = self._out(W, self.D * (self.D + 1) // 2, ld)
+        logdet = self._out(W)
+        ok = self._out(W, dtype=torch.int32)
         phi = torch.empty_strided((n, self.D, W), (self.D * ld, ld, 1), dtype=torch.float64, device=dev) if n else None
         self._check(self.lib.octo_draws_pathfinder_fit_device(self._h, W, ld, m, cnt.data_ptr(), head.data_ptr(), S.data_ptr(), Y.data_ptr(), x.data_ptr(),
                                                               g.data_ptr(), alpha.data_ptr(), mu.data_ptr(), chol.data_ptr(), logdet.data_ptr(), ok.data_ptr(), n,
-                                                              None if z is None else z.data_ptr(), None if phi is None else phi.data_ptr(),
-                                                              self._stream(stream, dev)))
+                                                              ptr(z), ptr(phi), self._stream(stream, dev)))
         self._keep = (cnt, head, S, Y, x, g, alpha, z)
         return dict(mu=mu, chol=chol, logdet=logdet, ok=ok, phi=phi)
 
@@ -313,75 +352,45 @@ class PriorDraws(companion.Handle):
         Returns lbfgs's dict plus elbo [W] (−Inf without a fit), elbo_iter int32 [W] (the iters of the kept fit, −1 without one), n_fits int32 [W].
         Asynchronous on `stream`."""
         import torch
-        dev = torch.device("cuda", self.device_index)
-        W, ld = self._chain_matrix(theta_t, "pathfinder")
-        im = self._device_vector(inv_mass, self.D, dev, "inv_mass")
-        lp, gn, elbo = (torch.empty(W, dtype=torch.float64, device=dev) for _ in range(3))
-        status, iters, evals, elbo_iter, n_fits = (torch.empty(W, dtype=torch.int32, device=dev) for _ in range(5))
-        ihd = torch.empty_strided((self.D, W), (ld, 1), dtype=torch.float64, device=dev) if want_inv_hess_diag else None
-        self._check(self.lib.octo_draws_pathfinder_device(self._h, int(seed), int(chain0), W, ld, theta_t.data_ptr(), None if im is None else im.data_ptr(), int(m),
-                                                          int(n_rounds), float(gtol), float(ftol), int(n_elbo), 1 if resume else 0, lp.data_ptr(), gn.data_ptr(),
-                                                          status.data_ptr(), iters.data_ptr(), evals.data_ptr(), None if ihd is None else ihd.data_ptr(),
-                                                          elbo.data_ptr(), elbo_iter.data_ptr(), n_fits.data_ptr(), self._stream(stream, dev)))
+        W, ld, im, r = self._optimizer_outputs("pathfinder", theta_t, inv_mass, want_inv_hess_diag)
+        r.update(elbo=self._out(W), elbo_iter=self._out(W, dtype=torch.int32), n_fits=self._out(W, dtype=torch.int32))
+        self._check(self.lib.octo_draws_pathfinder_device(self._h, int(seed), int(chain0), W, ld, theta_t.data_ptr(), ptr(im), int(m), int(n_rounds), float(gtol),
+                                                          float(ftol), int(n_elbo), 1 if resume else 0, *(ptr(t) for t in r.values()),
+                                                          self._stream(stream, self.device)))
         self._keep = (theta_t, im)
-        return dict(logpost=lp, gnorm=gn, status=status, iters=iters, evals=evals, inv_hess_diag=ihd, elbo=elbo, elbo_iter=elbo_iter, n_fits=n_fits)
+        return r
 
     def pathfinder_draw(self, theta_t, n_draws, seed=0, chain0=0, stream=None):
         """n_draws draws from the kept fit of every chain of the previous pathfinder call (theta_t as that call left it, the same chain0):
         (φ [D, n_draws·W] in θ_t, draw j of chain c in column j·W + c; log q [n_draws·W]; ℓπ [n_draws·W]). A chain without a fit gives its
         x, log q = NaN and ℓπ = −Inf. Asynchronous on `stream`."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
-        W, ld = self._chain_matrix(theta_t, "pathfinder_draw")
+        _, W, ld = chain_matrix(theta_t, self.D, self.device, "pathfinder_draw")
         n = int(n_draws)
         cols = max(n, 0) * W
-        phi = torch.empty((self.D, cols), dtype=torch.float64, device=dev)
-        logq, lp = (torch.empty(cols, dtype=torch.float64, device=dev) for _ in range(2))
+        phi, logq, lp = self._out(cols, self.D), self._out(cols), self._out(cols)
         self._check(self.lib.octo_draws_pathfinder_draw_device(self._h, int(seed), int(chain0), W, ld, theta_t.data_ptr(), n, cols, phi.data_ptr(), logq.data_ptr(),
-                                                               lp.data_ptr(), self._stream(stream, dev)))
+                                                               lp.data_ptr(), self._stream(stream, self.device)))
         self._keep = (theta_t,)
         return phi, logq, lp
 
     # ---- warm-up (include/octofitter_hip_draws.h, "Warm-up of the explorer"): K = the rows of x, not the handle's D
-    def _rows(self, x, what, name="x"):
-        """(K, W, ld) of a float64 [K, W] tensor on the handle's device with contiguous rows."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
-        if x.dtype != torch.float64 or x.ndim != 2 or x.device != dev or (x.shape[1] and x.stride(1) != 1):
-            raise ValueError(f"{what}: {name} must be a float64 [K, W] tensor on {dev} with contiguous rows")
-        K, W = int(x.shape[0]), int(x.shape[1])
-        return K, W, (int(x.stride(0)) if K > 1 and W else W)
-
-    def _groups(self, group, W, dev, what):
-        """None, or the int32 [W] group ids on `dev`."""
-        import torch
-        if group is None:
-            return None
-        g = torch.as_tensor(group, device=dev).to(torch.int32).contiguous()
-        if g.shape != (W,):
-            raise ValueError(f"{what}: group takes {W} ids")
-        return g
-
     def moments(self, x, group=None, G=1, out=None, accumulate=False, stream=None):
         """Cross-chain moments of x [K, W] per group (group: int32 [W] ids, None = one group; ids outside 0 … G − 1 and chains with a
         non-finite value are excluded): (count [G], mean [G, K], m2 [G, K] = Σ(x − mean)²), device tensors. out=(count, mean, m2): write into these;
         with accumulate=True Chan-merge this call's block into what they hold. Asynchronous on `stream`."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
-        K, W, ld = self._rows(x, "moments")
-        g = self._groups(group, W, dev, "moments")
+        K, W, ld = chain_matrix(x, None, self.device, "moments", "x")
+        g = group_ids(group, W, self.device, "moments")
         G = int(G)
         if accumulate and out is None:
             raise ValueError("moments: accumulate=True needs out=(count, mean, m2)")
         if out is None:
-            cnt = torch.empty(G, dtype=torch.float64, device=dev)
-            mean, m2 = (torch.empty((G, K), dtype=torch.float64, device=dev) for _ in range(2))
+            cnt, mean, m2 = self._out(G), self._out(K, G), self._out(K, G)
         else:
             cnt, mean, m2 = out
             if cnt.shape != (G,) or mean.shape != (G, K) or m2.shape != (G, K) or not (cnt.is_contiguous() and mean.is_contiguous() and m2.is_contiguous()):
                 raise ValueError(f"moments: out must be contiguous (count [{G}], mean [{G}, {K}], m2 [{G}, {K}])")
-        self._check(self.lib.octo_draws_moments_device(self._h, W, ld, K, x.data_ptr(), None if g is None else g.data_ptr(), G, 1 if accumulate else 0,
-                                                       cnt.data_ptr(), mean.data_ptr(), m2.data_ptr(), self._stream(stream, dev)))
+        self._check(self.lib.octo_draws_moments_device(self._h, W, ld, K, x.data_ptr(), ptr(g), G, 1 if accumulate else 0,
+                                                       cnt.data_ptr(), mean.data_ptr(), m2.data_ptr(), self._stream(stream, self.device)))
         self._keep = (x, g)
         return cnt, mean, m2
 
@@ -389,29 +398,27 @@ class PriorDraws(companion.Handle):
         """inv_mass [K] (updated in place, returned) from ONE group's moments: count [1], mean [K], m2 [K] (rows of moments' outputs).
         M2/(n − 1), with regularize Stan's shrinkage towards 1e-3; entries with n < 2 or a variance not finite and > 0 keep their value."""
         import torch
-        dev = torch.device("cuda", self.device_index)
         K = int(m2.numel())
         for t, n in ((count, 1), (mean, K), (m2, K), (inv_mass, K)):
-            if t.dtype != torch.float64 or t.device != dev or t.numel() != n or not t.is_contiguous():
+            if t.dtype != torch.float64 or t.device != self.device or t.numel() != n or not t.is_contiguous():
                 raise ValueError("metric: count [1], mean [K], m2 [K] and inv_mass [K] must be contiguous float64 tensors on the handle's device")
         self._check(self.lib.octo_draws_metric_device(self._h, K, count.data_ptr(), mean.data_ptr(), m2.data_ptr(), 1 if regularize else 0, inv_mass.data_ptr(),
-                                                      self._stream(stream, dev)))
+                                                      self._stream(stream, self.device)))
         self._keep = (count, mean, m2, inv_mass)
         return inv_mass
 
     def adapt_init(self, G, eps0, state=None, stream=None):
         """The dual-averaging state [G, 4] = (log ε, log ε̄, H̄, μ) started at eps0 (a number, or one value per group); state: written in place."""
         import torch
-        dev = torch.device("cuda", self.device_index)
         G = int(G)
         per_group = torch.is_tensor(eps0) or np.ndim(eps0) > 0
-        e = self._device_vector(eps0, G, dev, "eps0") if per_group else None
+        e = device_vector(eps0, G, self.device, "eps0") if per_group else None
         if state is None:
-            state = torch.empty((G, 4), dtype=torch.float64, device=dev)
-        elif state.dtype != torch.float64 or state.device != dev or state.shape != (G, 4) or not state.is_contiguous():
-            raise ValueError(f"adapt_init: state must be a contiguous float64 [{G}, 4] tensor on {dev}")
-        self._check(self.lib.octo_draws_hmc_adapt_init_device(self._h, G, None if e is None else e.data_ptr(), 0.0 if per_group else float(eps0), state.data_ptr(),
-                                                              self._stream(stream, dev)))
+            state = self._out(4, G)
+        elif not is_adapt_state(state, G, self.device):
+            raise ValueError(f"adapt_init: state must be a contiguous float64 [{G}, 4] tensor on {self.device}")
+        self._check(self.lib.octo_draws_hmc_adapt_init_device(self._h, G, ptr(e), 0.0 if per_group else float(eps0), state.data_ptr(),
+                                                              self._stream(stream, self.device)))
         self._keep = (e, state)
         return state
 
@@ -421,31 +428,28 @@ class PriorDraws(companion.Handle):
         None (G = 1). Returns (accept_stat [G], the mean of min(1, exp(dH)) per group, NaN for an empty one; eps_w [W], ε — with use_average
         ε̄ — of every chain's group, what hmc_step takes as eps; None with want_eps=False). eps_w: written in place where a chain has a group."""
         import torch
-        dev = torch.device("cuda", self.device_index)
+        dev = self.device
         W, G = int(dH.numel()), int(state.shape[0])
         if dH.dtype != torch.float64 or accepted.dtype != torch.int32 or accepted.numel() != W or not (dH.is_contiguous() and accepted.is_contiguous()) \
-                or state.dtype != torch.float64 or state.shape != (G, 4) or not state.is_contiguous() or dH.device != dev or accepted.device != dev or state.device != dev:
+                or not is_adapt_state(state, G, dev) or dH.device != dev or accepted.device != dev:
             raise ValueError(f"adapt_step: dH float64 [W], accepted int32 [W] and state float64 [G, 4], contiguous on {dev}")
-        g = self._groups(group, W, dev, "adapt_step")
-        a = torch.empty(G, dtype=torch.float64, device=dev)
+        g = group_ids(group, W, dev, "adapt_step")
+        a = self._out(G)
         if eps_w is None and want_eps:
-            eps_w = torch.empty(W, dtype=torch.float64, device=dev)
-        self._check(self.lib.octo_draws_hmc_adapt_device(self._h, W, None if g is None else g.data_ptr(), G, dH.data_ptr(), accepted.data_ptr(), int(k), float(delta),
-                                                         float(gamma), float(t0), float(kappa), state.data_ptr(), a.data_ptr(), 1 if use_average else 0,
-                                                         None if eps_w is None else eps_w.data_ptr(), self._stream(stream, dev)))
+            eps_w = self._out(W)
+        self._check(self.lib.octo_draws_hmc_adapt_device(self._h, W, ptr(g), G, dH.data_ptr(), accepted.data_ptr(), int(k), float(delta), float(gamma), float(t0),
+                                                         float(kappa), state.data_ptr(), a.data_ptr(), 1 if use_average else 0, ptr(eps_w), self._stream(stream, dev)))
         self._keep = (state, dH, accepted, g, eps_w)
         return a, eps_w
 
     def chain_moments(self, x, k, cmean, cm2, stream=None):
         """Sample number k >= 1 of every chain's running moments over time: cmean, cm2 [K, W] of x's shape and leading dimension, in place
         (k = 1 starts them). R̂ follows from two moments calls on them (include/octofitter_hip_draws.h)."""
-        import torch
-        dev = torch.device("cuda", self.device_index)
-        K, W, ld = self._rows(x, "chain_moments")
+        K, W, ld = chain_matrix(x, None, self.device, "chain_moments", "x")
         for t, name in ((cmean, "cmean"), (cm2, "cm2")):
-            if self._rows(t, "chain_moments", name) != (K, W, ld):
+            if chain_matrix(t, None, self.device, "chain_moments", name) != (K, W, ld):
                 raise ValueError(f"chain_moments: {name} must have x's shape and leading dimension")
-        self._check(self.lib.octo_draws_chain_moments_device(self._h, W, ld, K, int(k), x.data_ptr(), cmean.data_ptr(), cm2.data_ptr(), self._stream(stream, dev)))
+        self._check(self.lib.octo_draws_chain_moments_device(self._h, W, ld, K, int(k), x.data_ptr(), cmean.data_ptr(), cm2.data_ptr(), self._stream(stream, self.device)))
         self._keep = (x, cmean, cm2)
         return cmean, cm2
 
