@@ -38,6 +38,13 @@
  * The sixth is the explorer's warm-up: grouped cross-chain moments, the diagonal metric they give, dual averaging of the step size and
  * per-chain running moments (octo_draws_moments_device … octo_draws_chain_moments_device; tests/adapt_reference.py restates them). No random number.
  *
+ * The seventh is the no-U-turn sampler (octo_draws_nuts_device): one NUTS transition of every chain of a batch, the trees built in lockstep,
+ * stated in full at its declaration (tests/nuts_reference.py restates it). Its momenta are purpose 2's, the HMC step's; its three streams add
+ *   purpose 6: the direction of doubling j of chain c at `step`, counter (c, j, 6, step), word 0
+ *   purpose 7: the proposal uniform of the chain's leaf number k = 1, 2, … of the transition, counter (c, k, 7, step), word 0
+ *   purpose 8: the merge uniform of doubling j, counter (c, j, 8, step), word 0
+ * Counter word 1, which holds d / 4 for the other purposes, holds j or the leaf number here.
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -57,6 +64,9 @@ extern "C" {
 #define OCTO_DRAWS_PURPOSE_ACCEPT   3
 #define OCTO_DRAWS_PURPOSE_ELBO       4
 #define OCTO_DRAWS_PURPOSE_PATHFINDER 5
+#define OCTO_DRAWS_PURPOSE_NUTS_DIRECTION 6
+#define OCTO_DRAWS_PURPOSE_NUTS_LEAF      7
+#define OCTO_DRAWS_PURPOSE_NUTS_MERGE     8
 
 typedef struct octo_draws octo_draws;
 
@@ -344,6 +354,56 @@ int32_t octo_draws_hmc_adapt_device(octo_draws* h, int64_t W, const int32_t* d_g
  *   R̂_d = √(((n − 1)/n·Wv + B/n)/Wv). */
 int32_t octo_draws_chain_moments_device(octo_draws* h, int64_t W, int64_t ld, int32_t K, int64_t k, const double* d_x, double* d_cmean,
                                         double* d_cm2, void* hip_stream);
+
+/* ---- The no-U-turn sampler (Hoffman & Gelman 2014; the reference samples with AdvancedHMC's NUTS: multinomial sampling, the generalised
+ * no-U-turn criterion, tree depth <= 10, Δ_max = 1000). One transition of W chains, built in lockstep: a ROUND is one log-posterior call at the
+ * trial points of all W chains and one leapfrog of every chain still building. Chain c = chain0 + w at `step`. E, ∇E, dead states, ℓprior_t, β
+ * and the handle without a model are exactly those of the HMC step above (a term of ℓprior_t is non-finite also where the linked x rounds onto a
+ * bound of the prior's support, log|J| = log 0: such a point is dead); ⟨a,b⟩ = Σ_d inv_mass_d·a_d·b_d; every sum over d runs in index order.
+ *
+ * Open       p₀: the momenta octo_draws_hmc_step_device draws for (seed, step, c). The start is evaluated: H₀ = −E₀ + K₀, K as in the HMC step.
+ *            A dead start ends the transition at once: θ_t is not written, n_leapfrog = 0, accepted = 0. Otherwise the tree is the start
+ *            point: both endpoints (θ_t, p₀, ∇E₀), the proposal θ_t, ρ = p₀, log w = 0, depth j = 0.
+ * Doubling j adds a subtree of 2^j leaves in the direction v = +1 if u < ½, else −1, u of counter (c, j, 6, step), built from the endpoint on
+ *            that side, which every new leaf replaces. A leaf is one leapfrog: p½ = p + v(ε/2)∇E, q′ = q + vε·inv_mass⊙p½, the evaluation at
+ *            q′, p′ = p½ + v(ε/2)∇E′. Δ = (−E′ + K′) − H₀. The leaf DIVERGES if q′ is dead or not (Δ <= 1000) — NaN diverges. Its weight is
+ *            log w_leaf = −Δ (−Inf when it diverges); it adds min(1, exp(−Δ)) (0 when it diverges) to the acceptance statistic.
+ * Subtree    leaf n = 0 … 2^j − 1: log w_s <- logaddexp(log w_s, log w_leaf) (n = 0: log w_leaf). The subtree's proposal becomes the leaf iff
+ *            n = 0 or log u < log w_leaf − log w_s (the new one), u of counter (c, k, 7, step), k = 1, 2, … the chain's leaf number in this
+ *            transition. ρ_s is the running sum of the subtree's p′ in build order.
+ *            Checkpoints, i_max = popcount(n >> 1), t = the trailing one-bits of n, i_min = i_max − t + 1: an even n stores (p′, ρ_s) in slot
+ *            i_max; an odd n tests, for i = i_max down to i_min, ρ = ρ_s − ρ_ckpt[i] + p_ckpt[i]: the subtree TURNS iff ⟨p_ckpt[i], ρ⟩ <= 0 or
+ *            ⟨p′, ρ⟩ <= 0, and the first turn stops the tests. That tests every aligned sub-subtree that ends at leaf n (the test is symmetric in
+ *            the direction) with max_depth slots. A turning or diverging subtree ends the transition with the tree's proposal unchanged.
+ * Merge      of a completed subtree: the tree's proposal becomes the subtree's iff log u < log w_s − log w (biased progressive sampling), u of
+ *            counter (c, j, 8, step); log w <- logaddexp(log w, log w_s); ρ <- ρ + ρ_s; j <- j + 1. The transition ends if ⟨p_left, ρ⟩ <= 0
+ *            or ⟨p_right, ρ⟩ <= 0, or if j = max_depth. No further junction test is made.
+ * End        θ_t takes the proposal — it is written only if the proposal is not the start point —, and ℓπ and ℓ of it are returned. depth is j,
+ *            the doublings merged; n_leapfrog counts every leaf made, the one that diverged or turned included. A chain that has ended is
+ *            FROZEN, as in the L-BFGS: its trial point is its θ_t, the result there is ignored, and θ_t and every output keep their bits for the
+ *            rest of the call and across `resume`.
+ *
+ * On DEVICE buffers, asynchronous on hip_stream: no host synchronisation, no allocation once the handle's work array holds
+ * ((14 + 2·max_depth)·D + 18)·ld doubles (it grows behind the handle's own stream), no graph capture, no floating-point atomic. resume = 0 opens and
+ * makes n_rounds rounds: n_rounds + 1 log-posterior calls. resume = 1 continues the state the handle holds with n_rounds more rounds: the same W, ld,
+ * max_depth, seed, step and chain0 as the call before it, and the other inputs and d_theta_t as that call had and left them. Two calls of a and b
+ * rounds give the bits of one call of a + b; 2^max_depth − 1 rounds always finish every chain. A chain's outputs depend only on chain0 + c, never
+ * on W, ld, its position or how the rounds were cut.
+ *   d_theta_t, d_beta, d_eps, eps, d_inv_mass   as octo_draws_hmc_step_device
+ *   d_logpost, d_loglike [W]   or NULL: ℓπ and ℓ of θ_t as the call leaves it (of a chain still building: of its start)
+ *   d_log_accept [W]           or NULL: the log of the mean acceptance statistic over the leaves made; NaN with n_leapfrog = 0. min(1, exp(·)) of
+ *                              it is what octo_draws_hmc_adapt_device makes of its d_dH argument: the warm-up calls take it where dH went.
+ *   d_accepted   [W]           int32: 1 iff θ_t was written
+ *   d_depth, d_n_leapfrog, d_diverged [W]   int32 or NULL (of a chain still building: so far)
+ *   d_n_active   [1]           int32 or NULL: the chains still building after the call
+ * OCTO_EINVAL: as octo_draws_hmc_step_device (without n_leapfrog); max_depth outside 1 … OCTO_DRAWS_NUTS_MAX_DEPTH; n_rounds < 0; resume without
+ * a previous call of the same W, ld, max_depth, seed, step and chain0. */
+#define OCTO_DRAWS_NUTS_MAX_DEPTH 10
+int32_t octo_draws_nuts_device(octo_draws* h, uint64_t seed, uint64_t step, uint64_t chain0, int64_t W, int64_t ld, double* d_theta_t,
+                               const double* d_beta, const double* d_eps, double eps, const double* d_inv_mass, int32_t max_depth,
+                               int32_t n_rounds, int32_t resume, double* d_logpost, double* d_loglike, double* d_log_accept,
+                               int32_t* d_accepted, int32_t* d_depth, int32_t* d_n_leapfrog, int32_t* d_diverged, int32_t* d_n_active,
+                               void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 // octo_draws_common.h — what the translation units of liboctofitter_hip_draws.so share: the handle, the counter generator, the prior
-// helpers on top of octo_model.h's device routines, and the argument checks their functions repeat. Five units include it: octo_draws.hip
-// (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC explorer), octo_draws_lbfgs.hip (the
-// multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder on its paths) and octo_draws_adapt.hip (the warm-up statistics of the explorer). Everything but the handle lives in an unnamed namespace,
+// helpers on top of octo_model.h's device routines, the tempered target of the two samplers, and the argument checks their functions repeat.
+// Six units include it: octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
+// explorer), octo_draws_nuts.hip (the no-U-turn sampler), octo_draws_lbfgs.hip (the multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder
+// on its paths) and octo_draws_adapt.hip (the warm-up statistics of the explorer). Everything but the handle lives in an unnamed namespace,
 // one copy per unit. How the handle's work allocations are cut into their parts is octo_draws_layout.h.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
@@ -82,6 +83,39 @@ __device__ __forceinline__ double prior_link_forward(const PriorBounds& B, doubl
     return x;
 }
 
+// ---- the tempered target of the HMC step and of NUTS (include/octofitter_hip_draws.h, "Target" and "Decision")
+// E = ℓprior_t + β(ℓπ − ℓprior_t); β = 0 never consults ℓπ
+__device__ __forceinline__ double tempered_energy(double beta, double lp, double lpt) { return beta == 0.0 ? lpt : lpt + beta * (lp - lpt); }
+
+__device__ __forceinline__ bool dead_state(double beta, double E, double lp, double lpt) {
+    return !isfinite(E) || lpt == HEALED || (beta > 0.0 && !isfinite(lp));
+}
+
+// ∇E at offset o from ∇ℓπ (glp, read only where β != 0: null without a model) and ∇ℓprior_t there (gp); β = 1 takes ∇ℓπ bit for bit
+__device__ __forceinline__ double tempered_gradient(double beta, const double* glp, int64_t o, double gp) {
+    return beta == 1.0 ? glp[o] : (beta == 0.0 ? gp : beta * glp[o] + (1.0 - beta) * gp);
+}
+
+// ℓprior_t of chain wl at the point `at` [D][ld]: every transcendental (link, density), summed in declaration order — the routine and the
+// order of k_draw's logprior_t. It leaves ∇ℓprior_t in gpr (live lanes: w = wl) because whether the prior was healed (and its derivative is 0
+// in EVERY coordinate, as k_model_fwd has it) is known only after the last coordinate. prior_link_lanes and prior_density_lanes vote across
+// the wave: every lane of a wave calls this, a lane beyond the batch with the last chain's column.
+__device__ __forceinline__ double prior_loop(const octo_prior* priors, const double* pc, int32_t D, const double* __restrict__ at, int64_t ld, int64_t w,
+                                             int64_t wl, bool live, double* gpr, bool& healed) {
+    double lpt = 0.0;
+    healed = false;
+    for (int d = 0; d < D; ++d) {
+        const octo_prior pr = priors[d];
+        double xv, xd, pv, pd;
+        prior_link_lanes(pr, at[(int64_t)d * ld + wl], xv, xd);
+        prior_density_lanes(pr, xv, xd, pv, pd, pc + PRIOR_NC * d);
+        healed = healed || !isfinite(pv);
+        lpt += pv;
+        if (live) gpr[(int64_t)d * ld + w] = pd;
+    }
+    return healed ? HEALED : lpt;
+}
+
 }  // namespace
 
 struct octo_draws : CompanionBase {
@@ -111,6 +145,11 @@ struct octo_draws : CompanionBase {
     double* d_pfb = nullptr; int64_t cap_pfb = 0;
     // warm-up (octo_draws_adapt.hip), grown on demand: the block partials of the grouped moments
     double* d_mom = nullptr; int64_t cap_mom = 0;
+    // NUTS (octo_draws_nuts.hip), grown on demand: the chains' trees in one allocation with the transition it was opened for (nuts_depth = 0:
+    // nothing to resume)
+    double* d_nuts = nullptr; int64_t cap_nuts = 0;
+    int64_t nuts_W = 0, nuts_ld = 0; int32_t nuts_depth = 0;
+    uint64_t nuts_seed = 0, nuts_step = 0, nuts_chain0 = 0;
 };
 
 namespace {

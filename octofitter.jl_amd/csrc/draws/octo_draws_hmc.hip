@@ -57,16 +57,8 @@ struct HmcArgs {
     int32_t* o_acc;
 };
 
-// E = ℓprior_t + β(ℓπ − ℓprior_t); β = 0 never consults ℓπ
-__device__ __forceinline__ double tempered_energy(double beta, double lp, double lpt) { return beta == 0.0 ? lpt : lpt + beta * (lp - lpt); }
-
-__device__ __forceinline__ bool dead_state(double beta, double E, double lp, double lpt) {
-    return !isfinite(E) || lpt == HEALED || (beta > 0.0 && !isfinite(lp));
-}
-
-// Two loops over the coordinates. The first holds every transcendental (link, density) and sums ℓprior_t in declaration order — the
-// routine and the order of k_draw's logprior_t; it leaves ∇ℓprior_t in a.gpr because whether the prior was healed (and its derivative
-// is 0 in EVERY coordinate, as k_model_fwd has it) is known only after the last one. The second is arithmetic alone.
+// Two loops over the coordinates. The first is prior_loop (octo_draws_common.h, shared with the no-U-turn sampler): every transcendental, and
+// ∇ℓprior_t left in a.gpr. The second is arithmetic alone.
 template <int PHASE>
 __global__ __launch_bounds__(TPB) void k_hmc_leap(HmcArgs a) {
     const int64_t w = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -75,18 +67,8 @@ __global__ __launch_bounds__(TPB) void k_hmc_leap(HmcArgs a) {
     const double beta = a.has_model ? (a.beta ? a.beta[wl] : 1.0) : 0.0;
     const double eps = a.eps_w ? a.eps_w[wl] : a.eps;
     const double* __restrict__ at = PHASE == HMC_OPEN ? a.theta_t : a.q;
-    double lpt = 0.0;
-    bool healed = false;
-    for (int d = 0; d < a.D; ++d) {
-        const octo_prior pr = a.priors[d];
-        double xv, xd, pv, pd;
-        prior_link_lanes(pr, at[(int64_t)d * a.ld + wl], xv, xd);
-        prior_density_lanes(pr, xv, xd, pv, pd, a.pc + PRIOR_NC * d);
-        healed = healed || !isfinite(pv);
-        lpt += pv;
-        if (live) a.gpr[(int64_t)d * a.ld + w] = pd;
-    }
-    lpt = healed ? HEALED : lpt;
+    bool healed;
+    const double lpt = prior_loop(a.priors, a.pc, a.D, at, a.ld, w, wl, live, a.gpr, healed);
     const double lp = a.has_model ? a.lp[wl] : 0.0;      // E and ∇E consult it only where β != 0; the outputs report it for every chain
     const double kick = PHASE == HMC_STEP ? eps : 0.5 * eps;
     double K = 0.0;
@@ -94,7 +76,7 @@ __global__ __launch_bounds__(TPB) void k_hmc_leap(HmcArgs a) {
         const int64_t o = (int64_t)d * a.ld + wl;
         const double im = a.inv_mass ? a.inv_mass[d] : 1.0;
         const double gp = healed ? 0.0 : a.gpr[o];
-        const double g = beta == 1.0 ? a.glp[o] : (beta == 0.0 ? gp : beta * a.glp[o] + (1.0 - beta) * gp);
+        const double g = tempered_gradient(beta, a.glp, o, gp);
         double pd = a.p[o];
         if (PHASE == HMC_OPEN) K += im * pd * pd;
         pd += kick * g;

@@ -66,6 +66,32 @@ inline HmcWork hmc_work(Carve& c, int64_t D, int64_t ld) {
     return {c.take(D * ld), c.take(D * ld), c.take(D * ld), c.take(D * ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld)};
 }
 
+// The trees of one NUTS transition (octo_draws_nuts.hip), d_nuts: ((14 + 2·max_depth)·D + 18)·ld. The kernels take it by value (NutsArgs): its
+// members and their order are their argument layout.
+struct NutsWork {
+    double *trial, *pt;                          // [D][ld] the point of the next log-posterior call and its half-kicked momentum
+    double *qL, *pL, *gL, *qR, *pR, *gR;         // [D][ld] the tree's two endpoints: θ_t, p, ∇E
+    double *prop, *sprop;                        // [D][ld] the proposal of the tree and of the subtree being built
+    double *rho, *rho_s;                         // [D][ld] Σp of the tree and of the subtree
+    double *gpr, *glp;                           // [D][ld] ∇ℓprior_t and ∇ℓπ at the point of a launch
+    double *ck_p, *ck_r;                         // [max_depth][D][ld] the checkpoints: p′ and ρ_s at the leaf that opened a sub-subtree
+    double *lp, *H0, *logw, *logw_s, *sum_acc;   // [ld] ℓπ at the point of a launch · H₀ · log w, log w_s · Σ of the leaves' acceptance statistics
+    double *prop_lp, *prop_lpt, *sprop_lp, *sprop_lpt, *out_lp, *out_lpt;      // [ld] ℓπ and ℓprior_t of the two proposals and of θ_t as it stands
+    int32_t *status, *depth, *n, *nleaf, *v, *sel, *ssel;      // [ld] stop reason (0: building) · j · leaf of the subtree · leaves made · ±1 · leaf numbers of the proposals
+};
+inline NutsWork nuts_work(Carve& c, int64_t D, int64_t ld, int64_t max_depth) {
+    const int64_t plane = D * ld;
+    return {c.take(plane), c.take(plane),
+            c.take(plane), c.take(plane), c.take(plane), c.take(plane), c.take(plane), c.take(plane),
+            c.take(plane), c.take(plane),
+            c.take(plane), c.take(plane),
+            c.take(plane), c.take(plane),
+            c.take(max_depth * plane), c.take(max_depth * plane),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld)};
+}
+
 // The block partials of the grouped moments (octo_draws_adapt.hip), d_mom: nblk·G·(2K + 1). Per block of 256 chains and group: the number
 // of chains it holds · per row their sum and Σ(x − the block's mean)². sum and m2 of a (block, group) with cnt = 0 are never written or read.
 struct MomentsPartials { double *cnt, *sum, *m2; };      // [nblk][G] · [nblk][G][K] · [nblk][G][K]

@@ -270,8 +270,14 @@ def warmup_windows(n_warmup):
     return init, windows, term
 
 
+def _tree_means(depth, n_leapfrog, diverged):
+    """[3] on the device: the mean depth, the mean n_leapfrog and the number of divergences of one NUTS round"""
+    import torch
+    return torch.stack([depth.double().mean(), n_leapfrog.double().mean(), diverged.double().sum()])
+
+
 def hmc_warmup(pd, theta_t, n_warmup, n_leapfrog=8, eps=0.1, inv_mass=None, target_accept=0.8, seed=0, step=0, chain0=0, gamma=0.05, t0=10.0, kappa=0.75,
-               record=None):
+               record=None, max_depth=None):
     """Warm-up of PriorDraws.hmc_step on the W chains of theta_t ([D, W] on the device, updated in place) at β = 1 — on a handle without a
     model: on the prior. n_warmup rounds on the schedule of warmup_windows; round r is one hmc_step with step number step + r and then
       * the dual-averaging update of ε from the round's mean acceptance probability (PriorDraws.adapt_step, one group, δ = target_accept);
@@ -281,6 +287,9 @@ def hmc_warmup(pd, theta_t, n_warmup, n_leapfrog=8, eps=0.1, inv_mass=None, targ
     After the last round ε = ε̄. Nothing is read back: every statistic stays on the device.
     record: a list that receives one dict a round with copies of what each call of the round read and wrote (dH, accepted, theta_t, the
     dual-averaging state before and after, the moments before and after, inv_mass after), for a caller who follows the adaptation.
+    max_depth: None, or the tree depth of PriorDraws.nuts_step, which then is the round's step (n_leapfrog is not used): its log_accept goes where
+    dH went — min(1, exp(·)) of it is the transition's mean acceptance statistic — and the result gains tree [n_warmup, 3], per round the mean
+    depth, the mean n_leapfrog and the number of divergences.
     inv_mass: [D] (a copy is adapted) or None = 1. Returns dict(theta_t, eps (a [1] tensor), inv_mass [D], accept_stat [n_warmup], step (the
     next step number)), device tensors."""
     import torch
@@ -298,9 +307,14 @@ def hmc_warmup(pd, theta_t, n_warmup, n_leapfrog=8, eps=0.1, inv_mass=None, targ
     state = pd.adapt_init(1, eps)
     eps_w = torch.exp(state[:, 0]).expand(W).contiguous()
     accept_stat = torch.empty(n, dtype=torch.float64, device=dev)
+    tree = None if max_depth is None else torch.empty((n, 3), dtype=torch.float64, device=dev)
     mom, in_window, k = None, False, 0
     for r in range(n):
-        _lp, _ll, dH, acc = pd.hmc_step(theta_t, eps=eps_w, n_leapfrog=n_leapfrog, inv_mass=inv_mass, seed=seed, step=step + r, chain0=chain0)
+        if max_depth is None:
+            _lp, _ll, dH, acc = pd.hmc_step(theta_t, eps=eps_w, n_leapfrog=n_leapfrog, inv_mass=inv_mass, seed=seed, step=step + r, chain0=chain0)
+        else:
+            _lp, _ll, dH, acc, *counts = pd.nuts_step(theta_t, eps=eps_w, inv_mass=inv_mass, max_depth=max_depth, seed=seed, step=step + r, chain0=chain0)
+            tree[r] = _tree_means(*counts)
         k += 1
         rec = None if record is None else dict(round=r, k=k, dH=dH, accepted=acc, theta_t=theta_t.clone(), state_in=state.clone(), use_average=r == n - 1,
                                                mom_in=None if mom is None else tuple(t.clone() for t in mom))
@@ -320,7 +334,10 @@ def hmc_warmup(pd, theta_t, n_warmup, n_leapfrog=8, eps=0.1, inv_mass=None, targ
             in_window, k = False, 0
             if rec is not None:
                 rec.update(inv_mass=inv_mass.clone(), state_restart=state.clone())
-    return dict(theta_t=theta_t, eps=eps_w[:1].clone() if W else torch.exp(state[:, 1]), inv_mass=inv_mass, accept_stat=accept_stat, step=step + n)
+    out = dict(theta_t=theta_t, eps=eps_w[:1].clone() if W else torch.exp(state[:, 1]), inv_mass=inv_mass, accept_stat=accept_stat, step=step + n)
+    if tree is not None:
+        out["tree"] = tree
+    return out
 
 
 def rhat_from_chain_moments(pd, cmean, cm2, n):
@@ -376,6 +393,50 @@ def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leap
         return dict(**_recorded(model, rec_t, rec_lp),
                     accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
                     rhat=rhat.cpu().numpy(), names=list(model.names), state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns))
+
+
+def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_depth=10, target_accept=0.8, init=None, eps=0.1, seed=0):
+    """octofit_hmc_device with the reference's own sampler: every round is one NUTS transition (PriorDraws.nuts_step: multinomial sampling, the
+    generalised no-U-turn criterion, trees of depth <= max_depth) instead of a static trajectory. The starts, the metric, the warm-up
+    (hmc_warmup(max_depth=max_depth)), the recording and R̂ are octofit_hmc_device's.
+    Returns its dict — accept_stat is the mean over the chains of each transition's mean acceptance statistic — plus, per round of warm-up and
+    sampling, depth and n_leapfrog [n_warmup + n_samples] (means over the chains) and diverged [n_warmup + n_samples] (counts)."""
+    import torch
+    from .draws import PriorDraws
+    Cn, nw, ns = int(n_chains), int(n_warmup), int(n_samples)
+    if Cn < 2 or nw < 0 or ns < 1:
+        raise ValueError("octofit_nuts_device: n_chains >= 2, n_warmup >= 0, n_samples >= 1")
+    dev = torch.device("cuda", model.ln_like.device_index)
+    D = int(model.D)
+    if init is None:
+        init = pathfinder_device(model, n_draws=Cn, seed=seed)["theta_t"]
+    theta_t = torch.as_tensor(init, dtype=torch.float64, device=dev).clone().contiguous()
+    if tuple(theta_t.shape) != (D, Cn):
+        raise ValueError(f"octofit_nuts_device: init must be [D = {D}, n_chains = {Cn}] in θ_t")
+    with PriorDraws(model) as pd:
+        inv_mass = _default_metric(pd, seed, dev, None)
+        wu = hmc_warmup(pd, theta_t, nw, eps=eps, inv_mass=inv_mass, target_accept=target_accept, seed=seed, max_depth=max_depth)
+        eps_w, inv_mass = wu["eps"].expand(Cn).contiguous(), wu["inv_mass"]
+        rec_t = torch.empty((ns, D, Cn), dtype=torch.float64, device=dev)
+        rec_lp = torch.empty((ns, Cn), dtype=torch.float64, device=dev)
+        acc_s = torch.empty(ns, dtype=torch.float64, device=dev)
+        tree = torch.empty((ns, 3), dtype=torch.float64, device=dev)
+        cmean, cm2 = torch.empty_like(theta_t), torch.empty_like(theta_t)
+        state = pd.adapt_init(1, eps)      # never fed back: adapt_step is the reduction that gives the round's acceptance statistic
+        for r in range(ns):
+            lp, _ll, la, acc, *counts = pd.nuts_step(theta_t, eps=eps_w, inv_mass=inv_mass, max_depth=max_depth, seed=seed, step=nw + r)
+            acc_s[r:r + 1] = pd.adapt_step(state, la, acc, r + 1, delta=target_accept, want_eps=False)[0]
+            tree[r] = _tree_means(*counts)
+            rec_t[r] = theta_t
+            rec_lp[r] = lp
+            pd.chain_moments(theta_t, r + 1, cmean, cm2)
+        rhat = rhat_from_chain_moments(pd, cmean, cm2, ns)
+        torch.cuda.synchronize(dev)
+        tree = torch.cat([wu["tree"], tree]).cpu().numpy()
+        return dict(**_recorded(model, rec_t, rec_lp),
+                    accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
+                    rhat=rhat.cpu().numpy(), depth=tree[:, 0], n_leapfrog=tree[:, 1], diverged=tree[:, 2].astype(np.int64), names=list(model.names),
+                    state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns))
 
 
 def _optimizer_starts(pd, model, N, n_starts, seed, dev, inv_mass):

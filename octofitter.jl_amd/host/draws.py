@@ -10,6 +10,7 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     r = draws.lbfgs(θ_t, inv_mass=v, n_rounds=50)           # 50 rounds of L-BFGS on every column, θ_t updated in place: dict of device tensors
     r = draws.pathfinder(θ_t, inv_mass=v, n_rounds=50, seed=seed)      # the same rounds with Pathfinder's fits along the path: also elbo, elbo_iter, n_fits
     φ, logq, logpost = draws.pathfinder_draw(θ_t, 256, seed=seed)      # [D, 256·W], [256·W], [256·W]: draws from every chain's kept fit
+    lp, ll, log_accept, acc, depth, n_leapfrog, diverged = draws.nuts_step(θ_t, eps=0.1, max_depth=10, seed=seed, step=step)      # one NUTS transition
     count, mean, m2 = draws.moments(θ_t)                    # warm-up: pooled moments of the chains, [1], [1, D], [1, D] (or per group)
     draws.metric(count[0:1], mean[0], m2[0], inv_mass)      # … the diagonal metric they give, written into inv_mass [D]
     state = draws.adapt_init(1, 0.1)                        # … dual averaging of ε: the state [G, 4]
@@ -32,6 +33,8 @@ DRAWS_LIB_PATH = capi.PKG_DIR / "lib" / "liboctofitter_hip_draws.so"
 MAX_KEEP = 64                      # OCTO_DRAWS_MAX_KEEP
 PHILOX_KEY1 = 0x6F63746F64726177   # second key word; the first is the seed
 PURPOSE_PRIOR, PURPOSE_UNIFORM, PURPOSE_MOMENTUM, PURPOSE_ACCEPT, PURPOSE_ELBO, PURPOSE_PATHFINDER = 0, 1, 2, 3, 4, 5
+PURPOSE_NUTS_DIRECTION, PURPOSE_NUTS_LEAF, PURPOSE_NUTS_MERGE = 6, 7, 8
+NUTS_MAX_DEPTH = 10                # OCTO_DRAWS_NUTS_MAX_DEPTH
 LBFGS_MAX_M = 8                    # OCTO_DRAWS_LBFGS_MAX_M
 LBFGS_ACTIVE, LBFGS_GTOL, LBFGS_FTOL, LBFGS_LINESEARCH, LBFGS_DEAD = 0, 1, 2, 3, 4      # OCTO_DRAWS_LBFGS_*
 PF_MAX_D = 64                      # OCTO_DRAWS_PF_MAX_D
@@ -74,6 +77,8 @@ _SIGS = {
     "octo_draws_hmc_adapt_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,
                                                 C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "octo_draws_chain_moments_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_nuts_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                           C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -284,6 +289,48 @@ class PriorDraws(companion.Handle):
                                                         dH.data_ptr(), acc.data_ptr(), self._stream(stream, dev)))
         self._keep = (theta_t, be, eps_w, im)
         return (lp, ll, dH, acc, prop) if want_proposal else (lp, ll, dH, acc)
+
+    def nuts(self, theta_t, beta=None, eps=None, inv_mass=None, max_depth=10, n_rounds=0, resume=False, seed=0, step=0, chain0=0, out=None, stream=None):
+        """octo_draws_nuts_device, the raw call: opens (resume=False) or continues (resume=True: the same arguments, and out= the dict the
+        opening call returned) one NUTS transition of the W chains in theta_t and makes n_rounds rounds of it, a leapfrog per chain still
+        building. beta, eps, inv_mass as in hmc_step.
+        Returns dict(logpost, loglike (None on a handle made from priors alone), log_accept [W], accepted, depth, n_leapfrog, diverged int32 [W],
+        n_active int32 [1]: the chains still building), device tensors. Asynchronous on `stream`."""
+        import torch
+        dev = self.device
+        _, W, ld = chain_matrix(theta_t, self.D, dev, "nuts")
+        if eps is None:
+            raise ValueError("nuts: eps is required (a number, or one value per chain)")
+        per_chain = torch.is_tensor(eps) or np.ndim(eps) > 0
+        eps_w = device_vector(eps, W, dev, "eps") if per_chain else None
+        be = device_vector(beta, W, dev, "beta")
+        im = device_vector(inv_mass, self.D, dev, "inv_mass")
+        if out is None:
+            i32 = lambda n: self._out(n, dtype=torch.int32)      # noqa: E731
+            lp, ll = (self._out(W), self._out(W)) if self.model is not None else (None, None)
+            out = dict(logpost=lp, loglike=ll, log_accept=self._out(W), accepted=i32(W), depth=i32(W), n_leapfrog=i32(W), diverged=i32(W), n_active=i32(1))
+        self._check(self.lib.octo_draws_nuts_device(self._h, int(seed), int(step), int(chain0), W, ld, theta_t.data_ptr(), ptr(be), ptr(eps_w),
+                                                    0.0 if per_chain else float(eps), ptr(im), int(max_depth), int(n_rounds), 1 if resume else 0,
+                                                    *(ptr(out[k]) for k in ("logpost", "loglike", "log_accept", "accepted", "depth", "n_leapfrog", "diverged", "n_active")),
+                                                    self._stream(stream, dev)))
+        self._keep = (theta_t, be, eps_w, im, out)
+        return out
+
+    def nuts_step(self, theta_t, beta=None, eps=None, inv_mass=None, max_depth=10, seed=0, step=0, chain0=0, check_from=3, stream=None):
+        """One whole NUTS transition of the W chains in theta_t (torch float64 [D, W] on the handle's device, rows contiguous; a chain's
+        column is written where its proposal is not its start). After 2^j − 1 rounds every unfinished chain stands at a doubling boundary: at
+        those counts with j >= check_from the number of chains still building is read (a 4-byte copy, the only synchronisation) and the
+        transition stops at 0. check_from=None: all 2^max_depth − 1 rounds, no synchronisation — the same bits.
+        Returns (logpost [W], loglike [W], log_accept [W], accepted int32 [W], depth, n_leapfrog, diverged int32 [W]): hmc_step's tuple with the
+        log of the mean acceptance statistic where dH is (adapt_step takes it as dH), and the tree's three counts."""
+        md = int(max_depth)
+        args = dict(beta=beta, eps=eps, inv_mass=inv_mass, max_depth=md, seed=seed, step=step, chain0=chain0, stream=stream)
+        j = md if check_from is None else min(max(int(check_from), 0), md)
+        out = self.nuts(theta_t, n_rounds=(1 << j) - 1, **args)
+        while j < md and int(out["n_active"].item()) > 0:
+            out = self.nuts(theta_t, n_rounds=1 << j, resume=True, out=out, **args)
+            j += 1
+        return tuple(out[k] for k in ("logpost", "loglike", "log_accept", "accepted", "depth", "n_leapfrog", "diverged"))
 
     def lbfgs_direction(self, cnt, head, S, Y, g, inv_mass=None, stream=None):
         """The two-loop recursion of every chain on its own history: d [D, W] = −H·g with H₀ = γ·diag(inv_mass). cnt, head: int32 [W] (stored
