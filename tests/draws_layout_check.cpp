@@ -59,7 +59,7 @@ static void report(const char* layout, std::vector<int64_t> shape, int64_t size,
     } while (0)
 
 int main() {
-    const int64_t shapes[3][3] = {{1, 1, 1}, {3, 5, 2}, {64, 7, 8}};
+    const int64_t shapes[3][3] = {{1, 1, 1}, {3, 5, 2}, {64, 7, 8}};      // (D, ld, m) of the ten layouts of the optimisers, the HMC step and the drivers
     for (const auto& sh : shapes) {
         const int64_t D = sh[0], ld = sh[1], m = sh[2], plane = D * ld, KW = 5 * ld, P = D * (D + 1) / 2;
         const std::vector<int64_t> dlm = {D, ld, m}, dl = {D, ld};
@@ -103,6 +103,26 @@ int main() {
         RUN("draw_arrays", draw_arrays, (std::vector<int64_t>{ld, m}), arr, ld, m);
         auto out = [&](const Outputs& s) { return std::vector<Part>{PART(s, ix, ld), PART(s, ll, ld), PART(s, lp, ld), PART(s, theta, D * ld)}; };
         RUN("outputs", outputs, dl, out, D, ld);
+    }
+    const int64_t moment_shapes[4][3] = {{1, 1, 1}, {3, 5, 2}, {7, 64, 64}, {4, 3, 11}};      // (nblk, G, K): the block partials of the grouped moments
+    for (const auto& sh : moment_shapes) {
+        const int64_t nblk = sh[0], G = sh[1], K = sh[2];
+        auto mom = [&](const MomentsPartials& s) { return std::vector<Part>{PART(s, cnt, nblk * G), PART(s, sum, nblk * G * K), PART(s, m2, nblk * G * K)}; };
+        RUN("moments_partials", moments_partials, (std::vector<int64_t>{nblk, G, K}), mom, nblk, G, K);
+    }
+    const int64_t nuts_shapes[5][3] = {{1, 1, 1}, {14, 72, 4}, {5, 65536, 5}, {64, 3, 10}, {3, 257, 2}};      // (D, ld, max_depth): the trees of a NUTS transition
+    for (const auto& sh : nuts_shapes) {
+        const int64_t D = sh[0], ld = sh[1], md = sh[2], plane = D * ld;
+        auto tree = [&](const NutsWork& s) {
+            return std::vector<Part>{
+                PART(s, trial, plane), PART(s, pt, plane), PART(s, qL, plane), PART(s, pL, plane), PART(s, gL, plane), PART(s, qR, plane), PART(s, pR, plane),
+                PART(s, gR, plane), PART(s, prop, plane), PART(s, sprop, plane), PART(s, rho, plane), PART(s, rho_s, plane), PART(s, gpr, plane), PART(s, glp, plane),
+                PART(s, ck_p, md * plane), PART(s, ck_r, md * plane),
+                PART(s, lp, ld), PART(s, H0, ld), PART(s, logw, ld), PART(s, logw_s, ld), PART(s, sum_acc, ld), PART(s, prop_lp, ld), PART(s, prop_lpt, ld),
+                PART(s, sprop_lp, ld), PART(s, sprop_lpt, ld), PART(s, out_lp, ld), PART(s, out_lpt, ld),
+                PART(s, status, ld), PART(s, depth, ld), PART(s, n, ld), PART(s, nleaf, ld), PART(s, v, ld), PART(s, sel, ld), PART(s, ssel, ld)};
+        };
+        RUN("nuts_work", nuts_work, (std::vector<int64_t>{D, ld, md}), tree, D, ld, md);
     }
     return 0;
 }

@@ -2,9 +2,10 @@
 The warm-up statistics on the device (include/octofitter_hip_draws.h: octo_draws_moments_device, octo_draws_metric_device,
 octo_draws_hmc_adapt_init_device, octo_draws_hmc_adapt_device, octo_draws_chain_moments_device; host/draws.py: PriorDraws.moments / metric /
 adapt_init / adapt_step / chain_moments; host/callers.py: hmc_warmup, octofit_hmc_device, octofit_pt_device(adapt="device")) against exact
-arithmetic and the NumPy restatement (tests/adapt_reference.py), on the inputs, bars and seeds of tests/test_adapt_reference.py.
+arithmetic and the NumPy restatement (tests/adapt_reference.py), on the inputs, bars and seeds of tests/draws_cases.py that
+tests/test_adapt_reference.py establishes on the CPU.
 
-Tolerances: the moments' three bars of that module; metric 1e-14 relative (arithmetic only); dual-averaging state, acceptance statistic and ε
+Tolerances: the moments' three bars of tests/draws_cases.py; metric 1e-14 relative (arithmetic only); dual-averaging state, acceptance statistic and ε
 the project's device-transcendental bar 1e-11 relative to max(1, |ref|); per-chain moments 1e-12 relative; R̂ 1e-10 relative; the free-running
 warm-up max(1e-8, 100·s) with the s measured there; Kolmogorov-Smirnov at the 0.1 % level.
 """
@@ -15,98 +16,60 @@ import numpy as np
 import pytest
 
 import adapt_reference as ref
-import hmc_reference as hmc
-import test_adapt_reference as acond
-import test_hmc as th
-import test_hmc_reference as cond
+import draws_cases as cases
+from draws_device import TRANS_BAR, close, dev, draws_mod, hmc_model, host, mirror_priors, padded_view, set_batch_invariant      # noqa: F401
 
 pytestmark = pytest.mark.gpu
-TRANS_BAR = 1e-11
-
-
-@pytest.fixture(scope="module")
-def draws_mod(pkg):
-    from octofitter_jl_amd.host import draws
-    draws.load_library()
-    return draws
 
 
 @pytest.fixture(scope="module")
 def pd(pkg, draws_mod):
     """a handle without a model on the five priors of the stationarity condition"""
-    h = draws_mod.PriorDraws(priors=th.mirror_priors(pkg, cond.STAT_PRIORS))
+    h = draws_mod.PriorDraws(priors=mirror_priors(pkg, cases.STAT_PRIORS))
     yield h
     h.close()
 
 
-def dev(x, dtype=None):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x), device="cuda") if dtype is None else torch.as_tensor(np.ascontiguousarray(x), device="cuda", dtype=dtype)
-
-
-def padded(x, extra=5, fill=float("nan")):
-    """A [K, W] view with leading dimension W + extra of a buffer filled with `fill` beyond column W."""
-    import torch
-    x = dev(x)
-    buf = torch.full((x.shape[0], x.shape[1] + extra), fill, dtype=torch.float64, device="cuda")
-    buf[:, :x.shape[1]] = x
-    return buf[:, :x.shape[1]]
-
-
-def host(ts):
-    return tuple(t.cpu().numpy() for t in ts)
-
-
-def close(got, want, bar, scale_one=True):
-    """|got − want| <= bar·max(1, |want|) (scale_one) or bar·|want|, NaN equal to NaN"""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    if not np.array_equal(np.isnan(got), np.isnan(want)):
-        return False
-    ok = ~np.isnan(want)
-    den = np.maximum(1.0, np.abs(want[ok])) if scale_one else np.abs(want[ok])
-    return bool(np.all(np.abs(got[ok] - want[ok]) <= bar * den))
-
-
 # ---------------------------------------------------------------------------------------------------- 1. moments against the exact reference
-@pytest.mark.parametrize("G", acond.MOMENT_G)
-@pytest.mark.parametrize("K", acond.MOMENT_K)
+@pytest.mark.parametrize("G", cases.MOMENT_G)
+@pytest.mark.parametrize("K", cases.MOMENT_K)
 def test_gpu_moments_against_exact_arithmetic(pd, K, G):
     import torch
     worst = (0.0, 0.0)
-    for W in acond.MOMENT_W:
-        x, group = acond.moments_case(W, K, G)
+    for W in cases.MOMENT_W:
+        x, group = cases.moments_case(W, K, G)
         exact = ref.exact_moments(x, group, G)
         g = None if group is None else dev(group)
-        view = padded(x)
+        view = padded_view(x)
         got = host(pd.moments(view, g, G))
-        w = acond.check_moments(got, exact, (W, K, G))
+        w = cases.check_moments(got, exact, (W, K, G))
         worst = (max(worst[0], w[0]), max(worst[1], w[1]))
         if G > 1:
             assert got[0][G - 1] == 0 and np.all(got[1][G - 1] == 0) and np.all(got[2][G - 1] == 0)      # the empty group on overwrite
         # the same bits: the call again, another leading dimension with other values beyond column W, other values in excluded chains
         assert all(np.array_equal(a, b) for a, b in zip(got, host(pd.moments(view, g, G))))
-        assert all(np.array_equal(a, b) for a, b in zip(got, host(pd.moments(padded(x, 64, float("inf")), g, G))))
+        assert all(np.array_equal(a, b) for a, b in zip(got, host(pd.moments(padded_view(x, 64, float("inf")), g, G))))
         if W >= 63:
             x2 = x.copy()
             x2[:K - 1, 5] = 123.0                  # the chain with the NaN in its last row
             x2[:K - 1, 7] = -4.5e6
             if G > 1:
                 x2[:, 2], x2[:, 3] = 1e300, -7.0   # the chains with ids −1 and G
-            assert all(np.array_equal(a, b) for a, b in zip(got, host(pd.moments(padded(x2), g, G))))
+            assert all(np.array_equal(a, b) for a, b in zip(got, host(pd.moments(padded_view(x2), g, G))))
         # accumulate: three calls on thirds of the chains against one call on all of them
         out = None
-        for k, (a, b) in enumerate(acond.thirds(W)):
+        for k, (a, b) in enumerate(cases.thirds(W)):
             out = pd.moments(view[:, a:b], None if g is None else g[a:b].contiguous(), G, out=out, accumulate=k > 0)
         torch.cuda.synchronize()
-        acond.check_moments(host(out), exact, (W, K, G, "thirds"))
+        cases.check_moments(host(out), exact, (W, K, G, "thirds"))
     print(f"K {K} G {G}: worst mean error / bar {worst[0]:.3f}, worst M2 relative error {worst[1]:.3e}")
 
 
 # ---------------------------------------------------------------------------------------------------- 2. metric
 def test_gpu_metric(pd):
     import torch
-    x, group = acond.moments_case(257, 11, 3)
-    cnt, mean, m2 = pd.moments(padded(x), dev(group), 3)
+    x, group = cases.moments_case(257, 11, 3)
+    cnt, mean, m2 = pd.moments(padded_view(x), dev(group), 3)
     hc, _, hm2 = host((cnt, mean, m2))
     assert hc[1] == 1 and hc[2] == 0
     for reg in (True, False):
@@ -129,7 +92,7 @@ def test_gpu_metric(pd):
 @pytest.mark.parametrize("G", (1, 8))
 def test_gpu_dual_averaging(pd, G):
     import torch
-    dH0, acc, group = acond.dual_averaging_case(G)
+    dH0, acc, group = cases.dual_averaging_case(G)
     W = dH0.size
     eps0 = 0.1 if G == 1 else 0.05 * (1 + np.arange(G))
     state = pd.adapt_init(G, eps0 if G == 1 else dev(eps0))
@@ -201,13 +164,13 @@ def test_gpu_argument_checks(pkg, pd):
 def test_gpu_chain_moments_and_rhat(pd):
     import torch
     from octofitter_jl_amd.host import callers
-    s = acond.rhat_case()
+    s = cases.rhat_case()
     n, K, W = s.shape
-    cmean, cm2 = padded(np.zeros((K, W))), padded(np.zeros((K, W)))      # NaN everywhere beyond column W, and k = 1 ignores what they hold
+    cmean, cm2 = padded_view(np.zeros((K, W))), padded_view(np.zeros((K, W)))      # NaN everywhere beyond column W, and k = 1 ignores what they hold
     cmean[:] = float("nan")
     rmean = rm2 = None
     for k in range(1, n + 1):
-        pd.chain_moments(padded(s[k - 1]), k, cmean, cm2)
+        pd.chain_moments(padded_view(s[k - 1]), k, cmean, cm2)
         rmean, rm2 = ref.chain_moments(s[k - 1], k, rmean, rm2)
         assert close(cmean.cpu().numpy(), rmean, 1e-12, scale_one=False) and close(cm2.cpu().numpy(), rm2, 1e-12, scale_one=False), k
     got = cmean.cpu().numpy()
@@ -217,7 +180,7 @@ def test_gpu_chain_moments_and_rhat(pd):
     print(f"R̂ {r.min():.4f} … {r.max():.4f}; against the direct formula {np.max(np.abs(r - direct) / direct):.3e}")
     assert np.all(np.abs(r - direct) <= 1e-10 * direct)
     with pytest.raises(ValueError):
-        pd.chain_moments(padded(s[0]), 1, cmean, torch.zeros((K, W), dtype=torch.float64, device="cuda"))      # another leading dimension
+        pd.chain_moments(padded_view(s[0]), 1, cmean, torch.zeros((K, W), dtype=torch.float64, device="cuda"))      # another leading dimension
 
 
 # ---------------------------------------------------------------------------------------------------- 5. the warm-up loop on the prior
@@ -225,36 +188,36 @@ def test_gpu_chain_moments_and_rhat(pd):
 def loop(pkg, pd):
     """pkg.hmc_warmup on the handle without a model, every round recorded, and the restatement's own run from the device's start"""
     import torch
-    start = pd.sample(acond.LOOP_SEED, 0, acond.LOOP_W, theta=False, logprior_t=False)[1]
+    start = pd.sample(cases.LOOP_SEED, 0, cases.LOOP_W, theta=False, logprior_t=False)[1]
     record = []
-    out = pkg.hmc_warmup(pd, start.clone(), acond.LOOP_WARMUP, n_leapfrog=acond.LOOP_LEAPFROG, eps=acond.LOOP_EPS, seed=acond.LOOP_SEED, record=record)
+    out = pkg.hmc_warmup(pd, start.clone(), cases.LOOP_WARMUP, n_leapfrog=cases.LOOP_LEAPFROG, eps=cases.LOOP_EPS, seed=cases.LOOP_SEED, record=record)
     torch.cuda.synchronize()
-    own = ref.hmc_warmup(cond.STAT_PRIORS, start.cpu().numpy(), acond.LOOP_WARMUP, acond.LOOP_LEAPFROG, acond.LOOP_EPS, np.ones(5), acond.LOOP_SEED)
+    own = ref.hmc_warmup(cases.STAT_PRIORS, start.cpu().numpy(), cases.LOOP_WARMUP, cases.LOOP_LEAPFROG, cases.LOOP_EPS, np.ones(5), cases.LOOP_SEED)
     return out, record, own
 
 
 def test_gpu_warmup_teacher_forced(loop):
     """every round's adapt and moments outputs against the restatement applied to the DEVICE's inputs of that round"""
     out, record, _ = loop
-    flags = ref.round_flags(acond.LOOP_WARMUP)
-    assert len(record) == acond.LOOP_WARMUP and out["step"] == acond.LOOP_WARMUP
+    flags = ref.round_flags(cases.LOOP_WARMUP)
+    assert len(record) == cases.LOOP_WARMUP and out["step"] == cases.LOOP_WARMUP
     k, windows = 0, 0
     for r, rec in enumerate(record):
         k += 1
-        assert (rec["in_window"], rec["first"], rec["last"]) == flags[r] and rec["k"] == k and rec["use_average"] == (r == acond.LOOP_WARMUP - 1)
+        assert (rec["in_window"], rec["first"], rec["last"]) == flags[r] and rec["k"] == k and rec["use_average"] == (r == cases.LOOP_WARMUP - 1)
         state, a = ref.adapt_step(rec["state_in"].cpu().numpy(), rec["dH"].cpu().numpy(), rec["accepted"].cpu().numpy(), k)
         assert close(rec["state"].cpu().numpy(), state, TRANS_BAR) and close(rec["accept_stat"].cpu().numpy(), a, TRANS_BAR), r
-        assert close(rec["eps_w"].cpu().numpy(), np.full(acond.LOOP_W, math.exp(state[0, 1 if rec["use_average"] else 0])), TRANS_BAR), r
+        assert close(rec["eps_w"].cpu().numpy(), np.full(cases.LOOP_W, math.exp(state[0, 1 if rec["use_average"] else 0])), TRANS_BAR), r
         assert close(out["accept_stat"][r].cpu().numpy(), a[0], TRANS_BAR)
         if rec["in_window"]:
             tt = rec["theta_t"].cpu().numpy()
             got = host(rec["mom"])
             if rec["first"]:
-                acond.check_moments(got, ref.exact_moments(tt), ("round", r))
+                cases.check_moments(got, ref.exact_moments(tt), ("round", r))
             else:                     # the merge: the restatement's Chan step on what the device held, at the same bars
                 cnt, mean, m2 = ref.moments(tt, held=host(rec["mom_in"]))
                 amax = np.maximum(np.max(np.abs(tt), axis=1), np.abs(mean[0]))
-                assert np.array_equal(got[0], cnt) and np.all(np.abs(got[1] - mean) <= cnt[0] * acond.U * amax) and np.all(np.abs(got[2] - m2) <= acond.M2_BAR * m2), r
+                assert np.array_equal(got[0], cnt) and np.all(np.abs(got[1] - mean) <= cnt[0] * cases.U * amax) and np.all(np.abs(got[2] - m2) <= cases.M2_BAR * m2), r
         if rec["last"]:
             windows += 1
             hm = host(rec["mom"])
@@ -269,39 +232,39 @@ def test_gpu_warmup_free_running(loop):
     out, record, own = loop
     got = dict(eps=out["eps"].cpu().numpy()[0], inv_mass=out["inv_mass"].cpu().numpy(), theta_t=out["theta_t"].cpu().numpy())
     dev_acc = np.array([rec["accepted"].cpu().numpy() != 0 for rec in record])
-    d = acond.loop_deviation(got, own)
-    print(f"free-running warm-up: deviation {d:.3e} (bar {acond.LOOP_BAR:.3e}); ε {got['eps']:.6f} (restatement {own['eps']:.6f}); flags differing {np.sum(dev_acc != own['accepted'])}")
+    d = cases.loop_deviation(got, own)
+    print(f"free-running warm-up: deviation {d:.3e} (bar {cases.LOOP_BAR:.3e}); ε {got['eps']:.6f} (restatement {own['eps']:.6f}); flags differing {np.sum(dev_acc != own['accepted'])}")
     assert np.array_equal(dev_acc, own["accepted"])
-    assert d <= acond.LOOP_BAR
+    assert d <= cases.LOOP_BAR
     assert not np.allclose(got["inv_mass"], 1.0)
 
 
-@pytest.mark.parametrize("seed", acond.FROZEN_SEEDS)
+@pytest.mark.parametrize("seed", cases.FROZEN_SEEDS)
 def test_gpu_frozen_kernel_is_stationary(pkg, pd, seed):
     """(ε, inv_mass) of a warm-up on chains 0 … 4095, then a fresh batch of 65 536 exact prior draws through six steps"""
-    start = pd.sample(seed, 0, acond.FROZEN_WARM_W, theta=False, logprior_t=False)[1]
-    wu = pkg.hmc_warmup(pd, start, acond.LOOP_WARMUP, n_leapfrog=acond.LOOP_LEAPFROG, eps=acond.LOOP_EPS, seed=seed)
+    start = pd.sample(seed, 0, cases.FROZEN_WARM_W, theta=False, logprior_t=False)[1]
+    wu = pkg.hmc_warmup(pd, start, cases.LOOP_WARMUP, n_leapfrog=cases.LOOP_LEAPFROG, eps=cases.LOOP_EPS, seed=seed)
     eps, im = float(wu["eps"][0]), wu["inv_mass"]
-    fresh = pd.sample(seed, acond.FROZEN_WARM_W, acond.FROZEN_W, theta=False, logprior_t=False)[1]
+    fresh = pd.sample(seed, cases.FROZEN_WARM_W, cases.FROZEN_W, theta=False, logprior_t=False)[1]
 
     accs = []
-    for j in range(acond.FROZEN_STEPS):
-        _, _, _, a = pd.hmc_step(fresh, eps=eps, n_leapfrog=acond.LOOP_LEAPFROG, inv_mass=im, seed=seed, step=acond.LOOP_WARMUP + j, chain0=acond.FROZEN_WARM_W)
+    for j in range(cases.FROZEN_STEPS):
+        _, _, _, a = pd.hmc_step(fresh, eps=eps, n_leapfrog=cases.LOOP_LEAPFROG, inv_mass=im, seed=seed, step=cases.LOOP_WARMUP + j, chain0=cases.FROZEN_WARM_W)
         accs.append(float(a.double().mean()))
     acc = float(np.mean(accs))
-    stat = cond.stationarity_statistics(fresh.cpu().numpy())
-    wu_ref, (stat_ref, acc_ref) = acond.frozen_reference(seed)
-    print(f"seed {seed}: device ε {eps:.5f} (restatement {wu_ref['eps']:.5f}); max D_n {stat:.3e} (restatement {stat_ref:.3e}, bar {cond.STAT_BAR:.3e}); "
+    stat = cases.stationarity_statistics(fresh.cpu().numpy())
+    wu_ref, (stat_ref, acc_ref) = cases.frozen_reference(seed)
+    print(f"seed {seed}: device ε {eps:.5f} (restatement {wu_ref['eps']:.5f}); max D_n {stat:.3e} (restatement {stat_ref:.3e}, bar {cases.STAT_BAR:.3e}); "
           f"acceptance {acc:.4f} (restatement {acc_ref:.4f})")
-    assert stat < cond.STAT_BAR
-    assert abs(acc - acc_ref) <= 3 * 0.5 / math.sqrt(acond.FROZEN_STEPS * acond.FROZEN_W)      # the binomial bound
+    assert stat < cases.STAT_BAR
+    assert abs(acc - acc_ref) <= 3 * 0.5 / math.sqrt(cases.FROZEN_STEPS * cases.FROZEN_W)      # the binomial bound
 
 
 # ---------------------------------------------------------------------------------------------------- 6. the drivers
 @pytest.fixture(scope="module")
 def model(pkg):
-    m = th.hmc_model(pkg)
-    th.set_batch_invariant(pkg, m, 1)
+    m = hmc_model(pkg)
+    set_batch_invariant(pkg, m, 1)
     yield m
     m.close()
 

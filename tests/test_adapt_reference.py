@@ -14,59 +14,15 @@ import numpy as np
 import pytest
 
 import adapt_reference as ref
+import draws_cases as cases
 import hmc_reference as hmc
-import test_hmc_reference as cond
-
-U = 2.0 ** -53
-M2_BAR = 1e-10
-MOMENT_W = (1, 63, 64, 65, 255, 256, 257, 1000)      # a partial wave, a wave edge, a partial block, several blocks
-MOMENT_K = (1, 11, 64)
-MOMENT_G = (1, 3, 64)                                # 1: a NULL group array
 
 
-def moments_case(W, K, G):
-    """(x [K][W], group [W] or None). Row 0 is a `tp` in MJD: mean 5e4, deviation 0.5; the other rows have scales from 1e-2 to 1e2 and means
-    of either sign. With a group array: ids −1 and G (excluded), group G − 1 empty, group 1 with a single member. One chain has a NaN and one
-    an Inf coordinate (in the last row: the exclusion has to look at every row). Chains too few for a role do without it."""
-    rng = np.random.default_rng(1000 * W + 10 * K + G)
-    scale = 10.0 ** ((np.arange(K) % 5) - 2)
-    x = rng.normal(size=(K, W)) * scale[:, None] + (np.arange(K) % 3 - 1)[:, None] * 3.0 * scale[:, None]
-    x[0] = 5e4 + 0.5 * rng.normal(size=W)
-    group = None
-    if G > 1:
-        group = rng.integers(0, G - 1, size=W).astype(np.int32)      # group G − 1 stays empty
-        if W >= 63:
-            group[group == 1] = 0
-            group[11] = 1
-            group[2], group[3] = -1, G
-    if W >= 63:
-        x[K - 1, 5] = np.nan
-        x[K - 1, 7] = np.inf
-    return x, group
-
-
-def check_moments(got, exact, what):
-    """the three bars of the module's docstring"""
-    cnt, mean, m2 = (np.asarray(t, dtype=np.float64) for t in got)
-    ecnt, emean, em2, amax = exact
-    assert np.array_equal(cnt, ecnt), (what, cnt, ecnt)
-    err_mean = np.abs(mean - emean)
-    assert np.all(err_mean <= ecnt[:, None] * U * amax), (what, "mean", float(np.max(err_mean - ecnt[:, None] * U * amax)))
-    err_m2 = np.abs(m2 - em2)
-    assert np.all(err_m2 <= M2_BAR * em2), (what, "M2", float(np.max(err_m2 / np.where(em2 > 0, em2, 1.0))))
-    rel = np.max(err_m2 / np.where(em2 > 0, em2, 1.0)) if em2.size else 0.0
-    return float(np.max(err_mean / np.where(amax > 0, ecnt[:, None] * U * amax, 1.0))), float(rel)
-
-
-def thirds(W):
-    return [(0, W // 3), (W // 3, 2 * W // 3), (2 * W // 3, W)]
-
-
-@pytest.mark.parametrize("G", MOMENT_G)
-@pytest.mark.parametrize("K", MOMENT_K)
+@pytest.mark.parametrize("G", cases.MOMENT_G)
+@pytest.mark.parametrize("K", cases.MOMENT_K)
 def test_moments_restatement_against_exact_arithmetic(K, G):
-    for W in MOMENT_W:
-        x, group = moments_case(W, K, G)
+    for W in cases.MOMENT_W:
+        x, group = cases.moments_case(W, K, G)
         exact = ref.exact_moments(x, group, G)
         if W >= 63:
             assert exact[0].sum() == W - 2 - (2 if G > 1 else 0)          # the NaN and the Inf chain, ids −1 and G
@@ -74,24 +30,24 @@ def test_moments_restatement_against_exact_arithmetic(K, G):
                 assert exact[0][1] == 1 and exact[2][1].max() == 0.0     # the single member: M2 = 0
         if G > 1:
             assert exact[0][G - 1] == 0
-        worst = check_moments(ref.moments(x, group, G), exact, (W, K, G))
+        worst = cases.check_moments(ref.moments(x, group, G), exact, (W, K, G))
         # the naive form misses the M2 bar on the offset row by decades: the bar separates them
         keep, gid = ref.included(x, group, G)
         v = x[0, keep & (gid == 0)]
         if v.size >= 255:
             naive = np.sum(v * v) - v.size * np.mean(v) ** 2
-            assert abs(naive - exact[2][0, 0]) > 100 * M2_BAR * exact[2][0, 0]
+            assert abs(naive - exact[2][0, 0]) > 100 * cases.M2_BAR * exact[2][0, 0]
         # accumulate: three calls on thirds of the chains against one call on all of them
         held = None
-        for a, b in thirds(W):
+        for a, b in cases.thirds(W):
             part = ref.moments(x[:, a:b], None if group is None else group[a:b], G)
             held = part if held is None else ref.moments(x[:, a:b], None if group is None else group[a:b], G, held=held)
-        check_moments(held, exact, (W, K, G, "thirds"))
-    print(f"K {K} G {G}: worst mean error / bar {worst[0]:.3f}, worst M2 relative error {worst[1]:.3e} (W = {MOMENT_W[-1]})")
+        cases.check_moments(held, exact, (W, K, G, "thirds"))
+    print(f"K {K} G {G}: worst mean error / bar {worst[0]:.3f}, worst M2 relative error {worst[1]:.3e} (W = {cases.MOMENT_W[-1]})")
 
 
 def test_merge_leaves_an_empty_block_and_takes_over_an_empty_state():
-    x, group = moments_case(257, 3, 3)
+    x, group = cases.moments_case(257, 3, 3)
     full = ref.moments(x, group, 3)
     none = ref.moments(x[:, :0], group[:0], 3, held=full)
     assert all(np.array_equal(a, b) for a, b in zip(full, none))
@@ -140,130 +96,62 @@ def test_dual_averaging_is_stans_learn_stepsize():
             # one chain whose dH gives exactly this acceptance probability: a = 0 and 1 through the NaN branch
             dH, acc = (np.array([np.nan]), np.array([int(a)])) if a in (0.0, 1.0) else (np.array([math.log(a)]), np.array([0]))
             state, a_g = ref.adapt_step(state, dH, acc, k)
-            assert abs(a_g[0] - a) <= 2 * U
+            assert abs(a_g[0] - a) <= 2 * cases.U
             eps, eps_bar = stan[k - 1]
             assert abs(math.exp(state[0, 0]) - eps) <= 1e-12 * eps and abs(math.exp(state[0, 1]) - eps_bar) <= 1e-12 * eps_bar, k
 
 
-DA_W = 300
-
-
-def dual_averaging_case(G):
-    """(dH [W], accepted [W], group [W] or None): finite values of both signs, ±Inf, NaN with accepted 0 and 1, values above 700; with groups:
-    ids −1 and G, and group G − 2 empty."""
-    rng = np.random.default_rng(77 + G)
-    dH = rng.normal(-0.3, 1.0, DA_W)
-    acc = (rng.uniform(size=DA_W) < np.minimum(1.0, np.exp(dH))).astype(np.int32)
-    dH[[3, 70, 140]] = np.inf
-    dH[[4, 71, 141]] = -np.inf
-    dH[[5, 72, 142, 143]] = np.nan
-    acc[[5, 142]] = 1
-    acc[[72, 143]] = 0
-    dH[[6, 73, 144]] = (710.0, 1e6, 700.5)
-    group = None
-    if G > 1:
-        group = (np.arange(DA_W) % G).astype(np.int32)
-        group[group == G - 2] = 0
-        group[[9, 200]] = (-1, G)
-    return dH, acc, group
-
-
 def test_dual_averaging_case_is_defined_everywhere():
     for G in (1, 8):
-        dH, acc, group = dual_averaging_case(G)
+        dH, acc, group = cases.dual_averaging_case(G)
         a = ref.accept_prob(dH, acc)
         assert np.all((a >= 0) & (a <= 1)) and a[5] == 1.0 and a[72] == 0.0 and a[3] == 1.0 and a[4] == 0.0 and a[6] == 1.0
         state, a_g = ref.adapt_step(ref.adapt_init(0.1, G), dH, acc, 1, group)
         assert np.all(np.isfinite(state)) and (G == 1 or (np.isnan(a_g[G - 2]) and np.isfinite(np.delete(a_g, G - 2)).all()))
         if G > 1:
             assert np.array_equal(state[G - 2], ref.adapt_init(0.1, G)[G - 2])
-            e = ref.eps_of(state, group, DA_W)
+            e = ref.eps_of(state, group, cases.DA_W)
             assert np.isnan(e[9]) and np.isnan(e[200]) and np.isfinite(np.delete(e, [9, 200])).all()
 
 
-RHAT_W, RHAT_K, RHAT_N = 257, 11, 12
-
-
-def rhat_case():
-    """samples [n][K][W], row k around 5·(k + 1) so that a relative bar on the running means is meaningful; chain 100 has one NaN (sample 4, row 3)"""
-    rng = np.random.default_rng(12)
-    s = rng.normal(size=(RHAT_N, RHAT_K, RHAT_W)) + 0.3 * rng.normal(size=(1, RHAT_K, RHAT_W)) + 5.0 * (1 + np.arange(RHAT_K))[None, :, None]
-    s[4, 3, 100] = np.nan
-    return s
-
-
 def test_rhat_identity_against_the_direct_formula():
-    s = rhat_case()
+    s = cases.rhat_case()
     cmean = cm2 = None
-    for k in range(1, RHAT_N + 1):
+    for k in range(1, cases.RHAT_N + 1):
         cmean, cm2 = ref.chain_moments(s[k - 1], k, cmean, cm2)
-    ok = np.arange(RHAT_W) != 100
+    ok = np.arange(cases.RHAT_W) != 100
     assert np.all(np.isnan(cmean[3, 100])) and np.all(np.isnan(cm2[3, 100]))      # the chain with the NaN carries it
-    assert np.allclose(cmean[:, ok], s[:, :, ok].mean(axis=0), rtol=1e-13, atol=0) and np.allclose(cm2[:, ok], s[:, :, ok].var(axis=0) * RHAT_N, rtol=1e-12)
-    r, direct = ref.rhat(cmean, cm2, RHAT_N), ref.rhat_direct(s)
+    assert np.allclose(cmean[:, ok], s[:, :, ok].mean(axis=0), rtol=1e-13, atol=0) and np.allclose(cm2[:, ok], s[:, :, ok].var(axis=0) * cases.RHAT_N, rtol=1e-12)
+    r, direct = ref.rhat(cmean, cm2, cases.RHAT_N), ref.rhat_direct(s)
     assert np.all(np.abs(r - direct) <= 1e-10 * direct) and np.all((r > 0.9) & (r < 1.5))
 
 
 # ---------------------------------------------------------------------------------------------------- the warm-up loop on the prior
-LOOP_W, LOOP_WARMUP, LOOP_LEAPFROG, LOOP_SEED, LOOP_EPS = 192, 30, 3, 51, 0.1
-# The largest deviation, relative to max(1, |value|), of ε, inv_mass and the final θ_t between two runs of the restatement whose starts differ
-# by one ulp in every coordinate, measured by test_warmup_loop_sensitivity_to_one_ulp below: 3.105e-8
-# (thirty rounds of three leapfrog steps amplify an ulp that far on the chain that moves most). The free-running comparison of
-# tests/test_adapt.py is held to max(1e-8, 100·s).
-LOOP_S = 3.11e-8
-LOOP_BAR = max(1e-8, 100 * LOOP_S)
-
-
 def loop_start():
-    return hmc.prior_sample(cond.STAT_PRIORS, LOOP_SEED, np.arange(LOOP_W, dtype=np.uint64))[1]
-
-
-def loop_deviation(a, b):
-    return max(float(np.max(np.abs(np.asarray(a[k]) - np.asarray(b[k])) / np.maximum(1.0, np.abs(np.asarray(b[k]))))) for k in ("eps", "inv_mass", "theta_t"))
+    return hmc.prior_sample(cases.STAT_PRIORS, cases.LOOP_SEED, np.arange(cases.LOOP_W, dtype=np.uint64))[1]
 
 
 def test_warmup_loop_sensitivity_to_one_ulp():
     start = loop_start()
-    run = lambda tt: ref.hmc_warmup(cond.STAT_PRIORS, tt, LOOP_WARMUP, LOOP_LEAPFROG, LOOP_EPS, np.ones(5), LOOP_SEED)      # noqa: E731
+    run = lambda tt: ref.hmc_warmup(cases.STAT_PRIORS, tt, cases.LOOP_WARMUP, cases.LOOP_LEAPFROG, cases.LOOP_EPS, np.ones(5), cases.LOOP_SEED)      # noqa: E731
     a, b = run(start), run(np.nextafter(start, np.inf))
-    s = loop_deviation(b, a)
+    s = cases.loop_deviation(b, a)
     print(f"warm-up loop, start moved by one ulp: s = {s:.3e}; ε {a['eps']:.6f}, inv_mass {a['inv_mass']}, acceptance {a['accept_stat'].mean():.3f}")
     assert np.array_equal(a["accepted"], b["accepted"])
-    assert s <= LOOP_S
+    assert s <= cases.LOOP_S
     assert not np.array_equal(a["inv_mass"], np.ones(5)) and 0.3 < a["accept_stat"][-5:].mean() <= 1.0
 
 
-# The kernel a warm-up freezes leaves the prior invariant: (ε, inv_mass) from a warm-up on chains 0 … 4095, then a fresh batch of exact prior
-# draws (draws and chains 4096 … 4096 + 65535) through six steps, one-sample KS per coordinate under cond.STAT_BAR. The seeds are the first
-# two of 21, 22, 23, … for which the restatement stays under the bar; tests/test_adapt.py uses the same ones on the device.
-FROZEN_WARM_W, FROZEN_W, FROZEN_STEPS = 4096, cond.STAT_W, cond.STAT_STEPS
+# cases.FROZEN_SEEDS are the first two of these for which the restatement stays under the bar
 FROZEN_CANDIDATES = (21, 22)
-FROZEN_SEEDS = (21, 22)
-
-
-def frozen_run(seed, eps, inv_mass):
-    """(max D_n over the coordinates, mean acceptance flag) of the fresh batch after six steps at step numbers LOOP_WARMUP …"""
-    tt = hmc.prior_sample(cond.STAT_PRIORS, seed, FROZEN_WARM_W + np.arange(FROZEN_W, dtype=np.uint64))[1]
-    acc = []
-    for j in range(FROZEN_STEPS):
-        r = hmc.hmc_step(cond.STAT_PRIORS, tt, None, eps, LOOP_LEAPFROG, inv_mass, seed, LOOP_WARMUP + j, chain0=FROZEN_WARM_W)
-        tt = r["theta_t"]
-        acc.append(np.mean(r["accepted"]))
-    return cond.stationarity_statistics(tt), float(np.mean(acc))
-
-
-def frozen_reference(seed):
-    start = hmc.prior_sample(cond.STAT_PRIORS, seed, np.arange(FROZEN_WARM_W, dtype=np.uint64))[1]
-    wu = ref.hmc_warmup(cond.STAT_PRIORS, start, LOOP_WARMUP, LOOP_LEAPFROG, LOOP_EPS, np.ones(5), seed)
-    return wu, frozen_run(seed, wu["eps"], wu["inv_mass"])
 
 
 def test_frozen_kernel_is_stationary():
     passed = []
     for seed in FROZEN_CANDIDATES:
-        wu, (stat, acc) = frozen_reference(seed)
+        wu, (stat, acc) = cases.frozen_reference(seed)
         print(f"seed {seed}: warm-up ε {wu['eps']:.5f} inv_mass {np.array2string(wu['inv_mass'], precision=4)}; fresh batch max D_n {stat:.3e} "
-              f"(bar {cond.STAT_BAR:.3e}), acceptance {acc:.4f}")
-        if stat < cond.STAT_BAR:
+              f"(bar {cases.STAT_BAR:.3e}), acceptance {acc:.4f}")
+        if stat < cases.STAT_BAR:
             passed.append(seed)
-    assert tuple(passed[:2]) == FROZEN_SEEDS
+    assert tuple(passed[:2]) == cases.FROZEN_SEEDS

@@ -13,62 +13,11 @@ import math
 import numpy as np
 import pytest
 
+import draws_cases as cases
 import hmc_reference as ref
-import test_hmc_reference as cond
+from draws_device import draws_mod, hmc_model, mirror_priors, padded, same_bits, set_batch_invariant      # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def draws_mod(pkg):
-    from octofitter_jl_amd.host import draws
-    draws.load_library()
-    return draws
-
-
-def mirror_priors(pkg, priors):
-    """host/priors.py priors of the restatement's dicts"""
-    out = []
-    for p in priors:
-        k = p["kind"]
-        out.append(pkg.Uniform(p["p0"], p["p1"]) if k == ref.UNIFORM else pkg.LogUniform(p["p0"], p["p1"]) if k == ref.LOGUNIFORM
-                   else pkg.Normal(p["p0"], p["p1"]) if k == ref.NORMAL else pkg.Sine() if k == ref.SINE
-                   else pkg.truncated(pkg.Normal(p["p0"], p["p1"]), lower=None if p["lo"] == -math.inf else p["lo"], upper=None if p["hi"] == math.inf else p["hi"]))
-    return out
-
-
-def hmc_model(pkg, e_prior=None):
-    """The test model through the mirror; its priors and sources are the ones tests/test_hmc_reference.py hands the oracle."""
-    astrom_t, rv_t = cond.model_tables()
-    astrom = pkg.PlanetRelAstromObs(astrom_t, name="sim")
-    rv = pkg.StarAbsoluteRVObs(rv_t, name="rv", variables=pkg.variables(offset=pkg.Normal(0, 20), jitter=pkg.LogUniform(0.1, 20.0)))
-    b = pkg.Planet(name="b", basis="Visual{KepOrbit}", observations=[astrom],
-                   variables=pkg.variables(a=pkg.LogUniform(5, 20), e=e_prior or pkg.Uniform(0.0, 0.6), i=pkg.Sine(), ω=pkg.UniformCircular(),
-                                           Ω=pkg.UniformCircular(), θ=pkg.UniformCircular(), tp=pkg.θ_at_epoch_to_tperi("θ", 50000),
-                                           mass=pkg.LogUniform(1.0, 50.0)))
-    sys_ = pkg.System(name="sim", companions=[b], observations=[rv],
-                      variables=pkg.variables(M=pkg.truncated(pkg.Normal(1.2, 0.05), lower=0.1), plx=pkg.truncated(pkg.Normal(50.0, 0.1), lower=0.1)))
-    model = pkg.LogDensityModel(sys_)
-    assert model.names == cond.MODEL_NAMES
-    if e_prior is None:
-        for k, p in enumerate(cond.MODEL_PRIORS):
-            c = model._c_priors[k]
-            lo, hi = ref.support(p) if p["kind"] != ref.NORMAL else (-math.inf, math.inf)
-            assert (c.kind, c.p0, c.p1) == (p["kind"], p["p0"], p["p1"]) and (p["kind"] != ref.TRUNCNORMAL or (c.lo, c.hi) == (lo, hi)), k
-    assert [tuple(t) for t in model._esrc] == cond.MODEL_ESRC and [tuple(t) for t in model._nsrc] == cond.MODEL_NSRC
-    return model
-
-
-def set_batch_invariant(pkg, model, on=1):
-    fn = model.ln_like
-    fn._check(fn.lib.octo_ctx_set_option(fn._ctx, pkg.capi.OPT_BATCH_INVARIANT, on), "octo_ctx_set_option")
-
-
-def padded(torch, x, ld):
-    """A [D, W] view with leading dimension ld of a NaN-filled buffer holding x."""
-    buf = torch.full((x.shape[0], ld), float("nan"), dtype=torch.float64, device=x.device)
-    buf[:, :x.shape[1]] = x
-    return buf, buf[:, :x.shape[1]]
 
 
 # ---------------------------------------------------------------------------------------------------- 1. momentum
@@ -100,7 +49,7 @@ def test_gpu_momentum(pkg, draws_mod, D):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. one step against the restatement
-STEP_W, STEP_LD, STEP_SEED, step_inputs = cond.STEP_W, cond.STEP_LD, cond.STEP_SEED, cond.step_inputs
+STEP_W, STEP_LD, STEP_SEED, step_inputs = cases.STEP_W, cases.STEP_LD, cases.STEP_SEED, cases.step_inputs
 
 
 @pytest.fixture(scope="module")
@@ -117,12 +66,12 @@ def test_gpu_one_step_against_the_restatement(pkg, oracle, draws_mod, step_model
     import torch
     model, pd = step_model
     set_batch_invariant(pkg, model, 0)
-    W, ld, seed, step = STEP_W, STEP_LD, STEP_SEED, cond.STEP_STEP
+    W, ld, seed, step = STEP_W, STEP_LD, STEP_SEED, cases.STEP_STEP
     beta, eps, im = step_inputs()
     start = pd.sample(seed, 0, W, theta=False, logprior_t=False)[1]
     buf, tt = padded(torch, start, ld)
     dev = tt.device
-    r = ref.hmc_step(cond.MODEL_PRIORS, start.cpu().numpy(), beta, eps, n_leapfrog, im, seed, cond.STEP_STEP, logpost=cond.oracle_logpost(oracle, cond.oracle_model(oracle)))
+    r = ref.hmc_step(cases.MODEL_PRIORS, start.cpu().numpy(), beta, eps, n_leapfrog, im, seed, cases.STEP_STEP, logpost=cases.oracle_logpost(oracle, cases.oracle_model(oracle)))
     margin = np.abs(r["dH"] - r["log_u"])
     decided = margin > 1e-6
     print(f"L {n_leapfrog}: reference acceptance {r['accepted'].mean():.3f}; {np.sum(~decided)} of {W} chains within 1e-6 of the decision")
@@ -149,39 +98,39 @@ def test_gpu_one_step_against_the_restatement(pkg, oracle, draws_mod, step_model
 
 
 # ---------------------------------------------------------------------------------------------------- 3. β = 0 stationarity
-@pytest.mark.parametrize("eps,n_leapfrog", cond.STAT_SETTINGS)
+@pytest.mark.parametrize("eps,n_leapfrog", cases.STAT_SETTINGS)
 def test_gpu_prior_is_stationary(pkg, draws_mod, eps, n_leapfrog):
-    pd = draws_mod.PriorDraws(priors=mirror_priors(pkg, cond.STAT_PRIORS))
-    for seed in cond.STAT_SEEDS:
-        tt = pd.sample(seed, 0, cond.STAT_W, theta=False, logprior_t=False)[1]
+    pd = draws_mod.PriorDraws(priors=mirror_priors(pkg, cases.STAT_PRIORS))
+    for seed in cases.STAT_SEEDS:
+        tt = pd.sample(seed, 0, cases.STAT_W, theta=False, logprior_t=False)[1]
         start = tt.clone()
         accs = []
-        for step in range(cond.STAT_STEPS):
-            lp, ll, _dH, acc = pd.hmc_step(tt, eps=eps, n_leapfrog=n_leapfrog, inv_mass=cond.STAT_INV_MASS, seed=seed, step=step)
+        for step in range(cases.STAT_STEPS):
+            lp, ll, _dH, acc = pd.hmc_step(tt, eps=eps, n_leapfrog=n_leapfrog, inv_mass=cases.STAT_INV_MASS, seed=seed, step=step)
             assert lp is None and ll is None
             accs.append(float(acc.double().mean()))
         moved = float((tt != start).any(dim=0).double().mean())
-        stat = cond.stationarity_statistics(tt.cpu().numpy())
-        print(f"seed {seed} (ε {eps}, L {n_leapfrog}): acceptance {np.mean(accs):.3f}, moved {moved:.3f}, max D_n {stat:.3e} (bar {cond.STAT_BAR:.3e})")
-        assert stat < cond.STAT_BAR and np.mean(accs) >= 0.6 and moved >= 0.9, (seed, stat, accs, moved)
+        stat = cases.stationarity_statistics(tt.cpu().numpy())
+        print(f"seed {seed} (ε {eps}, L {n_leapfrog}): acceptance {np.mean(accs):.3f}, moved {moved:.3f}, max D_n {stat:.3e} (bar {cases.STAT_BAR:.3e})")
+        assert stat < cases.STAT_BAR and np.mean(accs) >= 0.6 and moved >= 0.9, (seed, stat, accs, moved)
     pd.close()
 
 
 # ---------------------------------------------------------------------------------------------------- 4. β = 1 stationarity
-@pytest.mark.parametrize("seed", cond.POST_SEEDS)
+@pytest.mark.parametrize("seed", cases.POST_SEEDS)
 def test_gpu_posterior_is_stationary(pkg, draws_mod, step_model, seed):
     import torch
     model, pd = step_model
     set_batch_invariant(pkg, model, 0)
-    a, b = (model.link(pd.rejection(seed, cond.POST_N, first=first)["samples"]) for first in cond.POST_FIRST)
-    im = cond.posterior_inv_mass(b)
+    a, b = (model.link(pd.rejection(seed, cases.POST_N, first=first)["samples"]) for first in cases.POST_FIRST)
+    im = cases.posterior_inv_mass(b)
 
     def step_fn(tt, step):
         t = torch.as_tensor(tt, device="cuda").contiguous()
-        _lp, _ll, _dH, acc = pd.hmc_step(t, eps=cond.POST_EPS, n_leapfrog=cond.POST_LEAPFROG, inv_mass=im, seed=seed, step=step)
+        _lp, _ll, _dH, acc = pd.hmc_step(t, eps=cases.POST_EPS, n_leapfrog=cases.POST_LEAPFROG, inv_mass=im, seed=seed, step=step)
         return t.cpu().numpy(), acc.cpu().numpy()
 
-    cond.check_posterior_stationary(a, b, step_fn, f"seed {seed} (device)")
+    cases.check_posterior_stationary(a, b, step_fn, f"seed {seed} (device)")
 
 
 # ---------------------------------------------------------------------------------------------------- 5. determinism
@@ -192,10 +141,6 @@ def run_step(torch, pd, start, beta, eps, im, seed=STEP_SEED, step=2, chain0=0, 
     lp, ll, dH, acc = pd.hmc_step(tt, beta=torch.as_tensor(beta, device=dev), eps=torch.as_tensor(eps, device=dev), n_leapfrog=n_leapfrog, inv_mass=im,
                                   seed=seed, step=step, chain0=chain0)
     return [x.cpu().numpy() for x in (tt, lp, ll, dH, acc)]
-
-
-def same_bits(x, y):
-    return all(np.array_equal(a, b, equal_nan=True) for a, b in zip(x, y))
 
 
 def test_gpu_determinism(pkg, draws_mod, step_model):
@@ -232,7 +177,7 @@ def test_gpu_dead_states(pkg, draws_mod):
     model = hmc_model(pkg, e_prior=pkg.Uniform(0.0, 1.6))
     pd = draws_mod.PriorDraws(model)
     set_batch_invariant(pkg, model, 1)
-    W, seed, ie = 64, 43, cond.MODEL_NAMES.index("b_e")
+    W, seed, ie = 64, 43, cases.MODEL_NAMES.index("b_e")
     clean = pd.sample(seed, 0, W, theta=False, logprior_t=False)[1]
     e_link = lambda e: math.log(e / 1.6) - math.log1p(-e / 1.6)      # noqa: E731
     clean[ie] = torch.clamp(clean[ie], max=e_link(0.9))               # every chain of the clean batch starts on a bound orbit
@@ -284,7 +229,7 @@ def test_gpu_octofit_pt_device(pkg, draws_mod):
     # the replicas that sat at β = 0 in the last round hold the prior draws of their indices
     st = out["state"]
     assert st["refreshed_first"] == T * Cn + (R - 1) * Cn and st["refreshed"].shape == (Cn,)
-    _, fresh = ref.prior_sample(cond.MODEL_PRIORS, seed, st["refreshed_first"] + np.arange(Cn, dtype=np.uint64))
+    _, fresh = ref.prior_sample(cases.MODEL_PRIORS, seed, st["refreshed_first"] + np.arange(Cn, dtype=np.uint64))
     got = st["theta_t"][:, st["refreshed"]]
     assert np.max(np.abs(got - fresh) / np.maximum(1.0, np.abs(fresh))) <= 1e-11
     pd = draws_mod.PriorDraws(model)
@@ -319,7 +264,7 @@ def test_gpu_hmc_argument_checks(pkg, draws_mod, step_model):
     assert call(pd._h, 0, 0, 0.1, 1) == 0
     torch.cuda.synchronize()
     assert torch.equal(tt, before)
-    nomodel = draws_mod.PriorDraws(priors=mirror_priors(pkg, cond.MODEL_PRIORS))
+    nomodel = draws_mod.PriorDraws(priors=mirror_priors(pkg, cases.MODEL_PRIORS))
     assert call(nomodel._h, W, W, 0.1, 1, d_lp=lp.data_ptr()) == EINVAL and b"no model" in lib.octo_draws_last_error(nomodel._h)
     assert call(nomodel._h, W, W, 0.1, 1) == 0
     assert lib.octo_draws_momentum_device(pd._h, 0, 0, 0, W, W - 1, None, tt.data_ptr(), st) == EINVAL

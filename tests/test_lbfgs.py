@@ -15,61 +15,20 @@ import math
 import numpy as np
 import pytest
 
+import draws_cases as cases
 import lbfgs_reference as ref
-import test_hmc_reference as hcond
-import test_lbfgs_reference as cond
+from draws_device import differing, draws_mod, host_outputs, padded, rel, set_batch_invariant, tight_model      # noqa: F401
+
+# tools/lbfgs_bench.py and tools/pathfinder_bench.py read tight_model from this module (test_lbfgs.tight_model): keep the name importable here
 
 pytestmark = pytest.mark.gpu
 
-W, LD, M, GTOL = cond.SHORT_W, cond.SHORT_LD, cond.M, cond.GTOL
+W, LD, M, GTOL = cases.LBFGS_SHORT_W, cases.LBFGS_SHORT_LD, cases.LBFGS_M, cases.LBFGS_GRAD_TOL
 OUT_KEYS = ("logpost", "gnorm", "status", "iters", "evals", "inv_hess_diag")
 
 
-@pytest.fixture(scope="module")
-def draws_mod(pkg):
-    from octofitter_jl_amd.host import draws
-    draws.load_library()
-    return draws
-
-
-def tight_model(pkg):
-    """The model of tests/test_hmc.py on the tight tables; its priors and sources are the ones the oracle gets."""
-    astrom_t, rv_t = cond.tight_tables()
-    astrom = pkg.PlanetRelAstromObs(astrom_t, name="sim")
-    rv = pkg.StarAbsoluteRVObs(rv_t, name="rv", variables=pkg.variables(offset=pkg.Normal(0, 20), jitter=pkg.LogUniform(0.1, 20.0)))
-    b = pkg.Planet(name="b", basis="Visual{KepOrbit}", observations=[astrom],
-                   variables=pkg.variables(a=pkg.LogUniform(5, 20), e=pkg.Uniform(0.0, 0.6), i=pkg.Sine(), ω=pkg.UniformCircular(), Ω=pkg.UniformCircular(),
-                                           θ=pkg.UniformCircular(), tp=pkg.θ_at_epoch_to_tperi("θ", 50000), mass=pkg.LogUniform(1.0, 50.0)))
-    sys_ = pkg.System(name="sim", companions=[b], observations=[rv],
-                      variables=pkg.variables(M=pkg.truncated(pkg.Normal(1.2, 0.05), lower=0.1), plx=pkg.truncated(pkg.Normal(50.0, 0.1), lower=0.1)))
-    model = pkg.LogDensityModel(sys_)
-    assert model.names == hcond.MODEL_NAMES
-    assert [tuple(t) for t in model._esrc] == hcond.MODEL_ESRC and [tuple(t) for t in model._nsrc] == hcond.MODEL_NSRC
-    return model
-
-
-def set_batch_invariant(pkg, model, on=1):
-    fn = model.ln_like
-    fn._check(fn.lib.octo_ctx_set_option(fn._ctx, pkg.capi.OPT_BATCH_INVARIANT, on), "octo_ctx_set_option")
-
-
-def padded(torch, x, ld):
-    """A view with leading dimension ld of a NaN-filled buffer holding x (the chain index last)."""
-    buf = torch.full(tuple(x.shape[:-1]) + (ld,), float("nan"), dtype=torch.float64, device="cuda")
-    buf[..., :x.shape[-1]] = torch.as_tensor(x, device="cuda")
-    return buf, buf[..., :x.shape[-1]]
-
-
-def host(r, tt):
-    return dict(theta_t=tt.cpu().numpy(), **{k: v.cpu().numpy() for k, v in r.items() if v is not None})
-
-
-def same_bits(a, b, keys=("theta_t",) + OUT_KEYS, cols=slice(None)):
-    return [k for k in keys if not np.array_equal(a[k][..., cols], b[k][..., cols], equal_nan=True)] == []
-
-
-def rel(x, y):
-    return np.abs(x - y) / np.maximum(1.0, np.abs(y))
+def same_outputs(a, b):
+    return differing(a, b, ("theta_t",) + OUT_KEYS) == []
 
 
 @pytest.fixture(scope="module")
@@ -79,13 +38,13 @@ def case(pkg, oracle, draws_mod):
     import torch
     model = tight_model(pkg)
     pd = draws_mod.PriorDraws(model)
-    v = pd.sample(cond.SEED, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1).cpu().numpy()
-    θ0, lp0, _ = pd.best(cond.SEED, cond.N_DRAWS, keep=cond.N_STARTS)
+    v = pd.sample(cases.LBFGS_SEED, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1).cpu().numpy()
+    θ0, lp0, _ = pd.best(cases.LBFGS_SEED, cases.LBFGS_N_DRAWS, keep=cases.LBFGS_N_STARTS)
     starts = np.ascontiguousarray(model.link(θ0))
-    logpost = cond.tight_logpost(oracle)
+    logpost = cases.tight_logpost(oracle)
     tt = torch.as_tensor(starts, device="cuda").clone()
-    full = host(pd.lbfgs(tt, inv_mass=v, m=M, n_rounds=cond.ROUNDS, gtol=GTOL, want_inv_hess_diag=True), tt)
-    full_ref = ref.lbfgs(logpost, starts, v, m=M, n_rounds=cond.ROUNDS, gtol=GTOL)
+    full = host_outputs(pd.lbfgs(tt, inv_mass=v, m=M, n_rounds=cases.LBFGS_ROUNDS, gtol=GTOL, want_inv_hess_diag=True), tt)
+    full_ref = ref.lbfgs(logpost, starts, v, m=M, n_rounds=cases.LBFGS_ROUNDS, gtol=GTOL)
     yield dict(model=model, pd=pd, v=v, starts=starts, lp0=lp0, logpost=logpost, full=full, full_ref=full_ref)
     pd.close()
     model.close()
@@ -97,7 +56,7 @@ def test_gpu_direction_against_the_restatement(pkg, draws_mod, D, m):
     import torch
     pd = draws_mod.PriorDraws(priors=[pkg.Uniform(0, 1)] * D)
     rng = np.random.default_rng(100 * D + m)
-    cnt, head, S, Y, g, v = cond.random_history(rng, m, D, W)
+    cnt, head, S, Y, g, v = cases.random_history(rng, m, D, W)
     assert (cnt == 0).any() and (cnt == m).any()
     want = ref.direction(cnt, head, S, Y, g, v)
     worst = 0.0
@@ -116,18 +75,18 @@ def test_gpu_direction_against_the_restatement(pkg, draws_mod, D, m):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. four rounds
-@pytest.mark.parametrize("ftol", cond.SHORT_FTOLS)
+@pytest.mark.parametrize("ftol", cases.LBFGS_SHORT_FTOLS)
 def test_gpu_four_rounds_against_the_restatement(pkg, case, ftol):
     import torch
     model, pd, v = case["model"], case["pd"], case["v"]
     set_batch_invariant(pkg, model, 0)
-    start = pd.sample(cond.SEED, 0, W, theta=False, logprior_t=False)[1]
-    r = ref.lbfgs(case["logpost"], start.cpu().numpy(), v, m=M, n_rounds=cond.SHORT_ROUNDS, gtol=GTOL, ftol=ftol)
-    decided = r["margin"] > cond.MARGIN
-    print(f"ftol {ftol}: {np.sum(~decided)} of {W} chains within {cond.MARGIN} of a decision; status counts {np.bincount(r['status'], minlength=5)}; reference accepted steps {r['iters'].min()} … {r['iters'].max()}")
+    start = pd.sample(cases.LBFGS_SEED, 0, W, theta=False, logprior_t=False)[1]
+    r = ref.lbfgs(case["logpost"], start.cpu().numpy(), v, m=M, n_rounds=cases.LBFGS_SHORT_ROUNDS, gtol=GTOL, ftol=ftol)
+    decided = r["margin"] > cases.LBFGS_MARGIN
+    print(f"ftol {ftol}: {np.sum(~decided)} of {W} chains within {cases.LBFGS_MARGIN} of a decision; status counts {np.bincount(r['status'], minlength=5)}; reference accepted steps {r['iters'].min()} … {r['iters'].max()}")
     assert np.mean(~decided) <= 0.05, "condition on the seed (the reference alone)"
     buf, tt = padded(torch, start, LD)
-    got = host(pd.lbfgs(tt, inv_mass=v, m=M, n_rounds=cond.SHORT_ROUNDS, gtol=GTOL, ftol=ftol, want_inv_hess_diag=True), tt)
+    got = host_outputs(pd.lbfgs(tt, inv_mass=v, m=M, n_rounds=cases.LBFGS_SHORT_ROUNDS, gtol=GTOL, ftol=ftol, want_inv_hess_diag=True), tt)
     assert bool(torch.isnan(buf[:, W:]).all())                                  # nothing written beyond column W
     for k in ("status", "iters", "evals"):
         assert np.array_equal(got[k][decided], r[k][decided]), k
@@ -135,15 +94,15 @@ def test_gpu_four_rounds_against_the_restatement(pkg, case, ftol):
     e_ih = np.max(np.abs(got["inv_hess_diag"][:, decided] / r["inv_hess_diag"][:, decided] - 1.0))
     print(f"four rounds: max errors — θ_t {e_th:.3e}, ℓπ {e_lp:.3e} (relative to max(1, |ref|)); inverse-Hessian diagonal {e_ih:.3e} (relative)")
     assert e_th <= 1e-8 and e_lp <= 1e-8 and e_ih <= 1e-6
-    assert got["iters"].max() >= 2 and got["iters"].min() < cond.SHORT_ROUNDS
-    assert np.all(got["evals"] == cond.SHORT_ROUNDS + 1) if ftol == 0.0 else np.any(got["status"] == ref.FTOL)
+    assert got["iters"].max() >= 2 and got["iters"].min() < cases.LBFGS_SHORT_ROUNDS
+    assert np.all(got["evals"] == cases.LBFGS_SHORT_ROUNDS + 1) if ftol == 0.0 else np.any(got["status"] == ref.FTOL)
 
 
 # ---------------------------------------------------------------------------------------------------- 3. the full run
 def test_gpu_full_run(pkg, oracle, case):
     import torch
     pd, v, starts, full, r = case["pd"], case["v"], case["starts"], case["full"], case["full_ref"]
-    n = cond.N_STARTS
+    n = cases.LBFGS_N_STARTS
     print(f"device: status counts {np.bincount(full['status'], minlength=5)}, evals {full['evals'].min()} … {full['evals'].max()}, best ℓπ {full['logpost'].max():.8f}; "
           f"restatement: status counts {np.bincount(r['status'], minlength=5)}, best ℓπ {r['logpost'].max():.8f}")
     assert np.all(full["logpost"] >= case["lp0"])                               # Armijo: no chain ends below its start
@@ -163,13 +122,13 @@ def test_gpu_full_run(pkg, oracle, case):
     # the decisions of every round, from a run in segments of one round (which is the same run, bit for bit)
     tt = torch.as_tensor(starts, device="cuda").clone()
     its, sts = [], []
-    for k in range(cond.ROUNDS):
+    for k in range(cases.LBFGS_ROUNDS):
         seg = pd.lbfgs(tt, inv_mass=v, m=M, n_rounds=1, gtol=GTOL, resume=k > 0, want_inv_hess_diag=True)
         its.append(seg["iters"]), sts.append(seg["status"])
-        if k + 1 == cond.MID_ROUNDS:
+        if k + 1 == cases.LBFGS_MID_ROUNDS:
             ihd_mid = seg["inv_hess_diag"].cpu().numpy()
-    seg = host(seg, tt)
-    assert same_bits(seg, full)
+    seg = host_outputs(seg, tt)
+    assert same_outputs(seg, full)
     its, sts = torch.stack(its).cpu().numpy(), torch.stack(sts).cpu().numpy()
     active = np.vstack([np.ones((1, n), dtype=bool), sts[:-1] == ref.ACTIVE])
     accepted = np.diff(np.vstack([np.zeros((1, n), dtype=its.dtype), its]), axis=0) > 0
@@ -177,47 +136,47 @@ def test_gpu_full_run(pkg, oracle, case):
     dec_ref = np.zeros_like(dec)
     dec_ref[:r["decisions"].shape[0]] = r["decisions"]
     matched = np.all(dec == dec_ref, axis=0)
-    first = np.where(matched, cond.ROUNDS, np.argmax(dec != dec_ref, axis=0))
+    first = np.where(matched, cases.LBFGS_ROUNDS, np.argmax(dec != dec_ref, axis=0))
     e_ih = np.max(np.abs(ihd[:, matched] / r["inv_hess_diag"][:, matched] - 1.0)) if matched.any() else 0.0
     print(f"{matched.sum()} of {n} chains made the restatement's decision in every round (the first other decision: round {first.min()} at the earliest, "
           f"median {int(np.median(first))}); their inverse-Hessian diagonals differ by at most {e_ih:.3e} (relative)")
     assert e_ih <= 1e-6
     # … through DECIDED_ROUNDS rounds the decided chains make the restatement's decisions, and after MID_ROUNDS rounds their diagonals agree:
     # as far as the restatement's own response to inputs disturbed at the device's level stays below the bar (tests/test_lbfgs_reference.py)
-    for rounds in (cond.DECIDED_ROUNDS, cond.MID_ROUNDS):
+    for rounds in (cases.LBFGS_DECIDED_ROUNDS, cases.LBFGS_MID_ROUNDS):
         mid = ref.lbfgs(case["logpost"], starts, v, m=M, n_rounds=rounds, gtol=GTOL)
-        decided = mid["margin"] > cond.MARGIN
+        decided = mid["margin"] > cases.LBFGS_MARGIN
         assert decided.mean() >= 0.5, "condition on the starts (the reference alone)"
         assert np.array_equal(dec[:rounds, decided], mid["decisions"][:, decided])
     e_mid = np.max(np.abs(ihd_mid[:, decided] / mid["inv_hess_diag"][:, decided] - 1.0))
-    print(f"after {cond.MID_ROUNDS} rounds: {decided.sum()} of {n} chains decided, their inverse-Hessian diagonals differ by at most {e_mid:.3e} (relative)")
+    print(f"after {cases.LBFGS_MID_ROUNDS} rounds: {decided.sum()} of {n} chains decided, their inverse-Hessian diagonals differ by at most {e_mid:.3e} (relative)")
     assert e_mid <= 1e-6
 
 
 # ---------------------------------------------------------------------------------------------------- 4. batch invariance, 5. resume
 def run(torch, pd, x, v, n_rounds, ld=None, **kw):
     _buf, tt = padded(torch, x, ld or x.shape[1])
-    return host(pd.lbfgs(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=n_rounds, want_inv_hess_diag=True, **kw), tt), tt
+    return host_outputs(pd.lbfgs(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=n_rounds, want_inv_hess_diag=True, **kw), tt), tt
 
 
 def test_gpu_batch_invariance_and_resume(pkg, case):
     import torch
     model, pd, v = case["model"], case["pd"], case["v"]
-    start = pd.sample(cond.SEED, 0, W, theta=False, logprior_t=False)[1].cpu().numpy()
+    start = pd.sample(cases.LBFGS_SEED, 0, W, theta=False, logprior_t=False)[1].cpu().numpy()
     set_batch_invariant(pkg, model, 1)
     try:
         whole, _ = run(torch, pd, start, v, 40, ld=LD)
         part, _ = run(torch, pd, np.ascontiguousarray(start[:, 5:9]), v, 40)
-        assert same_bits({k: x[..., 5:9] for k, x in whole.items()}, part)
+        assert same_outputs({k: x[..., 5:9] for k, x in whole.items()}, part)
         assert whole["iters"][5:9].min() >= 5
     finally:
         set_batch_invariant(pkg, model, 0)
     one, _ = run(torch, pd, start, v, 40, ld=LD)
     _, tt = run(torch, pd, start, v, 20, ld=LD)
-    two = host(pd.lbfgs(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=20, resume=True, want_inv_hess_diag=True), tt)
-    assert same_bits(one, two)
+    two = host_outputs(pd.lbfgs(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=20, resume=True, want_inv_hess_diag=True), tt)
+    assert same_outputs(one, two)
     assert np.all(one["evals"] == 41)
-    assert same_bits(two, host(pd.lbfgs(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=0, resume=True, want_inv_hess_diag=True), tt))      # no round: the outputs alone
+    assert same_outputs(two, host_outputs(pd.lbfgs(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=0, resume=True, want_inv_hess_diag=True), tt))      # no round: the outputs alone
 
 
 # ---------------------------------------------------------------------------------------------------- 6. frozen and dead chains
@@ -227,8 +186,8 @@ def test_gpu_frozen_and_dead_chains(pkg, case):
     mid, tt = run(torch, pd, starts, v, 400)
     frozen = mid["status"] != ref.ACTIVE
     assert frozen.any() and not frozen.all(), np.bincount(mid["status"], minlength=5)
-    more = host(pd.lbfgs(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=10, resume=True, want_inv_hess_diag=True), tt)
-    assert same_bits({k: x[..., frozen] for k, x in mid.items()}, {k: x[..., frozen] for k, x in more.items()})
+    more = host_outputs(pd.lbfgs(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=10, resume=True, want_inv_hess_diag=True), tt)
+    assert same_outputs({k: x[..., frozen] for k, x in mid.items()}, {k: x[..., frozen] for k, x in more.items()})
     assert np.all(more["evals"][~frozen] > mid["evals"][~frozen])
     dirty = starts.copy()
     dirty[3, 7] = np.nan
@@ -243,7 +202,7 @@ def test_gpu_frozen_and_dead_chains(pkg, case):
 def test_gpu_host_twin(pkg, case):
     import torch
     pd, v = case["pd"], case["v"]
-    start = pd.sample(cond.SEED, 0, W, theta=False, logprior_t=False)[1].cpu().numpy()
+    start = pd.sample(cases.LBFGS_SEED, 0, W, theta=False, logprior_t=False)[1].cpu().numpy()
     dev, _ = run(torch, pd, start, v, 30, ld=LD)
     D = start.shape[0]
     th = np.full((D, LD), np.nan)
@@ -254,7 +213,7 @@ def test_gpu_host_twin(pkg, case):
     dp, ip = pkg.capi._dptr, lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))      # noqa: E731
     pd._check(pd.lib.octo_draws_lbfgs(pd._h, W, LD, dp(th), dp(np.ascontiguousarray(v)), M, 30, GTOL, 0.0, dp(lp), dp(gn), ip(status), ip(iters), ip(evals), dp(ihd)))
     twin = dict(theta_t=th[:, :W], logpost=lp, gnorm=gn, status=status, iters=iters, evals=evals, inv_hess_diag=ihd[:, :W])
-    assert same_bits(dev, twin)
+    assert same_outputs(dev, twin)
     assert np.all(np.isnan(th[:, W:]))
 
 
@@ -309,16 +268,16 @@ def test_gpu_lbfgs_argument_checks(pkg, draws_mod, case):
 # ---------------------------------------------------------------------------------------------------- 9. the driver
 def test_gpu_optimize_starting_points_device(pkg, oracle, case, draws_mod):
     model = case["model"]
-    out = pkg.optimize_starting_points_device(model, N=cond.N_DRAWS, n_starts=cond.N_STARTS, seed=cond.SEED)
-    D, n = model.D, cond.N_STARTS
+    out = pkg.optimize_starting_points_device(model, N=cases.LBFGS_N_DRAWS, n_starts=cases.LBFGS_N_STARTS, seed=cases.LBFGS_SEED)
+    D, n = model.D, cases.LBFGS_N_STARTS
     assert out["theta"].shape == out["theta_t"].shape == out["inv_hess_diag"].shape == (D, n) and out["names"] == list(model.names)
     assert all(out[k].shape == (n,) for k in ("logpost", "start_logpost", "status", "iters", "evals"))
     print(f"driver: status counts {np.bincount(out['status'], minlength=5)}, evals {out['evals'].min()} … {out['evals'].max()}, best ℓπ {out['logpost'][out['best']]:.8f}")
     assert not np.any(out["status"] == draws_mod.LBFGS_ACTIVE)
     assert np.array_equal(out["start_logpost"], case["lp0"]) and np.all(out["logpost"] >= out["start_logpost"])
-    _, lp_guess = pkg.guess_starting_position_device(model, N=cond.N_DRAWS, seed=cond.SEED)
+    _, lp_guess = pkg.guess_starting_position_device(model, N=cases.LBFGS_N_DRAWS, seed=cases.LBFGS_SEED)
     best = out["logpost"][out["best"]]
     assert best == out["logpost"].max() and best >= lp_guess
-    optimum = cond.reference_case(oracle)[3]["logpost"].max()
+    optimum = cases.reference_case(oracle)[3]["logpost"].max()
     assert abs(best - optimum) <= 1e-8 * max(1.0, abs(optimum))
     assert np.max(rel(model.ℓπcallback(out["theta_t"]), out["logpost"])) <= 1e-8 and np.array_equal(model.link(out["theta"]).shape, (D, n))

@@ -3,83 +3,21 @@ Conditions on the NumPy restatement of the batched L-BFGS (tests/lbfgs_reference
 the Pathfinder diagonal mean (against dense BFGS algebra, and against the same recursion in extended precision), the optimiser against
 scipy's L-BFGS-B on the oracle's callback, and the conditions the GPU tests of tests/test_lbfgs.py rest on, from the reference alone.
 
-The model is the one of tests/test_hmc_reference.py with the noise its tables were actually drawn with as their σ (60 mas, 30 m/s): a
-posterior with one dominant optimum that the scaled L-BFGS reaches from the best prior draws. The scaling v is the variance of prior draws
-0 … 4095 in θ_t, the default of the device drivers.
+The tight model, its 64 starts, the scaling v and the settings of the runs are those of tests/draws_cases.py.
 """
 import ctypes as C
-import functools
 import math
 
 import numpy as np
 import pytest
 
-import hmc_reference as href
+import draws_cases as cases
 import lbfgs_reference as ref
-import test_hmc_reference as cond
 
-SEED, N_DRAWS, N_STARTS = 77, 65536, 64
-M, GTOL, ROUNDS = 6, 1e-6, 800
-SHORT_W, SHORT_LD, SHORT_ROUNDS = 67, 71, 4      # one full wave plus three lanes, a padded leading dimension
-DECIDED_ROUNDS = 40                              # how far into the full run the decisions of the decided chains are compared
-MID_ROUNDS, INPUT_NOISE = 10, 1e-12              # where its Pathfinder diagonal is compared; the level at which device and oracle ℓπ agree
-MARGIN = 1e-6
-SHORT_FTOLS = (0.0, 0.05)                        # without the ftol test, and with one that stops about half of the chains in the short run
-TIGHT_SIGMA_ASTROM, TIGHT_SIGMA_RV = 60.0, 30.0
-
-
-def tight_tables():
-    """cond.model_tables() with σ the noise that was drawn"""
-    astrom, rv = cond.model_tables()
-    astrom = dict(astrom, σ_ra=np.full(12, TIGHT_SIGMA_ASTROM), σ_dec=np.full(12, TIGHT_SIGMA_ASTROM))
-    return astrom, dict(rv, σ_rv=np.full(8, TIGHT_SIGMA_RV))
-
-
-def tight_logpost(oracle, n_threads=0):
-    """logpost(θ_t) -> (ℓπ, ∇ℓπ) of the tight model from the oracle's callback (n_threads = 1 for one θ_t at a time: no thread start a call)"""
-    astrom, rv = tight_tables()
-    obs = [dict(kind=0, planet=0, epoch=astrom["epoch"], y1=astrom["ra"], y2=astrom["dec"], s1=astrom["σ_ra"], s2=astrom["σ_dec"], cor=None, extra=None),
-           dict(kind=2, planet=-1, epoch=rv["epoch"], y1=rv["rv"], y2=None, s1=rv["σ_rv"], s2=None, cor=None, extra=None)]
-    _, planets, priors, esrc, nsrc = cond.oracle_model(oracle)
-    return lambda th: oracle.oracle_model_logpost(obs, planets, priors, esrc, nsrc, np.ascontiguousarray(th), grad=True, n_threads=n_threads)
-
-
-def prior_theta_t(first, n):
-    return href.prior_sample(cond.MODEL_PRIORS, SEED, np.uint64(first) + np.arange(n, dtype=np.uint64))[1]
-
-
-def default_inv_mass(theta_t_4096):
-    """the unbiased per-coordinate variance, as torch.var gives the device drivers"""
-    return np.var(theta_t_4096, axis=1, ddof=1)
-
-
-@functools.lru_cache(maxsize=None)
-def reference_case(oracle):
-    """(starts [D, 64] best first, their ℓπ, v, the restatement's result from them) — computed once, shared, never modified"""
-    logpost = tight_logpost(oracle)
-    tt = prior_theta_t(0, N_DRAWS)
-    lp = np.concatenate([logpost(tt[:, k:k + 8192])[0] for k in range(0, N_DRAWS, 8192)])
-    order = np.argsort(-np.where(np.isfinite(lp), lp, -np.inf), kind="stable")[:N_STARTS]
-    starts, v = np.ascontiguousarray(tt[:, order]), default_inv_mass(tt[:, :4096])
-    res = ref.lbfgs(logpost, starts, v, m=M, n_rounds=ROUNDS, gtol=GTOL)
-    for a in (starts, v, *[x for x in res.values() if isinstance(x, np.ndarray)]):
-        a.setflags(write=False)
-    return starts, lp[order], v, res
+INPUT_NOISE = 1e-12      # the level at which device and oracle ℓπ agree
 
 
 # ---------------------------------------------------------------------------------------------------- what the recursion means
-def random_history(rng, m, D, W, dtype=np.float64):
-    """s random, y = A·s with A SPD of condition <= 1e3 (one A per chain); cnt cycles through 0 … m, head through 0 … m − 1"""
-    S, Y = np.zeros((m, D, W), dtype=dtype), np.zeros((m, D, W), dtype=dtype)
-    for w in range(W):
-        Q, _ = np.linalg.qr(rng.normal(size=(D, D)))
-        A = (Q * np.logspace(0, 3 * rng.uniform(), D)) @ Q.T
-        s = rng.normal(size=(m, D))
-        S[:, :, w], Y[:, :, w] = s, s @ A.T
-    cnt, head = np.arange(W) % (m + 1), (np.arange(W) * 3 + 1) % m
-    return cnt, head, S, Y, rng.normal(size=(D, W)).astype(dtype), np.exp(rng.uniform(-3, 3, D)).astype(dtype)
-
-
 @pytest.mark.parametrize("D,m", [(1, 1), (14, 6), (64, 8), (5, 3)])
 def test_two_loop_is_the_dense_inverse_bfgs(D, m):
     """d = −H·g, H the inverse-BFGS updates of γ·diag(v) by the chain's cnt newest pairs; the float64 restatement is within 1e-10·max|d| of
@@ -87,7 +25,7 @@ def test_two_loop_is_the_dense_inverse_bfgs(D, m):
     and the long-double dense product are the same function: their bar is κ·ε·m·D with κ <= 1e3 — 5e-14 at the largest shape — taken as 1e-12."""
     rng = np.random.default_rng(1000 * D + m)
     W = 23
-    cnt, head, S, Y, g, v = random_history(rng, m, D, W)
+    cnt, head, S, Y, g, v = cases.random_history(rng, m, D, W)
     d64 = ref.direction(cnt, head, S, Y, g, v)
     L = np.longdouble
     dl = ref.direction(cnt, head, S.astype(L), Y.astype(L), g.astype(L), v.astype(L))
@@ -126,10 +64,10 @@ def test_alpha_update_is_the_diagonal_of_the_dense_bfgs_update():
 # ---------------------------------------------------------------------------------------------------- against scipy
 def test_restatement_against_scipy(oracle):
     from scipy.optimize import minimize
-    starts, lp0, v, res = reference_case(oracle)
-    logpost = tight_logpost(oracle, n_threads=1)
+    starts, lp0, v, res = cases.reference_case(oracle)
+    logpost = cases.tight_logpost(oracle, n_threads=1)
     conv = res["status"] == ref.GTOL
-    print(f"restatement: {conv.sum()} of {N_STARTS} chains at gtol {GTOL} within {ROUNDS} rounds; status counts {np.bincount(res['status'], minlength=5)}; "
+    print(f"restatement: {conv.sum()} of {cases.LBFGS_N_STARTS} chains at gtol {cases.LBFGS_GRAD_TOL} within {cases.LBFGS_ROUNDS} rounds; status counts {np.bincount(res['status'], minlength=5)}; "
           f"evals {res['evals'].min()} … {res['evals'].max()}; best ℓπ {res['logpost'].max():.8f}")
     assert conv.mean() >= 0.75
     assert np.all(res["logpost"] >= lp0)
@@ -140,39 +78,39 @@ def test_restatement_against_scipy(oracle):
         return -float(lp[0]), -g[:, 0] * sc
 
     worst, n_cmp, its = 0.0, 0, []
-    for w in range(N_STARTS):
+    for w in range(cases.LBFGS_N_STARTS):
         r = minimize(fun, starts[:, w] / sc, jac=True, method="L-BFGS-B", options=dict(maxiter=5000, maxfun=20000, ftol=1e-15, gtol=1e-7, maxcor=10))
         its.append(r.nit)
         if conv[w] and r.success and np.max(np.abs(r.jac)) <= 1e-5:
             n_cmp += 1
             worst = max(worst, abs(-r.fun - res["logpost"][w]) / max(1.0, abs(r.fun)))
     print(f"scipy L-BFGS-B: {n_cmp} chains compared, ℓπ differs by at most {worst:.3e} (relative); scipy iterations {min(its)} … {max(its)}")
-    assert n_cmp >= 0.75 * N_STARTS and worst <= 1e-8
+    assert n_cmp >= 0.75 * cases.LBFGS_N_STARTS and worst <= 1e-8
 
 
 # ---------------------------------------------------------------------------------------------------- conditions of the GPU tests
-@pytest.mark.parametrize("ftol", SHORT_FTOLS)
+@pytest.mark.parametrize("ftol", cases.LBFGS_SHORT_FTOLS)
 def test_first_rounds_are_decided_for_the_seed(oracle, ftol):
     """tests/test_lbfgs.py compares decisions on chains whose Armijo margin (and, with ftol > 0, the margin of the ftol test) stays above
     1e-6·max(1, |f|) and may leave out at most 5 %."""
-    logpost = tight_logpost(oracle)
-    _, _, v, _ = reference_case(oracle)
-    r = ref.lbfgs(logpost, prior_theta_t(0, SHORT_W), v, m=M, n_rounds=SHORT_ROUNDS, gtol=GTOL, ftol=ftol)
-    close = r["margin"] <= MARGIN
-    print(f"ftol {ftol}: {close.sum()} of {SHORT_W} chains within {MARGIN} of a decision in {SHORT_ROUNDS} rounds; accepted steps {r['iters'].min()} … {r['iters'].max()}; "
+    logpost = cases.tight_logpost(oracle)
+    _, _, v, _ = cases.reference_case(oracle)
+    r = ref.lbfgs(logpost, cases.prior_theta_t(0, cases.LBFGS_SHORT_W), v, m=cases.LBFGS_M, n_rounds=cases.LBFGS_SHORT_ROUNDS, gtol=cases.LBFGS_GRAD_TOL, ftol=ftol)
+    close = r["margin"] <= cases.LBFGS_MARGIN
+    print(f"ftol {ftol}: {close.sum()} of {cases.LBFGS_SHORT_W} chains within {cases.LBFGS_MARGIN} of a decision in {cases.LBFGS_SHORT_ROUNDS} rounds; accepted steps {r['iters'].min()} … {r['iters'].max()}; "
           f"status counts {np.bincount(r['status'], minlength=5)}")
     assert close.mean() <= 0.05 and np.all(r["status"] != ref.DEAD) and r["iters"].max() >= 2 and (r["decisions"] == -1).any()
     n_ftol = np.sum(r["status"] == ref.FTOL)
-    assert (n_ftol == 0) if ftol == 0.0 else (SHORT_W // 4 <= n_ftol <= 3 * SHORT_W // 4)
+    assert (n_ftol == 0) if ftol == 0.0 else (cases.LBFGS_SHORT_W // 4 <= n_ftol <= 3 * cases.LBFGS_SHORT_W // 4)
 
 
 def test_forty_rounds_are_decided_for_most_starts(oracle):
-    """tests/test_lbfgs.py compares the decisions of the full run through DECIDED_ROUNDS rounds on chains whose every decision so far had a
+    """tests/test_lbfgs.py compares the decisions of the full run through cases.LBFGS_DECIDED_ROUNDS rounds on chains whose every decision so far had a
     margin: most of the 64 starts are such chains. (Over the whole run none is: near the optimum f_t − f is rounding noise.)"""
-    starts, _, v, res = reference_case(oracle)
-    r = ref.lbfgs(tight_logpost(oracle), starts, v, m=M, n_rounds=DECIDED_ROUNDS, gtol=GTOL)
-    decided = r["margin"] > MARGIN
-    print(f"{decided.sum()} of {N_STARTS} chains keep an Armijo margin above {MARGIN} through {DECIDED_ROUNDS} rounds; over the whole run {(res['margin'] > MARGIN).sum()}")
+    starts, _, v, res = cases.reference_case(oracle)
+    r = ref.lbfgs(cases.tight_logpost(oracle), starts, v, m=cases.LBFGS_M, n_rounds=cases.LBFGS_DECIDED_ROUNDS, gtol=cases.LBFGS_GRAD_TOL)
+    decided = r["margin"] > cases.LBFGS_MARGIN
+    print(f"{decided.sum()} of {cases.LBFGS_N_STARTS} chains keep an Armijo margin above {cases.LBFGS_MARGIN} through {cases.LBFGS_DECIDED_ROUNDS} rounds; over the whole run {(res['margin'] > cases.LBFGS_MARGIN).sum()}")
     assert decided.mean() >= 0.5 and np.all(r["status"] == ref.ACTIVE)
 
 
@@ -180,44 +118,44 @@ def test_pathfinder_diagonal_is_well_conditioned_for_ten_rounds(oracle):
     """The diagonal is a function of differences of gradients along the path, and the path amplifies a perturbation of ℓπ and ∇ℓπ from round
     to round: with inputs disturbed at INPUT_NOISE (relative), the restatement's own diagonal moves by 1e-9 after 10 rounds, 1e-7 after 20
     and 5e-4 after 40 (decisions unchanged). tests/test_lbfgs.py therefore holds the device's diagonal to 1e-6 after the four rounds of its
-    short run and after MID_ROUNDS rounds of the full run, where the restatement's own response stays a factor 100 below that bar."""
-    logpost = tight_logpost(oracle)
-    starts, _, v, _ = reference_case(oracle)
+    short run and after cases.LBFGS_MID_ROUNDS rounds of the full run, where the restatement's own response stays a factor 100 below that bar."""
+    logpost = cases.tight_logpost(oracle)
+    starts, _, v, _ = cases.reference_case(oracle)
     rng = np.random.default_rng(0)
 
     def disturbed(th):
         lp, g = logpost(th)
         return lp * (1.0 + INPUT_NOISE * rng.uniform(-1, 1, lp.shape)), g * (1.0 + INPUT_NOISE * rng.uniform(-1, 1, g.shape))
 
-    a = ref.lbfgs(logpost, starts, v, m=M, n_rounds=MID_ROUNDS, gtol=GTOL)
-    b = ref.lbfgs(disturbed, starts, v, m=M, n_rounds=MID_ROUNDS, gtol=GTOL)
-    decided = a["margin"] > MARGIN
+    a = ref.lbfgs(logpost, starts, v, m=cases.LBFGS_M, n_rounds=cases.LBFGS_MID_ROUNDS, gtol=cases.LBFGS_GRAD_TOL)
+    b = ref.lbfgs(disturbed, starts, v, m=cases.LBFGS_M, n_rounds=cases.LBFGS_MID_ROUNDS, gtol=cases.LBFGS_GRAD_TOL)
+    decided = a["margin"] > cases.LBFGS_MARGIN
     assert decided.mean() >= 0.5 and np.array_equal(a["decisions"][:, decided], b["decisions"][:, decided])
     moved = np.max(np.abs(b["inv_hess_diag"][:, decided] / a["inv_hess_diag"][:, decided] - 1.0))
-    print(f"after {MID_ROUNDS} rounds with inputs disturbed at {INPUT_NOISE}: {decided.sum()} chains decided, the restatement's diagonal moves by at most {moved:.3e}")
+    print(f"after {cases.LBFGS_MID_ROUNDS} rounds with inputs disturbed at {INPUT_NOISE}: {decided.sum()} chains decided, the restatement's diagonal moves by at most {moved:.3e}")
     assert moved <= 1e-8
 
 
 def test_perturbed_starts_reach_the_same_optimum(oracle):
-    logpost = tight_logpost(oracle)
-    starts, _, v, res = reference_case(oracle)
-    pert = ref.lbfgs(logpost, starts * (1.0 + 1e-9), v, m=M, n_rounds=ROUNDS, gtol=GTOL)
+    logpost = cases.tight_logpost(oracle)
+    starts, _, v, res = cases.reference_case(oracle)
+    pert = ref.lbfgs(logpost, starts * (1.0 + 1e-9), v, m=cases.LBFGS_M, n_rounds=cases.LBFGS_ROUNDS, gtol=cases.LBFGS_GRAD_TOL)
     both = (res["status"] == ref.GTOL) & (pert["status"] == ref.GTOL)
     diff = np.abs(pert["logpost"][both] - res["logpost"][both]) / np.maximum(1.0, np.abs(res["logpost"][both]))
-    print(f"{both.sum()} of {N_STARTS} chains converge in both runs; their ℓπ differ by at most {diff.max():.3e}")
+    print(f"{both.sum()} of {cases.LBFGS_N_STARTS} chains converge in both runs; their ℓπ differ by at most {diff.max():.3e}")
     assert both.mean() >= 0.75 and diff.max() <= 1e-8
 
 
 def test_frozen_chains_and_resume_in_the_restatement(oracle):
     """two segments equal one run, and a converged chain no longer moves"""
-    logpost = tight_logpost(oracle)
-    starts, _, v, _ = reference_case(oracle)
+    logpost = cases.tight_logpost(oracle)
+    starts, _, v, _ = cases.reference_case(oracle)
     x = starts[:, ::4]
-    one = ref.lbfgs(logpost, x, v, m=M, n_rounds=500, gtol=GTOL)
-    half = ref.lbfgs(logpost, x, v, m=M, n_rounds=400, gtol=GTOL)
+    one = ref.lbfgs(logpost, x, v, m=cases.LBFGS_M, n_rounds=500, gtol=cases.LBFGS_GRAD_TOL)
+    half = ref.lbfgs(logpost, x, v, m=cases.LBFGS_M, n_rounds=400, gtol=cases.LBFGS_GRAD_TOL)
     frozen = half["status"] != ref.ACTIVE
     kept = {k: half[k][..., frozen].copy() for k in ("theta_t", "logpost", "inv_hess_diag")}
-    two = ref.lbfgs(logpost, None, v, m=M, n_rounds=100, gtol=GTOL, state=half["state"])
+    two = ref.lbfgs(logpost, None, v, m=cases.LBFGS_M, n_rounds=100, gtol=cases.LBFGS_GRAD_TOL, state=half["state"])
     assert all(np.array_equal(two[k][..., frozen], kept[k]) for k in kept)
     for k in ("theta_t", "logpost", "gnorm", "status", "iters", "evals", "inv_hess_diag"):
         assert np.array_equal(one[k], two[k]), k

@@ -14,34 +14,25 @@ import numpy as np
 import pytest
 
 import adapt_reference as aref
+import draws_cases as cases
 import nuts_reference as nuts
-import test_adapt as ta
-import test_hmc as th
-import test_hmc_reference as cond
-import test_nuts_reference as ncond
+from draws_device import TRANS_BAR, close, draws_mod, hmc_model, host, mirror_priors, padded, same_bits, set_batch_invariant      # noqa: F401
 
 pytestmark = pytest.mark.gpu
 OUTPUTS = ("logpost", "loglike", "log_accept", "accepted", "depth", "n_leapfrog", "diverged")
 
 
 @pytest.fixture(scope="module")
-def draws_mod(pkg):
-    from octofitter_jl_amd.host import draws
-    draws.load_library()
-    return draws
-
-
-@pytest.fixture(scope="module")
 def prior_pd(pkg, draws_mod):
     """a handle without a model on the five priors of the stationarity condition"""
-    h = draws_mod.PriorDraws(priors=th.mirror_priors(pkg, cond.STAT_PRIORS))
+    h = draws_mod.PriorDraws(priors=mirror_priors(pkg, cases.STAT_PRIORS))
     yield h
     h.close()
 
 
 @pytest.fixture(scope="module")
 def model_pd(pkg, draws_mod):
-    model = th.hmc_model(pkg)
+    model = hmc_model(pkg)
     pd = draws_mod.PriorDraws(model)
     yield model, pd
     pd.close()
@@ -51,10 +42,6 @@ def model_pd(pkg, draws_mod):
 def numpy_outputs(tt, out):
     """[θ_t, the seven outputs] as NumPy arrays (None stays None)"""
     return [tt.cpu().numpy()] + [None if out[k] is None else out[k].cpu().numpy() for k in OUTPUTS]
-
-
-def same_bits(x, y):
-    return all((a is None and b is None) or np.array_equal(a, b, equal_nan=True) for a, b in zip(x, y))
 
 
 def columns(x, sel):
@@ -89,15 +76,15 @@ def against_the_restatement(got, r, start, what):
 def test_gpu_one_transition_against_the_restatement(pkg, oracle, model_pd):
     import torch
     model, pd = model_pd
-    th.set_batch_invariant(pkg, model, 0)
-    W, ld = ncond.ONE_W, ncond.ONE_LD
-    beta, eps, im = ncond.one_inputs()
-    start = pd.sample(ncond.ONE_SEED, 0, W, theta=False, logprior_t=False)[1]
-    r = ncond.one_transition(oracle, start.cpu().numpy())
-    ncond.check_one_transition_is_decided(r)                                   # the condition on the seed, before the device runs
-    buf, tt = th.padded(torch, start, ld)
-    out = pd.nuts(tt, beta=torch.as_tensor(beta, device="cuda"), eps=torch.as_tensor(eps, device="cuda"), inv_mass=im, max_depth=ncond.ONE_DEPTH,
-                  n_rounds=(1 << ncond.ONE_DEPTH) - 1, seed=ncond.ONE_SEED, step=ncond.ONE_STEP)
+    set_batch_invariant(pkg, model, 0)
+    W, ld = cases.ONE_W, cases.ONE_LD
+    beta, eps, im = cases.one_inputs()
+    start = pd.sample(cases.ONE_SEED, 0, W, theta=False, logprior_t=False)[1]
+    r = cases.one_transition(oracle, start.cpu().numpy())
+    cases.check_one_transition_is_decided(r)                                   # the condition on the seed, before the device runs
+    buf, tt = padded(torch, start, ld)
+    out = pd.nuts(tt, beta=torch.as_tensor(beta, device="cuda"), eps=torch.as_tensor(eps, device="cuda"), inv_mass=im, max_depth=cases.ONE_DEPTH,
+                  n_rounds=(1 << cases.ONE_DEPTH) - 1, seed=cases.ONE_SEED, step=cases.ONE_STEP)
     torch.cuda.synchronize()
     assert bool(torch.isnan(buf[:, W:]).all())                                  # nothing written beyond column W
     assert int(out["n_active"].item()) == 0
@@ -117,9 +104,9 @@ def test_gpu_tree_shapes(prior_pd):
     for W in (1, 64, 257):
         start = pd.sample(SHAPE_SEED, 0, W, theta=False, logprior_t=False)[1]
         for eps in (SHAPE_EPS_SMALL, SHAPE_EPS_LARGE):
-            r = nuts.nuts_transition(cond.STAT_PRIORS, start.cpu().numpy(), None, eps, cond.STAT_INV_MASS, SHAPE_DEPTH, SHAPE_SEED, 2)
+            r = nuts.nuts_transition(cases.STAT_PRIORS, start.cpu().numpy(), None, eps, cases.STAT_INV_MASS, SHAPE_DEPTH, SHAPE_SEED, 2)
             tt = start.clone()
-            out = pd.nuts(tt, eps=eps, inv_mass=cond.STAT_INV_MASS, max_depth=SHAPE_DEPTH, n_rounds=(1 << SHAPE_DEPTH) - 1, seed=SHAPE_SEED, step=2)
+            out = pd.nuts(tt, eps=eps, inv_mass=cases.STAT_INV_MASS, max_depth=SHAPE_DEPTH, n_rounds=(1 << SHAPE_DEPTH) - 1, seed=SHAPE_SEED, step=2)
             assert out["logpost"] is None and out["loglike"] is None and int(out["n_active"].item()) == 0
             got = numpy_outputs(tt, out)
             against_the_restatement(got, r, start.cpu().numpy(), f"W {W}, ε {eps}")
@@ -136,12 +123,12 @@ def test_gpu_tree_shapes(prior_pd):
 
 
 # ---------------------------------------------------------------------------------------------------- 3. invariance, resume and freezing
-def run_rounds(torch, pd, start, beta, eps, im, cuts, chain0=0, ld=None, max_depth=ncond.ONE_DEPTH, snapshots=None):
-    """the transition of ncond's seed cut into calls of `cuts` rounds: [θ_t, outputs] at the end; snapshots: the same after every call"""
+def run_rounds(torch, pd, start, beta, eps, im, cuts, chain0=0, ld=None, max_depth=cases.ONE_DEPTH, snapshots=None):
+    """the transition of cases.ONE_SEED cut into calls of `cuts` rounds: [θ_t, outputs] at the end; snapshots: the same after every call"""
     W = start.shape[1]
-    _buf, tt = th.padded(torch, start, ld or W)
-    args = dict(beta=torch.as_tensor(beta, device="cuda"), eps=torch.as_tensor(eps, device="cuda"), inv_mass=im, max_depth=max_depth, seed=ncond.ONE_SEED,
-                step=ncond.ONE_STEP, chain0=chain0)
+    _buf, tt = padded(torch, start, ld or W)
+    args = dict(beta=torch.as_tensor(beta, device="cuda"), eps=torch.as_tensor(eps, device="cuda"), inv_mass=im, max_depth=max_depth, seed=cases.ONE_SEED,
+                step=cases.ONE_STEP, chain0=chain0)
     out = None
     for k, n in enumerate(cuts):
         out = pd.nuts(tt, n_rounds=n, resume=k > 0, out=out, **args)
@@ -153,16 +140,16 @@ def run_rounds(torch, pd, start, beta, eps, im, cuts, chain0=0, ld=None, max_dep
 def test_gpu_invariance_resume_and_freezing(pkg, model_pd):
     import torch
     model, pd = model_pd
-    W, total = ncond.ONE_W, (1 << ncond.ONE_DEPTH) - 1
-    beta, eps, im = ncond.one_inputs()
-    start = pd.sample(ncond.ONE_SEED, 0, W, theta=False, logprior_t=False)[1]
+    W, total = cases.ONE_W, (1 << cases.ONE_DEPTH) - 1
+    beta, eps, im = cases.one_inputs()
+    start = pd.sample(cases.ONE_SEED, 0, W, theta=False, logprior_t=False)[1]
     dead = 7
     start[3, dead] = float("nan")                                                # a dead start among the others
-    th.set_batch_invariant(pkg, model, 1)
+    set_batch_invariant(pkg, model, 1)
     try:
         full = run_rounds(torch, pd, start, beta, eps, im, (total,))
         assert same_bits(full, run_rounds(torch, pd, start, beta, eps, im, (total,)))
-        assert same_bits(full, run_rounds(torch, pd, start, beta, eps, im, (total,), ld=ncond.ONE_LD))       # another leading dimension
+        assert same_bits(full, run_rounds(torch, pd, start, beta, eps, im, (total,), ld=cases.ONE_LD))       # another leading dimension
         part = run_rounds(torch, pd, start[:, 20:41].contiguous(), beta[20:41], eps[20:41], im, (total,), chain0=20)      # chains 20 … 40 alone
         assert same_bits(columns(full, slice(20, 41)), part)
         snaps = []
@@ -186,28 +173,28 @@ def test_gpu_invariance_resume_and_freezing(pkg, model_pd):
         others = np.arange(W) != dead
         assert same_bits(columns(full, others), columns(run_rounds(torch, pd, clean, beta, eps, im, (total,)), others))
     finally:
-        th.set_batch_invariant(pkg, model, 0)
+        set_batch_invariant(pkg, model, 0)
 
 
 # ---------------------------------------------------------------------------------------------------- 4. nuts_step and the warm-up
 def test_gpu_nuts_step_reads_the_count_or_runs_every_round(pkg, model_pd):
     import torch
     model, pd = model_pd
-    beta, eps, im = ncond.one_inputs()
-    start = pd.sample(ncond.ONE_SEED, 0, ncond.ONE_W, theta=False, logprior_t=False)[1]
-    th.set_batch_invariant(pkg, model, 1)
+    beta, eps, im = cases.one_inputs()
+    start = pd.sample(cases.ONE_SEED, 0, cases.ONE_W, theta=False, logprior_t=False)[1]
+    set_batch_invariant(pkg, model, 1)
     try:
         runs = []
         for check_from in (3, None, 0):
             tt = start.clone()
-            res = pd.nuts_step(tt, beta=torch.as_tensor(beta, device="cuda"), eps=torch.as_tensor(eps, device="cuda"), inv_mass=im, max_depth=6, seed=ncond.ONE_SEED,
-                               step=ncond.ONE_STEP, check_from=check_from)
+            res = pd.nuts_step(tt, beta=torch.as_tensor(beta, device="cuda"), eps=torch.as_tensor(eps, device="cuda"), inv_mass=im, max_depth=6, seed=cases.ONE_SEED,
+                               step=cases.ONE_STEP, check_from=check_from)
             assert len(res) == 7
             runs.append([tt.cpu().numpy()] + [x.cpu().numpy() for x in res])
         assert same_bits(runs[0], runs[1]) and same_bits(runs[0], runs[2])
         assert runs[0][6].max() > 7      # a tree beyond the first check
     finally:
-        th.set_batch_invariant(pkg, model, 0)
+        set_batch_invariant(pkg, model, 0)
 
 
 WARM_W, WARM_ROUNDS, WARM_DEPTH, WARM_EPS, WARM_SEED = 192, 30, 4, 0.2, 77
@@ -231,16 +218,16 @@ def test_gpu_warmup_with_nuts_teacher_forced(pkg, prior_pd):
         la = rec["dH"].cpu().numpy()
         assert np.all(la[~np.isnan(la)] <= 0.0)                                 # the log of a mean of min(1, ·)
         state, a = aref.adapt_step(rec["state_in"].cpu().numpy(), la, rec["accepted"].cpu().numpy(), k)
-        assert ta.close(rec["state"].cpu().numpy(), state, ta.TRANS_BAR) and ta.close(rec["accept_stat"].cpu().numpy(), a, ta.TRANS_BAR), r
-        assert ta.close(rec["eps_w"].cpu().numpy(), np.full(WARM_W, math.exp(state[0, 1 if rec["use_average"] else 0])), ta.TRANS_BAR), r
-        assert ta.close(out["accept_stat"][r].cpu().numpy(), a[0], ta.TRANS_BAR)
+        assert close(rec["state"].cpu().numpy(), state, TRANS_BAR) and close(rec["accept_stat"].cpu().numpy(), a, TRANS_BAR), r
+        assert close(rec["eps_w"].cpu().numpy(), np.full(WARM_W, math.exp(state[0, 1 if rec["use_average"] else 0])), TRANS_BAR), r
+        assert close(out["accept_stat"][r].cpu().numpy(), a[0], TRANS_BAR)
         if rec["in_window"] and rec["first"]:
-            ta.acond.check_moments(ta.host(rec["mom"]), aref.exact_moments(rec["theta_t"].cpu().numpy()), ("round", r))
+            cases.check_moments(host(rec["mom"]), aref.exact_moments(rec["theta_t"].cpu().numpy()), ("round", r))
         if rec["last"]:
             windows += 1
-            hm = ta.host(rec["mom"])
-            assert ta.close(rec["inv_mass"].cpu().numpy(), aref.metric(hm[0][0], hm[2][0], rec["inv_mass_in"].cpu().numpy(), regularize=True), 1e-14, scale_one=False)
-            assert ta.close(rec["state_restart"].cpu().numpy(), aref.adapt_init(np.exp(rec["state"].cpu().numpy()[:, 1])), ta.TRANS_BAR)
+            hm = host(rec["mom"])
+            assert close(rec["inv_mass"].cpu().numpy(), aref.metric(hm[0][0], hm[2][0], rec["inv_mass_in"].cpu().numpy(), regularize=True), 1e-14, scale_one=False)
+            assert close(rec["state_restart"].cpu().numpy(), aref.adapt_init(np.exp(rec["state"].cpu().numpy()[:, 1])), TRANS_BAR)
             k = 0
     tree = out["tree"].cpu().numpy()
     print(f"warm-up with NUTS: ε {WARM_EPS} -> {float(out['eps'][0]):.4f}; mean depth {tree[:, 0].mean():.2f}, mean leaves {tree[:, 1].mean():.2f}, divergences {int(tree[:, 2].sum())}")
@@ -248,20 +235,20 @@ def test_gpu_warmup_with_nuts_teacher_forced(pkg, prior_pd):
 
 
 # ---------------------------------------------------------------------------------------------------- 5. stationarity on the device
-@pytest.mark.parametrize("seed", cond.STAT_SEEDS)
+@pytest.mark.parametrize("seed", cases.STAT_SEEDS)
 def test_gpu_prior_is_stationary(prior_pd, seed):
     pd = prior_pd
-    eps = ncond.NUTS_STAT_EPS[0]
-    tt = pd.sample(seed, 0, cond.STAT_W, theta=False, logprior_t=False)[1]
+    eps = cases.NUTS_STAT_EPS[0]
+    tt = pd.sample(seed, 0, cases.STAT_W, theta=False, logprior_t=False)[1]
     start = tt.clone()
     leaves = []
-    for step in range(cond.STAT_STEPS):
-        _lp, _ll, _la, _acc, _depth, nleaf, _div = pd.nuts_step(tt, eps=eps, inv_mass=cond.STAT_INV_MASS, max_depth=ncond.NUTS_STAT_DEPTH, seed=seed, step=step)
+    for step in range(cases.STAT_STEPS):
+        _lp, _ll, _la, _acc, _depth, nleaf, _div = pd.nuts_step(tt, eps=eps, inv_mass=cases.STAT_INV_MASS, max_depth=cases.NUTS_STAT_DEPTH, seed=seed, step=step)
         leaves.append(float(nleaf.double().mean()))
     moved = float((tt != start).any(dim=0).double().mean())
-    stat = cond.stationarity_statistics(tt.cpu().numpy())
-    print(f"seed {seed} (ε {eps}, depth <= {ncond.NUTS_STAT_DEPTH}): mean leaves {np.mean(leaves):.2f}, moved {moved:.3f}, max D_n {stat:.3e} (bar {cond.STAT_BAR:.3e})")
-    assert stat < cond.STAT_BAR and moved >= 0.9, (seed, stat, moved)
+    stat = cases.stationarity_statistics(tt.cpu().numpy())
+    print(f"seed {seed} (ε {eps}, depth <= {cases.NUTS_STAT_DEPTH}): mean leaves {np.mean(leaves):.2f}, moved {moved:.3f}, max D_n {stat:.3e} (bar {cases.STAT_BAR:.3e})")
+    assert stat < cases.STAT_BAR and moved >= 0.9, (seed, stat, moved)
 
 
 # ---------------------------------------------------------------------------------------------------- 6. the driver and the arguments

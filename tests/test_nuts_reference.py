@@ -12,9 +12,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import draws_cases as cases
 import hmc_reference as ref
 import nuts_reference as nuts
-import test_hmc_reference as cond
 
 MARGIN = nuts.MARGIN
 
@@ -62,11 +62,11 @@ BRUTE_SETTINGS = ((0.5, 5), (0.25, 3), (1.6, 4))      # (ε, max_depth): mostly 
 
 
 def test_stopping_rule_against_brute_force():
-    _, tt = ref.prior_sample(cond.STAT_PRIORS, 5, np.arange(BRUTE_W, dtype=np.uint64))
+    _, tt = ref.prior_sample(cases.STAT_PRIORS, 5, np.arange(BRUTE_W, dtype=np.uint64))
     reasons = set()
     for eps, max_depth in BRUTE_SETTINGS:
-        r = nuts.nuts_transition(cond.STAT_PRIORS, tt, None, eps, cond.STAT_INV_MASS, max_depth, 5, 0)
-        b = nuts.nuts_brute_force(cond.STAT_PRIORS, tt, None, eps, cond.STAT_INV_MASS, max_depth, 5, 0)
+        r = nuts.nuts_transition(cases.STAT_PRIORS, tt, None, eps, cases.STAT_INV_MASS, max_depth, 5, 0)
+        b = nuts.nuts_brute_force(cases.STAT_PRIORS, tt, None, eps, cases.STAT_INV_MASS, max_depth, 5, 0)
         decided = r["margin"] > MARGIN
         print(f"ε {eps}, depth <= {max_depth}: {np.sum(~decided)} of {BRUTE_W} chains undecided; stop reasons {np.bincount(r['stop'], minlength=6)[1:]}; "
               f"mean leaves {r['n_leapfrog'].mean():.2f}, rounds {r['rounds']}")
@@ -84,11 +84,11 @@ def test_stopping_rule_against_brute_force():
 
 
 def test_a_dead_start_ends_at_once():
-    _, tt = ref.prior_sample(cond.STAT_PRIORS, 5, np.arange(8, dtype=np.uint64))
+    _, tt = ref.prior_sample(cases.STAT_PRIORS, 5, np.arange(8, dtype=np.uint64))
     tt[2, 3] = np.nan
     tt[0, 5] = np.inf
-    r = nuts.nuts_transition(cond.STAT_PRIORS, tt, None, 0.5, cond.STAT_INV_MASS, 3, 5, 0)
-    clean = nuts.nuts_transition(cond.STAT_PRIORS, np.delete(tt, (3, 5), axis=1)[:, :3], None, 0.5, cond.STAT_INV_MASS, 3, 5, 0)
+    r = nuts.nuts_transition(cases.STAT_PRIORS, tt, None, 0.5, cases.STAT_INV_MASS, 3, 5, 0)
+    clean = nuts.nuts_transition(cases.STAT_PRIORS, np.delete(tt, (3, 5), axis=1)[:, :3], None, 0.5, cases.STAT_INV_MASS, 3, 5, 0)
     for c in (3, 5):
         assert r["stop"][c] == nuts.STOP_DEAD and r["n_leapfrog"][c] == 0 and not r["accepted"][c] and np.isnan(r["log_accept"][c])
         assert np.array_equal(r["theta_t"][:, c], tt[:, c], equal_nan=True)
@@ -96,83 +96,55 @@ def test_a_dead_start_ends_at_once():
 
 
 # ---------------------------------------------------------------------------------------------------- β = 0: the prior is stationary
-NUTS_STAT_EPS = (0.5, 0.8)
-NUTS_STAT_DEPTH = 5
 NUTS_WRONG = ("uniform_leaf", 0.8)      # the wrong sampler and the ε it is run at: a subtree's proposal picked with equal weights
 
 
 def run_stationarity(seed, eps, variant=None):
-    _, tt = ref.prior_sample(cond.STAT_PRIORS, seed, np.arange(cond.STAT_W, dtype=np.uint64))
+    _, tt = ref.prior_sample(cases.STAT_PRIORS, seed, np.arange(cases.STAT_W, dtype=np.uint64))
     leaves, used = [], []
-    for step in range(cond.STAT_STEPS):
-        r = nuts.nuts_transition(cond.STAT_PRIORS, tt, None, eps, cond.STAT_INV_MASS, NUTS_STAT_DEPTH, seed, step, variant=variant)
+    for step in range(cases.STAT_STEPS):
+        r = nuts.nuts_transition(cases.STAT_PRIORS, tt, None, eps, cases.STAT_INV_MASS, cases.NUTS_STAT_DEPTH, seed, step, variant=variant)
         tt = r["theta_t"]
         leaves.append(r["n_leapfrog"].mean())
-        used.append(r["n_leapfrog"].sum() / (cond.STAT_W * r["rounds"]))
-    return cond.stationarity_statistics(tt), float(np.mean(leaves)), float(np.mean(used))
+        used.append(r["n_leapfrog"].sum() / (cases.STAT_W * r["rounds"]))
+    return cases.stationarity_statistics(tt), float(np.mean(leaves)), float(np.mean(used))
 
 
-@pytest.mark.parametrize("seed", cond.STAT_SEEDS)
+@pytest.mark.parametrize("seed", cases.STAT_SEEDS)
 def test_prior_is_stationary_and_a_wrong_sampler_is_not(seed):
-    for eps in NUTS_STAT_EPS:
+    for eps in cases.NUTS_STAT_EPS:
         stat, leaves, used = run_stationarity(seed, eps)
-        print(f"seed {seed} (ε {eps}): correct       max D_n {stat:.3e} (bar {cond.STAT_BAR:.3e}); mean leaves {leaves:.2f}, lockstep utilisation {used:.3f}")
-        assert stat < cond.STAT_BAR, (seed, eps, stat)
+        print(f"seed {seed} (ε {eps}): correct       max D_n {stat:.3e} (bar {cases.STAT_BAR:.3e}); mean leaves {leaves:.2f}, lockstep utilisation {used:.3f}")
+        assert stat < cases.STAT_BAR, (seed, eps, stat)
     variant, eps = NUTS_WRONG
     bad, leaves, _ = run_stationarity(seed, eps, variant)
     print(f"seed {seed} (ε {eps}): {variant}  max D_n {bad:.3e}; mean leaves {leaves:.2f}")
-    assert bad > cond.STAT_BAR, (seed, bad)
+    assert bad > cases.STAT_BAR, (seed, bad)
 
 
 # ---------------------------------------------------------------------------------------------------- β = 1: the posterior is stationary
 POST_DEPTH = 4
 
 
-@pytest.mark.parametrize("seed", cond.POST_SEEDS)
+@pytest.mark.parametrize("seed", cases.POST_SEEDS)
 def test_posterior_is_stationary(oracle, seed):
-    om = cond.oracle_model(oracle)
-    a, b = (cond.rejection_batch(oracle, om, seed, first) for first in cond.POST_FIRST)
-    im = cond.posterior_inv_mass(b)
-    logpost = cond.oracle_logpost(oracle, om)
+    om = cases.oracle_model(oracle)
+    a, b = (cases.rejection_batch(oracle, om, seed, first) for first in cases.POST_FIRST)
+    im = cases.posterior_inv_mass(b)
+    logpost = cases.oracle_logpost(oracle, om)
 
     def step_fn(tt, step):
-        r = nuts.nuts_transition(cond.MODEL_PRIORS, tt, None, cond.POST_EPS, im, POST_DEPTH, seed, step, logpost=logpost)
+        r = nuts.nuts_transition(cases.MODEL_PRIORS, tt, None, cases.POST_EPS, im, POST_DEPTH, seed, step, logpost=logpost)
         return r["theta_t"], r["accepted"]
 
-    cond.check_posterior_stationary(a, b, step_fn, f"seed {seed} (CPU, NUTS)")
+    cases.check_posterior_stationary(a, b, step_fn, f"seed {seed} (CPU, NUTS)")
 
 
 # ---------------------------------------------------------------------------------------------------- one transition: the condition on its seed
-ONE_W, ONE_LD, ONE_SEED, ONE_STEP, ONE_DEPTH = 65, 72, 41, 5, 4      # a partial second wave, a padded leading dimension
-ONE_BETAS = (0.0, 0.3, 1.0)
-ONE_UNDECIDED = 0.05
-
-
-def one_inputs(W=ONE_W):
-    """(β, ε, inv_mass) of the one-transition comparison of tests/test_nuts.py: β cycles through ONE_BETAS, ε (on the scale of
-    test_hmc_reference.step_inputs) differs from chain to chain."""
-    beta = np.array([ONE_BETAS[w % 3] for w in range(W)])
-    _, eps, im = cond.step_inputs(W)
-    return beta, eps, im
-
-
-def one_transition(oracle, start):
-    beta, eps, im = one_inputs(start.shape[1])
-    return nuts.nuts_transition(cond.MODEL_PRIORS, start, beta, eps, im, ONE_DEPTH, ONE_SEED, ONE_STEP, logpost=cond.oracle_logpost(oracle, cond.oracle_model(oracle)))
-
-
-def check_one_transition_is_decided(r):
-    undecided = r["margin"] <= MARGIN
-    print(f"one transition: {undecided.sum()} of {undecided.size} chains undecided; stop reasons {np.bincount(r['stop'], minlength=6)[1:]}; "
-          f"mean leaves {r['n_leapfrog'].mean():.2f}; moved {r['accepted'].mean():.3f}")
-    assert undecided.mean() <= ONE_UNDECIDED, "condition on the seed (the reference alone)"
-    assert np.all(np.isfinite(r["theta_t"])) and r["accepted"].mean() > 0.5 and len(set(r["depth"])) >= 2
-
-
 def test_one_transition_is_decided_for_the_seed(oracle):
     """at the restated prior draws; the device's differ in the last bits"""
-    _, start = ref.prior_sample(cond.MODEL_PRIORS, ONE_SEED, np.arange(ONE_W, dtype=np.uint64))
-    check_one_transition_is_decided(one_transition(oracle, start))
+    _, start = ref.prior_sample(cases.MODEL_PRIORS, cases.ONE_SEED, np.arange(cases.ONE_W, dtype=np.uint64))
+    cases.check_one_transition_is_decided(cases.one_transition(oracle, start))
 
 
 # ---------------------------------------------------------------------------------------------------- argument checks without a device

@@ -14,39 +14,23 @@ import math
 import numpy as np
 import pytest
 
+import draws_cases as cases
 import lbfgs_reference as lref
 import pathfinder_reference as ref
-import test_lbfgs_reference as lcond
-import test_pathfinder_reference as cond
-from test_lbfgs import padded, rel, set_batch_invariant, tight_model
+from draws_device import differing, draws_mod, host_outputs, padded, rel, set_batch_invariant, tight_model      # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-SEED, CHAIN0, K, M, GTOL = cond.SEED, cond.CHAIN0, cond.N_ELBO, lcond.M, lcond.GTOL
+SEED, CHAIN0, K, M, GTOL = cases.PF_SEED, cases.PF_CHAIN0, cases.PF_N_ELBO, cases.LBFGS_M, cases.LBFGS_GRAD_TOL
 LB_KEYS = ("logpost", "gnorm", "status", "iters", "evals", "inv_hess_diag")
 PF_KEYS = LB_KEYS + ("elbo", "elbo_iter", "n_fits")
 N_FINAL = 4
 
 
-@pytest.fixture(scope="module")
-def draws_mod(pkg):
-    from octofitter_jl_amd.host import draws
-    draws.load_library()
-    return draws
-
-
-def host(r, tt):
-    return dict(theta_t=tt.cpu().numpy(), **{k: v.cpu().numpy() for k, v in r.items() if v is not None})
-
-
-def differing(a, b, keys, cols=slice(None)):
-    return [k for k in keys if not np.array_equal(a[k][..., cols], b[k][..., cols], equal_nan=True)]
-
-
 def run(torch, pd, x, v, n_rounds, ld=None, chain0=CHAIN0, n_elbo=K, n_final=0, **kw):
     """pathfinder from x (padded to ld) and, with n_final, the final draws: everything on the host, and the device θ_t"""
     _buf, tt = padded(torch, x, ld or x.shape[1])
-    out = host(pd.pathfinder(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=n_rounds, want_inv_hess_diag=True, seed=SEED, chain0=chain0, n_elbo=n_elbo, **kw), tt)
+    out = host_outputs(pd.pathfinder(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=n_rounds, want_inv_hess_diag=True, seed=SEED, chain0=chain0, n_elbo=n_elbo, **kw), tt)
     if n_final:
         phi, logq, lp = pd.pathfinder_draw(tt, n_final, seed=SEED, chain0=chain0)
         W = x.shape[1]
@@ -64,27 +48,27 @@ def case(pkg, oracle, draws_mod):
     import torch
     model = tight_model(pkg)
     pd = draws_mod.PriorDraws(model)
-    v = pd.sample(lcond.SEED, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1).cpu().numpy()
-    θ0, lp0, _ = pd.best(lcond.SEED, lcond.N_DRAWS, keep=lcond.N_STARTS)
+    v = pd.sample(cases.LBFGS_SEED, 0, 4096, theta=False, logprior_t=False)[1].var(dim=1).cpu().numpy()
+    θ0, lp0, _ = pd.best(cases.LBFGS_SEED, cases.LBFGS_N_DRAWS, keep=cases.LBFGS_N_STARTS)
     starts = np.ascontiguousarray(model.link(θ0))
-    logpost = lcond.tight_logpost(oracle)
-    got, _ = run(torch, pd, starts, v, cond.ROUNDS, n_final=N_FINAL)
+    logpost = cases.tight_logpost(oracle)
+    got, _ = run(torch, pd, starts, v, cases.PF_ROUNDS, n_final=N_FINAL)
     tt = torch.as_tensor(starts, device="cuda").clone()
-    plain = host(pd.lbfgs(tt, inv_mass=v, m=M, n_rounds=cond.ROUNDS, gtol=GTOL, want_inv_hess_diag=True), tt)
-    r = ref.pathfinder(logpost, starts, v, m=M, n_rounds=cond.ROUNDS, gtol=GTOL, seed=SEED, chain0=CHAIN0, n_elbo=K)
-    decided = cond.decided_chains(r) & (r["margin"] > lcond.MARGIN)
+    plain = host_outputs(pd.lbfgs(tt, inv_mass=v, m=M, n_rounds=cases.PF_ROUNDS, gtol=GTOL, want_inv_hess_diag=True), tt)
+    r = ref.pathfinder(logpost, starts, v, m=M, n_rounds=cases.PF_ROUNDS, gtol=GTOL, seed=SEED, chain0=CHAIN0, n_elbo=K)
+    decided = cases.decided_chains(r) & (r["margin"] > cases.LBFGS_MARGIN)
     yield dict(model=model, pd=pd, v=v, starts=starts, lp0=lp0, logpost=logpost, got=got, plain=plain, ref=r, decided=decided)
     pd.close()
     model.close()
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the fit
-@pytest.mark.parametrize("D,m", cond.FIT_SHAPES)
+@pytest.mark.parametrize("D,m", cases.PF_FIT_SHAPES)
 def test_gpu_fit_against_the_restatement(pkg, draws_mod, D, m):
     import torch
-    W, LD, n = cond.FIT_W, cond.FIT_LD, 3
+    W, LD, n = cases.PF_FIT_W, cases.PF_FIT_LD, 3
     pd = draws_mod.PriorDraws(priors=[pkg.Uniform(0, 1)] * D)
-    cnt, head, S, Y, x, g, alpha = cond.fit_inputs(D, m)
+    cnt, head, S, Y, x, g, alpha = cases.fit_inputs(D, m)
     z = np.random.default_rng(D + m).normal(size=(n, D, W))
     bad = int(np.nonzero(cnt >= 1)[0][1 if D > 1 else 0])      # one chain whose NEWEST pair gets sᵀy < 0: H̃ỹ = s̃ then has ỹᵀH̃ỹ < 0
     Yb = Y.copy()
@@ -112,7 +96,7 @@ def test_gpu_fit_against_the_restatement(pkg, draws_mod, D, m):
 # ---------------------------------------------------------------------------------------------------- 2. ten rounds
 def test_gpu_ten_rounds_against_the_restatement(case):
     got, r, decided = case["got"], case["ref"], case["decided"]
-    n = lcond.N_STARTS
+    n = cases.LBFGS_N_STARTS
     left = np.nonzero(~decided)[0]
     print(f"{decided.sum()} of {n} chains decided; left out: {left.tolist()} (ELBO gap {r['margin_elbo'][left]}, Armijo margin {r['margin'][left]})")
     assert decided.sum() >= 7 * n // 8, "condition on the starts (the reference alone)"
@@ -129,7 +113,7 @@ def test_gpu_ten_rounds_against_the_restatement(case):
 # ---------------------------------------------------------------------------------------------------- 3. the final draws
 def test_gpu_draws_from_the_kept_fit(case):
     got, r, decided = case["got"], case["ref"], case["decided"]
-    W = lcond.N_STARTS
+    W = cases.LBFGS_N_STARTS
     phi, logq, _ = ref.pathfinder_draw(lambda th: (np.zeros(th.shape[1]), None), r["state"], SEED, CHAIN0, N_FINAL)
     phi, logq = phi.reshape(-1, N_FINAL, W), logq.reshape(N_FINAL, W)
     e_phi, e_q = np.max(rel(got["phi"][:, :, decided], phi[:, :, decided])), np.max(rel(got["logq"][:, decided], logq[:, decided]))
@@ -161,9 +145,9 @@ def test_gpu_batch_invariance_resume_and_n_elbo(pkg, case):
         assert differing(shifted, moved, ("theta_t",) + LB_KEYS) == [] and not np.array_equal(shifted["elbo"], moved["elbo"])
         # a + b rounds in two calls
         _, tt = run(torch, pd, start, v, 3, ld=32)
-        two = host(pd.pathfinder(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=5, resume=True, want_inv_hess_diag=True, seed=SEED, chain0=CHAIN0, n_elbo=K), tt)
+        two = host_outputs(pd.pathfinder(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=5, resume=True, want_inv_hess_diag=True, seed=SEED, chain0=CHAIN0, n_elbo=K), tt)
         assert differing(whole, two, ("theta_t",) + PF_KEYS) == []
-        same = host(pd.pathfinder(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=0, resume=True, want_inv_hess_diag=True, seed=SEED, chain0=CHAIN0, n_elbo=K), tt)
+        same = host_outputs(pd.pathfinder(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=0, resume=True, want_inv_hess_diag=True, seed=SEED, chain0=CHAIN0, n_elbo=K), tt)
         assert differing(two, same, ("theta_t",) + PF_KEYS) == []      # no round: the outputs alone
         phi, logq, lp = pd.pathfinder_draw(tt, 3, seed=SEED, chain0=CHAIN0)
         assert np.array_equal(phi.cpu().numpy().reshape(-1, 3, 24), whole["phi"]) and np.array_equal(logq.cpu().numpy().reshape(3, 24), whole["logq"])
@@ -184,7 +168,7 @@ def test_gpu_frozen_and_dead_chains(case):
     mid, tt = run(torch, pd, starts, v, 400, n_final=2)
     frozen = mid["status"] != lref.ACTIVE
     assert frozen.any(), np.bincount(mid["status"], minlength=5)
-    more = host(pd.pathfinder(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=10, resume=True, want_inv_hess_diag=True, seed=SEED, chain0=CHAIN0, n_elbo=K), tt)
+    more = host_outputs(pd.pathfinder(tt, inv_mass=v, m=M, gtol=GTOL, n_rounds=10, resume=True, want_inv_hess_diag=True, seed=SEED, chain0=CHAIN0, n_elbo=K), tt)
     assert differing({k: x[..., frozen] for k, x in mid.items()}, {k: x[..., frozen] for k, x in more.items()}, ("theta_t",) + PF_KEYS) == []
     assert np.all(more["n_fits"] >= mid["n_fits"]) and np.all(mid["elbo_iter"][frozen] >= 1)
     dirty = starts[:, :16].copy()
@@ -274,9 +258,9 @@ def test_gpu_pathfinder_argument_checks(pkg, draws_mod, case):
 def test_gpu_pathfinder_device(pkg, case):
     import psis_reference as pr
     model = case["model"]
-    kw = dict(N=lcond.N_DRAWS, n_paths=lcond.N_STARTS, seed=lcond.SEED)      # n_draws = 1000 of 256 a path
+    kw = dict(N=cases.LBFGS_N_DRAWS, n_paths=cases.LBFGS_N_STARTS, seed=cases.LBFGS_SEED)      # n_draws = 1000 of 256 a path
     out = pkg.pathfinder_device(model, **kw)
-    D, n, P = model.D, 1000, lcond.N_STARTS
+    D, n, P = model.D, 1000, cases.LBFGS_N_STARTS
     assert out["theta"].shape == out["theta_t"].shape == (D, n) and out["logpost"].shape == out["path"].shape == (n,) and out["names"] == list(model.names)
     assert all(out[k].shape == (P,) for k in ("elbo", "elbo_iter", "n_fits", "status", "iters", "evals", "gnorm", "start_logpost", "path_logpost"))
     assert out["inv_hess_diag"].shape == out["path_theta_t"].shape == (D, P) and out["log_ratios"].shape == out["log_weights"].shape == (256 * P,)

@@ -10,36 +10,22 @@ import math
 import numpy as np
 import pytest
 
+import draws_cases as cases
 import lbfgs_reference as lref
 import pathfinder_reference as ref
-import test_lbfgs_reference as lcond
-
-SEED, CHAIN0, N_ELBO = lcond.SEED, 1000, 5
-ROUNDS = 10                    # the rounds of the GPU comparison on the tight model
-MARGIN = 1e-6                  # a chain is decided if its two best ELBOs differ by more than MARGIN·max(1, |ELBO|)
-FIT_SHAPES = [(1, 1), (5, 3), (14, 6), (64, 8)]      # (D, m): the smallest, 2·cnt > D, the test model's, the top of D
-FIT_W, FIT_LD = 23, 32
-
-
-def fit_inputs(D, m, W=FIT_W):
-    """random_history of tests/test_lbfgs_reference.py (cnt over 0 … m, wrapped heads) with an α per chain and a point x"""
-    rng = np.random.default_rng(7000 * D + m)
-    cnt, head, S, Y, g, _ = lcond.random_history(rng, m, D, W)
-    alpha = np.exp(rng.uniform(-3, 3, (D, W)))
-    return cnt, head, S, Y, rng.normal(size=(D, W)), g, alpha
 
 
 # ---------------------------------------------------------------------------------------------------- what the fit means
-@pytest.mark.parametrize("D,m", FIT_SHAPES)
+@pytest.mark.parametrize("D,m", cases.PF_FIT_SHAPES)
 def test_sigma_is_the_dense_inverse_bfgs_and_the_compact_form(D, m):
     """Σ of the restatement is lbfgs_reference.dense_inverse_bfgs(pairs, α, 1) and the paper's diag(α) + [αY, S]·γ·[αY, S]ᵀ: in long double
     to 1e-12 of max|Σ| (the bar and the reasoning of test_two_loop_is_the_dense_inverse_bfgs: κ·ε·m·D with κ <= 1e3 is 5e-14 at the largest
     shape), and the float64 restatement is within 1e-10 of the long-double one, so the GPU bar of 1e-8 does not hide the reference's noise."""
-    cnt, head, S, Y, x, g, alpha = fit_inputs(D, m)
+    cnt, head, S, Y, x, g, alpha = cases.fit_inputs(D, m)
     Lg = np.longdouble
     assert (cnt == 0).any() and (cnt == m).any() and ((D, m) != (5, 3) or 2 * cnt.max() > D)
     worst = dict(dense=0.0, compact=0.0, f64=0.0)
-    for w in range(FIT_W):
+    for w in range(cases.PF_FIT_W):
         pl = ref.pairs_of(cnt[w], head[w], S.astype(Lg), Y.astype(Lg), w)
         fl = ref.fit_chain(pl, x[:, w].astype(Lg), g[:, w].astype(Lg), alpha[:, w].astype(Lg))
         f64 = ref.fit_chain(ref.pairs_of(cnt[w], head[w], S, Y, w), x[:, w], g[:, w], alpha[:, w])
@@ -55,13 +41,13 @@ def test_sigma_is_the_dense_inverse_bfgs_and_the_compact_form(D, m):
     assert worst["dense"] <= 1e-12 and worst["compact"] <= 1e-12 and worst["f64"] <= 1e-10
 
 
-@pytest.mark.parametrize("D,m", FIT_SHAPES)
+@pytest.mark.parametrize("D,m", cases.PF_FIT_SHAPES)
 def test_square_root_mean_and_logdet(D, m):
     """T = diag(√α)·L̃ is a square root of Σ, μ = x − Σ·g, logdet is numpy's slogdet of Σ: float64 against float64 at 1e-10 of the scale,
     the bar the float64 restatement keeps against long double above."""
-    cnt, head, S, Y, x, g, alpha = fit_inputs(D, m)
+    cnt, head, S, Y, x, g, alpha = cases.fit_inputs(D, m)
     worst = dict(tt=0.0, mu=0.0, logdet=0.0)
-    for w in range(FIT_W):
+    for w in range(cases.PF_FIT_W):
         f = ref.fit_chain(ref.pairs_of(cnt[w], head[w], S, Y, w), x[:, w], g[:, w], alpha[:, w])
         sg = ref.sigma(f)
         T = f["sqa"][:, None] * f["L"]
@@ -80,11 +66,11 @@ def test_square_root_mean_and_logdet(D, m):
 def test_log_q_against_scipy():
     from scipy.stats import multivariate_normal
     D, m = 5, 3
-    cnt, head, S, Y, x, g, alpha = fit_inputs(D, m)
+    cnt, head, S, Y, x, g, alpha = cases.fit_inputs(D, m)
     worst = 0.0
-    for w in range(FIT_W):
+    for w in range(cases.PF_FIT_W):
         f = ref.fit_chain(ref.pairs_of(cnt[w], head[w], S, Y, w), x[:, w], g[:, w], alpha[:, w])
-        z = ref.final_normals(SEED, CHAIN0 + w, D, 7)
+        z = ref.final_normals(cases.PF_SEED, cases.PF_CHAIN0 + w, D, 7)
         phi, logq = ref.draw_map(f["mu"], f["sqa"], f["L"], f["logdet"], z)
         want = multivariate_normal(mean=f["mu"], cov=ref.sigma(f)).logpdf(phi.T)
         worst = max(worst, np.max(np.abs(logq - want) / np.maximum(1.0, np.abs(want))))
@@ -96,12 +82,12 @@ def test_normals_are_the_momentum_map_on_their_own_streams():
     """purpose 4 at t = iters·32 + k and purpose 5 at t = j: the u -> z map of the momentum kernel with inv_mass = 1, other words than purpose 2's"""
     import hmc_reference as href
     D = 6
-    z = ref.elbo_normals(SEED, CHAIN0 + 3, D, iters=2, K=4)
-    assert z.shape == (D, 4) and np.array_equal(z[:, 1], ref.normals(SEED, CHAIN0 + 3, D, 4, [2 * 32 + 1])[:, 0])
-    assert not np.array_equal(z[:, 1], href.momentum(SEED, 2 * 32 + 1, CHAIN0 + 3, 1, D)[:, 0])
-    f = ref.final_normals(SEED, CHAIN0 + 3, D, 3)
-    assert np.array_equal(f[:, 2], ref.normals(SEED, CHAIN0 + 3, D, 5, [2])[:, 0]) and not np.array_equal(f[:, :3], z[:, :3])
-    assert abs(np.mean(ref.final_normals(SEED, 0, 4, 20000))) < 0.02
+    z = ref.elbo_normals(cases.PF_SEED, cases.PF_CHAIN0 + 3, D, iters=2, K=4)
+    assert z.shape == (D, 4) and np.array_equal(z[:, 1], ref.normals(cases.PF_SEED, cases.PF_CHAIN0 + 3, D, 4, [2 * 32 + 1])[:, 0])
+    assert not np.array_equal(z[:, 1], href.momentum(cases.PF_SEED, 2 * 32 + 1, cases.PF_CHAIN0 + 3, 1, D)[:, 0])
+    f = ref.final_normals(cases.PF_SEED, cases.PF_CHAIN0 + 3, D, 3)
+    assert np.array_equal(f[:, 2], ref.normals(cases.PF_SEED, cases.PF_CHAIN0 + 3, D, 5, [2])[:, 0]) and not np.array_equal(f[:, :3], z[:, :3])
+    assert abs(np.mean(ref.final_normals(cases.PF_SEED, 0, 4, 20000))) < 0.02
 
 
 def test_elbo_of_an_exactly_fitted_gaussian_is_the_log_normaliser():
@@ -146,7 +132,7 @@ OUT = ("theta_t", "logpost", "gnorm", "status", "iters", "evals", "inv_hess_diag
 
 
 def test_selection_keeps_the_greatest_elbo_and_the_earliest_of_a_tie():
-    r = ref.pathfinder(quartic, quartic_starts(), m=4, n_rounds=12, gtol=1e-9, seed=SEED, chain0=CHAIN0, n_elbo=N_ELBO)
+    r = ref.pathfinder(quartic, quartic_starts(), m=4, n_rounds=12, gtol=1e-9, seed=cases.PF_SEED, chain0=cases.PF_CHAIN0, n_elbo=cases.PF_N_ELBO)
     ps = r["state"]
     live = np.arange(7) != 4
     assert np.all(r["n_fits"][live] == r["iters"][live]) and r["iters"][live].min() >= 3
@@ -162,13 +148,13 @@ def test_selection_keeps_the_greatest_elbo_and_the_earliest_of_a_tie():
         assert ps2.elbo_iter[0] == {1: -1, 2: -1, 3: 3, 4: 3, 5: 3, 6: 6, 7: 6}[it]
     # a target that is −Inf wherever a draw lands: candidates are counted, none is kept
     blind = lambda th: quartic(th) if th.shape[1] == 7 else (np.full(th.shape[1], -np.inf), np.zeros_like(th))      # noqa: E731
-    rb = ref.pathfinder(blind, quartic_starts(), m=4, n_rounds=6, gtol=1e-9, seed=SEED, chain0=CHAIN0, n_elbo=N_ELBO)
+    rb = ref.pathfinder(blind, quartic_starts(), m=4, n_rounds=6, gtol=1e-9, seed=cases.PF_SEED, chain0=cases.PF_CHAIN0, n_elbo=cases.PF_N_ELBO)
     assert np.all(rb["elbo"] == -np.inf) and np.all(rb["elbo_iter"] == -1) and np.all(rb["n_fits"][live] > 0)
 
 
 def test_dead_and_frozen_chains_and_resume_in_the_restatement():
     x0 = quartic_starts()
-    kw = dict(m=4, gtol=1e-5, seed=SEED, chain0=CHAIN0, n_elbo=N_ELBO)
+    kw = dict(m=4, gtol=1e-5, seed=cases.PF_SEED, chain0=cases.PF_CHAIN0, n_elbo=cases.PF_N_ELBO)
     one = ref.pathfinder(quartic, x0, n_rounds=30, **kw)
     assert one["status"][4] == lref.DEAD and one["elbo"][4] == -np.inf and one["elbo_iter"][4] == -1 and one["n_fits"][4] == 0
     assert np.array_equal(one["theta_t"][:, 4], x0[:, 4], equal_nan=True)
@@ -183,8 +169,8 @@ def test_dead_and_frozen_chains_and_resume_in_the_restatement():
         assert np.array_equal(one[k][..., frozen], more[k][..., frozen]), k
     assert np.all(one["elbo_iter"][frozen] >= 1) and np.all(one["elbo_iter"][frozen] <= one["iters"][frozen])
     # the first n_elbo = 3 draws are the first three of n_elbo = 5: the candidates' counters do not depend on K
-    assert np.array_equal(ref.elbo_normals(SEED, 9, 3, 4, 3), ref.elbo_normals(SEED, 9, 3, 4, 5)[:, :3])
-    phi, logq, lp = ref.pathfinder_draw(quartic, one["state"], SEED, CHAIN0, 4)
+    assert np.array_equal(ref.elbo_normals(cases.PF_SEED, 9, 3, 4, 3), ref.elbo_normals(cases.PF_SEED, 9, 3, 4, 5)[:, :3])
+    phi, logq, lp = ref.pathfinder_draw(quartic, one["state"], cases.PF_SEED, cases.PF_CHAIN0, 4)
     cols = np.arange(4) * 7 + 4
     assert np.all(np.isnan(logq[cols])) and np.all(lp[cols] == -np.inf) and np.array_equal(phi[:, cols], np.repeat(x0[:, 4:5], 4, axis=1), equal_nan=True)
     others = np.setdiff1d(np.arange(28), cols)
@@ -211,23 +197,19 @@ def test_argument_checks_that_need_no_device(pkg):
 # ---------------------------------------------------------------------------------------------------- the condition of the GPU comparison
 @functools.lru_cache(maxsize=None)
 def reference_rounds(oracle):
-    """the restatement's ROUNDS rounds from the 64 starts of lcond.reference_case, fed by the oracle — computed once, shared, never modified"""
-    starts, _, v, _ = lcond.reference_case(oracle)
-    return ref.pathfinder(lcond.tight_logpost(oracle), starts, v, m=lcond.M, n_rounds=ROUNDS, gtol=lcond.GTOL, seed=SEED, chain0=CHAIN0, n_elbo=N_ELBO)
-
-
-def decided_chains(r):
-    return (r["elbo_iter"] >= 0) & (r["margin_elbo"] > MARGIN)
+    """the restatement's cases.PF_ROUNDS rounds from the 64 starts of cases.reference_case, fed by the oracle — computed once, shared, never modified"""
+    starts, _, v, _ = cases.reference_case(oracle)
+    return ref.pathfinder(cases.tight_logpost(oracle), starts, v, m=cases.LBFGS_M, n_rounds=cases.PF_ROUNDS, gtol=cases.LBFGS_GRAD_TOL, seed=cases.PF_SEED, chain0=cases.PF_CHAIN0, n_elbo=cases.PF_N_ELBO)
 
 
 def test_ten_rounds_are_decided_for_most_starts(oracle):
     """tests/test_pathfinder.py compares elbo_iter, n_fits and the ELBO on chains that have a fit and whose two best ELBOs differ by more
-    than MARGIN·max(1, |ELBO|), and may leave out at most 1/8 of the 64. With K = 5 draws the ELBOs of neighbouring iterates differ at
+    than cases.PF_MARGIN·max(1, |ELBO|), and may leave out at most 1/8 of the 64. With K = 5 draws the ELBOs of neighbouring iterates differ at
     order one, so the reference clears this by far."""
     r = reference_rounds(oracle)
-    decided = decided_chains(r)
+    decided = cases.decided_chains(r)
     gaps = r["margin_elbo"][r["elbo_iter"] >= 0]
-    print(f"{decided.sum()} of {lcond.N_STARTS} chains decided after {ROUNDS} rounds; fits a chain {r['n_fits'].min()} … {r['n_fits'].max()}; the smallest gap between the "
+    print(f"{decided.sum()} of {cases.LBFGS_N_STARTS} chains decided after {cases.PF_ROUNDS} rounds; fits a chain {r['n_fits'].min()} … {r['n_fits'].max()}; the smallest gap between the "
           f"two best ELBOs {gaps.min():.3e}; best ELBO {r['elbo'].max():.6f}; kept iterates {np.bincount(r['elbo_iter'][r['elbo_iter'] >= 0])}")
-    assert decided.sum() >= 7 * lcond.N_STARTS // 8
+    assert decided.sum() >= 7 * cases.LBFGS_N_STARTS // 8
     assert r["n_fits"].max() >= 3 and np.all(r["status"] != lref.DEAD)

@@ -3,7 +3,7 @@ Prior draws on the device (include/octofitter_hip_draws.h, host/draws.py): the c
 the density, and the two drivers built on them — octo_draws_best (guess_starting_position, src/initialization.jl:14-66) and
 octo_draws_rejection (octofit_rejection, src/sampling.jl:168-268).
 
-The generator is restated here in integers (philox_int) and pinned to numpy.random.Philox; everything the device draws is a
+The generator is restated in integers (philox_int of tests/hmc_reference.py) and pinned here to numpy.random.Philox; everything the device draws is a
 deterministic function of uniforms this restatement reproduces, so every check below is against an independent value: the bits of
 the uniforms, scipy.stats CDFs and densities, host/priors.py's link, the oracle's callback on the same draws.
 
@@ -12,79 +12,16 @@ log-likelihood is a difference lp − logprior_t of numbers that cancel, held to
 bar 1.95/√n is the 0.1 % critical value.
 """
 import math
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-
-M64 = (1 << 64) - 1
-PHILOX_M0, PHILOX_M1 = 0xD2E7470EE14C6C93, 0xCA5A826395121157
-PHILOX_W0, PHILOX_W1 = 0x9E3779B97F4A7C15, 0xBB67AE8584CAA73B
-KEY1 = 0x6F63746F64726177
+from draws_cases import ks_statistic
+from draws_device import draws_mod      # noqa: F401
+from hmc_reference import KEY1, M64, philox_int, philox_vec, prior_uniforms, rejection_uniforms, u01
 
 
 # ---------------------------------------------------------------------------------------------------- the generator, restated
-def philox_int(key, ctr):
-    """Philox4x64-10 on Python integers: key (k0, k1), counter (c0, c1, c2, c3) -> four 64-bit words."""
-    k0, k1 = key
-    c0, c1, c2, c3 = ctr
-    for _ in range(10):
-        p0, p1 = PHILOX_M0 * c0, PHILOX_M1 * c2
-        c0, c1, c2, c3 = (p1 >> 64) ^ c1 ^ k0, p1 & M64, (p0 >> 64) ^ c3 ^ k1, p0 & M64
-        k0, k1 = (k0 + PHILOX_W0) & M64, (k1 + PHILOX_W1) & M64
-    return c0, c1, c2, c3
-
-
-def _mulhilo(a, b):
-    """(high, low) 64-bit halves of a·b: a a Python integer constant, b a uint64 array."""
-    a0, a1 = np.uint64(a & 0xFFFFFFFF), np.uint64(a >> 32)
-    m32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
-    b0, b1 = b & m32, b >> s32
-    p00, p01, p10, p11 = a0 * b0, a0 * b1, a1 * b0, a1 * b1
-    mid = (p00 >> s32) + (p01 & m32) + (p10 & m32)
-    hi = p11 + (p01 >> s32) + (p10 >> s32) + (mid >> s32)
-    lo = (mid << s32) | (p00 & m32)
-    return hi, lo
-
-
-def philox_vec(key, c0, c1, c2, c3):
-    """The same rounds on uint64 arrays (one counter per element)."""
-    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, dtype=np.uint64) for c in (c0, c1, c2, c3)])
-    k0, k1 = key
-    with np.errstate(over="ignore"):
-        for _ in range(10):
-            hi0, lo0 = _mulhilo(PHILOX_M0, c0)
-            hi1, lo1 = _mulhilo(PHILOX_M1, c2)
-            c0, c1, c2, c3 = hi1 ^ c1 ^ np.uint64(k0), lo1, hi0 ^ c3 ^ np.uint64(k1), lo0
-            k0, k1 = (k0 + PHILOX_W0) & M64, (k1 + PHILOX_W1) & M64
-    return c0, c1, c2, c3
-
-
-def u01(x):
-    """(2·(x >> 12) + 1)·2⁻⁵³"""
-    return ((x >> np.uint64(12)) * np.uint64(2) + np.uint64(1)).astype(np.float64) * 2.0 ** -53
-
-
-def prior_uniforms(seed, idx, D):
-    """u[d][k] of draw idx[k]: counter (i, d // 4, 0, 0), word d % 4."""
-    idx = np.asarray(idx, dtype=np.uint64)
-    out = np.empty((D, idx.size))
-    for j in range((D + 3) // 4):
-        words = philox_vec((seed, KEY1), idx, j, 0, 0)
-        for q in range(4):
-            if 4 * j + q < D:
-                out[4 * j + q] = u01(words[q])
-    return out
-
-
-def rejection_uniforms(seed, idx):
-    """counter (i, 0, 1, 0), word 0"""
-    return u01(philox_vec((seed, KEY1), np.asarray(idx, dtype=np.uint64), 0, 1, 0)[0])
-
-
 def test_philox_restatement_is_numpy_philox():
     """numpy.random.Philox(counter=c, key=k) hands out the block of counter c + 1 first (it increments before it generates)."""
     cases = [((0, 0), (0, 0, 0, 0)), ((1, KEY1), (41, 3, 0, 0)), ((0xDEADBEEFCAFEF00D, KEY1), (M64, 5, 1, 0)),      # a counter word at 2⁶⁴ − 1: the carry
@@ -101,14 +38,6 @@ def test_philox_restatement_is_numpy_philox():
 
 
 # ---------------------------------------------------------------------------------------------------- distributions
-def ks_statistic(x, cdf):
-    """One-sample Kolmogorov-Smirnov D_n."""
-    F = np.sort(cdf(np.asarray(x)))
-    n = F.size
-    k = np.arange(1, n + 1)
-    return max(np.max(k / n - F), np.max(F - (k - 1) / n))
-
-
 def ks_cases(pkg):
     """(prior of host/priors.py, scipy CDF, scipy quantile, support)"""
     import scipy.stats as ss
@@ -150,13 +79,6 @@ def _log_jacobian(lo, hi, y):
     if math.isfinite(lo) or math.isfinite(hi):
         return y
     return np.zeros_like(y)
-
-
-@pytest.fixture(scope="module")
-def draws_mod(pkg):
-    from octofitter_jl_amd.host import draws
-    draws.load_library()
-    return draws
 
 
 @pytest.mark.gpu
