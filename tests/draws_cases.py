@@ -394,3 +394,92 @@ def check_one_transition_is_decided(r):
     assert undecided.mean() <= ONE_UNDECIDED, "condition on the seed (the reference alone)"
     assert np.all(np.isfinite(r["theta_t"])) and r["accepted"].mean() > 0.5 and len(set(r["depth"])) >= 2, \
         (bool(np.all(np.isfinite(r["theta_t"]))), r["accepted"].mean(), sorted(set(r["depth"])))
+
+
+# Deep trees. The checkpoint slot of leaf n of a subtree is popc(n >> 1): a tree of depth <= 5 (n <= 15) uses the slots 0 … 3 only, the slots
+# 4 … 8 need subtrees of 32 … 512 leaves. Two cases reach max_depth = 10, each with ε differing from chain to chain so that every depth below
+# occurs as well.
+DEEP_DEPTH = 10
+# Priors only, against nuts_brute_force (tests/test_nuts_reference.py): ε spread geometrically over 0.004 … 0.3, one value per chain. The
+# seed is the first of 1, 2, 3, … with a decided chain at every depth from 3 to 10 and one stopped by each of the depth limit, a turn of a
+# subtree and a turn of the tree (few trees of these priors reach the limit without turning).
+BRUTE_DEEP_W, BRUTE_DEEP_SEED, BRUTE_DEEP_EPS = 24, 8, (0.004, 0.3)
+
+
+def brute_deep_inputs():
+    """(starts, ε [W]) of the deep brute-force setting"""
+    _, tt = ref.prior_sample(STAT_PRIORS, BRUTE_DEEP_SEED, np.arange(BRUTE_DEEP_W, dtype=np.uint64))
+    return tt, np.geomspace(*BRUTE_DEEP_EPS, BRUTE_DEEP_W)
+
+
+# The test model: the one-transition comparison with ε scaled per chain by DEEP_SCALES[w % 4] and max_depth = 10, everything else unchanged.
+# The order of the four scales is a condition on the seed: in the order (1, 1/4, 1/16, 1/64) no chain of ONE_SEED stops at depth 3.
+DEEP_SCALES = (1 / 16, 1 / 64, 1.0, 1 / 4)
+DEEP_FULL = 5                       # at least that many chains build all 1023 leaves
+
+
+def deep_inputs(W=ONE_W):
+    """one_inputs() with ε multiplied per chain by DEEP_SCALES[w % 4]"""
+    beta, eps, im = one_inputs(W)
+    return beta, eps * np.array([DEEP_SCALES[w % 4] for w in range(W)]), im
+
+
+def deep_transition(oracle, start):
+    beta, eps, im = deep_inputs(start.shape[1])
+    return nuts.nuts_transition(MODEL_PRIORS, start, beta, eps, im, DEEP_DEPTH, ONE_SEED, ONE_STEP, logpost=oracle_logpost(oracle, oracle_model(oracle)))
+
+
+def tree_summary(r):
+    decided = r["margin"] > nuts.MARGIN
+    return (f"{np.sum(~decided)} of {decided.size} chains undecided; decided chains by depth 0 … {np.bincount(r['depth'][decided], minlength=DEEP_DEPTH + 1)}; "
+            f"stop reasons {np.bincount(r['stop'], minlength=6)[1:]}; mean leaves {r['n_leapfrog'].mean():.1f}; rounds {r['rounds']}")
+
+
+def check_deep_transition_is_decided(r):
+    """the conditions on the deep case, from the restatement alone"""
+    decided = r["margin"] > nuts.MARGIN
+    print(f"deep transition: {tree_summary(r)}; moved {r['accepted'].mean():.3f}")
+    assert np.mean(~decided) <= ONE_UNDECIDED, "condition on the seed (the reference alone)"
+    assert set(range(2, DEEP_DEPTH + 1)) <= set(r["depth"][decided]), sorted(set(r["depth"][decided]))
+    assert {nuts.STOP_MAX_DEPTH, nuts.STOP_TURN_SUBTREE, nuts.STOP_TURN_TREE, nuts.STOP_DIVERGED} <= set(r["stop"]), sorted(set(r["stop"]))
+    assert np.sum(r["n_leapfrog"] == (1 << DEEP_DEPTH) - 1) >= DEEP_FULL, int(np.sum(r["n_leapfrog"] == (1 << DEEP_DEPTH) - 1))
+    assert np.all(np.isfinite(r["theta_t"]))
+
+
+# The largest deviation of θ_t, ℓπ (relative to max(1, |value|)) and log_accept (absolute) between runs of the restatement whose starts differ by
+# one ulp in every coordinate, measured by tests/test_nuts_reference.py::test_deep_transition_sensitivity_to_one_ulp: 5.062e-13.
+# The device is held to max(1e-8, 100·s): the factor covers its other summation order and its transcendentals over about 1000 leapfrogs.
+DEEP_S = 5.07e-13
+DEEP_BAR = max(1e-8, 100 * DEEP_S)
+
+
+def transition_deviation(a, b):
+    """the largest deviation of θ_t, ℓπ (relative to max(1, |value|)) and log_accept (absolute) between two results of the restatement, over
+    the chains on which every decision of the two is the same; and how many chains those are"""
+    same = np.all([a[k] == b[k] for k in ("depth", "stop", "selected", "n_leapfrog")], axis=0)
+    rel = lambda x, y: float(np.max(np.abs(x - y) / np.maximum(1.0, np.abs(y)), initial=0.0))      # noqa: E731
+    made = same & (a["n_leapfrog"] > 0)
+    with np.errstate(invalid="ignore"):
+        la = np.where(a["log_accept"][made] == b["log_accept"][made], 0.0, np.abs(a["log_accept"][made] - b["log_accept"][made]))
+    return max(rel(a["theta_t"][:, same], b["theta_t"][:, same]), rel(a["logpost"][same], b["logpost"][same]), float(np.max(la, initial=0.0))), int(same.sum())
+
+
+# Other dimensions, and inv_mass = None: handles without a model at D = 1 and D = 64, the priors cycling through STAT_PRIORS and the metric
+# through STAT_INV_MASS, ε spread geometrically over the chains. Without a metric the 64-dimensional case is stiff (the Normal(1.2, 0.05)
+# coordinates diverge from ε ≈ 0.1 on): its chains end at depth 0 or 1 by a divergence or build to the limit.
+DIM_DS, DIM_W, DIM_LD, DIM_DEPTH, DIM_SEED, DIM_STEP = (1, 64), 65, 72, 7, 5, 3
+DIM_EPS = (0.005, 0.6)
+DIM_DEPTHS = 3                      # at least that many distinct depths among the decided chains
+
+
+def dim_priors(D):
+    return [STAT_PRIORS[d % len(STAT_PRIORS)] for d in range(D)]
+
+
+def dim_inputs(D):
+    """(ε [W], inv_mass [D])"""
+    return np.geomspace(*DIM_EPS, DIM_W), np.array([STAT_INV_MASS[d % len(STAT_INV_MASS)] for d in range(D)])
+
+
+# The throughput kernels under NUTS: nine waves and a lane, three blocks of 256 threads with the last partial, a padded leading dimension.
+BIG_W, BIG_LD, BIG_DEPTH, BIG_DEAD = 577, 584, 3, 300

@@ -15,8 +15,11 @@ computation that differs in the last bits makes the same decisions.
 nuts_brute_force states the stopping rule a second time, as plainly as it can be: every doubling is built in full, its leaves laid out in
 a list, and every aligned block of 2^k leaves inside it tested by direct sums.
 
-One deliberately wrong sampler serves the stationarity condition of tests/test_nuts_reference.py: variant="uniform_leaf" picks a
-subtree's proposal with equal weights.
+Two deliberately wrong samplers serve conditions of tests/test_nuts_reference.py. variant="uniform_leaf" picks a subtree's proposal with
+equal weights: the stationarity condition fails on it. variant="short_stack" stores its checkpoints in slot min(imax, SHORT_STACK − 1), a stack of
+four planes, while the walk-back reads the slots imin … imax it always reads: identical while popc(n >> 1) <= 3, that is in subtrees of at
+most 16 leaves (trees of depth <= 5), and wrong from leaf n = 30 of a longer subtree on — the store of n = 30 overwrites the checkpoint
+of n = 28, and the test of n = 31 reads a plane that was never written.
 """
 import math
 
@@ -29,6 +32,7 @@ MAX_DEPTH = 10
 DELTA_MAX = 1000.0
 STOP_NONE, STOP_MAX_DEPTH, STOP_TURN_SUBTREE, STOP_TURN_TREE, STOP_DIVERGED, STOP_DEAD = 0, 1, 2, 3, 4, 5
 MARGIN = 1e-6
+SHORT_STACK = 4      # the planes of variant="short_stack": popc(n >> 1) <= 3 for n <= 15
 
 
 def nuts_counter(purpose, c, word1, step):
@@ -109,7 +113,8 @@ def _finish(S, theta_t, out_lp, out_lpt, sum_acc, nleaf, accepted, depth, diverg
 
 
 def nuts_transition(priors, theta_t, beta, eps, inv_mass, max_depth, seed, step, chain0=0, logpost=None, variant=None):
-    assert 1 <= max_depth <= MAX_DEPTH and variant in (None, "uniform_leaf")
+    assert 1 <= max_depth <= MAX_DEPTH and variant in (None, "uniform_leaf", "short_stack")
+    slot = (lambda i: np.minimum(i, SHORT_STACK - 1)) if variant == "short_stack" else (lambda i: i)      # where a checkpoint is stored
     S = _Setup(priors, theta_t, beta, eps, inv_mass, seed, step, chain0, logpost)
     D, W = S.D, S.W
     with np.errstate(all="ignore"):
@@ -178,8 +183,8 @@ def nuts_transition(priors, theta_t, beta, eps, inv_mass, max_depth, seed, step,
             tz = np.array([(int(x) ^ (int(x) + 1)).bit_length() - 1 for x in ns], dtype=np.int64)      # trailing one-bits of n
             imin = imax - tz + 1
             even = ns % 2 == 0
-            ck_p[imax[even], :, s[even]] = p1[:, even].T
-            ck_r[imax[even], :, s[even]] = rs[:, even].T
+            ck_p[slot(imax[even]), :, s[even]] = p1[:, even].T
+            ck_r[slot(imax[even]), :, s[even]] = rs[:, even].T
             turned = np.zeros(s.size, dtype=bool)
             for k in range(max_depth):
                 i = imax - k

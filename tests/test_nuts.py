@@ -4,8 +4,9 @@ host/callers.py: hmc_warmup(max_depth=…), octofit_nuts_device) against its Num
 callback, and against the conditions tests/test_nuts_reference.py establishes for the same seeds on the CPU.
 
 Decisions (depth, n_leapfrog, diverged, accepted) are compared on DECIDED chains — those whose smallest decision margin in the restatement
-exceeds 1e-6. Tolerances: θ_t, ℓπ and ℓ the project's oracle bar 1e-8 relative to max(1, |ref|); log_accept 1e-8 absolute; the warm-up's
-adaptation outputs the bars of tests/test_adapt.py; Kolmogorov-Smirnov at the 0.1 % level.
+exceeds 1e-6. Tolerances: θ_t, ℓπ and ℓ the project's oracle bar 1e-8 relative to max(1, |ref|); log_accept 1e-8 absolute; the deep transition
+(1023 leapfrogs) cases.DEEP_BAR = max(1e-8, 100·s), s the restatement's own sensitivity to one ulp of the starts; the warm-up's adaptation
+outputs the bars of tests/test_adapt.py; Kolmogorov-Smirnov at the 0.1 % level.
 """
 import ctypes as C
 import math
@@ -48,7 +49,7 @@ def columns(x, sel):
     return [None if a is None else a[..., sel] for a in x]
 
 
-def against_the_restatement(got, r, start, what):
+def against_the_restatement(got, r, start, what, bar=1e-8):
     """decisions on decided chains, values at the oracle bar, a chain that did not move keeps its bits"""
     tt, lp, ll, la, acc, depth, nleaf, div = got
     decided = r["margin"] > nuts.MARGIN
@@ -65,7 +66,7 @@ def against_the_restatement(got, r, start, what):
         made = same & (r["n_leapfrog"] > 0)
         e_la = float(np.max(np.where(la[made] == r["log_accept"][made], 0.0, np.abs(la[made] - r["log_accept"][made])), initial=0.0))      # −Inf: every leaf diverged
     print(f"{what}: {np.sum(~decided)} of {decided.size} undecided; max errors — θ_t {e_tt:.3e}, ℓπ {e_lp:.3e}, ℓ {e_ll:.3e} (relative to max(1, |ref|)); log_accept {e_la:.3e}")
-    assert e_tt <= 1e-8 and e_lp <= 1e-8 and e_ll <= 1e-8 and e_la <= 1e-8
+    assert e_tt <= bar and e_lp <= bar and e_ll <= bar and e_la <= bar
     assert ll is None or np.array_equal(ll[same & ~fin], r["loglike"][same & ~fin])
     assert np.all(np.isnan(la[r["n_leapfrog"] == 0]))
     stay = acc == 0
@@ -91,35 +92,135 @@ def test_gpu_one_transition_against_the_restatement(pkg, oracle, model_pd):
     against_the_restatement(numpy_outputs(tt, out), r, start.cpu().numpy(), "one transition")
 
 
+def test_gpu_deep_transition_against_the_restatement(pkg, oracle, model_pd):
+    """max_depth = 10, ε scaled per chain so that every depth from 2 to 10 occurs: subtrees of up to 512 leaves, every checkpoint slot
+    popc(n >> 1) = 0 … 8 stored and walked back, leaf numbers up to 1023 in the generator's counter, 1023 rounds in one call."""
+    import torch
+    model, pd = model_pd
+    set_batch_invariant(pkg, model, 0)
+    W, ld, total = cases.ONE_W, cases.ONE_LD, (1 << cases.DEEP_DEPTH) - 1
+    beta, eps, im = cases.deep_inputs()
+    start = pd.sample(cases.ONE_SEED, 0, W, theta=False, logprior_t=False)[1]
+    r = cases.deep_transition(oracle, start.cpu().numpy())
+    cases.check_deep_transition_is_decided(r)                                  # the conditions on the seed, before the device runs
+    buf, tt = padded(torch, start, ld)
+    out = pd.nuts(tt, beta=torch.as_tensor(beta, device="cuda"), eps=torch.as_tensor(eps, device="cuda"), inv_mass=im, max_depth=cases.DEEP_DEPTH,
+                  n_rounds=total, seed=cases.ONE_SEED, step=cases.ONE_STEP)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(buf[:, W:]).all())                                  # nothing written beyond column W
+    assert int(out["n_active"].item()) == 0
+    against_the_restatement(numpy_outputs(tt, out), r, start.cpu().numpy(), "deep transition", bar=cases.DEEP_BAR)
+
+
+def without(r, col):
+    """the restatement's result without one chain"""
+    return {k: (np.delete(v, col, axis=-1) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
+
+
+@pytest.mark.parametrize("route", ("fused", "throughput"))
+def test_gpu_one_transition_at_577_chains(pkg, oracle, draws_mod, route):
+    """W = 577 with the model, on both kernel families of the callback. What decides the route is small_eligible (csrc/octo_api.hip): the
+    fused launch k_small<MODEL> takes a batch with W·P <= the limit, and the limit of a whole single-planet callback is
+    max(small_w, small_w_model) = max(512, 768) — so 577 chains of the one-planet test model take the FUSED launch by default, not the
+    throughput kernels. An explicit octo_ctx_set_small_batch holds for the callback too (small_w_model = 0): with the limit 0 every call goes
+    through k_model_fwd, k_main and k_finish. Both run here, on a model of the test's own (the limit cannot be taken back).
+    Chain BIG_DEAD starts with a NaN coordinate: its column is not written and it makes no leaf."""
+    import torch
+    model = hmc_model(pkg)
+    pd = None
+    try:
+        if route == "throughput":
+            fn = model.ln_like
+            fn._check(fn.lib.octo_ctx_set_small_batch(fn._ctx, 0), "octo_ctx_set_small_batch")
+        pd = draws_mod.PriorDraws(model)
+        W, ld, dead, total = cases.BIG_W, cases.BIG_LD, cases.BIG_DEAD, (1 << cases.BIG_DEPTH) - 1
+        beta, eps, im = cases.one_inputs(W)
+        start = pd.sample(cases.ONE_SEED, 0, W, theta=False, logprior_t=False)[1]
+        start[3, dead] = float("nan")
+        start_h = start.cpu().numpy()
+        r = nuts.nuts_transition(cases.MODEL_PRIORS, start_h, beta, eps, im, cases.BIG_DEPTH, cases.ONE_SEED, cases.ONE_STEP,
+                                 logpost=cases.oracle_logpost(oracle, cases.oracle_model(oracle)))
+        print(f"W {W} ({route}): {cases.tree_summary(r)}")
+        assert np.mean(r["margin"] <= nuts.MARGIN) <= cases.ONE_UNDECIDED and r["stop"][dead] == nuts.STOP_DEAD, "condition on the seed (the reference alone)"
+        buf, tt = padded(torch, start, ld)
+        out = pd.nuts(tt, beta=torch.as_tensor(beta, device="cuda"), eps=torch.as_tensor(eps, device="cuda"), inv_mass=im, max_depth=cases.BIG_DEPTH,
+                      n_rounds=total, seed=cases.ONE_SEED, step=cases.ONE_STEP)
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(buf[:, W:]).all()) and int(out["n_active"].item()) == 0
+        got = numpy_outputs(tt, out)
+        others = np.arange(W) != dead
+        against_the_restatement(columns(got, others), without(r, dead), start_h[:, others], f"W {W} ({route})")
+        # the dead start: its column is never written, no leaf, not accepted
+        assert np.array_equal(got[0][:, dead], start_h[:, dead], equal_nan=True) and np.isnan(got[0][3, dead])
+        assert got[4][dead] == 0 and got[6][dead] == 0 and got[5][dead] == 0 and np.isnan(got[3][dead]) and got[7][dead] == 0
+    finally:
+        if pd is not None:
+            pd.close()
+        model.close()
+
+
 # ---------------------------------------------------------------------------------------------------- 2. tree shapes
 SHAPE_DEPTH, SHAPE_SEED = 3, 5
 SHAPE_EPS_SMALL, SHAPE_EPS_LARGE = 0.01, 1.6
 
 
+SHAPE_DEPTHS = (1, 2, SHAPE_DEPTH)      # at depth 1 the first leaf completes the tree
+
+
 def test_gpu_tree_shapes(prior_pd):
-    """ε small: every chain reaches max_depth, seven leaves. ε large: turns inside the first subtrees, turns of the tree, divergences."""
+    """ε small: every chain reaches max_depth, 2^max_depth − 1 leaves (1, 3, 7). ε large: turns inside the first subtrees, turns of the tree,
+    divergences."""
     import torch
     pd = prior_pd
     seen = set()
     for W in (1, 64, 257):
         start = pd.sample(SHAPE_SEED, 0, W, theta=False, logprior_t=False)[1]
-        for eps in (SHAPE_EPS_SMALL, SHAPE_EPS_LARGE):
-            r = nuts.nuts_transition(cases.STAT_PRIORS, start.cpu().numpy(), None, eps, cases.STAT_INV_MASS, SHAPE_DEPTH, SHAPE_SEED, 2)
-            tt = start.clone()
-            out = pd.nuts(tt, eps=eps, inv_mass=cases.STAT_INV_MASS, max_depth=SHAPE_DEPTH, n_rounds=(1 << SHAPE_DEPTH) - 1, seed=SHAPE_SEED, step=2)
-            assert out["logpost"] is None and out["loglike"] is None and int(out["n_active"].item()) == 0
-            got = numpy_outputs(tt, out)
-            against_the_restatement(got, r, start.cpu().numpy(), f"W {W}, ε {eps}")
-            depth, nleaf, div = got[5], got[6], got[7]
-            if eps == SHAPE_EPS_SMALL:
-                assert np.all(nleaf == 7) and np.all(depth == SHAPE_DEPTH) and not div.any() and np.all(got[4] == 1)
-            else:
-                decided = r["margin"] > nuts.MARGIN
-                seen |= set(r["stop"][decided])
-                assert np.all(nleaf >= 1) and np.all(nleaf <= 7)
-                if W == 257:
-                    assert np.any((depth == 1) & (div == 0))      # a turn at depth 1
+        for max_depth in SHAPE_DEPTHS:
+            total = (1 << max_depth) - 1
+            for eps in (SHAPE_EPS_SMALL, SHAPE_EPS_LARGE):
+                r = nuts.nuts_transition(cases.STAT_PRIORS, start.cpu().numpy(), None, eps, cases.STAT_INV_MASS, max_depth, SHAPE_SEED, 2)
+                tt = start.clone()
+                out = pd.nuts(tt, eps=eps, inv_mass=cases.STAT_INV_MASS, max_depth=max_depth, n_rounds=total, seed=SHAPE_SEED, step=2)
+                assert out["logpost"] is None and out["loglike"] is None and int(out["n_active"].item()) == 0
+                got = numpy_outputs(tt, out)
+                against_the_restatement(got, r, start.cpu().numpy(), f"W {W}, depth <= {max_depth}, ε {eps}")
+                depth, nleaf, div = got[5], got[6], got[7]
+                if eps == SHAPE_EPS_SMALL:
+                    assert np.all(nleaf == total) and np.all(depth == max_depth) and not div.any() and np.all(got[4] == 1)
+                else:
+                    decided = r["margin"] > nuts.MARGIN
+                    assert np.all(nleaf >= 1) and np.all(nleaf <= total)
+                    if max_depth == SHAPE_DEPTH:
+                        seen |= set(r["stop"][decided])
+                        if W == 257:
+                            assert np.any((depth == 1) & (div == 0))      # a turn at depth 1
     assert {nuts.STOP_TURN_SUBTREE, nuts.STOP_TURN_TREE, nuts.STOP_DIVERGED} <= seen, seen      # with ε small: STOP_MAX_DEPTH, the fourth
+
+
+@pytest.mark.parametrize("D", cases.DIM_DS)
+def test_gpu_dimensions_and_a_null_mass(pkg, draws_mod, D):
+    """D = 1 and D = 64 (the largest a handle takes), each with a metric and with inv_mass = None (= 1), to depth 7"""
+    import torch
+    priors = cases.dim_priors(D)
+    eps, im = cases.dim_inputs(D)
+    W, ld, total = cases.DIM_W, cases.DIM_LD, (1 << cases.DIM_DEPTH) - 1
+    pd = draws_mod.PriorDraws(priors=mirror_priors(pkg, priors))
+    try:
+        start = pd.sample(cases.DIM_SEED, 0, W, theta=False, logprior_t=False)[1]
+        assert tuple(start.shape) == (D, W)
+        for mass in (im, None):
+            what = f"D {D}, inv_mass {'given' if mass is not None else 'None'}"
+            r = nuts.nuts_transition(priors, start.cpu().numpy(), None, eps, mass, cases.DIM_DEPTH, cases.DIM_SEED, cases.DIM_STEP)
+            decided = r["margin"] > nuts.MARGIN
+            print(f"{what}: {cases.tree_summary(r)}")
+            assert np.mean(~decided) <= cases.ONE_UNDECIDED and len(set(r["depth"][decided])) >= cases.DIM_DEPTHS, "condition on the seed (the reference alone)"
+            buf, tt = padded(torch, start, ld)
+            out = pd.nuts(tt, eps=torch.as_tensor(eps, device="cuda"), inv_mass=mass, max_depth=cases.DIM_DEPTH, n_rounds=total, seed=cases.DIM_SEED, step=cases.DIM_STEP)
+            torch.cuda.synchronize()
+            assert bool(torch.isnan(buf[:, W:]).all()) and int(out["n_active"].item()) == 0
+            against_the_restatement(numpy_outputs(tt, out), r, start.cpu().numpy(), what)
+    finally:
+        pd.close()
 
 
 # ---------------------------------------------------------------------------------------------------- 3. invariance, resume and freezing
@@ -172,6 +273,37 @@ def test_gpu_invariance_resume_and_freezing(pkg, model_pd):
         clean[3, dead] = 0.1
         others = np.arange(W) != dead
         assert same_bits(columns(full, others), columns(run_rounds(torch, pd, clean, beta, eps, im, (total,)), others))
+    finally:
+        set_batch_invariant(pkg, model, 0)
+
+
+DEEP_CUTS = ((500, 523), (0, 16, 1, 1006, 0))      # a cut inside the subtree of 256 leaves; an empty opening call, a cut one leaf into the subtree of 16, the next a round on, an empty last call
+
+
+def test_gpu_deep_resume_and_freezing(pkg, model_pd):
+    """the deep transition of test_gpu_deep_transition_against_the_restatement cut into calls, and a slice of its chains alone: the same bits"""
+    import torch
+    model, pd = model_pd
+    W, total = cases.ONE_W, (1 << cases.DEEP_DEPTH) - 1
+    beta, eps, im = cases.deep_inputs()
+    start = pd.sample(cases.ONE_SEED, 0, W, theta=False, logprior_t=False)[1]
+    deep = dict(ld=cases.ONE_LD, max_depth=cases.DEEP_DEPTH)
+    set_batch_invariant(pkg, model, 1)
+    try:
+        full = run_rounds(torch, pd, start, beta, eps, im, (total,), **deep)
+        nleaf = full[6]
+        assert nleaf.max() == total and len(set(nleaf)) >= 8
+        for cuts in DEEP_CUTS:
+            assert sum(cuts) == total
+            snaps = []
+            assert same_bits(full, run_rounds(torch, pd, start, beta, eps, im, cuts, snapshots=snaps, **deep)), cuts
+            # a chain of m leaves ended in round m: from there on θ_t and every output keep their bits while the others build
+            for rounds, (snap, n_active) in zip(np.cumsum(cuts), snaps):
+                ended = nleaf <= rounds
+                assert same_bits(columns(snap, ended), columns(full, ended)), (cuts, rounds)
+                assert n_active == np.sum(~ended), (cuts, rounds)
+        part = run_rounds(torch, pd, start[:, 20:41].contiguous(), beta[20:41], eps[20:41], im, (total,), chain0=20, max_depth=cases.DEEP_DEPTH)      # chains 20 … 40 alone
+        assert same_bits(columns(full, slice(20, 41)), part)
     finally:
         set_batch_invariant(pkg, model, 0)
 

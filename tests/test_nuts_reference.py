@@ -1,8 +1,9 @@
 """
 Conditions on the NumPy restatement of the NUTS transition (tests/nuts_reference.py) that need no device: the counters of the three new
 purposes, the stopping rule against its plainest statement by brute force, the two stationarity conditions of tests/test_hmc_reference.py
-with the transition in the step's place (a deliberately wrong sampler fails the same bar), the condition on the seed of the one-transition
-comparison of tests/test_nuts.py, and the argument checks that need no device.
+with the transition in the step's place (a deliberately wrong sampler fails the same bar), the conditions on the seeds of the one-transition
+and deep-transition comparisons of tests/test_nuts.py with the sensitivity that sets the deep one's bar, and the argument checks that need
+no device.
 
 A chain is DECIDED if the smallest margin of any decision it made exceeds MARGIN = 1e-6 (the bar of the L-BFGS tests): two computations that
 differ in the last bits then make the same decisions, and tests compare decisions on decided chains only.
@@ -61,26 +62,61 @@ BRUTE_W = 512
 BRUTE_SETTINGS = ((0.5, 5), (0.25, 3), (1.6, 4))      # (ε, max_depth): mostly turns · mostly the depth limit · turns at depth 1 and divergences
 
 
+BRUTE_KEYS = ("depth", "stop", "selected", "n_leapfrog")
+
+
+def differing_keys(r, b, decided):
+    """the compared keys (θ_t: the same bits) under which two results disagree on a decided chain"""
+    return [k for k in BRUTE_KEYS if not np.array_equal(r[k][decided], b[k][decided])] + \
+        ([] if np.array_equal(r["theta_t"][:, decided], b["theta_t"][:, decided]) else ["theta_t"])
+
+
+def check_against_brute_force(r, b, tt, max_depth, what):
+    decided = r["margin"] > MARGIN
+    assert differing_keys(r, b, decided) == [], what
+    assert np.array_equal(r["accepted"], r["selected"] != 0) and np.array_equal(r["diverged"], r["stop"] == nuts.STOP_DIVERGED)
+    assert np.array_equal(r["theta_t"][:, ~r["accepted"]], tt[:, ~r["accepted"]])
+    assert r["rounds"] <= (1 << max_depth) - 1 and np.all(r["n_leapfrog"] <= (1 << max_depth) - 1)
+    full = r["stop"] == nuts.STOP_MAX_DEPTH
+    assert np.all(r["n_leapfrog"][full] == (1 << max_depth) - 1) and np.all(r["depth"][full] == max_depth)
+    return decided
+
+
 def test_stopping_rule_against_brute_force():
+    """The last lines state the gap these settings leave: a sampler whose checkpoint stack holds four planes is the right one on all of them."""
     _, tt = ref.prior_sample(cases.STAT_PRIORS, 5, np.arange(BRUTE_W, dtype=np.uint64))
     reasons = set()
     for eps, max_depth in BRUTE_SETTINGS:
         r = nuts.nuts_transition(cases.STAT_PRIORS, tt, None, eps, cases.STAT_INV_MASS, max_depth, 5, 0)
         b = nuts.nuts_brute_force(cases.STAT_PRIORS, tt, None, eps, cases.STAT_INV_MASS, max_depth, 5, 0)
-        decided = r["margin"] > MARGIN
+        decided = check_against_brute_force(r, b, tt, max_depth, eps)
         print(f"ε {eps}, depth <= {max_depth}: {np.sum(~decided)} of {BRUTE_W} chains undecided; stop reasons {np.bincount(r['stop'], minlength=6)[1:]}; "
               f"mean leaves {r['n_leapfrog'].mean():.2f}, rounds {r['rounds']}")
         assert decided.sum() >= 256 and decided.mean() >= 0.95
-        for k in ("depth", "stop", "selected", "n_leapfrog"):
-            assert np.array_equal(r[k][decided], b[k][decided]), (eps, k)
-        assert np.array_equal(r["theta_t"][:, decided], b["theta_t"][:, decided])      # the same bits
-        assert np.array_equal(r["accepted"], r["selected"] != 0) and np.array_equal(r["diverged"], r["stop"] == nuts.STOP_DIVERGED)
-        assert np.array_equal(r["theta_t"][:, ~r["accepted"]], tt[:, ~r["accepted"]])
-        assert r["rounds"] <= (1 << max_depth) - 1 and np.all(r["n_leapfrog"] <= (1 << max_depth) - 1)
-        full = r["stop"] == nuts.STOP_MAX_DEPTH
-        assert np.all(r["n_leapfrog"][full] == (1 << max_depth) - 1) and np.all(r["depth"][full] == max_depth)
         reasons |= set(np.unique(r["stop"]))
+        short = nuts.nuts_transition(cases.STAT_PRIORS, tt, None, eps, cases.STAT_INV_MASS, max_depth, 5, 0, variant="short_stack")
+        assert differing_keys(short, b, decided) == [] and differing_keys(short, r, np.ones(BRUTE_W, dtype=bool)) == [], eps
     assert reasons == {nuts.STOP_MAX_DEPTH, nuts.STOP_TURN_SUBTREE, nuts.STOP_TURN_TREE, nuts.STOP_DIVERGED}
+
+
+def test_stopping_rule_against_brute_force_to_depth_10():
+    """cases.brute_deep_inputs(): ε from 0.004 to 0.3 over 24 chains, so that every depth from 3 to the limit occurs and with it every
+    checkpoint slot 0 … 8 (slot popc(n >> 1) of leaf n, subtrees of up to 512 leaves). The sampler with the short stack, which the settings
+    above cannot tell from the right one, disagrees here."""
+    tt, eps = cases.brute_deep_inputs()
+    args = (cases.STAT_PRIORS, tt, None, eps, cases.STAT_INV_MASS, cases.DEEP_DEPTH, cases.BRUTE_DEEP_SEED, 0)
+    r, b = nuts.nuts_transition(*args), nuts.nuts_brute_force(*args)
+    decided = check_against_brute_force(r, b, tt, cases.DEEP_DEPTH, "deep")
+    print(f"ε {eps[0]} … {eps[-1]}, depth <= {cases.DEEP_DEPTH}: {cases.tree_summary(r)}")
+    assert set(range(3, cases.DEEP_DEPTH + 1)) <= set(r["depth"][decided]), "condition on the seed"
+    assert {nuts.STOP_MAX_DEPTH, nuts.STOP_TURN_SUBTREE, nuts.STOP_TURN_TREE} <= set(r["stop"][decided]), "condition on the seed"
+    short = nuts.nuts_transition(*args, variant="short_stack")
+    wrong = differing_keys(short, b, decided)
+    caught = decided & (short["n_leapfrog"] != b["n_leapfrog"])
+    print(f"short stack: disagrees under {wrong}; {caught.sum()} decided chains with another leaf count, all of depth >= {r['depth'][caught].min()}")
+    assert wrong != [] and caught.any()
+    assert np.all(r["depth"][caught] >= 6)      # a tree of depth <= 5 never shows it
+    assert differing_keys(short, b, decided & (r["n_leapfrog"] <= 31)) == []
 
 
 def test_a_dead_start_ends_at_once():
@@ -145,6 +181,30 @@ def test_one_transition_is_decided_for_the_seed(oracle):
     """at the restated prior draws; the device's differ in the last bits"""
     _, start = ref.prior_sample(cases.MODEL_PRIORS, cases.ONE_SEED, np.arange(cases.ONE_W, dtype=np.uint64))
     cases.check_one_transition_is_decided(cases.one_transition(oracle, start))
+
+
+def test_deep_transition_is_decided_for_the_seed(oracle):
+    """cases.deep_inputs(): max_depth = 10 with ε of the one-transition case scaled per chain, at the restated prior draws"""
+    _, start = ref.prior_sample(cases.MODEL_PRIORS, cases.ONE_SEED, np.arange(cases.ONE_W, dtype=np.uint64))
+    cases.check_deep_transition_is_decided(cases.deep_transition(oracle, start))
+
+
+def test_deep_transition_sensitivity_to_one_ulp(oracle):
+    """Measures cases.DEEP_S: the restatement from starts moved by one ulp in every coordinate, up and down, against the one from the starts
+    themselves — the largest deviation of θ_t, ℓπ and log_accept over the chains whose decisions stayed the same. No decided chain may
+    change a decision."""
+    _, start = ref.prior_sample(cases.MODEL_PRIORS, cases.ONE_SEED, np.arange(cases.ONE_W, dtype=np.uint64))
+    r = cases.deep_transition(oracle, start)
+    decided = r["margin"] > MARGIN
+    s = 0.0
+    for moved in (np.nextafter(start, np.inf), np.nextafter(start, -np.inf)):
+        r2 = cases.deep_transition(oracle, moved)
+        assert differing_keys(r2, r, decided) in ([], ["theta_t"])
+        dev, n_same = cases.transition_deviation(r2, r)
+        assert n_same >= decided.sum()
+        s = max(s, dev)
+    print(f"deep transition, starts moved by one ulp: s = {s:.3e} (DEEP_S = {cases.DEEP_S:.3e}, DEEP_BAR = {cases.DEEP_BAR:.3e})")
+    assert s <= cases.DEEP_S
 
 
 # ---------------------------------------------------------------------------------------------------- argument checks without a device
