@@ -45,6 +45,10 @@
  *   purpose 8: the merge uniform of doubling j, counter (c, j, 8, step), word 0
  * Counter word 1, which holds d / 4 for the other purposes, holds j or the leaf number here.
  *
+ * The eighth reads what the samplers stored: the convergence diagnostics of a cube of draws (octo_draws_diagnose_device: rank-normalised split-R̂,
+ * bulk and tail ESS, three quantiles per row) and the rank step by itself (octo_draws_rank_device), stated in full at their declaration
+ * (tests/diag_reference.py restates them). No random number.
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -404,6 +408,67 @@ int32_t octo_draws_nuts_device(octo_draws* h, uint64_t seed, uint64_t step, uint
                                int32_t n_rounds, int32_t resume, double* d_logpost, double* d_loglike, double* d_log_accept,
                                int32_t* d_accepted, int32_t* d_depth, int32_t* d_n_leapfrog, int32_t* d_diverged, int32_t* d_n_active,
                                void* hip_stream);
+
+/* ---- Convergence diagnostics of stored draws (Vehtari, Gelman, Simpson, Carpenter & Bürkner 2021; the table the reference's user reads after
+ * octofit: ess_bulk, ess_tail and the rank-normalised split-R̂). The function is stated in full so that a restatement elsewhere
+ * (tests/diag_reference.py) and the device compute the same thing. On DEVICE arrays, asynchronous on hip_stream, no host synchronisation, no
+ * random number, no model needed; no allocation once the handle's work array holds octo_draws_diagnose_work_doubles(n, W, K) doubles.
+ *
+ * Input      d_x: n samples of K rows of W chains, element (i, k, w) at d_x[i·ls + k·ld + w], ld >= W, ls >= K·ld. The recorded θ_t of the samplers
+ *            is this with ls = D·ld, their recorded ℓπ with K = 1 and ls = ld. K is an argument of its own (1 … OCTO_DRAWS_MAX_GROUPS), not the handle's D.
+ * Split      N = ⌊n/2⌋. Split chain m = h·W + w (h = 0, 1) holds samples h·(n − N) … h·(n − N) + N − 1 of chain w: draw i of m is sample h·(n − N) + i.
+ *            With n odd the middle sample, number N, belongs to no split chain: it is UNUSED throughout (never read for a statistic, never written
+ *            by the rank step). With n even this is the split of posterior and ArviZ. M = 2W split chains, S = M·N used draws per row.
+ * Validity   A row with a used draw that is not finite, and a row whose used draws are all equal, has NaN in every statistic (the quantiles
+ *            included) and NaN in every rank and z of the rank step. The other rows are not affected.
+ * Quantiles  s = the S used draws of the row sorted ascending. Type 7: q_p = s[lo] + (h − lo)·(s[lo+1] − s[lo]), h = (S − 1)·p, lo = ⌊h⌋, every
+ *            operation rounded by itself (no fused multiply-add), for p = 0.05, 0.5 and 0.95. The median is q_0.5 by this formula.
+ * Ranks      r(x) = #{s < x} + (#{s = x} + 1)/2: the average rank, 1-based, exact in a double. The comparison is that of doubles: −0 = +0.
+ *            z(x) = normcdfinv((r − 3/8)/(S + 1/4)). Folded: the same applied to y = |x − median| among the S values of y.
+ * Sums over the split chains — Σ_m below — run in the order octo_draws_moments_device documents: within a block of 256 consecutive split
+ *            chains a butterfly over the 64 lanes of each wave (a lane beyond M holds 0), the four waves added in wave order from 0; the blocks
+ *            then added in block order from 0. No floating-point atomic anywhere.
+ * ESS(v)     of M split chains of N draws v_{m,i} (Stan's compute_effective_sample_size):
+ *              μ_m = (Σ_i v_{m,i})/N, summed in index order;
+ *              acov_m(t) = (Σ_{i=0}^{N−1−t} (v_{m,i} − μ_m)·(v_{m,i+t} − μ_m))/N, summed in index order (a product may be fused into the sum);
+ *              var_m = acov_m(0)·N/(N − 1);   W̄ = (Σ_m var_m)/M;   μ̄ = (Σ_m μ_m)/M;
+ *              var⁺ = W̄·(N − 1)/N + (Σ_m (μ_m − μ̄)²)/(M − 1);   Ā(t) = (Σ_m acov_m(t))/M;   ρ_0 = 1, ρ_t = 1 − (W̄ − Ā(t))/var⁺.
+ *            Geyer's truncation exactly as Stan writes it: even = 1, odd = ρ_1, t = 1; while t < N − 4 and even + odd > 0: even = ρ_{t+1},
+ *            odd = ρ_{t+2}, both are STORED as ρ̂_{t+1}, ρ̂_{t+2} iff even + odd >= 0, t += 2. max_t = t. If even > 0: ρ̂_{max_t+1} = even.
+ *            ρ̂_0 = 1, ρ̂_1 = ρ_1, and a ρ̂ that was not stored is 0. Monotone pass, for t = 1, 3, … <= max_t − 3: if ρ̂_{t+1} + ρ̂_{t+2} >
+ *            ρ̂_{t−1} + ρ̂_t, both take (ρ̂_{t−1} + ρ̂_t)/2. τ = −1 + 2·Σ_{t<max_t} ρ̂_t + ρ̂_{max_t+1}, summed in index order;
+ *            τ <- max(τ, 1/log10(S)); ESS = S/τ. A var⁺ that is not finite or not > 0 gives NaN.
+ * split-R̂(v) = √(var⁺/W̄), from the same lag-0 quantities.
+ * Outputs    d_out [OCTO_DRAWS_DIAG_N_STATS][K], statistic-major:
+ *              RHAT        max(split-R̂(z), split-R̂(z_folded)), NaN if either is
+ *              ESS_BULK    ESS(z)
+ *              ESS_TAIL    min(ESS(1[x <= q_0.05]), ESS(1[x <= q_0.95])), NaN if either is
+ *              RHAT_BASIC  split-R̂(x)            ESS_BASIC   ESS(x)
+ *              Q05, Q50, Q95   the three quantiles
+ * The outputs are the same bits from run to run, and they depend neither on ld, nor on ls, nor on what lies beyond column W or in the unused
+ * sample.
+ * Work       octo_draws_diagnose_work_doubles(n, W, K) = 2K(P + S) + 10KM + 4K·T·(nblk + 1) + 5K doubles, P = max(2048, the least power of two >= S),
+ *            T = 16·⌈N/16⌉, nblk = ⌈M/256⌉: the sorted keys of x and of y, z and z_folded, the chains' means and variances, the block sums of
+ *            acov_m(t) and ρ, the quantiles and two flags per row. Host only, no handle; 0 for arguments the two calls refuse.
+ * OCTO_EINVAL: NULL handle or array; K outside 1 … OCTO_DRAWS_MAX_GROUPS; n < 8; W < 1; ld < W; ls < K·ld. OCTO_ENOTSUP: S = 2·N·W > 2^24. */
+#define OCTO_DRAWS_DIAG_RHAT 0
+#define OCTO_DRAWS_DIAG_ESS_BULK 1
+#define OCTO_DRAWS_DIAG_ESS_TAIL 2
+#define OCTO_DRAWS_DIAG_RHAT_BASIC 3
+#define OCTO_DRAWS_DIAG_ESS_BASIC 4
+#define OCTO_DRAWS_DIAG_Q05 5
+#define OCTO_DRAWS_DIAG_Q50 6
+#define OCTO_DRAWS_DIAG_Q95 7
+#define OCTO_DRAWS_DIAG_N_STATS 8
+int32_t octo_draws_diagnose_device(octo_draws* h, int64_t n, int64_t W, int64_t ld, int64_t ls, int32_t K, const double* d_x, double* d_out,
+                                   void* hip_stream);
+int64_t octo_draws_diagnose_work_doubles(int64_t n, int64_t W, int32_t K);
+
+/* The rank step alone (the twin that octo_draws_lbfgs_direction_device is to the optimiser: the diagnosis launches the same kernels): r and/or z of
+ * every used draw, written on the strides of d_x — element (i, k, w) of d_rank and d_z at [i·ls + k·ld + w]. Either output may be NULL; an unused
+ * middle sample is not written. fold = 1 ranks y = |x − median|. The work array and the status codes are those of octo_draws_diagnose_device. */
+int32_t octo_draws_rank_device(octo_draws* h, int64_t n, int64_t W, int64_t ld, int64_t ls, int32_t K, const double* d_x, int32_t fold,
+                               double* d_rank, double* d_z, void* hip_stream);
 
 #ifdef __cplusplus
 }

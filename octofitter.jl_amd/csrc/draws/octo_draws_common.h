@@ -1,8 +1,8 @@
 // octo_draws_common.h — what the translation units of liboctofitter_hip_draws.so share: the handle, the counter generator, the prior
 // helpers on top of octo_model.h's device routines, the tempered target of the two samplers, and the argument checks their functions repeat.
-// Six units include it: octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
+// Seven units include it: octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
 // explorer), octo_draws_nuts.hip (the no-U-turn sampler), octo_draws_lbfgs.hip (the multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder
-// on its paths) and octo_draws_adapt.hip (the warm-up statistics of the explorer). Everything but the handle lives in an unnamed namespace,
+// on its paths), octo_draws_adapt.hip (the warm-up statistics of the explorer) and octo_draws_diag.hip (the convergence diagnostics of stored draws). Everything but the handle lives in an unnamed namespace,
 // one copy per unit. How the handle's work allocations are cut into their parts is octo_draws_layout.h.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
@@ -150,6 +150,8 @@ struct octo_draws : CompanionBase {
     double* d_nuts = nullptr; int64_t cap_nuts = 0;
     int64_t nuts_W = 0, nuts_ld = 0; int32_t nuts_depth = 0;
     uint64_t nuts_seed = 0, nuts_step = 0, nuts_chain0 = 0;
+    // the convergence diagnostics (octo_draws_diag.hip), grown on demand: sorted keys, rank-normalised draws, the chains' moments, ρ
+    double* d_diag = nullptr; int64_t cap_diag = 0;
 };
 
 namespace {

@@ -99,6 +99,23 @@ inline MomentsPartials moments_partials(Carve& c, int64_t nblk, int64_t G, int64
     return {c.take(nblk * G), c.take(nblk * G * K), c.take(nblk * G * K)};
 }
 
+// The convergence diagnostics of K rows (octo_draws_diag.hip), d_diag: 2K(P + S) + 10KM + 4K·T·(nblk + 1) + 5K. N draws of M = 2W split chains a row,
+// S = M·N used draws, P = the power of two the sort pads them to, T = the lags rounded up to whole blocks of 16, nblk = ⌈M/256⌉. The kernels take it
+// by value: its members and their order are their argument layout.
+struct DiagWork {
+    double *keys, *fkeys;      // [K][P] the used draws of a row and their |x − median|, sorted ascending, +Inf behind the S
+    double *z, *zf;            // [K][N][M] the rank-normalised draws, bulk and folded: lane = split chain
+    double *mu, *var;          // [K][5][M] the mean and the variance of every split chain: of z, x, 1[x <= q05], 1[x <= q95], z_folded
+    double* part;              // [K][4][T][nblk] the block sums of acov_m(t) of the first four
+    double* rho;               // [K][4][T] ρ_t, then ρ̂_t
+    double* q;                 // [3][K] q05, q50, q95
+    int32_t *bad, *ok;         // [K] a used draw is not finite · the row is valid
+};
+inline DiagWork diag_work(Carve& c, int64_t K, int64_t P, int64_t S, int64_t M, int64_t T, int64_t nblk) {
+    return {c.take(K * P), c.take(K * P), c.take(K * S), c.take(K * S), c.take(5 * K * M), c.take(5 * K * M), c.take(4 * K * T * nblk),
+            c.take(4 * K * T), c.take(3 * K), c.take<int32_t>(K), c.take<int32_t>(K)};
+}
+
 // The device side of the host-buffer twins, both on d_hst. octo_draws_lbfgs: 2·D·ld + 5·ld + D
 struct LbfgsStaging {
     double *theta_t, *inv_hess_diag;      // [D][ld]

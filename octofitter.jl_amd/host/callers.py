@@ -351,7 +351,39 @@ def rhat_from_chain_moments(pd, cmean, cm2, n):
     return torch.sqrt(((n - 1.0) / n * wv + b_over_n) / wv)
 
 
-def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leapfrog=8, target_accept=0.8, init=None, eps=0.1, seed=0):
+DIAGNOSE_KEYS = dict(ess_bulk="ess_bulk", ess_tail="ess_tail", rhat_rank="rhat", ess_basic="ess_basic")      # a sampler's key -> PriorDraws.diagnose's
+
+
+def _diagnosed(pd, rec_t):
+    """What diagnose=True adds to a sampler's dict: DIAGNOSE_KEYS of its recorded rounds rec_t [n, D, n_chains], [D] device tensors made before the
+    copy; NaN when there are fewer than 8 rounds."""
+    import torch
+    if rec_t.shape[0] < 8:
+        return {k: torch.full((rec_t.shape[1],), float("nan"), dtype=torch.float64, device=rec_t.device) for k in DIAGNOSE_KEYS}
+    d = pd.diagnose(rec_t)
+    return {k: d[v] for k, v in DIAGNOSE_KEYS.items()}
+
+
+def diagnose_draws_device(samples, device=0):
+    """The table the reference's user reads after octofit, of stored draws samples [n, D, n_chains] (NumPy or a tensor), n >= 8, on the device:
+    dict of NumPy [D] arrays — PriorDraws.diagnose's rhat (rank-normalised split-R̂), ess_bulk, ess_tail, rhat_basic, ess_basic, q05, q50, q95 — plus
+    mcse_mean = sd/√ess_basic, sd the standard deviation of all draws of the row."""
+    import torch
+    from .draws import PriorDraws
+    from .priors import Uniform
+    dev = torch.device("cuda", int(device))
+    x = samples if torch.is_tensor(samples) else torch.from_numpy(np.array(samples, dtype=np.float64))      # a copy: the array may be read-only
+    x = x.to(device=dev, dtype=torch.float64).contiguous()
+    if x.ndim != 3:
+        raise ValueError("diagnose_draws_device: samples must be [n, D, n_chains]")
+    with PriorDraws(priors=[Uniform(0.0, 1.0)], device=int(device)) as pd:      # the call needs no model: a handle that only samples serves
+        d = pd.diagnose(x)
+        d["mcse_mean"] = x.transpose(0, 1).reshape(x.shape[1], -1).std(dim=1) / torch.sqrt(d["ess_basic"])
+        torch.cuda.synchronize(dev)
+        return {k: v.cpu().numpy() for k, v in d.items()}
+
+
+def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leapfrog=8, target_accept=0.8, init=None, eps=0.1, seed=0, diagnose=False):
     """The reference's main entry (octofit: Pathfinder start, then HMC with step-size and metric adaptation) with every piece on the device:
     n_chains chains at β = 1, static trajectories of n_leapfrog steps, a diagonal metric.
       starts    init [D, n_chains] in θ_t, or pathfinder_device(model, n_draws=n_chains, seed=seed)["theta_t"];
@@ -360,7 +392,8 @@ def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leap
       sampling  n_samples rounds with ε and the metric fixed, step numbers going on; every round is recorded and enters the per-chain
                 running moments (PriorDraws.chain_moments); R̂ from two PriorDraws.moments calls at the end.
     Returns dict(samples [n_samples, D, n_chains] natural domain, samples_t the same as θ_t, logpost [n_samples, n_chains], accept_stat
-    [n_warmup + n_samples] (the mean of min(1, exp(dH)) of each round), eps, inv_mass [D], rhat [D], names, state = dict(theta_t, step)), NumPy."""
+    [n_warmup + n_samples] (the mean of min(1, exp(dH)) of each round), eps, inv_mass [D], rhat [D], names, state = dict(theta_t, step)), NumPy.
+    diagnose=True adds ess_bulk, ess_tail, rhat_rank and ess_basic [D] of samples_t (PriorDraws.diagnose; NaN with n_samples < 8)."""
     import torch
     from .draws import PriorDraws
     Cn, nw, ns = int(n_chains), int(n_warmup), int(n_samples)
@@ -389,18 +422,21 @@ def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leap
             rec_lp[r] = lp
             pd.chain_moments(theta_t, r + 1, cmean, cm2)
         rhat = rhat_from_chain_moments(pd, cmean, cm2, ns)
+        extra = _diagnosed(pd, rec_t) if diagnose else {}
         torch.cuda.synchronize(dev)
         return dict(**_recorded(model, rec_t, rec_lp),
                     accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
-                    rhat=rhat.cpu().numpy(), names=list(model.names), state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns))
+                    rhat=rhat.cpu().numpy(), names=list(model.names), state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns),
+                    **{k: v.cpu().numpy() for k, v in extra.items()})
 
 
-def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_depth=10, target_accept=0.8, init=None, eps=0.1, seed=0):
+def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_depth=10, target_accept=0.8, init=None, eps=0.1, seed=0, diagnose=False):
     """octofit_hmc_device with the reference's own sampler: every round is one NUTS transition (PriorDraws.nuts_step: multinomial sampling, the
     generalised no-U-turn criterion, trees of depth <= max_depth) instead of a static trajectory. The starts, the metric, the warm-up
     (hmc_warmup(max_depth=max_depth)), the recording and R̂ are octofit_hmc_device's.
     Returns its dict — accept_stat is the mean over the chains of each transition's mean acceptance statistic — plus, per round of warm-up and
-    sampling, depth and n_leapfrog [n_warmup + n_samples] (means over the chains) and diverged [n_warmup + n_samples] (counts)."""
+    sampling, depth and n_leapfrog [n_warmup + n_samples] (means over the chains) and diverged [n_warmup + n_samples] (counts); diagnose=True adds
+    octofit_hmc_device's four keys."""
     import torch
     from .draws import PriorDraws
     Cn, nw, ns = int(n_chains), int(n_warmup), int(n_samples)
@@ -431,12 +467,13 @@ def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_d
             rec_lp[r] = lp
             pd.chain_moments(theta_t, r + 1, cmean, cm2)
         rhat = rhat_from_chain_moments(pd, cmean, cm2, ns)
+        extra = _diagnosed(pd, rec_t) if diagnose else {}
         torch.cuda.synchronize(dev)
         tree = torch.cat([wu["tree"], tree]).cpu().numpy()
         return dict(**_recorded(model, rec_t, rec_lp),
                     accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
                     rhat=rhat.cpu().numpy(), depth=tree[:, 0], n_leapfrog=tree[:, 1], diverged=tree[:, 2].astype(np.int64), names=list(model.names),
-                    state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns))
+                    state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns), **{k: v.cpu().numpy() for k, v in extra.items()})
 
 
 def _optimizer_starts(pd, model, N, n_starts, seed, dev, inv_mass):

@@ -16,6 +16,8 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     state = draws.adapt_init(1, 0.1)                        # … dual averaging of ε: the state [G, 4]
     a, eps_w = draws.adapt_step(state, dH, acc, k)          # … update k from a step's dH and accepted: mean acceptance [G], ε per chain [W]
     draws.chain_moments(θ_t, k, cmean, cm2)                 # per-chain running mean and M2 over time (R̂: include/octofitter_hip_draws.h)
+    d = draws.diagnose(rec)                                 # stored draws [n, K, W]: dict of [K] tensors, rhat (rank-normalised split-R̂), ess_bulk, ess_tail, …
+    r, z = draws.ranks(rec)                                 # … the rank step alone: average ranks and normal scores, of rec's shape
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -40,6 +42,8 @@ LBFGS_ACTIVE, LBFGS_GTOL, LBFGS_FTOL, LBFGS_LINESEARCH, LBFGS_DEAD = 0, 1, 2, 3,
 PF_MAX_D = 64                      # OCTO_DRAWS_PF_MAX_D
 PF_MAX_ELBO_DRAWS = 32             # OCTO_DRAWS_PF_MAX_ELBO_DRAWS
 MAX_GROUPS = 64                    # OCTO_DRAWS_MAX_GROUPS
+DIAG_RHAT, DIAG_ESS_BULK, DIAG_ESS_TAIL, DIAG_RHAT_BASIC, DIAG_ESS_BASIC, DIAG_Q05, DIAG_Q50, DIAG_Q95, DIAG_N_STATS = range(9)      # OCTO_DRAWS_DIAG_*
+DIAG_NAMES = ("rhat", "ess_bulk", "ess_tail", "rhat_basic", "ess_basic", "q05", "q50", "q95")      # the rows of d_out, in order
 
 c_uint64_p = C.POINTER(C.c_uint64)
 
@@ -79,6 +83,10 @@ _SIGS = {
     "octo_draws_chain_moments_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "octo_draws_nuts_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                            C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9),
+    "octo_draws_diagnose_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_diagnose_work_doubles": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "octo_draws_rank_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -142,6 +150,17 @@ def history(cnt, head, S, Y, g, D, dev, what):
     if cnt.shape != (W,) or head.shape != (W,):
         raise ValueError(f"{what}: cnt and head take {W} values each")
     return W, ld, m, cnt, head
+
+
+def draw_cube(x, dev, what):
+    """(x as [n, K, W], n, K, W, ld, ls) of stored draws: a float64 [n, K, W] or [n, W] tensor on `dev` whose samples are chain matrices
+    (chain_matrix) a fixed distance ls apart."""
+    if x.ndim == 2:
+        x = x[:, None, :]
+    if x.ndim != 3 or x.shape[0] < 1:
+        raise ValueError(f"{what}: x must be a float64 [n, K, W] or [n, W] tensor on {dev}")
+    K, W, ld = chain_matrix(x[0], None, dev, what, "x")
+    return x, int(x.shape[0]), K, W, ld, int(x.stride(0))
 
 
 def device_vector(x, n, dev, what):
@@ -499,6 +518,32 @@ class PriorDraws(companion.Handle):
         self._check(self.lib.octo_draws_chain_moments_device(self._h, W, ld, K, int(k), x.data_ptr(), cmean.data_ptr(), cm2.data_ptr(), self._stream(stream, self.device)))
         self._keep = (x, cmean, cm2)
         return cmean, cm2
+
+    # ---- convergence diagnostics of stored draws (include/octofitter_hip_draws.h, "Convergence diagnostics"): K = the rows of x, no model needed
+    def diagnose(self, x, out=None, stream=None):
+        """Rank-normalised split-R̂, bulk and tail ESS, the basic pair and three quantiles of every row of the stored draws x [n, K, W] (or
+        [n, W]: one row), n >= 8; its strides give ld and ls. out: a contiguous float64 [DIAG_N_STATS, K] tensor to write into.
+        Returns a dict of [K] device tensors by DIAG_NAMES (rows of one tensor). Asynchronous on `stream`."""
+        import torch
+        x, n, K, W, ld, ls = draw_cube(x, self.device, "diagnose")
+        if out is None:
+            out = self._out(K, DIAG_N_STATS)
+        elif out.dtype != torch.float64 or out.device != self.device or out.shape != (DIAG_N_STATS, K) or not out.is_contiguous():
+            raise ValueError(f"diagnose: out must be a contiguous float64 [{DIAG_N_STATS}, {K}] tensor on {self.device}")
+        self._check(self.lib.octo_draws_diagnose_device(self._h, n, W, ld, ls, K, x.data_ptr(), out.data_ptr(), self._stream(stream, self.device)))
+        self._keep = (x, out)
+        return dict(zip(DIAG_NAMES, out))
+
+    def ranks(self, x, fold=False, z=True, stream=None):
+        """The rank step of diagnose alone: (r, z) of x's shape and strides — the average rank of every used draw among its row's (fold: of
+        |x − median|) and its normal score; z=False: (r, None). NaN in an unused middle sample and in an invalid row. Asynchronous on `stream`."""
+        import torch
+        cube, n, K, W, ld, ls = draw_cube(x, self.device, "ranks")
+        r, zs = (torch.empty_strided(x.shape, x.stride(), dtype=torch.float64, device=self.device).fill_(float("nan")) if want else None for want in (True, z))
+        self._check(self.lib.octo_draws_rank_device(self._h, n, W, ld, ls, K, cube.data_ptr(), 1 if fold else 0, r.data_ptr(), ptr(zs),
+                                                    self._stream(stream, self.device)))
+        self._keep = (cube,)
+        return r, zs
 
     def close(self):
         if getattr(self, "_h", None) and self.model is not None and not getattr(self.model.ln_like, "_ctx", None):
