@@ -4,6 +4,7 @@ one of them keeps its decision margins — and with tools/diag_bench.py, which r
 a pure function of its fixed seed. A plain module, not a test module.
 """
 import functools
+import itertools
 
 import numpy as np
 
@@ -59,14 +60,46 @@ def _constant_row(rng):
     return x
 
 
+def _finite_twin(rng):
+    return ar1(rng, 12, 4, 4, 0.0)
+
+
 def _nan_and_inf(rng):
-    x = ar1(rng, 12, 4, 4, 0.0)
+    x = _finite_twin(rng)
     x[3, 1, 2] = np.nan
     x[9, 3, 0] = np.inf
     return x
 
 
-# name -> (builder, seed, (n, W, K)). The first six are the shapes on which the kernels can go wrong; the last four one case of each kind of value.
+def _long_chain(rng):
+    return ar1(rng, 2082, 2, 3, (0.9995, 0.5))
+
+
+def _censored(rng):
+    x = ar1(rng, 80, 2, 64, (0.0, 0.3))
+    x[:, 0] = np.clip(x[:, 0], -0.2, 0.2)
+    x[:, 1] = np.minimum(x[:, 1], 1.0)
+    return x
+
+
+def _stuck_chain(rng):
+    x = ar1(rng, 24, 2, 5, (0.0, 0.4))
+    x[:, 1, 2] = 0.7
+    return x
+
+
+def _edge(rng, n, W):
+    return ar1(rng, n, 2, W, (0.0, 0.6))
+
+
+# The exact edges of the blocks: N on, one below and one above a multiple of the 16-lag window (an odd N drops a middle sample besides), M = 2W of
+# exactly one wave (64) and one chain block (256) and two chains more. S = 2048 (N 32, W 32), 4096 (N 16, W 128) and 8192 (N 32, W 128) are powers
+# of two: no +Inf behind the keys, and at 4096 the first global pass of the sort with a full last block. (name, seed, (n, W, K)).
+EDGES = tuple((f"edge_N{N}_W{W}", 41 + i, (2 * N + N % 2, W, 2))
+              for i, (N, W) in enumerate(itertools.product((15, 16, 17, 31, 32, 33), (32, 33, 128, 129))))
+
+# name -> (builder, seed, (n, W, K)). The first six, long_chain and the edges are the shapes on which the kernels can go wrong; the others one case of
+# each kind of value.
 CASES = {
     "smallest": (_smallest, 11, (8, 1, 1)),
     "odd_n": (_odd, 12, (9, 3, 2)),                       # the middle sample is dropped
@@ -78,7 +111,13 @@ CASES = {
     "signed_zero": (_signed_zero, 18, (16, 3, 1)),
     "constant_row": (_constant_row, 19, (12, 4, 3)),
     "nan_and_inf": (_nan_and_inf, 20, (12, 4, 4)),
+    "long_chain": (_long_chain, 21, (2082, 3, 2)),        # T = 1056 lags > 1024: ρ_t in the work array; row 0's Geyer loop runs past lag 1024, row 1's stops early
+    "stuck_chain": (_stuck_chain, 31, (24, 5, 2)),        # one chain of row 1 never moves: zero variance, N tied ranks, a constant indicator in one lane
+    "censored": (_censored, 32, (80, 64, 2)),             # tie runs longer than a sort block, from key 0 and up to key S; q95 = the maximum: ess_tail alone is NaN
+    **{name: (functools.partial(_edge, n=shape[0], W=shape[1]), seed, shape) for name, seed, shape in EDGES},
 }
+# nan_and_inf without its two poisoned entries: what a handle is given after a cube that flagged rows. Not a case of the parametrised tests.
+TWINS = {"nan_and_inf_finite": (_finite_twin, 20, (12, 4, 4))}
 INVALID_ROWS = {"constant_row": [1], "nan_and_inf": [1, 3]}
 STATISTICS = ("rhat", "ess_bulk", "ess_tail", "rhat_basic", "ess_basic")      # the five with a bar; the quantiles are bit for bit
 MARGIN_BAR = 1e-6
@@ -86,7 +125,7 @@ MARGIN_BAR = 1e-6
 
 @functools.lru_cache(maxsize=None)
 def draws(name):
-    build, seed, (n, W, K) = CASES[name]
+    build, seed, (n, W, K) = CASES[name] if name in CASES else TWINS[name]
     x = build(np.random.default_rng(seed))
     assert x.shape == (n, K, W) and x.dtype == np.float64, (name, x.shape)
     x.setflags(write=False)
@@ -114,9 +153,9 @@ def gaps(name):
 # The largest long-double gap of each statistic over CASES, as tools/diag_bench.py measured and profiles/diag_throughput.txt records them
 # (tests/test_diag_reference.py holds the two together). The bar of a statistic in tests/test_diag.py is max(TRANS_BAR, 100 × its gap).
 LONG_DOUBLE_GAP = {
-    "rhat": 1.5511793442788129e-16,
-    "ess_bulk": 1.236927619504586e-14,
-    "ess_tail": 1.146987705080705e-15,
+    "rhat": 1.7474833878483988e-16,
+    "ess_bulk": 2.344377615116149e-14,
+    "ess_tail": 6.264700271968548e-15,
     "rhat_basic": 6.2313977762518125e-15,
     "ess_basic": 9.51236505730538e-14,
 }

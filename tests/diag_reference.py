@@ -7,7 +7,8 @@ scores. dtype=np.longdouble runs the same statements in extended precision (the 
 tools/diag_bench.py records the gap between the two runs, and the bars of tests/test_diag.py are written from it. A plain module, not a test module.
 
 diagnose() also returns the DECISION MARGINS: the smallest |even + odd| any test of Geyer's loop met and the smallest gap of any comparison of
-the monotone pass. A case whose margins are far above the arithmetic's error takes the same branches on every implementation.
+the monotone pass. A case whose margins are far above the arithmetic's error takes the same branches on every implementation. With them comes the
+lag max_t at which each of Geyer's loops stopped: the suite pins by it which cases walk ρ_t beyond the lags the device keeps in LDS.
 """
 import math
 
@@ -111,8 +112,13 @@ def ordered_sum(a):
 
 
 class Margins:
+    """geyer, monotone: the margins. max_t: the lag at which Geyer's loop stopped, None where ess() is NaN before it: of one row a list in
+    the order of the calls of ess() (QUANTITIES), of a cube a dict row -> that list (valid rows only)."""
+    QUANTITIES = ("z", "x <= q05", "x <= q95", "x")
+
     def __init__(self):
         self.geyer, self.monotone = math.inf, math.inf
+        self.max_t = []
 
     def merge(self, other):
         self.geyer, self.monotone = min(self.geyer, other.geyer), min(self.monotone, other.monotone)
@@ -145,6 +151,8 @@ def ess(v, margins=None):
     S = M * N
     _, c, wbar, varplus = lag0(v)
     if not (np.isfinite(varplus) and varplus > 0):
+        if margins is not None:
+            margins.max_t.append(None)
         return t_(np.nan)
     cache = {}
 
@@ -170,6 +178,8 @@ def ess(v, margins=None):
             hat[t + 1], hat[t + 2] = even, odd
         t += 2
     max_t = t
+    if margins is not None:
+        margins.max_t.append(max_t)
     if even > 0:
         hat[max_t + 1] = even
     for t in range(1, max_t - 2, 2):
@@ -207,6 +217,7 @@ def diagnose(x, dtype=np.float64):
     stats = np.full((N_STATS, K), np.nan, dtype=dtype)
     planes = {name: np.full((K, M, N), np.nan, dtype=np.float64 if name.startswith("rank") else dtype) for name in ("rank", "z", "rank_folded", "z_folded")}
     margins = Margins()
+    margins.max_t = {}
     for k in range(K):
         row = v64[k]
         if not np.all(np.isfinite(row)) or row.min() == row.max():
@@ -225,6 +236,7 @@ def diagnose(x, dtype=np.float64):
         stats[ESS_BASIC, k] = ess(v, m)
         stats[Q05, k], stats[Q50, k], stats[Q95, k] = q05, q50, q95
         margins.merge(m)
+        margins.max_t[k] = m.max_t
     out = {name: unsplit(p, n) for name, p in planes.items()}
     out.update(stats=stats, margins=margins)
     return out

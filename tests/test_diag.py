@@ -5,7 +5,8 @@ PriorDraws.diagnose / ranks; host/callers.py: diagnose_draws_device, octofit_nut
 
 Bars: the ranks and the three quantiles bit for bit; z the project's device-transcendental bar TRANS_BAR relative to max(1, |ref|); R̂ and ESS
 max(TRANS_BAR, 100 × the statistic's long-double gap of profiles/diag_throughput.txt) relative to max(1, |ref|) — the restatement, never the
-device, is the yardstick. Two runs, and the same draws at another ld and ls, give the same bits.
+device, is the yardstick. Two runs, the same draws at another ld and ls, and a handle that ran other shapes or a cube with non-finite draws
+before, give the same bits.
 """
 import ctypes as C
 
@@ -14,7 +15,7 @@ import pytest
 
 import diag_cases as cases
 import diag_reference as ref
-from draws_device import TRANS_BAR, close, draws_mod, hmc_model, mirror_priors, rel      # noqa: F401
+from draws_device import TRANS_BAR, close, draws_mod, hmc_model, mirror_priors, rel, same_bits      # noqa: F401
 import draws_cases
 
 pytestmark = pytest.mark.gpu
@@ -81,7 +82,7 @@ def test_gpu_diagnose_and_ranks_against_the_restatement(pd, name):
     assert np.all(np.isnan(first[:, bad])) and not np.any(np.isnan(np.delete(first, bad, axis=1)[[0, 1, 3, 4, 5, 6, 7]])), name
 
 
-@pytest.mark.parametrize("name", ["two_blocks", "odd_n", "nan_and_inf"])
+@pytest.mark.parametrize("name", ["two_blocks", "odd_n", "nan_and_inf", "long_chain", "censored"])
 def test_gpu_other_strides_give_the_same_bits(pd, name):
     """ld = W + 5 with NaN beyond column W, ls > K·ld with NaN rows between the samples, and garbage in the unused middle sample"""
     import torch
@@ -103,6 +104,40 @@ def test_gpu_other_strides_give_the_same_bits(pd, name):
             assert bool(torch.isnan(r1[n // 2]).all()) and bool(torch.isnan(z1[n // 2]).all())      # the unused sample is not written
     r_only, none = pd.ranks(dense, z=False)
     assert none is None and torch.equal(torch.nan_to_num(r_only, nan=-1.0), torch.nan_to_num(pd.ranks(dense)[0], nan=-1.0))
+
+
+def diagnose_and_folded_ranks(h, name):
+    """[stats, r, z] of diagnose and ranks(fold=True) of a case on the handle h, on the host"""
+    x = on_device(cases.draws(name))
+    stats = stats_on_host(h.diagnose(x))
+    r, z = h.ranks(x, fold=True)
+    return [stats, r.cpu().numpy(), z.cpu().numpy()]
+
+
+def test_gpu_one_handle_reused_across_shapes_gives_the_bits_of_a_fresh_one(pkg, draws_mod):
+    """The work array is carved again for every shape, larger or smaller than the one before, and the flags of non-finite draws are cleared by
+    every call: whatever a handle did before, a call gives the bits of the same call on a handle that has done nothing else."""
+    order = ("global_passes", "smallest", "long_chain", "edge_N16_W128", "long_chain")
+
+    def handle():
+        return draws_mod.PriorDraws(priors=mirror_priors(pkg, draws_cases.STAT_PRIORS))
+
+    fresh = {}
+    for name in sorted(set(order)):
+        with handle() as h:
+            fresh[name] = diagnose_and_folded_ranks(h, name)
+    with handle() as h:
+        for step, name in enumerate(order):
+            assert same_bits(diagnose_and_folded_ranks(h, name), fresh[name]), (step, name)      # so the second long_chain equals the first
+        # a cube that flags rows 1 and 3, then a finite cube of the same shape on the same carving: no flag is left over
+        poisoned = stats_on_host(h.diagnose(on_device(cases.draws("nan_and_inf"))))
+        assert np.all(np.isnan(poisoned[:, [1, 3]])) and not np.any(np.isnan(poisoned[:, [0, 2]]))
+        stats, rf, zf = diagnose_and_folded_ranks(h, "nan_and_inf_finite")
+        r, z = (t.cpu().numpy() for t in h.ranks(on_device(cases.draws("nan_and_inf_finite"))))
+    assert not np.any(np.isnan(stats)) and not np.any(np.isnan(r)) and not np.any(np.isnan(zf))
+    check_against_reference("nan_and_inf_finite", stats, dict(rank=r, z=z, rank_folded=rf, z_folded=zf))
+    for name in ("long_chain", "edge_N16_W128"):
+        check_against_reference(name, fresh[name][0], dict(rank_folded=fresh[name][1], z_folded=fresh[name][2]))
 
 
 @pytest.mark.parametrize("name", ["smallest", "global_passes"])

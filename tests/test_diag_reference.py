@@ -66,7 +66,7 @@ def test_a_scale_difference_is_caught_by_the_folded_rhat_alone():
 
 
 def test_ties_get_average_ranks():
-    for name in ("ties", "signed_zero"):
+    for name in ("ties", "signed_zero", "censored"):
         x, r = cases.draws(name), cases.reference(name)
         for k in range(x.shape[1]):
             v = ref.used(x)[k]
@@ -74,6 +74,49 @@ def test_ties_get_average_ranks():
             assert np.array_equal(ref.used(r["rank"])[k], want), (name, k)
     z = ref.used(cases.reference("signed_zero")["rank"])[0][ref.used(cases.draws("signed_zero"))[0] == 0.0]
     assert z.size > 1 and np.all(z == z[0])      # −0 and +0 share one rank
+
+
+def tie_runs(s, longer_than):
+    """[(first key, length)] of the runs of equal keys of the sorted s that are longer than `longer_than`"""
+    _, first, count = np.unique(s, return_index=True, return_counts=True)
+    return [(int(f), int(c)) for f, c in zip(first, count) if c > longer_than]
+
+
+def test_long_chain_walks_rho_beyond_the_lags_held_in_lds():
+    """what the case is for: T > 1024 puts ρ_t into the work array, and row 0's Geyer loops run past lag 1024 while row 1's stop early"""
+    n, Wc, K = cases.CASES["long_chain"][2]
+    T = -(-(n // 2) // ref.LAG_BLOCK) * ref.LAG_BLOCK
+    assert T == 1056 and T > 1024 and (n // 2) % ref.LAG_BLOCK
+    m = cases.reference("long_chain")["margins"]
+    print("long_chain: max_t of " + ", ".join(ref.Margins.QUANTITIES) + f": row 0 {m.max_t[0]}, row 1 {m.max_t[1]}")
+    assert len(m.max_t[0]) == 4 and all(t is not None and t > 1024 for t in m.max_t[0]), m.max_t[0]
+    assert len(m.max_t[1]) == 4 and all(t is not None and t < 16 for t in m.max_t[1]), m.max_t[1]
+
+
+def test_censored_has_tie_runs_longer_than_a_sort_block_at_both_ends_and_no_tail_ess():
+    x, r = cases.draws("censored"), cases.reference("censored")
+    v = ref.used(x)
+    S = v[0].size
+    assert S == 5120
+    runs = [tie_runs(np.sort(v[k], axis=None), 100) for k in range(2)]
+    print(f"censored: tie runs (first key, length) of row 0 {runs[0]}, of row 1 {runs[1]}")
+    assert runs[0] == [(0, 2135), (2943, 2177)] and runs[1] == [(4303, 817)]
+    assert all(c > ref.SORT_BLOCK for _, c in runs[0])                               # each crosses a sort block whole
+    assert runs[0][0][0] == 0 and sum(runs[0][1]) == S and sum(runs[1][0]) == S      # one begins at key 0, two end at key S
+    s = r["stats"]
+    assert np.array_equal(s[ref.Q95], [x[:, 0].max(), x[:, 1].max()]) and np.array_equal(s[ref.Q95], [0.2, 1.0])
+    assert np.all(np.isnan(s[ref.ESS_TAIL])) and not np.any(np.isnan(np.delete(s, ref.ESS_TAIL, axis=0)))
+    assert all(r["margins"].max_t[k][2] is None and None not in r["margins"].max_t[k][:2] for k in range(2))      # 1[x <= q95] is constant; 1[x <= q05] is not
+
+
+def test_stuck_chain_has_one_chain_of_zero_variance_in_a_valid_row():
+    x, r = cases.draws("stuck_chain"), cases.reference("stuck_chain")
+    assert np.all(x[:, 1, 2] == 0.7) and sum(bool(np.all(x[:, k, w] == x[0, k, w])) for k in range(2) for w in range(5)) == 1
+    assert not np.any(np.isnan(r["stats"]))
+    z = ref.used(r["z"])[1]
+    assert np.all(z[[2, 7]] == z[2, 0]) and np.all(ref.used(r["rank"])[1][[2, 7]] == ref.used(r["rank"])[1][2, 0])      # both halves of it: N tied ranks each, one z
+    print(f"stuck_chain: rhat of row 1 {r['stats'][ref.RHAT, 1]:.4f}")
+    assert 1.05 < r["stats"][ref.RHAT, 1] < 1.2
 
 
 def test_odd_n_drops_the_middle_sample():
@@ -127,9 +170,24 @@ def test_every_gpu_case_keeps_its_decision_margins(name):
     assert m.geyer >= cases.MARGIN_BAR and m.monotone >= cases.MARGIN_BAR, (name, m.geyer, m.monotone)
 
 
+def test_the_finite_twin_is_nan_and_inf_without_its_two_entries_and_keeps_its_margins():
+    a, b = cases.draws("nan_and_inf"), cases.draws("nan_and_inf_finite")
+    assert a.shape == b.shape and np.all(np.isfinite(b)) and int(np.sum(a != b)) == 2 and not np.isfinite(a[3, 1, 2]) and not np.isfinite(a[9, 3, 0])
+    r = cases.reference("nan_and_inf_finite")
+    m = r["margins"]
+    print(f"nan_and_inf_finite: Geyer margin {m.geyer:.3e}, monotone margin {m.monotone:.3e}")
+    assert not np.any(np.isnan(r["stats"])) and m.geyer >= cases.MARGIN_BAR and m.monotone >= cases.MARGIN_BAR
+    for k in (0, 2):      # the rows the poison did not touch are the same rows
+        assert np.array_equal(r["stats"][:, k], cases.reference("nan_and_inf")["stats"][:, k])
+
+
 def test_shapes_of_the_cases_are_the_listed_ones():
-    listed = {(8, 1, 1), (9, 3, 2), (35, 257, 3), (400, 64, 2), (130, 1100, 1), (16, 2, 64)}
-    assert listed <= {shape for _, _, shape in cases.CASES.values()}
+    listed = {(8, 1, 1), (9, 3, 2), (35, 257, 3), (400, 64, 2), (130, 1100, 1), (16, 2, 64), (2082, 3, 2), (80, 64, 2), (24, 5, 2)}
+    edges = {(2 * Nh + Nh % 2, Wc, 2) for Nh in (15, 16, 17, 31, 32, 33) for Wc in (32, 33, 128, 129)}
+    assert len(edges) == 24 and len(cases.EDGES) == 24 and len(cases.CASES) == 37
+    assert listed | edges <= {shape for _, _, shape in cases.CASES.values()}
+    assert {2 * Wc * (n // 2) for n, Wc, _ in edges} >= {2048, 4096, 8192}      # S a power of two: no padding behind the keys
+    assert [(name, seed) for name, seed, _ in cases.EDGES][:2] == [("edge_N15_W32", 41), ("edge_N15_W33", 42)] and cases.CASES["edge_N16_W128"][2] == (32, 128, 2)
     for name in cases.CASES:
         cases.draws(name)
 
