@@ -1,5 +1,9 @@
 // octo_draws_common.h — what the translation units of liboctofitter_hip_draws.so share: the handle, the counter generator, the prior
-// helpers on top of octo_model.h's device routines, the tempered target of the two samplers, and the argument checks their functions repeat.
+// helpers on top of octo_model.h's device routines, the argument checks their functions repeat, and what the lockstep algorithms have in
+// common. On the device: the metric (inv_mass_at, momentum_of: the only readers of inv_mass), the head of the two samplers' kernel arguments
+// (SamplerHead), the per-lane preamble (Chain, chain_of) and the tempered target at a point (Target, target_at over prior_loop, tempered_energy,
+// dead_state). On the host: check_sampler_call, sampler_head, logpost_at (every octo_model_logpost_device call of the four units) and
+// run_rounds (the round driver of the L-BFGS and of NUTS).
 // Seven units include it: octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
 // explorer), octo_draws_nuts.hip (the no-U-turn sampler), octo_draws_lbfgs.hip (the multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder
 // on its paths), octo_draws_adapt.hip (the warm-up statistics of the explorer) and octo_draws_diag.hip (the convergence diagnostics of stored draws). Everything but the handle lives in an unnamed namespace,
@@ -116,6 +120,59 @@ __device__ __forceinline__ double prior_loop(const octo_prior* priors, const dou
     return healed ? HEALED : lpt;
 }
 
+// ---- the metric: every use of inv_mass in the library goes through these two
+// m⁻¹ of coordinate d of the diagonal metric inv_mass [D], null = the identity
+__device__ __forceinline__ double inv_mass_at(const double* inv_mass, int d) { return inv_mass ? inv_mass[d] : 1.0; }
+// the momentum p = z/√m⁻¹ of a standard normal z (a null metric takes z bit for bit)
+__device__ __forceinline__ double momentum_of(const double* inv_mass, int d, double z) { return inv_mass ? z / sqrt(inv_mass[d]) : z; }
+
+// ---- the head of the two samplers' kernel arguments (HmcArgs, NutsArgs derive from it), filled by sampler_head
+struct SamplerHead {
+    const octo_prior* priors;      // [D]
+    const double* pc;              // [D][PRIOR_NC]
+    const double* beta;            // [W] or null = 1 (ignored without a model: 0)
+    const double* eps_w;           // [W] or null = eps
+    const double* inv_mass;        // [D] or null = 1
+    double eps;
+    uint64_t seed, step, chain0;
+    int64_t W, ld;
+    int32_t D, has_model;
+    double* theta_t;               // [D][ld] the caller's states
+};
+
+// The chain of a lane: w its index, live = it is inside the batch, wl = the column it reads (a lane beyond the batch: the last chain's), its
+// β and ε. No kernel leaves a lane out ahead of target_at: prior_loop votes across the wave, so EVERY lane of the wave goes on to it.
+struct Chain {
+    int64_t w, wl;
+    bool live;
+    double beta, eps;
+};
+__device__ __forceinline__ Chain chain_of(const SamplerHead& a) {
+    const int64_t w = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    const bool live = w < a.W;
+    const int64_t wl = live ? w : a.W - 1;
+    return {w, wl, live, a.has_model ? (a.beta ? a.beta[wl] : 1.0) : 0.0, a.eps_w ? a.eps_w[wl] : a.eps};
+}
+
+// The target of chain c at the point `at` [D][ld]: ℓprior_t and whether the prior was healed (prior_loop; gpr [D][ld] receives ∇ℓprior_t), ℓπ from
+// lp [W] and ∇E at offset o from glp [D][ld] (∇ℓπ; both null without a model) and gpr, with ∇ℓprior_t = 0 in every coordinate of a healed
+// prior. ℓπ is 0 without a model (E and ∇E consult it only where β != 0, the outputs report it for every chain). lp(column) reads it where
+// the kernel asks: k_nuts_open and k_nuts_leaf do so once the lanes beyond the batch have left (read ahead of that exit, each takes 4 more VGPRs).
+struct Target {
+    double lpt, beta;
+    bool healed;
+    int32_t has_model;
+    const double *lpi, *glp, *gpr;
+    __device__ __forceinline__ double lp(int64_t w) const { return has_model ? lpi[w] : 0.0; }
+    __device__ __forceinline__ double grad(int64_t o) const { return tempered_gradient(beta, glp, o, healed ? 0.0 : gpr[o]); }
+};
+__device__ __forceinline__ Target target_at(const SamplerHead& a, const Chain& c, const double* __restrict__ at, const double* lp, const double* glp, double* gpr) {
+    Target t;
+    t.lpt = prior_loop(a.priors, a.pc, a.D, at, a.ld, c.w, c.wl, c.live, gpr, t.healed);
+    t.beta = c.beta; t.has_model = a.has_model; t.lpi = lp; t.glp = glp; t.gpr = gpr;
+    return t;
+}
+
 }  // namespace
 
 struct octo_draws : CompanionBase {
@@ -186,6 +243,48 @@ inline int check_chains(octo_draws* h, const char* who, int64_t W, int64_t ld, i
 inline int check_tolerances(octo_draws* h, const char* who, double gtol, double ftol) {
     if (!(std::isfinite(gtol) && gtol >= 0.0)) return fail(h, OCTO_EINVAL, std::string(who) + ": gtol must be finite and >= 0");
     return std::isfinite(ftol) && ftol >= 0.0 ? OCTO_OK : fail(h, OCTO_EINVAL, std::string(who) + ": ftol must be finite and >= 0");
+}
+// the checks of the two samplers, in their order: the chains, ε, and no ℓπ outputs from a handle without a model
+inline int check_sampler_call(octo_draws* h, const char* who, int64_t W, int64_t ld, const double* d_eps, double eps, bool has_model, const double* d_logpost,
+                              const double* d_loglike) {
+    if (int rc = check_chains(h, who, W, ld, MAX_CHAINS, "2^30")) return rc;
+    if (!d_eps && !(eps > 0.0 && std::isfinite(eps))) return fail(h, OCTO_EINVAL, std::string(who) + ": eps must be finite and > 0 when d_eps is NULL");
+    return has_model || !(d_logpost || d_loglike) ? OCTO_OK : fail(h, OCTO_EINVAL, std::string(who) + ": the handle has no model (created without one, or detached): d_logpost and d_loglike must be NULL");
+}
+
+inline SamplerHead sampler_head(const octo_draws* h, bool has_model, uint64_t seed, uint64_t step, uint64_t chain0, int64_t W, int64_t ld, double* d_theta_t,
+                                const double* d_beta, const double* d_eps, double eps, const double* d_inv_mass) {
+    return {h->d_priors, h->d_pc, d_beta, d_eps, d_inv_mass, eps, seed, step, chain0, W, ld, h->D, has_model ? 1 : 0, d_theta_t};
+}
+
+// ℓπ [W] and ∇ℓπ [D][ld] (or null) at the points `at` [D][ld] on the stream st; nothing to do on a handle without a model
+inline int logpost_at(octo_draws* h, hipStream_t st, bool has_model, const double* at, int64_t ld, int64_t W, double* lp, double* glp) {
+    return has_model ? main_call(h, octo_model_logpost_device(h->ctx, h->model, at, ld, W, lp, glp, (void*)st), "octo_model_logpost_device") : OCTO_OK;
+}
+
+// The round driver of the L-BFGS and of NUTS. Args holds W, ld, write_out and its state s with the trial points s.trial; lp and glp are where
+// ℓπ and ∇ℓπ go (a.s.lp and a.s.glp may be nulled for the kernels). Not resumed: ℓπ at θ_t and `open`, which writes the outputs when no
+// round follows; n_rounds times ℓπ at the trial points and `round`, the last writing the outputs; resumed with no round: `report`.
+template <class Args>
+int run_rounds(octo_draws* h, hipStream_t st, Args& a, bool has_model, const double* d_theta_t, double* lp, double* glp, int32_t n_rounds, bool resume,
+               void (*open)(Args), void (*round)(Args), void (*report)(Args)) {
+    const dim3 grid = grid_of(a.W), block(TPB);
+    if (!resume) {
+        if (int rc = logpost_at(h, st, has_model, d_theta_t, a.ld, a.W, lp, glp)) return rc;
+        a.write_out = n_rounds == 0;
+        hipLaunchKernelGGL(open, grid, block, 0, st, a);
+    }
+    for (int r = 1; r <= n_rounds; ++r) {
+        if (int rc = logpost_at(h, st, has_model, a.s.trial, a.ld, a.W, lp, glp)) return rc;
+        a.write_out = r == n_rounds;
+        hipLaunchKernelGGL(round, grid, block, 0, st, a);
+    }
+    if (resume && n_rounds == 0) {
+        a.write_out = 1;
+        hipLaunchKernelGGL(report, grid, block, 0, st, a);
+    }
+    OCHK(h, hipGetLastError());
+    return OCTO_OK;
 }
 
 }  // namespace

@@ -8,6 +8,8 @@
 //   k_hmc_leap<STEP>   a point inside the trajectory: prior value and derivative at it, the whole kick and the drift.
 //   k_hmc_leap<LAST>   the end point: the half kick, H₁, the decision, the selection and every output.
 // A step is ⌈D/4⌉ + 1 + n_leapfrog launches besides the n_leapfrog + 1 log-posterior calls; the host reads nothing.
+// From octo_draws_common.h: the head of HmcArgs and its filling, the lane's chain (chain_of), the target at a point (target_at), the metric
+// (inv_mass_at, momentum_of), the shared argument checks (check_sampler_call) and the log-posterior call (logpost_at).
 #include "octo_draws_common.h"
 
 namespace {
@@ -31,68 +33,52 @@ __global__ __launch_bounds__(TPB) void k_hmc_momentum(MomentumArgs a) {
     for (int q = 0; q < 4; ++q) {
         const int d = a.d0 + q;
         if (d >= a.D) break;
-        const double z = normcdfinv(u01(r[q]));
-        a.p[(int64_t)d * a.ld + t] = a.inv_mass ? z / sqrt(a.inv_mass[d]) : z;
+        a.p[(int64_t)d * a.ld + t] = momentum_of(a.inv_mass, d, normcdfinv(u01(r[q])));
     }
 }
 
-struct HmcArgs {
-    const octo_prior* priors;      // [D]
-    const double* pc;              // [D][PRIOR_NC]
-    const double* beta;            // [W] or null = 1 (ignored without a model: 0)
-    const double* eps_w;           // [W] or null = eps
-    const double* inv_mass;        // [D] or null = 1
-    double eps;
-    uint64_t seed, step, chain0;
-    int64_t W, ld;
-    int32_t D, has_model;
-    double* theta_t;               // [D][ld] the caller's states: read by OPEN, written by LAST where a chain accepts
-    double* q;                     // [D][ld] the moving point
-    double* p;                     // [D][ld] its momentum
-    const double* glp;             // [D][ld] ∇ℓπ at the point of this launch (null without a model)
-    double* gpr;                   // [D][ld] ∇ℓprior_t at it, between the two loops of a launch
-    const double* lp;              // [W] ℓπ at it (null without a model)
-    double *lp0, *lpt0, *K0;       // [W] of the start point, from OPEN to LAST
+// theta_t is read by OPEN and written by LAST where a chain accepts. Of s: q the moving point and p its momentum; glp and lp, ∇ℓπ and ℓπ at the
+// point of this launch (null without a model); gpr, ∇ℓprior_t at it, between the two loops of a launch; lp0, lpt0, K0 of the start point, from
+// OPEN to LAST.
+struct HmcArgs : SamplerHead {
+    HmcWork s;
     double *theta_prop, *o_lp, *o_ll, *o_dH;
     int32_t* o_acc;
 };
 
-// Two loops over the coordinates. The first is prior_loop (octo_draws_common.h, shared with the no-U-turn sampler): every transcendental, and
-// ∇ℓprior_t left in a.gpr. The second is arithmetic alone.
+// Two loops over the coordinates. The first is target_at's prior_loop() (octo_draws_common.h, shared with the no-U-turn sampler): every
+// transcendental, and ∇ℓprior_t left in a.s.gpr. The second is arithmetic alone.
 template <int PHASE>
 __global__ __launch_bounds__(TPB) void k_hmc_leap(HmcArgs a) {
-    const int64_t w = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    const bool live = w < a.W;                          // no early exit: prior_density_lanes votes across the wave
-    const int64_t wl = live ? w : a.W - 1;
-    const double beta = a.has_model ? (a.beta ? a.beta[wl] : 1.0) : 0.0;
-    const double eps = a.eps_w ? a.eps_w[wl] : a.eps;
-    const double* __restrict__ at = PHASE == HMC_OPEN ? a.theta_t : a.q;
-    bool healed;
-    const double lpt = prior_loop(a.priors, a.pc, a.D, at, a.ld, w, wl, live, a.gpr, healed);
-    const double lp = a.has_model ? a.lp[wl] : 0.0;      // E and ∇E consult it only where β != 0; the outputs report it for every chain
+    const Chain ch = chain_of(a);
+    const int64_t w = ch.w, wl = ch.wl;
+    const bool live = ch.live;
+    const double beta = ch.beta, eps = ch.eps;
+    const double* __restrict__ at = PHASE == HMC_OPEN ? a.theta_t : a.s.q;
+    const Target tg = target_at(a, ch, at, a.s.lp, a.s.glp, a.s.gpr);
+    const double lp = tg.lp(wl), lpt = tg.lpt;
     const double kick = PHASE == HMC_STEP ? eps : 0.5 * eps;
     double K = 0.0;
     for (int d = 0; d < a.D; ++d) {
         const int64_t o = (int64_t)d * a.ld + wl;
-        const double im = a.inv_mass ? a.inv_mass[d] : 1.0;
-        const double gp = healed ? 0.0 : a.gpr[o];
-        const double g = tempered_gradient(beta, a.glp, o, gp);
-        double pd = a.p[o];
+        const double im = inv_mass_at(a.inv_mass, d);
+        const double g = tg.grad(o);
+        double pd = a.s.p[o];
         if (PHASE == HMC_OPEN) K += im * pd * pd;
         pd += kick * g;
         if (PHASE == HMC_LAST) K += im * pd * pd;
         else if (live) {
-            a.p[o] = pd;
-            a.q[o] = at[o] + eps * (im * pd);
+            a.s.p[o] = pd;
+            a.s.q[o] = at[o] + eps * (im * pd);
         }
     }
     K *= 0.5;
-    if (PHASE == HMC_OPEN && live) { a.lp0[w] = lp; a.lpt0[w] = lpt; a.K0[w] = K; }
+    if (PHASE == HMC_OPEN && live) { a.s.lp0[w] = lp; a.s.lpt0[w] = lpt; a.s.K0[w] = K; }
     if (PHASE != HMC_LAST) return;
-    const double lp0 = a.lp0[wl], lpt0 = a.lpt0[wl];
+    const double lp0 = a.s.lp0[wl], lpt0 = a.s.lpt0[wl];
     const double E0 = tempered_energy(beta, lp0, lpt0), E1 = tempered_energy(beta, lp, lpt);
     const bool dead0 = dead_state(beta, E0, lp0, lpt0), dead1 = dead_state(beta, E1, lp, lpt);
-    const double dH = (-E0 + a.K0[wl]) - (-E1 + K);
+    const double dH = (-E0 + a.s.K0[wl]) - (-E1 + K);
     uint64_t r[4];
     philox4x64(a.seed, KEY1, a.chain0 + (uint64_t)wl, 0, OCTO_DRAWS_PURPOSE_ACCEPT, a.step, r);
     const bool acc = !dead1 && (dead0 || log(u01(r[0])) < dH);
@@ -100,7 +86,7 @@ __global__ __launch_bounds__(TPB) void k_hmc_leap(HmcArgs a) {
     if (acc || a.theta_prop)
         for (int d = 0; d < a.D; ++d) {
             const int64_t o = (int64_t)d * a.ld + w;
-            const double y = a.q[o];
+            const double y = a.s.q[o];
             if (a.theta_prop) a.theta_prop[o] = y;
             if (acc) a.theta_t[o] = y;
         }
@@ -140,32 +126,24 @@ int32_t octo_draws_hmc_step_device(octo_draws* h, uint64_t seed, uint64_t step, 
                                    double* d_theta_prop, double* d_logpost, double* d_loglike, double* d_dH, int32_t* d_accepted, void* hip_stream) {
     if (!h) return OCTO_EINVAL;
     if (n_leapfrog < 1) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: n_leapfrog >= 1");
-    if (int rc = check_chains(h, "octo_draws_hmc_step_device", W, ld, MAX_CHAINS, "2^30")) return rc;
-    if (!d_eps && !(eps > 0.0 && std::isfinite(eps))) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: eps must be finite and > 0 when d_eps is NULL");
     const bool has_model = h->model && h->ctx;
-    if (!has_model && (d_logpost || d_loglike))
-        return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: the handle has no model (created without one, or detached): d_logpost and d_loglike must be NULL");
+    if (int rc = check_sampler_call(h, "octo_draws_hmc_step_device", W, ld, d_eps, eps, has_model, d_logpost, d_loglike)) return rc;
     if (W == 0) return OCTO_OK;
     if (!d_theta_t || !d_accepted) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: d_theta_t and d_accepted are required");
     OCHK(h, hipSetDevice(h->device));
     const hipStream_t st = stream_of(h, hip_stream);
-    HmcWork w;
-    if (int rc = grow_to(h, h->d_hmc, h->cap_hmc, w, hmc_work, (int64_t)h->D, ld)) return rc;
-    HmcArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.priors = h->d_priors; a.pc = h->d_pc; a.beta = d_beta; a.eps_w = d_eps; a.inv_mass = d_inv_mass; a.eps = eps;
-    a.seed = seed; a.step = step; a.chain0 = chain0; a.W = W; a.ld = ld; a.D = h->D; a.has_model = has_model ? 1 : 0;
-    a.theta_t = d_theta_t;
-    a.q = w.q; a.p = w.p; a.gpr = w.gpr; a.lp0 = w.lp0; a.lpt0 = w.lpt0; a.K0 = w.K0;
-    if (has_model) { a.glp = w.glp; a.lp = w.lp; }
+    HmcArgs a{sampler_head(h, has_model, seed, step, chain0, W, ld, d_theta_t, d_beta, d_eps, eps, d_inv_mass)};
+    if (int rc = grow_to(h, h->d_hmc, h->cap_hmc, a.s, hmc_work, (int64_t)h->D, ld)) return rc;
+    double *lp = a.s.lp, *glp = a.s.glp;
+    if (!has_model) { a.s.lp = nullptr; a.s.glp = nullptr; }
     a.theta_prop = d_theta_prop; a.o_lp = d_logpost; a.o_ll = d_loglike; a.o_dH = d_dH; a.o_acc = d_accepted;
     const dim3 grid = grid_of(W), block(TPB);
-    launch_momentum(st, seed, step, chain0, W, ld, h->D, d_inv_mass, a.p);
+    launch_momentum(st, seed, step, chain0, W, ld, h->D, d_inv_mass, a.s.p);
     OCHK(h, hipGetLastError());
-    if (has_model) { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, d_theta_t, ld, W, w.lp, w.glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+    if (int rc = logpost_at(h, st, has_model, d_theta_t, ld, W, lp, glp)) return rc;
     hipLaunchKernelGGL(k_hmc_leap<HMC_OPEN>, grid, block, 0, st, a);
     for (int s = 1; s <= n_leapfrog; ++s) {
-        if (has_model) { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, a.q, ld, W, w.lp, w.glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+        if (int rc = logpost_at(h, st, has_model, a.s.q, ld, W, lp, glp)) return rc;
         if (s < n_leapfrog) hipLaunchKernelGGL(k_hmc_leap<HMC_STEP>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(k_hmc_leap<HMC_LAST>, grid, block, 0, st, a);
     }

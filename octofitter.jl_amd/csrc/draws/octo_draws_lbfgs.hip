@@ -10,6 +10,8 @@
 //                            new direction (lbfgs_two_loop); on reject the halved step. The last launch of a call writes the outputs.
 //   k_lbfgs_advance<REPORT>  the outputs alone: a resumed call of no rounds.
 //   k_lbfgs_direction        lbfgs_two_loop alone on a caller's history (octo_draws_lbfgs_direction_device).
+// LbfgsArgs holds the state as octo_draws_layout.h lays it out (a.s). From octo_draws_common.h: the metric v (inv_mass_at) and run_rounds, the
+// round driver shared with NUTS, which makes the log-posterior calls and the three launches in their order.
 #include "octo_draws_common.h"
 
 namespace {
@@ -45,11 +47,11 @@ __device__ __forceinline__ void lbfgs_two_loop(int32_t D, int32_t m, int64_t ld,
         double yy = 0.0;
         for (int d = 0; d < D; ++d) {
             const double yd = y[(int64_t)d * ld];
-            yy += yd * yd * (inv_mass ? inv_mass[d] : 1.0);
+            yy += yd * yd * inv_mass_at(inv_mass, d);
         }
         gamma = sy[(int64_t)newest * ld + w] / yy;
     }
-    for (int d = 0; d < D; ++d) dir[(int64_t)d * ld + w] *= gamma * (inv_mass ? inv_mass[d] : 1.0);
+    for (int d = 0; d < D; ++d) dir[(int64_t)d * ld + w] *= gamma * inv_mass_at(inv_mass, d);
     for (int k = m - 1; k >= 0; --k) {
         if (k >= cnt) continue;
         int32_t slot = head - 1 - k;
@@ -97,13 +99,7 @@ struct LbfgsArgs {
     int32_t D, m, write_out;
     double gtol, ftol;
     double* x;                     // [D][ld] the caller's θ_t: read everywhere, written where a chain accepts
-    double *trial, *g, *dir, *alpha;      // [D][ld]
-    double *S, *Y;                 // [m][D][ld]
-    const double* glp;             // [D][ld] ∇ℓπ at the point of this launch
-    const double* lp;              // [W] ℓπ at it
-    double *sy, *coef;             // [m][ld]
-    double *f, *t, *gd, *gn;       // [ld]
-    int32_t *status, *iters, *evals, *nbt, *cnt, *head;      // [ld]
+    LbfgsState s;                  // glp, lp: ∇ℓπ and ℓπ at the point of this launch
     double *o_lp, *o_gn, *o_ihd;
     int32_t *o_status, *o_iters, *o_evals;
 };
@@ -113,8 +109,8 @@ __device__ __forceinline__ double steepest(const LbfgsArgs& a, int64_t w) {
     double gd = 0.0;
     for (int d = 0; d < a.D; ++d) {
         const int64_t o = (int64_t)d * a.ld + w;
-        const double gv = a.g[o], dv = -(a.inv_mass ? a.inv_mass[d] : 1.0) * gv;
-        a.dir[o] = dv;
+        const double gv = a.s.g[o], dv = -inv_mass_at(a.inv_mass, d) * gv;
+        a.s.dir[o] = dv;
         gd += gv * dv;
     }
     return gd;
@@ -123,7 +119,7 @@ __device__ __forceinline__ double steepest(const LbfgsArgs& a, int64_t w) {
 __device__ __forceinline__ void set_trial(const LbfgsArgs& a, int64_t w, double t, bool moving) {
     for (int d = 0; d < a.D; ++d) {
         const int64_t o = (int64_t)d * a.ld + w;
-        a.trial[o] = moving ? a.x[o] + t * a.dir[o] : a.x[o];
+        a.s.trial[o] = moving ? a.x[o] + t * a.s.dir[o] : a.x[o];
     }
 }
 
@@ -133,90 +129,90 @@ __global__ __launch_bounds__(TPB) void k_lbfgs_advance(LbfgsArgs a) {
     if (w >= a.W) return;
     const int64_t plane = (int64_t)a.D * a.ld;
     if (PHASE == LB_OPEN) {
-        const double f = -a.lp[w];
+        const double f = -a.s.lp[w];
         bool fin = isfinite(f);
         double gg = 0.0, gn = 0.0;
         for (int d = 0; d < a.D; ++d) {
             const int64_t o = (int64_t)d * a.ld + w;
-            const double v = a.inv_mass ? a.inv_mass[d] : 1.0, gv = -a.glp[o];
+            const double v = inv_mass_at(a.inv_mass, d), gv = -a.s.glp[o];
             fin = fin && isfinite(gv);
-            a.g[o] = gv;
-            a.alpha[o] = v;
+            a.s.g[o] = gv;
+            a.s.alpha[o] = v;
             gg += v * gv * gv;
             gn = fmax(gn, fabs(gv) * sqrt(v));
         }
-        a.f[w] = f; a.gn[w] = fin ? gn : NAN;
-        a.iters[w] = 0; a.evals[w] = 1; a.nbt[w] = 0; a.cnt[w] = 0; a.head[w] = 0;
-        a.status[w] = fin ? OCTO_DRAWS_LBFGS_ACTIVE : OCTO_DRAWS_LBFGS_DEAD;
+        a.s.f[w] = f; a.s.gn[w] = fin ? gn : NAN;
+        a.s.iters[w] = 0; a.s.evals[w] = 1; a.s.nbt[w] = 0; a.s.cnt[w] = 0; a.s.head[w] = 0;
+        a.s.status[w] = fin ? OCTO_DRAWS_LBFGS_ACTIVE : OCTO_DRAWS_LBFGS_DEAD;
         double t = 0.0, gd = 0.0;
         if (fin) {
             gd = steepest(a, w);
             t = fmin(1.0, 1.0 / sqrt(gg));
         }
-        a.t[w] = t; a.gd[w] = gd;
+        a.s.t[w] = t; a.s.gd[w] = gd;
         set_trial(a, w, t, fin);
-    } else if (PHASE == LB_ROUND && a.status[w] == OCTO_DRAWS_LBFGS_ACTIVE) {
-        const double f = a.f[w], t = a.t[w], ft = -a.lp[w];
+    } else if (PHASE == LB_ROUND && a.s.status[w] == OCTO_DRAWS_LBFGS_ACTIVE) {
+        const double f = a.s.f[w], t = a.s.t[w], ft = -a.s.lp[w];
         bool fin = isfinite(ft);
-        for (int d = 0; d < a.D; ++d) fin = fin && isfinite(a.glp[(int64_t)d * a.ld + w]);
-        a.evals[w] += 1;
-        if (fin && ft <= f + LB_C1 * t * a.gd[w]) {
+        for (int d = 0; d < a.D; ++d) fin = fin && isfinite(a.s.glp[(int64_t)d * a.ld + w]);
+        a.s.evals[w] += 1;
+        if (fin && ft <= f + LB_C1 * t * a.s.gd[w]) {
             double sy = 0.0, ss = 0.0, yy = 0.0, pa = 0.0, pc = 0.0;
             for (int d = 0; d < a.D; ++d) {
                 const int64_t o = (int64_t)d * a.ld + w;
-                const double v = a.inv_mass ? a.inv_mass[d] : 1.0, al = a.alpha[o];
-                const double s = a.trial[o] - a.x[o], y = -a.glp[o] - a.g[o];
+                const double v = inv_mass_at(a.inv_mass, d), al = a.s.alpha[o];
+                const double s = a.s.trial[o] - a.x[o], y = -a.s.glp[o] - a.s.g[o];
                 sy += s * y; ss += s * s / v; yy += y * y * v; pa += y * y * al; pc += s * s / al;
             }
             const bool store = sy > LB_CURV * sqrt(ss * yy);
-            int32_t cnt = a.cnt[w], head = a.head[w];
-            double* __restrict__ Ss = a.S + head * plane;
-            double* __restrict__ Ys = a.Y + head * plane;
+            int32_t cnt = a.s.cnt[w], head = a.s.head[w];
+            double* __restrict__ Ss = a.s.S + head * plane;
+            double* __restrict__ Ys = a.s.Y + head * plane;
             double gn = 0.0;
             for (int d = 0; d < a.D; ++d) {
                 const int64_t o = (int64_t)d * a.ld + w;
-                const double v = a.inv_mass ? a.inv_mass[d] : 1.0;
-                const double xt = a.trial[o], gt = -a.glp[o];
-                const double s = xt - a.x[o], y = gt - a.g[o];
+                const double v = inv_mass_at(a.inv_mass, d);
+                const double xt = a.s.trial[o], gt = -a.s.glp[o];
+                const double s = xt - a.x[o], y = gt - a.s.g[o];
                 if (store) {
-                    const double al = a.alpha[o];
+                    const double al = a.s.alpha[o];
                     Ss[o] = s; Ys[o] = y;
-                    a.alpha[o] = 1.0 / (pa / (sy * al) + y * y / sy - pa * s * s / (sy * pc * al * al));
+                    a.s.alpha[o] = 1.0 / (pa / (sy * al) + y * y / sy - pa * s * s / (sy * pc * al * al));
                 }
-                a.x[o] = xt; a.g[o] = gt;
+                a.x[o] = xt; a.s.g[o] = gt;
                 gn = fmax(gn, fabs(gt) * sqrt(v));
             }
             if (store) {
-                a.sy[(int64_t)head * a.ld + w] = sy;
+                a.s.sy[(int64_t)head * a.ld + w] = sy;
                 head = head + 1 == a.m ? 0 : head + 1;
                 cnt = min(cnt + 1, a.m);
             }
-            a.f[w] = ft; a.gn[w] = gn; a.iters[w] += 1; a.nbt[w] = 0;
-            if (gn <= a.gtol) a.status[w] = OCTO_DRAWS_LBFGS_GTOL;      // the trial point is x already: a frozen chain's trial point
-            else if (a.ftol > 0.0 && fabs(f - ft) <= a.ftol * fmax(1.0, fabs(ft))) a.status[w] = OCTO_DRAWS_LBFGS_FTOL;
+            a.s.f[w] = ft; a.s.gn[w] = gn; a.s.iters[w] += 1; a.s.nbt[w] = 0;
+            if (gn <= a.gtol) a.s.status[w] = OCTO_DRAWS_LBFGS_GTOL;      // the trial point is x already: a frozen chain's trial point
+            else if (a.ftol > 0.0 && fabs(f - ft) <= a.ftol * fmax(1.0, fabs(ft))) a.s.status[w] = OCTO_DRAWS_LBFGS_FTOL;
             else {
-                lbfgs_two_loop(a.D, a.m, a.ld, w, cnt, head, a.S, a.Y, a.sy, a.g, a.inv_mass, a.coef, a.dir);
+                lbfgs_two_loop(a.D, a.m, a.ld, w, cnt, head, a.s.S, a.s.Y, a.s.sy, a.s.g, a.inv_mass, a.s.coef, a.s.dir);
                 double gd = 0.0;
-                for (int d = 0; d < a.D; ++d) gd += a.g[(int64_t)d * a.ld + w] * a.dir[(int64_t)d * a.ld + w];
+                for (int d = 0; d < a.D; ++d) gd += a.s.g[(int64_t)d * a.ld + w] * a.s.dir[(int64_t)d * a.ld + w];
                 if (!(gd < 0.0)) { cnt = 0; head = 0; gd = steepest(a, w); }
-                a.t[w] = 1.0; a.gd[w] = gd;
+                a.s.t[w] = 1.0; a.s.gd[w] = gd;
                 set_trial(a, w, 1.0, true);
             }
-            a.cnt[w] = cnt; a.head[w] = head;
+            a.s.cnt[w] = cnt; a.s.head[w] = head;
         } else {
-            const int32_t nbt = a.nbt[w] + 1;
+            const int32_t nbt = a.s.nbt[w] + 1;
             const double th = 0.5 * t;
-            a.nbt[w] = nbt; a.t[w] = th;
+            a.s.nbt[w] = nbt; a.s.t[w] = th;
             const bool failed = nbt > LB_MAX_BACKTRACKS;
-            if (failed) a.status[w] = OCTO_DRAWS_LBFGS_LINESEARCH;
+            if (failed) a.s.status[w] = OCTO_DRAWS_LBFGS_LINESEARCH;
             set_trial(a, w, th, !failed);
         }
     }
     if (!a.write_out) return;
-    a.o_lp[w] = -a.f[w]; a.o_gn[w] = a.gn[w];
-    a.o_status[w] = a.status[w]; a.o_iters[w] = a.iters[w]; a.o_evals[w] = a.evals[w];
+    a.o_lp[w] = -a.s.f[w]; a.o_gn[w] = a.s.gn[w];
+    a.o_status[w] = a.s.status[w]; a.o_iters[w] = a.s.iters[w]; a.o_evals[w] = a.s.evals[w];
     if (a.o_ihd)
-        for (int d = 0; d < a.D; ++d) a.o_ihd[(int64_t)d * a.ld + w] = a.alpha[(int64_t)d * a.ld + w];
+        for (int d = 0; d < a.D; ++d) a.o_ihd[(int64_t)d * a.ld + w] = a.s.alpha[(int64_t)d * a.ld + w];
 }
 
 }  // namespace
@@ -261,31 +257,13 @@ int32_t octo_draws_lbfgs_device(octo_draws* h, int64_t W, int64_t ld, double* d_
         h->lbf_m = 0;      // a call that fails below leaves nothing to resume
         int rc = grow(h, h->d_lbf, h->cap_lbf, carve_size(lbfgs_state, (int64_t)h->D, ld, (int64_t)m)); if (rc) return rc;
     }
-    const LbfgsState s = carve_at(h->d_lbf, lbfgs_state, (int64_t)h->D, ld, (int64_t)m);
-    LbfgsArgs a;
-    std::memset(&a, 0, sizeof(a));
+    LbfgsArgs a{};
     a.inv_mass = d_inv_mass; a.W = W; a.ld = ld; a.D = h->D; a.m = m; a.gtol = gtol; a.ftol = ftol;
     a.x = d_theta_t;
-    a.trial = s.trial; a.g = s.g; a.dir = s.dir; a.alpha = s.alpha; a.S = s.S; a.Y = s.Y; a.glp = s.glp; a.lp = s.lp; a.sy = s.sy; a.coef = s.coef;
-    a.f = s.f; a.t = s.t; a.gd = s.gd; a.gn = s.gn;
-    a.status = s.status; a.iters = s.iters; a.evals = s.evals; a.nbt = s.nbt; a.cnt = s.cnt; a.head = s.head;
+    a.s = carve_at(h->d_lbf, lbfgs_state, (int64_t)h->D, ld, (int64_t)m);
     a.o_lp = d_logpost; a.o_gn = d_gnorm; a.o_ihd = d_inv_hess_diag; a.o_status = d_status; a.o_iters = d_iters; a.o_evals = d_evals;
-    const dim3 grid = grid_of(W), block(TPB);
-    if (!resume) {
-        int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, d_theta_t, ld, W, s.lp, s.glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc;
-        a.write_out = n_rounds == 0;
-        hipLaunchKernelGGL(k_lbfgs_advance<LB_OPEN>, grid, block, 0, st, a);
-    }
-    for (int r = 1; r <= n_rounds; ++r) {
-        int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, a.trial, ld, W, s.lp, s.glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc;
-        a.write_out = r == n_rounds;
-        hipLaunchKernelGGL(k_lbfgs_advance<LB_ROUND>, grid, block, 0, st, a);
-    }
-    if (resume && n_rounds == 0) {
-        a.write_out = 1;
-        hipLaunchKernelGGL(k_lbfgs_advance<LB_REPORT>, grid, block, 0, st, a);
-    }
-    OCHK(h, hipGetLastError());
+    if (int rc = run_rounds(h, st, a, true, d_theta_t, a.s.lp, a.s.glp, n_rounds, resume != 0, k_lbfgs_advance<LB_OPEN>, k_lbfgs_advance<LB_ROUND>,
+                            k_lbfgs_advance<LB_REPORT>)) return rc;
     h->lbf_W = W; h->lbf_ld = ld; h->lbf_m = m;
     return OCTO_OK;
 }

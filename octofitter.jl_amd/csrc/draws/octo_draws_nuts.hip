@@ -11,6 +11,8 @@
 //                  the chain ends, and the opening half kick and drift of the next leaf.
 //   k_nuts_report  the outputs alone: a resumed call of no rounds.
 // The last launch of a call writes the outputs. The momenta are octo_draws_momentum_device's (purpose 2), the HMC step's.
+// From octo_draws_common.h, as the HMC step: the head of NutsArgs, chain_of, target_at, inv_mass_at, check_sampler_call; and run_rounds, the
+// round driver it shares with the L-BFGS (opening, rounds, report; the last launch writes the outputs).
 #include "octo_draws_common.h"
 
 namespace {
@@ -18,17 +20,9 @@ namespace {
 enum { NUTS_BUILDING = 0, NUTS_MAX_DEPTH = 1, NUTS_TURN_SUBTREE = 2, NUTS_TURN_TREE = 3, NUTS_DIVERGED = 4, NUTS_DEAD = 5 };
 constexpr double NUTS_DELTA_MAX = 1000.0;
 
-struct NutsArgs {
-    const octo_prior* priors;      // [D]
-    const double* pc;              // [D][PRIOR_NC]
-    const double* beta;            // [W] or null = 1 (ignored without a model: 0)
-    const double* eps_w;           // [W] or null = eps
-    const double* inv_mass;        // [D] or null = 1
-    double eps;
-    uint64_t seed, step, chain0;
-    int64_t W, ld;
-    int32_t D, has_model, max_depth, write_out;
-    double* theta_t;               // [D][ld] the caller's states: read by k_nuts_open, written where a chain ends on a leaf of its tree
+// theta_t is read by k_nuts_open and written where a chain ends on a leaf of its tree
+struct NutsArgs : SamplerHead {
+    int32_t max_depth, write_out;
     NutsWork s;
     double *o_lp, *o_ll, *o_la;
     int32_t *o_acc, *o_depth, *o_nleaf, *o_div, *o_nact;
@@ -54,7 +48,7 @@ __device__ __forceinline__ void next_leaf(const NutsArgs& a, int64_t w, int32_t 
         const int64_t o = (int64_t)d * a.ld + w;
         const double ph = pe[o] + hk * ge[o];
         a.s.pt[o] = ph;
-        a.s.trial[o] = qe[o] + dr * ((a.inv_mass ? a.inv_mass[d] : 1.0) * ph);
+        a.s.trial[o] = qe[o] + dr * (inv_mass_at(a.inv_mass, d) * ph);
     }
 }
 
@@ -85,20 +79,16 @@ __device__ __forceinline__ void report(const NutsArgs& a, int64_t w) {
 }
 
 __global__ __launch_bounds__(TPB) void k_nuts_open(NutsArgs a) {
-    const int64_t w = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    const bool live = w < a.W;                          // no early exit ahead of prior_loop: it votes across the wave
-    const int64_t wl = live ? w : a.W - 1;
-    const double beta = a.has_model ? (a.beta ? a.beta[wl] : 1.0) : 0.0;
-    const double eps = a.eps_w ? a.eps_w[wl] : a.eps;
-    bool healed;
-    const double lpt = prior_loop(a.priors, a.pc, a.D, a.theta_t, a.ld, w, wl, live, a.s.gpr, healed);
-    if (!live) return;
-    const double lp = a.has_model ? a.s.lp[w] : 0.0;
+    const Chain ch = chain_of(a);
+    const Target tg = target_at(a, ch, a.theta_t, a.s.lp, a.s.glp, a.s.gpr);      // every lane: its prior_loop() votes across the wave
+    if (!ch.live) return;
+    const int64_t w = ch.w;
+    const double beta = ch.beta, lp = tg.lp(w), lpt = tg.lpt;
     double K = 0.0;
     for (int d = 0; d < a.D; ++d) {
         const int64_t o = (int64_t)d * a.ld + w;
-        const double im = a.inv_mass ? a.inv_mass[d] : 1.0;
-        const double g = tempered_gradient(beta, a.s.glp, o, healed ? 0.0 : a.s.gpr[o]);
+        const double im = inv_mass_at(a.inv_mass, d);
+        const double g = tg.grad(o);
         const double p = a.s.pL[o], q = a.theta_t[o];      // the momenta were drawn into pL
         K += im * p * p;
         a.s.qL[o] = q; a.s.qR[o] = q; a.s.pR[o] = p; a.s.gL[o] = g; a.s.gR[o] = g;
@@ -114,22 +104,18 @@ __global__ __launch_bounds__(TPB) void k_nuts_open(NutsArgs a) {
     const int32_t v = nuts_uniform(a, w, 0, OCTO_DRAWS_PURPOSE_NUTS_DIRECTION) < 0.5 ? 1 : -1;
     a.s.v[w] = v;
     if (dead) finish(a, w, false, lp, lpt);
-    else next_leaf(a, w, v, eps);
+    else next_leaf(a, w, v, ch.eps);
     if (a.write_out) report(a, w);
 }
 
 __global__ __launch_bounds__(TPB) void k_nuts_leaf(NutsArgs a) {
-    const int64_t w = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    const bool live = w < a.W;                          // no early exit ahead of prior_loop: it votes across the wave
-    const int64_t wl = live ? w : a.W - 1;
-    const double beta = a.has_model ? (a.beta ? a.beta[wl] : 1.0) : 0.0;
-    const double eps = a.eps_w ? a.eps_w[wl] : a.eps;
-    bool healed;
-    const double lpt = prior_loop(a.priors, a.pc, a.D, a.s.trial, a.ld, w, wl, live, a.s.gpr, healed);      // a frozen chain: at its θ_t, ignored
-    if (!live) return;
+    const Chain ch = chain_of(a);
+    const Target tg = target_at(a, ch, a.s.trial, a.s.lp, a.s.glp, a.s.gpr);      // every lane: its prior_loop() votes across the wave; a frozen chain: at its θ_t, ignored
+    if (!ch.live) return;
+    const int64_t w = ch.w;
     if (a.s.status[w] == NUTS_BUILDING) {
         const int64_t plane = (int64_t)a.D * a.ld;
-        const double lp = a.has_model ? a.s.lp[w] : 0.0;
+        const double beta = ch.beta, eps = ch.eps, lp = tg.lp(w), lpt = tg.lpt;
         const int32_t v = a.s.v[w], n = a.s.n[w], nleaf = a.s.nleaf[w] + 1;
         int32_t j = a.s.depth[w];
         const bool first = n == 0, even = !(n & 1);
@@ -141,8 +127,8 @@ __global__ __launch_bounds__(TPB) void k_nuts_leaf(NutsArgs a) {
         double K = 0.0;
         for (int d = 0; d < a.D; ++d) {
             const int64_t o = (int64_t)d * a.ld + w;
-            const double im = a.inv_mass ? a.inv_mass[d] : 1.0;
-            const double g = tempered_gradient(beta, a.s.glp, o, healed ? 0.0 : a.s.gpr[o]);
+            const double im = inv_mass_at(a.inv_mass, d);
+            const double g = tg.grad(o);
             const double p = a.s.pt[o] + hk * g;
             K += im * p * p;
             const double rs = first ? p : a.s.rho_s[o] + p;
@@ -174,7 +160,7 @@ __global__ __launch_bounds__(TPB) void k_nuts_leaf(NutsArgs a) {
                 for (int d = 0; d < a.D; ++d) {
                     const int64_t o = (int64_t)d * a.ld + w;
                     const double c = cp[o];
-                    const double mr = (a.inv_mass ? a.inv_mass[d] : 1.0) * (a.s.rho_s[o] - cr[o] + c);
+                    const double mr = inv_mass_at(a.inv_mass, d) * (a.s.rho_s[o] - cr[o] + c);
                     ta += c * mr; tb += pe[o] * mr;
                 }
                 if (ta <= 0.0 || tb <= 0.0) status = NUTS_TURN_SUBTREE;
@@ -193,7 +179,7 @@ __global__ __launch_bounds__(TPB) void k_nuts_leaf(NutsArgs a) {
                 const int64_t o = (int64_t)d * a.ld + w;
                 const double r = a.s.rho[o] + a.s.rho_s[o];
                 a.s.rho[o] = r;
-                const double mr = (a.inv_mass ? a.inv_mass[d] : 1.0) * r;
+                const double mr = inv_mass_at(a.inv_mass, d) * r;
                 ta += a.s.pL[o] * mr; tb += a.s.pR[o] * mr;
             }
             j += 1;
@@ -230,11 +216,8 @@ int32_t octo_draws_nuts_device(octo_draws* h, uint64_t seed, uint64_t step, uint
     if (!h) return OCTO_EINVAL;
     if (max_depth < 1 || max_depth > OCTO_DRAWS_NUTS_MAX_DEPTH) return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: max_depth must be 1 ... OCTO_DRAWS_NUTS_MAX_DEPTH");
     if (n_rounds < 0) return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: n_rounds >= 0");
-    if (int rc = check_chains(h, "octo_draws_nuts_device", W, ld, MAX_CHAINS, "2^30")) return rc;
-    if (!d_eps && !(eps > 0.0 && std::isfinite(eps))) return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: eps must be finite and > 0 when d_eps is NULL");
     const bool has_model = h->model && h->ctx;
-    if (!has_model && (d_logpost || d_loglike))
-        return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: the handle has no model (created without one, or detached): d_logpost and d_loglike must be NULL");
+    if (int rc = check_sampler_call(h, "octo_draws_nuts_device", W, ld, d_eps, eps, has_model, d_logpost, d_loglike)) return rc;
     if (resume && (h->nuts_depth != max_depth || h->nuts_W != W || h->nuts_ld != ld || h->nuts_seed != seed || h->nuts_step != step || h->nuts_chain0 != chain0))
         return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: resume needs a previous call with the same W, ld, max_depth, seed, step and chain0");
     if (W == 0) {
@@ -248,31 +231,17 @@ int32_t octo_draws_nuts_device(octo_draws* h, uint64_t seed, uint64_t step, uint
         h->nuts_depth = 0;      // a call that fails below leaves nothing to resume
         int rc = grow(h, h->d_nuts, h->cap_nuts, carve_size(nuts_work, (int64_t)h->D, ld, (int64_t)max_depth)); if (rc) return rc;
     }
-    NutsArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.priors = h->d_priors; a.pc = h->d_pc; a.beta = d_beta; a.eps_w = d_eps; a.inv_mass = d_inv_mass; a.eps = eps;
-    a.seed = seed; a.step = step; a.chain0 = chain0; a.W = W; a.ld = ld; a.D = h->D; a.has_model = has_model ? 1 : 0; a.max_depth = max_depth;
-    a.theta_t = d_theta_t;
+    NutsArgs a{sampler_head(h, has_model, seed, step, chain0, W, ld, d_theta_t, d_beta, d_eps, eps, d_inv_mass)};
+    a.max_depth = max_depth;
     a.s = carve_at(h->d_nuts, nuts_work, (int64_t)h->D, ld, (int64_t)max_depth);
     double *lp = a.s.lp, *glp = a.s.glp;
     if (!has_model) { a.s.lp = nullptr; a.s.glp = nullptr; }
     a.o_lp = d_logpost; a.o_ll = d_loglike; a.o_la = d_log_accept; a.o_acc = d_accepted; a.o_depth = d_depth; a.o_nleaf = d_n_leapfrog; a.o_div = d_diverged;
     a.o_nact = d_n_active;
     if (d_n_active) OCHK(h, hipMemsetAsync(d_n_active, 0, sizeof(int32_t), st));      // the last launch of the call counts into it
-    const dim3 grid = grid_of(W), block(TPB);
-    if (!resume) {
+    if (!resume)
         if (int rc = octo_draws_momentum_device(h, seed, step, chain0, W, ld, d_inv_mass, a.s.pL, hip_stream)) return rc;
-        if (has_model) { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, d_theta_t, ld, W, lp, glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
-        a.write_out = n_rounds == 0;
-        hipLaunchKernelGGL(k_nuts_open, grid, block, 0, st, a);
-    }
-    for (int r = 1; r <= n_rounds; ++r) {
-        if (has_model) { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, a.s.trial, ld, W, lp, glp, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
-        a.write_out = r == n_rounds;
-        hipLaunchKernelGGL(k_nuts_leaf, grid, block, 0, st, a);
-    }
-    if (resume && n_rounds == 0) hipLaunchKernelGGL(k_nuts_report, grid, block, 0, st, a);
-    OCHK(h, hipGetLastError());
+    if (int rc = run_rounds(h, st, a, has_model, d_theta_t, lp, glp, n_rounds, resume != 0, k_nuts_open, k_nuts_leaf, k_nuts_report)) return rc;
     h->nuts_W = W; h->nuts_ld = ld; h->nuts_depth = max_depth; h->nuts_seed = seed; h->nuts_step = step; h->nuts_chain0 = chain0;
     return OCTO_OK;
 }

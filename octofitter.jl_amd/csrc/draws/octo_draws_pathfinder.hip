@@ -12,7 +12,8 @@
 //   k_pf_map      z -> φ = μ + √α ⊙ (L̃z) and log q, lane = chain, a thread per (draw, chain); in place, rows from the last to the first.
 //   k_pf_elbo     the ELBO of the candidate, the strict comparison with the kept one, the promotion (a flag flip) and the outputs.
 //   k_pf_mask     ℓπ = −Inf at the draws of a chain without a fit (octo_draws_pathfinder_draw_device).
-// Nothing of a chain lives in a private array. A round is 3 + ⌈D/4⌉ launches and one log-posterior call besides the L-BFGS round.
+// Nothing of a chain lives in a private array. A round is 3 + ⌈D/4⌉ launches and one log-posterior call (logpost_at of octo_draws_common.h,
+// without a gradient) besides the L-BFGS round.
 #include "octo_draws_common.h"
 
 namespace {
@@ -351,7 +352,7 @@ int32_t octo_draws_pathfinder_device(octo_draws* h, uint64_t seed, uint64_t chai
         launch_normals(st, z);
         hipLaunchKernelGGL(k_pf_map, grid_of(KW), dim3(TPB), 0, st, p);
         OCHK(h, hipGetLastError());
-        rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, b.phi, KW, KW, b.lp, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc;
+        rc = logpost_at(h, st, true, b.phi, KW, KW, b.lp, nullptr); if (rc) return rc;
         hipLaunchKernelGGL(k_pf_elbo, grid_of(W), dim3(TPB), 0, st, e);
     }
     if (n_rounds == 0) {
@@ -389,7 +390,7 @@ int32_t octo_draws_pathfinder_draw_device(octo_draws* h, uint64_t seed, uint64_t
     p.z = d_phi; p.phi = d_phi; p.logq = d_logq; p.W = W; p.n = n_draws; p.ld = ld; p.sj = W; p.sd = ld_out; p.D = h->D;
     hipLaunchKernelGGL(k_pf_map, grid_of(NW), dim3(TPB), 0, st, p);
     OCHK(h, hipGetLastError());
-    { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, d_phi, ld_out, NW, d_logpost, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+    if (int rc = logpost_at(h, st, true, d_phi, ld_out, NW, d_logpost, nullptr)) return rc;
     MaskArgs k;
     k.elbo_iter = s.elbo_iter; k.lp = d_logpost; k.W = W; k.n = n_draws;
     hipLaunchKernelGGL(k_pf_mask, grid_of(NW), dim3(TPB), 0, st, k);
