@@ -49,6 +49,11 @@
  * bulk and tail ESS, three quantiles per row) and the rank step by itself (octo_draws_rank_device), stated in full at their declaration
  * (tests/diag_reference.py restates them). No random number.
  *
+ * The ninth is a second explorer, a slice sampler (octo_draws_slice_device): coordinate-wise, gradient-free, with no step size and no metric,
+ * the W chains walking through their coordinates in lockstep rounds of one forward log-posterior call, stated in full at its declaration
+ * (tests/slice_reference.py restates it). Its stream adds
+ *   purpose 9: uniform number i of update j of chain c at `step`, counter (c, j·128 + i, 9, step), word 0 (the interval's position: word 1 of i = 0)
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -71,6 +76,7 @@ extern "C" {
 #define OCTO_DRAWS_PURPOSE_NUTS_DIRECTION 6
 #define OCTO_DRAWS_PURPOSE_NUTS_LEAF      7
 #define OCTO_DRAWS_PURPOSE_NUTS_MERGE     8
+#define OCTO_DRAWS_PURPOSE_SLICE 9
 
 typedef struct octo_draws octo_draws;
 
@@ -408,6 +414,59 @@ int32_t octo_draws_nuts_device(octo_draws* h, uint64_t seed, uint64_t step, uint
                                int32_t n_rounds, int32_t resume, double* d_logpost, double* d_loglike, double* d_log_accept,
                                int32_t* d_accepted, int32_t* d_depth, int32_t* d_n_leapfrog, int32_t* d_diverged, int32_t* d_n_active,
                                void* hip_stream);
+
+/* ---- The slice sampler (Neal 2003, "Slice sampling", Ann. Statist. 31: the doubling procedure of Fig. 4, the shrinkage of Fig. 5, the acceptance
+ * test of Fig. 6; the explorer the reference's octofit_pigeons runs, Pigeons' SliceSampler). One transition of W chains: n_passes sweeps over the
+ * D coordinates of θ_t in index order, update number j = pass·D + d changing coordinate d alone. Chain c = chain0 + w at `step`. The target is E
+ * of the HMC step above, with its ℓprior_t (the same routine, order and sentinel), its β = 1 and β = 0, its dead states and its handle without a
+ * model; a dead trial point has E = −Inf. No gradient is evaluated anywhere. A ROUND is one forward octo_model_logpost_device call at the trial
+ * points of all W chains — a chain's trial point is its θ_t but for the coordinate it is updating — and one step of every chain's state machine.
+ * Chains advance through their coordinates independently: none waits for another.
+ *
+ * Width      w_d = d_width[d], or the scalar w with d_width NULL. p = the number of doublings, max_shrink = the shrink proposals of an update.
+ * Uniforms   u_i = the uniform of word 0 of counter (c, j·128 + i, 9, step); u′ = that of word 1 of the counter of i = 0.
+ * Open       E₀ at θ_t. A dead start ends the chain at once: θ_t is not written, the status is DEAD, every count is 0.
+ * Level      x = coordinate d of θ_t. z = E₀ + log u_0; L = x − w_d·u′; R = L + w_d. E_L is evaluated, then E_R.
+ * Doubling   for k = 1 … p: stop if neither z < E_L nor z < E_R; otherwise, if u_k < ½, L <- L − (R − L) and E_L is evaluated, else
+ *            R <- R + (R − L) and E_R is evaluated.
+ * Shrink     from L̄ = L, R̄ = R, for s = 0 … max_shrink − 1: x′ = L̄ + u_{64+s}·(R̄ − L̄); E′ is evaluated. x′ is a candidate iff z < E′, and a
+ *            candidate is accepted iff it passes the test below. On acceptance coordinate d of θ_t is written with x′, and E₀, ℓπ and ℓprior_t of
+ *            the chain become those evaluated at x′: nothing is evaluated twice. Otherwise x′ < x sets L̄ <- x′, else R̄ <- x′. After max_shrink
+ *            proposals the coordinate keeps its value and n_stuck counts it.
+ * Test       L̂ = L, R̂ = R, E_L̂ = E_L, E_R̂ = E_R, the flag off. While R̂ − L̂ > 1.1·w_d: M = (L̂ + R̂)/2; the flag goes on if (x < M) != (x′ < M);
+ *            x′ < M sets R̂ <- M, else L̂ <- M; the new endpoint is evaluated, in every iteration; the candidate is rejected iff the flag is on and
+ *            z >= E_L̂ and z >= E_R̂. It passes when the loop ends. With p = 0 the loop never runs.
+ * End        after n_passes·D updates the status is DONE. A chain that is DONE or DEAD is FROZEN, as in NUTS: its trial point is its θ_t, the
+ *            result there is ignored, and θ_t and every output keep their bits for the rest of the call and across `resume`.
+ * An update takes 2 + (doublings made) + (shrink proposals) + (test midpoints) rounds: at most 2 + p + max_shrink·(1 + p).
+ *
+ * On DEVICE buffers, asynchronous on hip_stream: no host synchronisation, no allocation once the handle's work array holds (2·D + 28)·ld doubles
+ * (it grows behind the handle's own stream), no graph capture, no floating-point atomic. resume = 0 opens and makes n_rounds rounds: n_rounds + 1
+ * log-posterior calls. resume = 1 continues the state the handle holds with n_rounds more rounds: the same W, ld, p, n_passes, max_shrink, seed,
+ * step and chain0 as the call before it, and the other inputs and d_theta_t as that call had and left them. Two calls of a and b rounds give the
+ * bits of one call of a + b. A chain's outputs depend only on chain0 + c, never on W, ld, its position or how the rounds were cut.
+ *   d_theta_t    [D][ld]  in/out: a coordinate is written where its update accepts a proposal
+ *   d_beta       [W]      or NULL: β = 1 (as octo_draws_hmc_step_device)
+ *   d_width      [D]      or NULL: the scalar w for every coordinate
+ *   d_logpost, d_loglike [W]   or NULL: ℓπ and ℓ of θ_t as the call leaves it
+ *   d_n_eval, d_n_expand, d_n_shrink, d_n_stuck [W]   int32 or NULL: the rounds the chain took part in (its evaluations, the opening one not
+ *                         counted), the doublings made, the shrink proposals made, the updates that ran out of proposals — so far
+ *   d_status     [W]      int32 or NULL: OCTO_DRAWS_SLICE_*
+ *   d_n_active   [1]      int32 or NULL: the chains still ACTIVE after the call
+ * OCTO_EINVAL: NULL handle; w not finite or <= 0 with d_width NULL; p outside 0 … OCTO_DRAWS_SLICE_MAX_DOUBLINGS; max_shrink outside
+ * 1 … OCTO_DRAWS_SLICE_MAX_SHRINK; n_passes outside 1 … OCTO_DRAWS_SLICE_MAX_PASSES; n_rounds < 0; W < 0, ld < W, W > 2^30; d_logpost or d_loglike
+ * on a handle without a model; NULL d_theta_t with W > 0; resume without a previous call of the same W, ld, p, n_passes, max_shrink, seed, step
+ * and chain0. */
+#define OCTO_DRAWS_SLICE_MAX_DOUBLINGS 8
+#define OCTO_DRAWS_SLICE_MAX_SHRINK 64
+#define OCTO_DRAWS_SLICE_MAX_PASSES 1024
+#define OCTO_DRAWS_SLICE_ACTIVE 0
+#define OCTO_DRAWS_SLICE_DONE   1
+#define OCTO_DRAWS_SLICE_DEAD   2
+int32_t octo_draws_slice_device(octo_draws* h, uint64_t seed, uint64_t step, uint64_t chain0, int64_t W, int64_t ld, double* d_theta_t,
+                                const double* d_beta, const double* d_width, double w, int32_t p, int32_t n_passes, int32_t max_shrink,
+                                int32_t n_rounds, int32_t resume, double* d_logpost, double* d_loglike, int32_t* d_n_eval, int32_t* d_n_expand,
+                                int32_t* d_n_shrink, int32_t* d_n_stuck, int32_t* d_status, int32_t* d_n_active, void* hip_stream);
 
 /* ---- Convergence diagnostics of stored draws (Vehtari, Gelman, Simpson, Carpenter & Bürkner 2021; the table the reference's user reads after
  * octofit: ess_bulk, ess_tail and the rank-normalised split-R̂). The function is stated in full so that a restatement elsewhere

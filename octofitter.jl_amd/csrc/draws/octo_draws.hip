@@ -337,7 +337,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
         }
         if (release) (void)hipStreamDestroy(h->stream);
     }
-    for (void* p : std::initializer_list<void*>{h->d_priors, h->d_pc, h->d_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag})
+    for (void* p : std::initializer_list<void*>{h->d_priors, h->d_pc, h->d_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice})
         (void)hipFree(p);
     delete h;
     return OCTO_OK;

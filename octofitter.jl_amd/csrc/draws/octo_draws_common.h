@@ -4,8 +4,9 @@
 // (SamplerHead), the per-lane preamble (Chain, chain_of) and the tempered target at a point (Target, target_at over prior_loop, tempered_energy,
 // dead_state). On the host: check_sampler_call, sampler_head, logpost_at (every octo_model_logpost_device call of the four units) and
 // run_rounds (the round driver of the L-BFGS and of NUTS).
-// Seven units include it: octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
-// explorer), octo_draws_nuts.hip (the no-U-turn sampler), octo_draws_lbfgs.hip (the multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder
+// Eight units include it: octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
+// explorer), octo_draws_nuts.hip (the no-U-turn sampler), octo_draws_slice.hip (the slice sampler, which takes the samplers' head, preamble, target
+// and round driver without a gradient), octo_draws_lbfgs.hip (the multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder
 // on its paths), octo_draws_adapt.hip (the warm-up statistics of the explorer) and octo_draws_diag.hip (the convergence diagnostics of stored draws). Everything but the handle lives in an unnamed namespace,
 // one copy per unit. How the handle's work allocations are cut into their parts is octo_draws_layout.h.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
@@ -209,6 +210,11 @@ struct octo_draws : CompanionBase {
     uint64_t nuts_seed = 0, nuts_step = 0, nuts_chain0 = 0;
     // the convergence diagnostics (octo_draws_diag.hip), grown on demand: sorted keys, rank-normalised draws, the chains' moments, ρ
     double* d_diag = nullptr; int64_t cap_diag = 0;
+    // the slice sampler (octo_draws_slice.hip), grown on demand: the chains' state machines in one allocation with the transition it was opened
+    // for (slice_passes = 0: nothing to resume)
+    double* d_slice = nullptr; int64_t cap_slice = 0;
+    int64_t slice_W = 0, slice_ld = 0; int32_t slice_passes = 0, slice_p = 0, slice_shrink = 0;
+    uint64_t slice_seed = 0, slice_step = 0, slice_chain0 = 0;
 };
 
 namespace {

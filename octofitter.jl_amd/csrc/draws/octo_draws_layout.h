@@ -92,6 +92,30 @@ inline NutsWork nuts_work(Carve& c, int64_t D, int64_t ld, int64_t max_depth) {
             c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld)};
 }
 
+// The state machines of one slice-sampling transition (octo_draws_slice.hip), d_slice: (2·D + 28)·ld. The kernels take it by value (SliceArgs):
+// its members and their order are their argument layout.
+struct SliceWork {
+    double *trial, *gpr;                         // [D][ld] the point of the next log-posterior call: θ_t but for the coordinate being updated · ∇ℓprior_t (target_at's, not read)
+    double *lp, *E0, *out_lp, *out_lpt;          // [ld] ℓπ at the point of a launch · E, ℓπ and ℓprior_t of θ_t as it stands
+    double *z, *L, *R, *EL, *ER;                 // [ld] the level · the interval of the update and E at its ends
+    double *Lb, *Rb;                             // [ld] L̄, R̄: the shrunk interval
+    double *Lh, *Rh, *ELh, *ERh;                 // [ld] L̂, R̂ of the acceptance test and E at them
+    double *xp, *Ep, *lpp, *lptp;                // [ld] the proposal x′ and E, ℓπ, ℓprior_t there
+    int32_t *status, *j, *phase, *i, *flag;      // [ld] OCTO_DRAWS_SLICE_* · the update number · what the launch's evaluation is · the doubling or shrink number · the test's flag
+    int32_t *n_eval, *n_expand, *n_shrink, *n_stuck;      // [ld] the counts
+};
+inline SliceWork slice_work(Carve& c, int64_t D, int64_t ld) {
+    const int64_t plane = D * ld;
+    return {c.take(plane), c.take(plane),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take(ld), c.take(ld),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld),
+            c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld)};
+}
+
 // The block partials of the grouped moments (octo_draws_adapt.hip), d_mom: nblk·G·(2K + 1). Per block of 256 chains and group: the number
 // of chains it holds · per row their sum and Σ(x − the block's mean)². sum and m2 of a (block, group) with cnt = 0 are never written or read.
 struct MomentsPartials { double *cnt, *sum, *m2; };      // [nblk][G] · [nblk][G][K] · [nblk][G][K]

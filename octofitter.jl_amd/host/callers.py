@@ -157,7 +157,8 @@ def _recorded(model, rec_t, rec_lp):
     return dict(samples=np.stack([model.invlink(x) for x in samples_t]), samples_t=samples_t, logpost=rec_lp.cpu().numpy())
 
 
-def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None, betas=None, inv_mass=None, seed=0, n_adapt=None, adapt="host"):
+def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None, betas=None, inv_mass=None, seed=0, n_adapt=None, adapt="host",
+                      explorer="hmc", slice_w=10.0, slice_p=3, n_passes=3):
     """Parallel tempering with every piece on the device — the device-resident twin of julia/OctofitterHIP.jl: octofit_pigeons_hip, with a
     gradient-based explorer in place of its random walk: n_chains independent PT chains of n_temps replicas each (replica r of chain c is
     walker r·n_chains + c, the layout of TemperedSwap), θ_t never leaving the device during a round. Single rank.
@@ -175,6 +176,12 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
     (PriorDraws.adapt_init / adapt_step, group = ladder slot, update number = round + 1, Stan's constants); after the n_adapt rounds every
     temperature runs at its averaged ε̄. The metric is the same in both.
 
+    explorer="slice" explores with the reference's own explorer instead, Pigeons' SliceSampler (PriorDraws.slice_step: coordinate-wise, no
+    gradient, nothing to tune): step 2 of a round becomes one slice-sampling transition of every replica — n_passes sweeps over the
+    coordinates with width slice_w (a number, or one per coordinate of θ_t) and slice_p doublings. n_leapfrog, eps, inv_mass, n_adapt and
+    adapt are ignored in that mode, and the result carries slice_evals [n_temps] — the mean log-posterior evaluations per replica per round
+    of every temperature — in place of hmc_acceptance and eps.
+
     Returns dict(samples [n_rounds, D, n_chains] natural domain, samples_t the same as θ_t, logpost [n_rounds, n_chains] — the β = 1 replica of
     every chain after the exploration of each round —, hmc_acceptance [n_temps], swap_acceptance [n_temps − 1], eps [n_temps], betas, names,
     and state = dict(theta_t [D, n_temps·n_chains], slot2rep, refreshed (walker indices the last round redrew), refreshed_first (their first
@@ -188,23 +195,29 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
     n_adapt = R // 2 if n_adapt is None else int(n_adapt)
     if adapt not in ("host", "device"):
         raise ValueError('octofit_pt_device: adapt is "host" or "device"')
+    if explorer not in ("hmc", "slice"):
+        raise ValueError('octofit_pt_device: explorer is "hmc" or "slice"')
+    use_slice = explorer == "slice"
+    if use_slice:
+        n_adapt = 0      # nothing to adapt
     fn = model.ln_like
     dev = torch.device("cuda", fn.device_index)
     W, D = T * Cn, int(model.D)
     with PriorDraws(model) as pd:
         swap = TemperedSwap(fn, T, Cn, device=dev, seed=seed, betas=betas)
         cold_last = float(swap.beta[-1]) == 0.0      # the ladder ends at the prior: its replicas are redrawn IID every round
-        inv_mass = _default_metric(pd, seed, dev, inv_mass)
-        log_eps = torch.log(torch.as_tensor(0.1 if eps is None else eps, dtype=torch.float64, device=dev).expand(T).clone())
+        if not use_slice:
+            inv_mass = _default_metric(pd, seed, dev, inv_mass)
+        log_eps = torch.log(torch.as_tensor(0.1 if eps is None or use_slice else eps, dtype=torch.float64, device=dev).expand(T).clone())
         theta_t = pd.sample(seed, 0, W, theta=False, logprior_t=False)[1]
         da_state = None
-        if adapt == "device":
+        if adapt == "device" and not use_slice:
             da_state = pd.adapt_init(T, torch.as_tensor(0.1 if eps is None else eps, dtype=torch.float64, device=dev).expand(T).contiguous())
             log_eps = da_state[:, 0].clone()
         next_draw = W
         slots = torch.arange(T, dtype=torch.int32, device=dev).repeat(Cn, 1)
         chains = torch.arange(Cn, device=dev)
-        acc_sum = torch.zeros(T, dtype=torch.float64, device=dev)
+        acc_sum = torch.zeros(T, dtype=torch.float64, device=dev)      # with the slice sampler: the evaluations
         rec_t = torch.empty((R, D, Cn), dtype=torch.float64, device=dev)
         rec_lp = torch.empty((R, Cn), dtype=torch.float64, device=dev)
         refreshed = None
@@ -212,8 +225,12 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
             rep2slot = torch.empty_like(swap.slot2rep)
             rep2slot.scatter_(1, swap.slot2rep.long(), slots)
             slot_w = rep2slot.t().contiguous().reshape(-1).long()                     # the ladder slot of walker r·n_chains + c
-            lp, ll, _dH, acc = pd.hmc_step(theta_t, beta=swap.beta[slot_w], eps=torch.exp(log_eps)[slot_w], n_leapfrog=n_leapfrog,
-                                           inv_mass=inv_mass, seed=seed, step=r)
+            if use_slice:
+                so = pd.slice_step(theta_t, beta=swap.beta[slot_w], w=slice_w, p=slice_p, n_passes=n_passes, seed=seed, step=r)
+                lp, ll, acc = so["logpost"], so["loglike"], so["n_eval"]
+            else:
+                lp, ll, _dH, acc = pd.hmc_step(theta_t, beta=swap.beta[slot_w], eps=torch.exp(log_eps)[slot_w], n_leapfrog=n_leapfrog,
+                                               inv_mass=inv_mass, seed=seed, step=r)
             if cold_last:
                 refreshed = swap.slot2rep[:, T - 1].long() * Cn + chains
                 _, fresh, lpt = pd.sample(seed, next_draw, Cn, theta=False)
@@ -237,9 +254,9 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
         torch.cuda.synchronize(dev)
         pairs = np.arange(T - 1)
         attempts = np.array([(R + 1 - (t % 2)) // 2 for t in pairs]) * Cn            # pair (t, t + 1) is tried in the rounds of parity t % 2
-        return dict(**_recorded(model, rec_t, rec_lp),
-                    hmc_acceptance=(acc_sum / R).cpu().numpy(), swap_acceptance=swap.accepted.cpu().numpy()[:T - 1] / np.maximum(attempts, 1),
-                    eps=torch.exp(log_eps).cpu().numpy(), betas=swap.beta.cpu().numpy(), names=list(model.names),
+        explored = dict(slice_evals=(acc_sum / R).cpu().numpy()) if use_slice else dict(hmc_acceptance=(acc_sum / R).cpu().numpy())
+        return dict(**_recorded(model, rec_t, rec_lp), **explored, swap_acceptance=swap.accepted.cpu().numpy()[:T - 1] / np.maximum(attempts, 1),
+                    **({} if use_slice else dict(eps=torch.exp(log_eps).cpu().numpy())), betas=swap.beta.cpu().numpy(), names=list(model.names),
                     state=dict(theta_t=theta_t.cpu().numpy(), slot2rep=swap.slot2rep.cpu().numpy(),
                                refreshed=None if refreshed is None else refreshed.cpu().numpy(), refreshed_first=next_draw - Cn if cold_last else None))
 

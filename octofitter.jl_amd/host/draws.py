@@ -11,6 +11,7 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     r = draws.pathfinder(θ_t, inv_mass=v, n_rounds=50, seed=seed)      # the same rounds with Pathfinder's fits along the path: also elbo, elbo_iter, n_fits
     φ, logq, logpost = draws.pathfinder_draw(θ_t, 256, seed=seed)      # [D, 256·W], [256·W], [256·W]: draws from every chain's kept fit
     lp, ll, log_accept, acc, depth, n_leapfrog, diverged = draws.nuts_step(θ_t, eps=0.1, max_depth=10, seed=seed, step=step)      # one NUTS transition
+    r = draws.slice_step(θ_t, beta, w=10.0, p=3, n_passes=3, seed=seed, step=step)      # one slice-sampling transition (no gradient, no ε, no metric): dict
     count, mean, m2 = draws.moments(θ_t)                    # warm-up: pooled moments of the chains, [1], [1, D], [1, D] (or per group)
     draws.metric(count[0:1], mean[0], m2[0], inv_mass)      # … the diagonal metric they give, written into inv_mass [D]
     state = draws.adapt_init(1, 0.1)                        # … dual averaging of ε: the state [G, 4]
@@ -37,6 +38,10 @@ PHILOX_KEY1 = 0x6F63746F64726177   # second key word; the first is the seed
 PURPOSE_PRIOR, PURPOSE_UNIFORM, PURPOSE_MOMENTUM, PURPOSE_ACCEPT, PURPOSE_ELBO, PURPOSE_PATHFINDER = 0, 1, 2, 3, 4, 5
 PURPOSE_NUTS_DIRECTION, PURPOSE_NUTS_LEAF, PURPOSE_NUTS_MERGE = 6, 7, 8
 NUTS_MAX_DEPTH = 10                # OCTO_DRAWS_NUTS_MAX_DEPTH
+PURPOSE_SLICE = 9
+SLICE_MAX_DOUBLINGS, SLICE_MAX_SHRINK, SLICE_MAX_PASSES = 8, 64, 1024      # OCTO_DRAWS_SLICE_MAX_*
+SLICE_ACTIVE, SLICE_DONE, SLICE_DEAD = 0, 1, 2                            # OCTO_DRAWS_SLICE_*
+SLICE_OUTPUTS = ("logpost", "loglike", "n_eval", "n_expand", "n_shrink", "n_stuck", "status", "n_active")      # the outputs of octo_draws_slice_device, in order
 LBFGS_MAX_M = 8                    # OCTO_DRAWS_LBFGS_MAX_M
 LBFGS_ACTIVE, LBFGS_GTOL, LBFGS_FTOL, LBFGS_LINESEARCH, LBFGS_DEAD = 0, 1, 2, 3, 4      # OCTO_DRAWS_LBFGS_*
 PF_MAX_D = 64                      # OCTO_DRAWS_PF_MAX_D
@@ -83,6 +88,8 @@ _SIGS = {
     "octo_draws_chain_moments_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "octo_draws_nuts_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                            C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9),
+    "octo_draws_slice_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9),
     "octo_draws_diagnose_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "octo_draws_diagnose_work_doubles": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     "octo_draws_rank_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
@@ -350,6 +357,49 @@ class PriorDraws(companion.Handle):
             out = self.nuts(theta_t, n_rounds=1 << j, resume=True, out=out, **args)
             j += 1
         return tuple(out[k] for k in ("logpost", "loglike", "log_accept", "accepted", "depth", "n_leapfrog", "diverged"))
+
+    def slice(self, theta_t, beta=None, w=10.0, p=3, n_passes=3, max_shrink=SLICE_MAX_SHRINK, n_rounds=0, resume=False, seed=0, step=0, chain0=0, out=None,
+              stream=None):
+        """octo_draws_slice_device, the raw call: opens (resume=False) or continues (resume=True: the same arguments, and out= the dict the
+        opening call returned) one slice-sampling transition of the W chains in theta_t — n_passes sweeps over the coordinates — and makes
+        n_rounds rounds of it, one forward evaluation per chain still active. w: the width, a number or one per coordinate [D]; p: the
+        doublings; beta as in hmc_step.
+        Returns dict(logpost, loglike (None on a handle made from priors alone), n_eval, n_expand, n_shrink, n_stuck, status int32 [W],
+        n_active int32 [1]: the chains still active), device tensors. Asynchronous on `stream`."""
+        import torch
+        dev = self.device
+        _, W, ld = chain_matrix(theta_t, self.D, dev, "slice")
+        per_coordinate = torch.is_tensor(w) or np.ndim(w) > 0
+        width = device_vector(w, self.D, dev, "w") if per_coordinate else None
+        be = device_vector(beta, W, dev, "beta")
+        if out is None:
+            i32 = lambda n: self._out(n, dtype=torch.int32)      # noqa: E731
+            lp, ll = (self._out(W), self._out(W)) if self.model is not None else (None, None)
+            out = dict(logpost=lp, loglike=ll, n_eval=i32(W), n_expand=i32(W), n_shrink=i32(W), n_stuck=i32(W), status=i32(W), n_active=i32(1))
+        self._check(self.lib.octo_draws_slice_device(self._h, int(seed), int(step), int(chain0), W, ld, theta_t.data_ptr(), ptr(be), ptr(width),
+                                                     0.0 if per_coordinate else float(w), int(p), int(n_passes), int(max_shrink), int(n_rounds), 1 if resume else 0,
+                                                     *(ptr(out[k]) for k in SLICE_OUTPUTS), self._stream(stream, dev)))
+        self._keep = (theta_t, be, width, out)
+        return out
+
+    def slice_step(self, theta_t, beta=None, w=10.0, p=3, n_passes=3, max_shrink=SLICE_MAX_SHRINK, seed=0, step=0, chain0=0, rounds_per_call=None, stream=None):
+        """One whole slice-sampling transition of the W chains in theta_t (torch float64 [D, W] on the handle's device, rows contiguous; a
+        coordinate is written where its update accepts). The rounds run in segments of rounds_per_call (default: 4·n_passes·D, about half of
+        what a transition takes at the default p); after each the number of chains still active is read (a 4-byte copy, the only
+        synchronisation) and the transition stops at 0, at the latest after the n_passes·D·(2 + p + max_shrink·(1 + p)) rounds that finish
+        every chain. The same bits however the rounds are cut. Returns slice()'s dict."""
+        updates = int(n_passes) * self.D
+        per_call = 4 * updates if rounds_per_call is None else int(rounds_per_call)
+        if per_call < 1:
+            raise ValueError("slice_step: rounds_per_call >= 1")
+        args = dict(beta=beta, w=w, p=p, n_passes=n_passes, max_shrink=max_shrink, seed=seed, step=step, chain0=chain0, stream=stream)
+        done, out = 0, None
+        most = updates * (2 + int(p) + int(max_shrink) * (1 + int(p)))
+        while out is None or (done < most and int(out["n_active"].item()) > 0):
+            n = min(per_call, most - done)
+            out = self.slice(theta_t, n_rounds=n, resume=out is not None, out=out, **args)
+            done += n
+        return out
 
     def lbfgs_direction(self, cnt, head, S, Y, g, inv_mass=None, stream=None):
         """The two-loop recursion of every chain on its own history: d [D, W] = −H·g with H₀ = γ·diag(inv_mass). cnt, head: int32 [W] (stored
