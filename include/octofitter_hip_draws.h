@@ -54,6 +54,11 @@
  * (tests/slice_reference.py restates it). Its stream adds
  *   purpose 9: uniform number i of update j of chain c at `step`, counter (c, j·128 + i, 9, step), word 0 (the interval's position: word 1 of i = 0)
  *
+ * The tenth is what a parallel-tempering driver does between its scans (octo_draws_pt_stats_device, octo_draws_pt_schedule_device): the swap
+ * acceptance probabilities, the stepping-stone sums of the log evidence and the tempered restarts of every scan, and once a round the communication
+ * barrier and the ladder that equalises the rejection rates along it, stated in full at their declaration (tests/pt_reference.py restates them).
+ * No model, no random number.
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -528,6 +533,57 @@ int64_t octo_draws_diagnose_work_doubles(int64_t n, int64_t W, int32_t K);
  * middle sample is not written. fold = 1 ranks y = |x − median|. The work array and the status codes are those of octo_draws_diagnose_device. */
 int32_t octo_draws_rank_device(octo_draws* h, int64_t n, int64_t W, int64_t ld, int64_t ls, int32_t K, const double* d_x, int32_t fold,
                                double* d_rank, double* d_z, void* hip_stream);
+
+/* ---- Parallel tempering between the scans (non-reversible parallel tempering: Syed, Bouchard-Côté, Deligiannidis & Doucet 2021, the scheme of
+ * Pigeons, which the reference's octofit_pigeons runs; the stepping-stone estimator of Xie, Lewis, Fan, Kuo & Chen 2011). The layout is that of
+ * octo_pt_swap_device: d_ll [T][Cn] by replica (walker r·Cn + c), d_slot2rep [Cn][T] int32, d_beta [T] with slot 0 the target; T = 2 … OCTO_DRAWS_MAX_GROUPS,
+ * Cn = 1 … 2^24. On DEVICE arrays, asynchronous on hip_stream, no model, no random number, no floating-point atomic, no allocation once the
+ * handle's work array holds 7·(T − 1)·⌈Cn/256⌉ doubles (the array of octo_draws_moments_device's block partials).
+ *
+ * octo_draws_pt_stats_device: one call per scan, on the ℓ and the slot2rep the swap step is about to see. For chain c and pair t (slots t, t + 1):
+ * li = ℓ of the replica at slot t, lj = ℓ of the replica at slot t + 1, db = β_t − β_{t+1}. A replica index outside 0 … T − 1 reads ℓ = NaN.
+ * The caller-owned state d_acc [T − 1][8] of doubles holds (n, A, n_f, m_f, s_f, n_b, m_b, s_b) per pair; before its first call every m is −Inf
+ * and the rest 0.
+ *   α          the swap's acceptance PROBABILITY: both li and lj finite: min(1, exp(db·(lj − li))); otherwise 1 where the swap kernel accepts for every
+ *              uniform (lj finite, li not, β_t > β_{t+1}); otherwise 0. n += 1 and A += α for EVERY pair at every scan, whatever the parity the
+ *              swap step tries: the Rao-Blackwellised rate. The accepted-swap counts of octo_pt_swap_device are another statistic and stay.
+ *   Forward    stepping-stone term (the draws of slot t + 1 estimating Z_t/Z_{t+1}): v = db·lj, counted in n_f. lj = −Inf — a dead prior draw at the
+ *              cold end — adds exp(−Inf) = 0 to the sum and 1 to n_f, decided before the multiply so that db = 0 gives no NaN; lj NaN or +Inf is skipped.
+ *   Backward   term (the draws of slot t estimating Z_{t+1}/Z_t): v = −db·li, counted in n_b; skipped unless li is finite.
+ *   (m, s)     a streaming log-sum-exp: m the maximum so far, s = Σ exp(v − m). A call forms its own (m_call, s_call) first and merges them into
+ *              the held pair: m' = max(m, m_call), s' = s·exp(m − m') + s_call·exp(m_call − m'). A side without a term (m = −Inf) leaves the other's (m, s) untouched;
+ *              the counts add.
+ * Order of the sums: that of octo_draws_moments_device — a butterfly over the 64 lanes of a wave (a lane beyond Cn holds 0), the four waves of a
+ * block of 256 consecutive chains in wave order from 0, the blocks in block order from 0. A block's log-sum-exp takes the block maximum first
+ * (exact) and sums exp(v − max) in that order; the blocks merge in block order by the rule above, from an empty pair, and the call's pair then
+ * merges into the held one. A is the call's sum added to the held A. The outputs are the same bits from run to run, and they do not depend on
+ * what the excluded terms held.
+ *   Restarts   d_leg [Cn][T] (int32, 0/1, by replica) and d_restarts [Cn] (int32), both NULL or both given, zero before the first call: for each
+ *              chain the replica at slot T − 1 gets leg = 1; the replica at slot 0 with leg = 1 adds one to d_restarts[c] and gets leg = 0. A
+ *              tempered restart is a journey from the reference (β_{T−1}) to the target (β_0).
+ * OCTO_EINVAL: NULL handle, d_ll, d_slot2rep, d_beta or d_acc; one of d_leg, d_restarts without the other; T or Cn out of range. The values of
+ * d_beta are not read on the host here (the call stays asynchronous): α is defined for any β, and octo_draws_pt_schedule_device refuses a ladder
+ * that is not non-increasing. */
+int32_t octo_draws_pt_stats_device(octo_draws* h, int32_t T, int64_t Cn, const double* d_ll, const int32_t* d_slot2rep, const double* d_beta,
+                                   double* d_acc, int32_t* d_leg, int32_t* d_restarts, void* hip_stream);
+
+/* octo_draws_pt_schedule_device: one call per round, from d_acc. For t = 0 … T − 2:
+ *   r_t        = 1 − A/n clipped to [0, 1]: the rejection rate of pair t. With n = 0 it is NaN, and the ladder is left unchanged.
+ *   Λ          Λ_0 = 0, Λ_{t+1} = Λ_t + r_t, summed in t order; Λ = Λ_{T−1}, the communication barrier between the target and the reference.
+ *   β*         β*_0 = β_0 and β*_{T−1} = β_{T−1} bit for bit. For k = 1 … T − 2: g = k·Λ/(T − 1), t the first index with Λ_{t+1} >= g, and
+ *              β*_k = β_t + (β_{t+1} − β_t)·(g − Λ_t)/(Λ_{t+1} − Λ_t), every operation rounded by itself; the denominator is positive by
+ *              construction. If Λ is 0 or not finite the ladder is copied through. LINEAR interpolation of Λ(β) between the nodes is a
+ *              deliberate choice: Pigeons interpolates Λ monotonically with a smoother curve; a linear one needs no derivative estimate, keeps β*
+ *              inside [β_{t+1}, β_t] and has the same fixed point, equal rejection rates.
+ *   d_beta_out [T], may be d_beta itself · d_rej [T − 1] = r_t · d_summary [4] = (Λ, fwd, rev, ½(fwd + rev)) with the two stepping-stone estimates of
+ *              log Z: fwd = Σ_t (m_f + log(s_f/n_f)), rev = −Σ_t (m_b + log(s_b/n_b)), both summed in t order. A pair with nothing to say makes
+ *              its sum NaN, not silently smaller.
+ *   adapt = 0  statistics only: β is copied through. reset = 1 puts d_acc back to its state before the first call (every m = −Inf, the rest 0)
+ *              once it has been read, so that a driver starts the next round without a host call.
+ * The kernel is one wave. The call copies d_beta [T] to the host to check it and waits for hip_stream to do so: one synchronisation, once a round.
+ * OCTO_EINVAL: NULL handle or array; T out of range; a d_beta that is not non-increasing from slot 0 (a NaN included). */
+int32_t octo_draws_pt_schedule_device(octo_draws* h, int32_t T, double* d_acc, const double* d_beta, int32_t adapt, int32_t reset, double* d_beta_out,
+                                      double* d_rej, double* d_summary, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -26,13 +26,6 @@ struct PartialArgs {
     MomentsPartials p;
 };
 
-// the sum over the 64 lanes, the same bits in every lane (IEEE addition commutes, so both sides of every exchange add the same pair)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // the four waves' entries of group g in wave order; a wave without a member of g wrote none
 __device__ __forceinline__ double block_total(const double (&s)[WAVES][MAXG], const double (&n)[WAVES][MAXG], int g) {
     double t = 0.0;

@@ -4,10 +4,11 @@
 // (SamplerHead), the per-lane preamble (Chain, chain_of) and the tempered target at a point (Target, target_at over prior_loop, tempered_energy,
 // dead_state). On the host: check_sampler_call, sampler_head, logpost_at (every octo_model_logpost_device call of the four units) and
 // run_rounds (the round driver of the L-BFGS and of NUTS).
-// Eight units include it: octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
+// Nine units include it: octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
 // explorer), octo_draws_nuts.hip (the no-U-turn sampler), octo_draws_slice.hip (the slice sampler, which takes the samplers' head, preamble, target
 // and round driver without a gradient), octo_draws_lbfgs.hip (the multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder
-// on its paths), octo_draws_adapt.hip (the warm-up statistics of the explorer) and octo_draws_diag.hip (the convergence diagnostics of stored draws). Everything but the handle lives in an unnamed namespace,
+// on its paths), octo_draws_adapt.hip (the warm-up statistics of the explorer), octo_draws_diag.hip (the convergence diagnostics of stored draws) and
+// octo_draws_pt.hip (the tempering statistics between the scans, which take wave_sum and waves_total). Everything but the handle lives in an unnamed namespace,
 // one copy per unit. How the handle's work allocations are cut into their parts is octo_draws_layout.h.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
@@ -86,6 +87,21 @@ __device__ __forceinline__ double prior_link_forward(const PriorBounds& B, doubl
     if (B.fa) return log(x - B.a);
     if (B.fb) return log(B.b - x);
     return x;
+}
+
+// ---- the cross-chain sums of the warm-up statistics, the diagnostics and the tempering statistics (octo_draws_adapt.hip, _diag.hip, _pt.hip)
+// the sum over the 64 lanes, the same bits in every lane (IEEE addition commutes, so both sides of every exchange add the same pair)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// the four waves' sums of a block of TPB lanes in wave order from 0
+__device__ __forceinline__ double waves_total(const double (&s)[TPB / 64]) {
+    double t = 0.0;
+#pragma unroll
+    for (int q = 0; q < TPB / 64; ++q) t += s[q];
+    return t;
 }
 
 // ---- the tempered target of the HMC step and of NUTS (include/octofitter_hip_draws.h, "Target" and "Decision")
@@ -201,7 +217,7 @@ struct octo_draws : CompanionBase {
     double* d_pf = nullptr; int64_t cap_pf = 0;
     int64_t pf_W = 0, pf_ld = 0;
     double* d_pfb = nullptr; int64_t cap_pfb = 0;
-    // warm-up (octo_draws_adapt.hip), grown on demand: the block partials of the grouped moments
+    // warm-up (octo_draws_adapt.hip) and the tempering statistics (octo_draws_pt.hip), grown on demand: the block partials of a call's sums
     double* d_mom = nullptr; int64_t cap_mom = 0;
     // NUTS (octo_draws_nuts.hip), grown on demand: the chains' trees in one allocation with the transition it was opened for (nuts_depth = 0:
     // nothing to resume)

@@ -218,13 +218,6 @@ __global__ __launch_bounds__(TPB) void k_diag_moments(ChainArgs a) {
     a.w.var[o] = ss / (double)N * (double)N / (double)(N - 1);
 }
 
-// the sum over the 64 lanes, the same bits in every lane
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // blockIdx.x = lag block·nblk + chain tile · blockIdx.y = row·4 + quantity
 __global__ __launch_bounds__(TPB) void k_diag_acov(ChainArgs a) {
     __shared__ double s_red[WAVES][LAGS];

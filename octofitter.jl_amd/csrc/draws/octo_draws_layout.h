@@ -123,6 +123,14 @@ inline MomentsPartials moments_partials(Carve& c, int64_t nblk, int64_t G, int64
     return {c.take(nblk * G), c.take(nblk * G * K), c.take(nblk * G * K)};
 }
 
+// The block partials of the tempering statistics (octo_draws_pt.hip), on d_mom as well: 7·P·nblk. Per pair of neighbouring slots (P = T − 1) and
+// block of 256 chains: Σα · the forward stepping-stone terms' count, maximum and Σ exp(v − maximum) · the backward terms' three. Pair-major, so
+// that the merge reads a pair's blocks side by side; m of a (pair, block) without a term is −Inf and its s is 0. The kernels take it by value.
+struct PtPartials { double *A, *nf, *mf, *sf, *nb, *mb, *sb; };      // [P][nblk] each
+inline PtPartials pt_partials(Carve& c, int64_t P, int64_t nblk) {
+    return {c.take(P * nblk), c.take(P * nblk), c.take(P * nblk), c.take(P * nblk), c.take(P * nblk), c.take(P * nblk), c.take(P * nblk)};
+}
+
 // The convergence diagnostics of K rows (octo_draws_diag.hip), d_diag: 2K(P + S) + 10KM + 4K·T·(nblk + 1) + 5K. N draws of M = 2W split chains a row,
 // S = M·N used draws, P = the power of two the sort pads them to, T = the lags rounded up to whole blocks of 16, nblk = ⌈M/256⌉. The kernels take it
 // by value: its members and their order are their argument layout.

@@ -11,6 +11,8 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
 
   octofit_pt_device: parallel tempering with a tempered HMC explorer, fresh prior draws at β = 0 and the swap step all on the device
   (PriorDraws.hmc_step, host/tempering.py: TemperedSwap) — the device-resident twin of julia/OctofitterHIP.jl: octofit_pigeons_hip.
+  octofit_pigeons_device: that driver in Pigeons' rounds — the ladder re-placed from the communication barrier, the log evidence and the tempered
+  restarts, from per-scan reductions on the device (PriorDraws.pt_stats / pt_schedule).
 
   warmup_windows / hmc_warmup / octofit_hmc_device: the single-temperature sampler — Pathfinder starts, then HMC whose step size (dual
   averaging on the mean acceptance probability) and diagonal metric (the pooled variance of the chains, Stan's windowed schedule) are adapted
@@ -259,6 +261,116 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
                     **({} if use_slice else dict(eps=torch.exp(log_eps).cpu().numpy())), betas=swap.beta.cpu().numpy(), names=list(model.names),
                     state=dict(theta_t=theta_t.cpu().numpy(), slot2rep=swap.slot2rep.cpu().numpy(),
                                refreshed=None if refreshed is None else refreshed.cpu().numpy(), refreshed_first=next_draw - Cn if cold_last else None))
+
+
+def octofit_pigeons_device(model, n_temps, n_chains, n_rounds, explorer="slice", n_leapfrog=4, eps=None, betas=None, inv_mass=None, seed=0, slice_w=10.0,
+                           slice_p=3, n_passes=3):
+    """octofit_pt_device with what Pigeons does BETWEEN its scans (non-reversible parallel tempering, Syed et al. 2021) — the device-resident twin of
+    the reference's octofit_pigeons in its round structure too. Round r = 1 … n_rounds makes 2^r scans, 2^(n_rounds + 1) − 2 in all. A scan is
+    exactly a round of octofit_pt_device (β per replica from slot2rep; explore; the β = 0 replicas redrawn IID; record the target replica; swap), its
+    step number the scan's number over the whole run, with PriorDraws.pt_stats on ℓ and slot2rep ahead of the swap: the swap acceptance
+    probabilities of every pair, the stepping-stone sums and the tempered restarts, accumulated on the device. Every round ends with one
+    PriorDraws.pt_schedule, which writes the ladder that equalises the rejection rates into TemperedSwap.beta in place and starts the next
+    round's sums; adaptation is off in the last round, whose ladder is the one its draws and its log evidence belong to. Only the last
+    round's 2^n_rounds draws are kept (Pigeons' rule).
+
+    explorer="slice" (the default here: Pigeons' own) or "hmc" (octofit_pt_device's default). With "hmc", ε of every ladder slot follows the
+    device dual averaging of octofit_pt_device(adapt="device") through every round but the last, which runs at the averaged ε̄. Inside a round the
+    host waits for nothing with "hmc"; "slice" keeps slice_step's 4-byte read per segment. pt_schedule waits once, at the end of a round.
+    betas: the starting ladder (default TemperedSwap's cubic one); its two ends stay.
+
+    Returns what octofit_pt_device returns — samples, samples_t [2^n_rounds, D, n_chains], logpost of the last round; hmc_acceptance and eps or
+    slice_evals, and swap_acceptance, over all scans; betas (the final ladder), names, state — plus log_evidence = dict(fwd, rev, mean: the
+    stepping-stone estimates of log Z of the last round; n, n_fwd, n_rev [n_temps − 1]: the pairs' scans × chains and the terms behind the two); betas_by_round [n_rounds + 1, n_temps] (row 0 the start, row r the ladder after round
+    r); rejection_by_round [n_rounds, n_temps − 1]; barrier_by_round [n_rounds] (Λ); restarts = dict(total, per_chain [n_chains]): the tempered
+    restarts over the run; n_scans. All NumPy."""
+    import torch
+    from .draws import PriorDraws
+    from .tempering import TemperedSwap
+    T, Cn, R = int(n_temps), int(n_chains), int(n_rounds)
+    if T < 2 or Cn < 1 or R < 1 or R > 24:
+        raise ValueError("octofit_pigeons_device: n_temps >= 2, n_chains >= 1, 1 <= n_rounds <= 24")
+    if explorer not in ("hmc", "slice"):
+        raise ValueError('octofit_pigeons_device: explorer is "hmc" or "slice"')
+    use_slice = explorer == "slice"
+    fn = model.ln_like
+    dev = torch.device("cuda", fn.device_index)
+    W, D = T * Cn, int(model.D)
+    n_scans, n_keep = 2 ** (R + 1) - 2, 2 ** R
+    n_adapt = 0 if use_slice else n_scans - n_keep
+    with PriorDraws(model) as pd:
+        swap = TemperedSwap(fn, T, Cn, device=dev, seed=seed, betas=betas)
+        cold_last = float(swap.beta[-1]) == 0.0      # the ladder ends at the prior: its replicas are redrawn IID every scan
+        theta_t = pd.sample(seed, 0, W, theta=False, logprior_t=False)[1]
+        da_state = log_eps = None
+        if not use_slice:
+            inv_mass = _default_metric(pd, seed, dev, inv_mass)
+            da_state = pd.adapt_init(T, torch.as_tensor(0.1 if eps is None else eps, dtype=torch.float64, device=dev).expand(T).contiguous())
+            log_eps = da_state[:, 0].clone()
+        next_draw = W
+        slots = torch.arange(T, dtype=torch.int32, device=dev).repeat(Cn, 1)
+        chains = torch.arange(Cn, device=dev)
+        acc_sum = torch.zeros(T, dtype=torch.float64, device=dev)      # with the slice sampler: the evaluations
+        rec_t = torch.empty((n_keep, D, Cn), dtype=torch.float64, device=dev)
+        rec_lp = torch.empty((n_keep, Cn), dtype=torch.float64, device=dev)
+        pt = pd.pt_state(T, Cn)
+        betas_by_round = torch.empty((R + 1, T), dtype=torch.float64, device=dev)
+        betas_by_round[0] = swap.beta
+        rejection_by_round = torch.empty((R, T - 1), dtype=torch.float64, device=dev)
+        summary_by_round = torch.empty((R, 4), dtype=torch.float64, device=dev)
+        refreshed, scan = None, 0
+        for r in range(1, R + 1):
+            for _ in range(2 ** r):
+                rep2slot = torch.empty_like(swap.slot2rep)
+                rep2slot.scatter_(1, swap.slot2rep.long(), slots)
+                slot_w = rep2slot.t().contiguous().reshape(-1).long()                 # the ladder slot of walker r·n_chains + c
+                if use_slice:
+                    so = pd.slice_step(theta_t, beta=swap.beta[slot_w], w=slice_w, p=slice_p, n_passes=n_passes, seed=seed, step=scan)
+                    lp, ll, acc = so["logpost"], so["loglike"], so["n_eval"]
+                else:
+                    lp, ll, dH, acc = pd.hmc_step(theta_t, beta=swap.beta[slot_w], eps=torch.exp(log_eps)[slot_w], n_leapfrog=n_leapfrog,
+                                                  inv_mass=inv_mass, seed=seed, step=scan)
+                if cold_last:
+                    refreshed = swap.slot2rep[:, T - 1].long() * Cn + chains
+                    _, fresh, lpt = pd.sample(seed, next_draw, Cn, theta=False)
+                    lp_f, _ = model.logpost_device(fresh, grad=False)
+                    theta_t[:, refreshed] = fresh
+                    lp[refreshed] = lp_f
+                    ll[refreshed] = _finite_or_neg_inf(lp_f - lpt)
+                    next_draw += Cn
+                acc_sum += torch.zeros(T, dtype=torch.float64, device=dev).index_add_(0, slot_w, acc.double()) / Cn
+                if scan < n_adapt:
+                    pd.adapt_step(da_state, dH, acc, scan + 1, group=slot_w.int(), want_eps=False)
+                    log_eps = da_state[:, 1 if scan == n_adapt - 1 else 0].clone()      # the next scan's slots differ: ε is gathered by slot there
+                if r == R:
+                    target = swap.slot2rep[:, 0].long() * Cn + chains
+                    rec_t[scan - (n_scans - n_keep)] = theta_t[:, target]
+                    rec_lp[scan - (n_scans - n_keep)] = lp[target]
+                pd.pt_stats(ll, swap.slot2rep, swap.beta, pt)
+                swap.swap_step(ll, scan)
+                scan += 1
+            if r == R:
+                counts = pt["acc"][:, [0, 2, 5]].clone()
+            s = pd.pt_schedule(pt, swap.beta, adapt=r < R, reset=True, beta_out=swap.beta)
+            betas_by_round[r] = swap.beta
+            rejection_by_round[r - 1] = s["rejection"]
+            summary_by_round[r - 1] = s["summary"]
+        torch.cuda.synchronize(dev)
+        pairs = np.arange(T - 1)
+        attempts = np.array([(n_scans + 1 - (t % 2)) // 2 for t in pairs]) * Cn      # pair (t, t + 1) is tried in the scans of parity t % 2
+        explored = dict(slice_evals=(acc_sum / n_scans).cpu().numpy()) if use_slice else dict(hmc_acceptance=(acc_sum / n_scans).cpu().numpy(),
+                                                                                             eps=torch.exp(log_eps).cpu().numpy())
+        summary = summary_by_round.cpu().numpy()
+        per_chain = pt["restarts"].cpu().numpy()
+        counts = counts.cpu().numpy().astype(np.int64)
+        return dict(**_recorded(model, rec_t, rec_lp), **explored, swap_acceptance=swap.accepted.cpu().numpy()[:T - 1] / np.maximum(attempts, 1),
+                    betas=swap.beta.cpu().numpy(), names=list(model.names),
+                    state=dict(theta_t=theta_t.cpu().numpy(), slot2rep=swap.slot2rep.cpu().numpy(),
+                               refreshed=None if refreshed is None else refreshed.cpu().numpy(), refreshed_first=next_draw - Cn if cold_last else None),
+                    log_evidence=dict(fwd=float(summary[-1, 1]), rev=float(summary[-1, 2]), mean=float(summary[-1, 3]), n=counts[:, 0], n_fwd=counts[:, 1],
+                                      n_rev=counts[:, 2]),
+                    betas_by_round=betas_by_round.cpu().numpy(), rejection_by_round=rejection_by_round.cpu().numpy(), barrier_by_round=summary[:, 0].copy(),
+                    restarts=dict(total=int(per_chain.sum()), per_chain=per_chain), n_scans=n_scans)
 
 
 def warmup_windows(n_warmup):

@@ -19,6 +19,9 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     draws.chain_moments(θ_t, k, cmean, cm2)                 # per-chain running mean and M2 over time (R̂: include/octofitter_hip_draws.h)
     d = draws.diagnose(rec)                                 # stored draws [n, K, W]: dict of [K] tensors, rhat (rank-normalised split-R̂), ess_bulk, ess_tail, …
     r, z = draws.ranks(rec)                                 # … the rank step alone: average ranks and normal scores, of rec's shape
+    state = draws.pt_state(T, Cn)                           # parallel tempering between the scans: the zeroed state (acc, leg, restarts)
+    draws.pt_stats(ll, slot2rep, beta, state)               # … a scan's swap probabilities, stepping-stone sums and tempered restarts, accumulated
+    r = draws.pt_schedule(state, beta)                      # … a round's rejection rates, barrier Λ, log evidence and the re-placed ladder: dict
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -48,6 +51,8 @@ PF_MAX_D = 64                      # OCTO_DRAWS_PF_MAX_D
 PF_MAX_ELBO_DRAWS = 32             # OCTO_DRAWS_PF_MAX_ELBO_DRAWS
 MAX_GROUPS = 64                    # OCTO_DRAWS_MAX_GROUPS
 DIAG_RHAT, DIAG_ESS_BULK, DIAG_ESS_TAIL, DIAG_RHAT_BASIC, DIAG_ESS_BASIC, DIAG_Q05, DIAG_Q50, DIAG_Q95, DIAG_N_STATS = range(9)      # OCTO_DRAWS_DIAG_*
+PT_ACC_COLUMNS = ("n", "A", "n_f", "m_f", "s_f", "n_b", "m_b", "s_b")      # the columns of d_acc [T − 1][8]
+PT_SUMMARY = ("barrier", "log_evidence_fwd", "log_evidence_rev", "log_evidence")      # the entries of d_summary, in order
 DIAG_NAMES = ("rhat", "ess_bulk", "ess_tail", "rhat_basic", "ess_basic", "q05", "q50", "q95")      # the rows of d_out, in order
 
 c_uint64_p = C.POINTER(C.c_uint64)
@@ -94,6 +99,8 @@ _SIGS = {
     "octo_draws_diagnose_work_doubles": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     "octo_draws_rank_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "octo_draws_pt_stats_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 7),
+    "octo_draws_pt_schedule_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -594,6 +601,68 @@ class PriorDraws(companion.Handle):
                                                     self._stream(stream, self.device)))
         self._keep = (cube,)
         return r, zs
+
+    # ---- parallel tempering between the scans (include/octofitter_hip_draws.h, "Parallel tempering between the scans"): no model needed
+    def pt_state(self, T, Cn):
+        """The state of pt_stats before its first call, for T temperatures and Cn chains: dict(acc float64 [T − 1, 8] (every m = −Inf, the rest
+        0), leg int32 [Cn, T], restarts int32 [Cn]), device tensors."""
+        import torch
+        T, Cn = int(T), int(Cn)
+        if not (2 <= T <= MAX_GROUPS and Cn >= 1):
+            raise ValueError(f"pt_state: T is 2 … {MAX_GROUPS}, Cn >= 1")
+        acc = torch.zeros((T - 1, 8), dtype=torch.float64, device=self.device)
+        acc[:, 3] = acc[:, 6] = -float("inf")
+        return dict(acc=acc, leg=torch.zeros((Cn, T), dtype=torch.int32, device=self.device), restarts=torch.zeros(Cn, dtype=torch.int32, device=self.device))
+
+    def _pt_acc(self, state, T, what):
+        import torch
+        acc = state["acc"]
+        if acc.dtype != torch.float64 or acc.device != self.device or acc.shape != (T - 1, 8) or not acc.is_contiguous():
+            raise ValueError(f"{what}: state['acc'] must be a contiguous float64 [{T - 1}, 8] tensor on {self.device} (pt_state makes it)")
+        return acc
+
+    def pt_stats(self, ll, slot2rep, beta, state, stream=None):
+        """One scan's statistics, accumulated into `state` (pt_state's dict, in place; returned): per pair of neighbouring slots the swap
+        acceptance probabilities and the two stepping-stone sums over every chain, and — unless state["leg"] is None — the tempered restarts.
+        ll: float64 [T·Cn] or [T, Cn] by replica; slot2rep: int32 [Cn, T]; beta: float64 [T] — TemperedSwap's three, as the swap step is about
+        to see them. Asynchronous on `stream`."""
+        import torch
+        dev = self.device
+        Cn, T = (int(n) for n in slot2rep.shape)
+        ok = ll.dtype == torch.float64 and ll.numel() == T * Cn and ll.is_contiguous() and slot2rep.dtype == torch.int32 and slot2rep.is_contiguous() \
+            and beta.dtype == torch.float64 and beta.shape == (T,) and beta.is_contiguous() and ll.device == dev and slot2rep.device == dev and beta.device == dev
+        if not ok:
+            raise ValueError(f"pt_stats: ll float64 [T·Cn], slot2rep int32 [Cn, T] and beta float64 [T], contiguous on {dev}")
+        acc = self._pt_acc(state, T, "pt_stats")
+        leg, rst = state.get("leg"), state.get("restarts")
+        if (leg is None) != (rst is None) or (leg is not None and not (leg.dtype == rst.dtype == torch.int32 and leg.shape == (Cn, T) and rst.shape == (Cn,)
+                                                                        and leg.is_contiguous() and rst.is_contiguous() and leg.device == dev and rst.device == dev)):
+            raise ValueError(f"pt_stats: state['leg'] int32 [Cn, T] and state['restarts'] int32 [Cn], contiguous on {dev}, or both None")
+        self._check(self.lib.octo_draws_pt_stats_device(self._h, T, Cn, ll.data_ptr(), slot2rep.data_ptr(), beta.data_ptr(), acc.data_ptr(), ptr(leg), ptr(rst),
+                                                        self._stream(stream, dev)))
+        self._keep = (ll, slot2rep, beta, state)
+        return state
+
+    def pt_schedule(self, state, beta, adapt=True, reset=True, beta_out=None, stream=None):
+        """A round's summary of `state` and the ladder that equalises the rejection rates along the barrier. beta: float64 [T]; beta_out: where
+        the ladder goes (default: a new tensor; beta itself may be given). adapt=False: statistics only, β copied through; reset: state["acc"]
+        is put back to zero once read (leg and restarts go on). Returns dict(beta [T], rejection [T − 1], summary [4], and its entries barrier,
+        log_evidence_fwd, log_evidence_rev, log_evidence as 0-d views), device tensors. Waits for `stream` once: β is checked on the host."""
+        import torch
+        dev = self.device
+        T = int(beta.numel())
+        if beta.dtype != torch.float64 or beta.device != dev or beta.ndim != 1 or not beta.is_contiguous():
+            raise ValueError(f"pt_schedule: beta must be a contiguous float64 [T] tensor on {dev}")
+        acc = self._pt_acc(state, T, "pt_schedule")
+        if beta_out is None:
+            beta_out = self._out(T)
+        elif beta_out.dtype != torch.float64 or beta_out.device != dev or beta_out.shape != (T,) or not beta_out.is_contiguous():
+            raise ValueError(f"pt_schedule: beta_out must be a contiguous float64 [{T}] tensor on {dev}")
+        rej, summary = self._out(max(T - 1, 0)), self._out(len(PT_SUMMARY))
+        self._check(self.lib.octo_draws_pt_schedule_device(self._h, T, acc.data_ptr(), beta.data_ptr(), 1 if adapt else 0, 1 if reset else 0, beta_out.data_ptr(),
+                                                           rej.data_ptr(), summary.data_ptr(), self._stream(stream, dev)))
+        self._keep = (state, beta, beta_out)
+        return dict(beta=beta_out, rejection=rej, summary=summary, **dict(zip(PT_SUMMARY, summary)))
 
     def close(self):
         if getattr(self, "_h", None) and self.model is not None and not getattr(self.model.ln_like, "_ctx", None):
