@@ -59,6 +59,11 @@
  * barrier and the ladder that equalises the rejection rates along it, stated in full at their declaration (tests/pt_reference.py restates them).
  * No model, no random number.
  *
+ * The eleventh is the variational reference of a second tempering leg (octo_draws_reference_set_device … octo_draws_reference_exchange_device): a
+ * mean-field normal on θ_t fitted to the target's own draws, kept as a prior table in caller-owned device memory, put under the handle's
+ * functions in place of its own table, and the exchange of the two legs' target replicas, stated in full at their declaration
+ * (tests/vref_reference.py restates them). No model, no random number.
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -584,6 +589,54 @@ int32_t octo_draws_pt_stats_device(octo_draws* h, int32_t T, int64_t Cn, const d
  * OCTO_EINVAL: NULL handle or array; T out of range; a d_beta that is not non-increasing from slot 0 (a NaN included). */
 int32_t octo_draws_pt_schedule_device(octo_draws* h, int32_t T, double* d_acc, const double* d_beta, int32_t adapt, int32_t reset, double* d_beta_out,
                                       double* d_rej, double* d_summary, void* hip_stream);
+
+/* ---- The variational reference of a tempering leg (Pigeons' GaussianReference, a mean-field normal in the unconstrained space, fitted by moment
+ * matching to the target's draws of the previous round; Surjanovic, Syed, Bouchard-Côté & Campbell 2022 anneal a second leg from it and join the
+ * two legs at the target. Recalled, not checked against Pigeons' source). A normal N(μ_d, σ_d) on θ_t is a prior of kind OCTO_PRIOR_NORMAL, whose
+ * link is the identity: with it as the handle's prior table ℓprior_t is log q(θ_t), the tempered target is (1 − β)·log q + β·ℓπ,
+ * octo_draws_sample_device draws μ + σ·Φ⁻¹(u), and the explorers' d_loglike is ℓπ − log q: the swap potential of a leg that anneals from q, what
+ * octo_pt_swap_device and octo_draws_pt_stats_device take. The handle's D is the number of coordinates throughout.
+ *
+ * The reference table d_ref: octo_draws_reference_doubles(D) = 15·D doubles of CALLER-owned device memory (0 for D < 1) — octo_prior [D] (40 bytes
+ * each), the density constants [D][4], the quantile constants [D][4], μ [D], σ [D], in this order. Host only, no handle.
+ *
+ * octo_draws_reference_set_device writes it from d_mean [D], d_sd [D]; octo_draws_reference_fit_device from ONE group's rows of
+ * octo_draws_moments_device (d_count_g [1], d_mean_g [D], d_m2_g [D]): μ_d = mean_d, σ_d = inflate·√(M2_d/(n − 1)), each operation rounded by itself.
+ * One wave, lane = coordinate. Coordinate d is BAD if μ_d or σ_d is not finite, σ_d <= 0, or (fit) n < 2. For every good coordinate:
+ *   octo_prior   kind = OCTO_PRIOR_NORMAL, pad = 0, p0 = μ, p1 = σ, lo = −Inf, hi = +Inf
+ *   constants    {NaN, 0 (= 1/(b − a) with both ends open), −log σ, 1/σ}: the entries octo_draws_create forms for a Normal; the quantile constants 0
+ *   μ, σ         as used
+ * A bad coordinate keeps every byte it had, so THE FIRST CALL ON A FRESH BUFFER MUST BE CLEAN: a table with a coordinate that was never written is
+ * no prior table. d_bad [1] (int32) receives the number of bad coordinates — written, not accumulated. No host synchronisation, no allocation:
+ * a driver re-fits between rounds and reads d_bad when it next waits anyway.
+ * OCTO_EINVAL: NULL handle or array; (fit) inflate not finite or <= 0. */
+int64_t octo_draws_reference_doubles(int32_t D);
+int32_t octo_draws_reference_set_device(octo_draws* h, const double* d_mean, const double* d_sd, double* d_ref, int32_t* d_bad, void* hip_stream);
+int32_t octo_draws_reference_fit_device(octo_draws* h, const double* d_count_g, const double* d_mean_g, const double* d_m2_g, double inflate, double* d_ref,
+                                        int32_t* d_bad, void* hip_stream);
+
+/* From the next call on, every function of the handle that reads the prior table — octo_draws_sample_device, octo_draws_best, octo_draws_rejection,
+ * the HMC step, NUTS, the slice sampler, the L-BFGS and Pathfinder — reads d_ref instead; NULL restores the handle's own table. Host only: two
+ * pointers change hands, nothing is copied, so the table may be re-fitted in place while it is active (work already enqueued reads whatever the
+ * table holds when it runs: order the re-fit on the same stream) and must outlive its use; its lifetime is the caller's. The call forgets the
+ * resume records of NUTS, the slice sampler and the L-BFGS: a transition is never resumed on another target. OCTO_EINVAL: NULL handle. */
+int32_t octo_draws_use_reference(octo_draws* h, const double* d_ref);
+
+/* The exchange of two legs at the target. Leg A (T_a slots) and leg B (T_b slots) hold Cn chains each in the layout of octo_pt_swap_device:
+ * d_slot2rep [Cn][T] int32, d_theta [D][ld] with replica r of chain c in column r·Cn + c, d_lp (ℓπ) and d_ll (the swap potential) by replica.
+ * d_ref_a, d_ref_b: the legs' reference tables, NULL = the handle's own prior (octo_draws_create's table, whether or not a reference is active). Lane = chain c;
+ * with column a = slot2rep_a[c][0]·Cn + c of leg A and b likewise of leg B:
+ *   θ_t    the D values of column a of d_theta_a and of column b of d_theta_b trade places, bit for bit; so do d_lp_a[a] and d_lp_b[b]
+ *   ℓ      each side's potential under ITS OWN reference at its NEW point: d_ll_a[a] = ℓπ_b − ℓprior_t,A(θ_b), d_ll_b[b] = ℓπ_a − ℓprior_t,B(θ_a),
+ *          ℓprior_t by the routine and in the order of the explorers; −Inf where the difference is not finite or the prior was healed.
+ * No other element of the six arrays is written. A chain with a slot-0 replica index outside 0 … T − 1 in either leg exchanges nothing.
+ * Why this is a valid move: both target replicas are at β = 1, where the tempered density of EITHER leg is π whatever its reference, and the two
+ * legs are independent; exchanging two independent states with the same marginal leaves the joint law unchanged, so the exchange is always
+ * accepted. It is how a tempered restart of one leg reaches the other.
+ * OCTO_EINVAL: NULL handle or array (the references excepted); T_a or T_b < 2; Cn < 1 or > 2^30; ld_a < T_a·Cn or ld_b < T_b·Cn; d_theta_a == d_theta_b. */
+int32_t octo_draws_reference_exchange_device(octo_draws* h, int64_t Cn, int32_t T_a, const int32_t* d_slot2rep_a, int64_t ld_a, double* d_theta_a,
+                                             double* d_lp_a, double* d_ll_a, const double* d_ref_a, int32_t T_b, const int32_t* d_slot2rep_b, int64_t ld_b,
+                                             double* d_theta_b, double* d_lp_b, double* d_ll_b, const double* d_ref_b, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -310,9 +310,10 @@ int32_t octo_draws_create(octo_ctx* ctx, octo_model* model, const octo_prior* pr
     { int rc = open_device(device_id, "octo_draws_create: ", h); if (rc) return rc; }
     h->ctx = ctx; h->model = model; h->D = D;
     auto bail = [&](int code, const char* msg) { octo_draws_destroy(h); return fail(nullptr, code, msg); };
-    if (hipMalloc((void**)&h->d_priors, sizeof(octo_prior) * D) != hipSuccess || hipMalloc((void**)&h->d_pc, sizeof(double) * pc.size()) != hipSuccess ||
-        hipMalloc((void**)&h->d_ic, sizeof(double) * ic.size()) != hipSuccess)
+    if (hipMalloc((void**)&h->own_priors, sizeof(octo_prior) * D) != hipSuccess || hipMalloc((void**)&h->own_pc, sizeof(double) * pc.size()) != hipSuccess ||
+        hipMalloc((void**)&h->own_ic, sizeof(double) * ic.size()) != hipSuccess)
         return bail(OCTO_ENOMEM, "octo_draws_create: hipMalloc failed");
+    h->d_priors = h->own_priors; h->d_pc = h->own_pc; h->d_ic = h->own_ic;      // the active table: the handle's own until octo_draws_use_reference
     if (hipMemcpy(h->d_priors, priors, sizeof(octo_prior) * D, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->d_pc, pc.data(), sizeof(double) * pc.size(), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->d_ic, ic.data(), sizeof(double) * ic.size(), hipMemcpyHostToDevice) != hipSuccess)
@@ -337,7 +338,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
         }
         if (release) (void)hipStreamDestroy(h->stream);
     }
-    for (void* p : std::initializer_list<void*>{h->d_priors, h->d_pc, h->d_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice})
+    for (void* p : std::initializer_list<void*>{h->own_priors, h->own_pc, h->own_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice})
         (void)hipFree(p);
     delete h;
     return OCTO_OK;

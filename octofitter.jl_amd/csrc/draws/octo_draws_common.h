@@ -4,7 +4,8 @@
 // (SamplerHead), the per-lane preamble (Chain, chain_of) and the tempered target at a point (Target, target_at over prior_loop, tempered_energy,
 // dead_state). On the host: check_sampler_call, sampler_head, logpost_at (every octo_model_logpost_device call of the four units) and
 // run_rounds (the round driver of the L-BFGS and of NUTS).
-// Nine units include it: octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
+// Ten units include it (the tenth: octo_draws_vref.hip, the reference table of a variational tempering leg and the exchange of two legs' target
+// replicas, which take prior_loop and the handle's active table): octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
 // explorer), octo_draws_nuts.hip (the no-U-turn sampler), octo_draws_slice.hip (the slice sampler, which takes the samplers' head, preamble, target
 // and round driver without a gradient), octo_draws_lbfgs.hip (the multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder
 // on its paths), octo_draws_adapt.hip (the warm-up statistics of the explorer), octo_draws_diag.hip (the convergence diagnostics of stored draws) and
@@ -197,8 +198,12 @@ struct octo_draws : CompanionBase {
     octo_model* model = nullptr;
     int D = 0;
     bool ctx_on_stream = false;      // the context was handed a stream (octo_model_logpost_device) and may still name it as its last stream
+    // the ACTIVE prior table, what every function reads: the handle's own (own_*, made by octo_draws_create and freed by octo_draws_destroy) or
+    // a caller's reference table (octo_draws_use_reference, octo_draws_vref.hip)
     octo_prior* d_priors = nullptr;
     double *d_pc = nullptr, *d_ic = nullptr;
+    octo_prior* own_priors = nullptr;
+    double *own_pc = nullptr, *own_ic = nullptr;
     // the drivers (octo_draws.hip), one allocation per group: the chunk buffers and candidate lists (fixed size), the per-draw arrays of a
     // call and the outputs before they go to the host (both grown on demand)
     double* d_chunk = nullptr; int64_t cap_chunk = 0;

@@ -131,6 +131,16 @@ inline PtPartials pt_partials(Carve& c, int64_t P, int64_t nblk) {
     return {c.take(P * nblk), c.take(P * nblk), c.take(P * nblk), c.take(P * nblk), c.take(P * nblk), c.take(P * nblk), c.take(P * nblk)};
 }
 
+// The reference table of a variational leg (octo_draws_vref.hip), CALLER-owned: 15·D doubles at D coordinates, PRIOR_NC = IC_N = 4. What a
+// handle's three prior arrays hold, side by side, and the fit they were made from: D octo_prior of 40 bytes — REF_PRIOR_DOUBLES doubles —
+// each, their constants, and μ and σ. octo_draws_reference_doubles sizes it; octo_draws_use_reference points the handle's active table at its
+// first three parts.
+constexpr int64_t REF_PRIOR_DOUBLES = 5;      // sizeof(octo_prior)/8: {int32 kind, pad; double p0, p1, lo, hi}
+struct RefTable { double *priors, *pc, *ic, *mean, *sd; };      // octo_prior [D] · [D][nc] · [D][icn] · [D] · [D]
+inline RefTable ref_table(Carve& c, int64_t D, int64_t nc, int64_t icn) {
+    return {c.take(REF_PRIOR_DOUBLES * D), c.take(nc * D), c.take(icn * D), c.take(D), c.take(D)};
+}
+
 // The convergence diagnostics of K rows (octo_draws_diag.hip), d_diag: 2K(P + S) + 10KM + 4K·T·(nblk + 1) + 5K. N draws of M = 2W split chains a row,
 // S = M·N used draws, P = the power of two the sort pads them to, T = the lags rounded up to whole blocks of 16, nblk = ⌈M/256⌉. The kernels take it
 // by value: its members and their order are their argument layout.

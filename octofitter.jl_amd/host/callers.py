@@ -12,7 +12,8 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   octofit_pt_device: parallel tempering with a tempered HMC explorer, fresh prior draws at β = 0 and the swap step all on the device
   (PriorDraws.hmc_step, host/tempering.py: TemperedSwap) — the device-resident twin of julia/OctofitterHIP.jl: octofit_pigeons_hip.
   octofit_pigeons_device: that driver in Pigeons' rounds — the ladder re-placed from the communication barrier, the log evidence and the tempered
-  restarts, from per-scan reductions on the device (PriorDraws.pt_stats / pt_schedule).
+  restarts, from per-scan reductions on the device (PriorDraws.pt_stats / pt_schedule). With n_temps_variational it runs Pigeons' second leg beside the
+  first: replicas annealed from a mean-field normal fitted to the target's own draws (PriorDraws.reference_fit / reference / reference_exchange).
 
   warmup_windows / hmc_warmup / octofit_hmc_device: the single-temperature sampler — Pathfinder starts, then HMC whose step size (dual
   averaging on the mean acceptance probability) and diagonal metric (the pooled variance of the chains, Stan's windowed schedule) are adapted
@@ -264,7 +265,7 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
 
 
 def octofit_pigeons_device(model, n_temps, n_chains, n_rounds, explorer="slice", n_leapfrog=4, eps=None, betas=None, inv_mass=None, seed=0, slice_w=10.0,
-                           slice_p=3, n_passes=3):
+                           slice_p=3, n_passes=3, n_temps_variational=0, first_tuning_round=5, inflate=1.0):
     """octofit_pt_device with what Pigeons does BETWEEN its scans (non-reversible parallel tempering, Syed et al. 2021) — the device-resident twin of
     the reference's octofit_pigeons in its round structure too. Round r = 1 … n_rounds makes 2^r scans, 2^(n_rounds + 1) − 2 in all. A scan is
     exactly a round of octofit_pt_device (β per replica from slot2rep; explore; the β = 0 replicas redrawn IID; record the target replica; swap), its
@@ -283,7 +284,27 @@ def octofit_pigeons_device(model, n_temps, n_chains, n_rounds, explorer="slice",
     slice_evals, and swap_acceptance, over all scans; betas (the final ladder), names, state — plus log_evidence = dict(fwd, rev, mean: the
     stepping-stone estimates of log Z of the last round; n, n_fwd, n_rev [n_temps − 1]: the pairs' scans × chains and the terms behind the two); betas_by_round [n_rounds + 1, n_temps] (row 0 the start, row r the ladder after round
     r); rejection_by_round [n_rounds, n_temps − 1]; barrier_by_round [n_rounds] (Λ); restarts = dict(total, per_chain [n_chains]): the tempered
-    restarts over the run; n_scans. All NumPy."""
+    restarts over the run; n_scans. All NumPy.
+
+    n_temps_variational = Tv >= 2 runs Pigeons' second leg beside the first (its default run is two-legged): Tv·n_chains more replicas that anneal
+    not from the prior but from a mean-field normal q on θ_t, fitted by moment matching to the target's own draws round after round
+    (PriorDraws.reference_fit on the grouped moments of the target replicas of BOTH legs; σ times `inflate`), the two legs joined at the
+    target. Recalled, not checked against Pigeons' source: the first tuning round, moment matching on the target's draws of the previous
+    round, and the two legs joined at the target. The second leg has its own TemperedSwap, pt_state, ladder (TemperedSwap's cubic one; `betas`
+    is the first leg's) and, with "hmc", dual-averaging state; the metric is shared. Its swap potential is ℓπ − log q. A scan is, in order:
+    explore both legs — the second under PriorDraws.reference(its table) once it has one, under the prior until then —; refresh each leg's
+    β = 0 replicas from its own reference; accumulate the target replicas of both legs into the round's moments; PriorDraws.reference_exchange
+    (the two target replicas of a chain trade places: always accepted, both are at β = 1); record the targets; pt_stats and the swap step per
+    leg. At the end of round r >= first_tuning_round − 1 (not of the last: its reference is the one its log evidence belongs to) the normal is
+    re-fitted from that round's moments into a staging table; every round ends by resetting the moments. The count of bad coordinates is read
+    right after the round's pt_schedule calls, which have waited for the stream anyway — no new synchronisation inside a round —, and with
+    bad > 0 the leg keeps the reference it had.
+    Counter ranges, so that no (seed, purpose, step, chain) tuple serves both legs: the first leg explores as chains 0 … n_temps·n_chains − 1,
+    takes prior draws 0, 1, … (below 2^50) and swaps at steps 0 … n_scans − 1; the second explores as chains n_temps·n_chains …
+    (n_temps + Tv)·n_chains − 1, takes draws 2^62, 2^62 + 1, … and swaps at steps 2^40 + scan (the same parity).
+    The result then gains variational = dict(log_evidence, betas_by_round, rejection_by_round, barrier_by_round, restarts as above, of the second
+    leg; samples, samples_t, logpost of ITS target replicas over the last round; mean_by_round, sd_by_round [n_rounds, D]: the reference the leg
+    holds after each round, NaN while it has none; bad_by_round [n_rounds]: the bad coordinates of each round's fit, 0 where none was made)."""
     import torch
     from .draws import PriorDraws
     from .tempering import TemperedSwap
@@ -292,6 +313,9 @@ def octofit_pigeons_device(model, n_temps, n_chains, n_rounds, explorer="slice",
         raise ValueError("octofit_pigeons_device: n_temps >= 2, n_chains >= 1, 1 <= n_rounds <= 24")
     if explorer not in ("hmc", "slice"):
         raise ValueError('octofit_pigeons_device: explorer is "hmc" or "slice"')
+    if int(n_temps_variational) != 0:
+        return _pigeons_two_legs(model, T, int(n_temps_variational), Cn, R, explorer == "slice", n_leapfrog, eps, betas, inv_mass, seed, slice_w, slice_p,
+                                 n_passes, int(first_tuning_round), float(inflate))
     use_slice = explorer == "slice"
     fn = model.ln_like
     dev = torch.device("cuda", fn.device_index)
@@ -371,6 +395,137 @@ def octofit_pigeons_device(model, n_temps, n_chains, n_rounds, explorer="slice",
                                       n_rev=counts[:, 2]),
                     betas_by_round=betas_by_round.cpu().numpy(), rejection_by_round=rejection_by_round.cpu().numpy(), barrier_by_round=summary[:, 0].copy(),
                     restarts=dict(total=int(per_chain.sum()), per_chain=per_chain), n_scans=n_scans)
+
+
+VARIATIONAL_FIRST_DRAW = 1 << 62      # the second leg's prior / reference draws start here; the first leg's stay below 2^50
+VARIATIONAL_SWAP_STEP = 1 << 40       # … and its swap steps (even: the parity of a scan is kept)
+
+
+def _pigeons_two_legs(model, T, Tv, Cn, R, use_slice, n_leapfrog, eps, betas, inv_mass, seed, slice_w, slice_p, n_passes, first_tuning_round, inflate):
+    """octofit_pigeons_device with a variational leg of Tv temperatures (its docstring states the scan, the fit and the counter ranges)."""
+    import math
+    from types import SimpleNamespace
+    import torch
+    from .draws import PriorDraws
+    from .tempering import TemperedSwap
+    if Tv < 2 or first_tuning_round < 1 or not (math.isfinite(inflate) and inflate > 0.0):
+        raise ValueError("octofit_pigeons_device: n_temps_variational is 0 or >= 2, first_tuning_round >= 1, inflate finite and > 0")
+    fn = model.ln_like
+    dev = torch.device("cuda", fn.device_index)
+    D = int(model.D)
+    n_scans, n_keep = 2 ** (R + 1) - 2, 2 ** R
+    n_adapt = 0 if use_slice else n_scans - n_keep
+    f64 = dict(dtype=torch.float64, device=dev)
+    with PriorDraws(model) as pd:
+        if not use_slice:
+            inv_mass = _default_metric(pd, seed, dev, inv_mass)
+        chains = torch.arange(Cn, device=dev)
+
+        def new_leg(Tl, chain0, draw0, step0, ladder):
+            swap = TemperedSwap(fn, Tl, Cn, device=dev, seed=seed, betas=ladder)
+            g = SimpleNamespace(T=Tl, chain0=chain0, next_draw=draw0 + Tl * Cn, step0=step0, swap=swap, cold_last=float(swap.beta[-1]) == 0.0,
+                                theta_t=pd.sample(seed, draw0, Tl * Cn, theta=False, logprior_t=False)[1], pt=pd.pt_state(Tl, Cn),
+                                slots=torch.arange(Tl, dtype=torch.int32, device=dev).repeat(Cn, 1), acc_sum=torch.zeros(Tl, **f64), da=None, log_eps=None,
+                                rec_t=torch.empty((n_keep, D, Cn), **f64), rec_lp=torch.empty((n_keep, Cn), **f64), betas_by_round=torch.empty((R + 1, Tl), **f64),
+                                rejection_by_round=torch.empty((R, Tl - 1), **f64), summary_by_round=torch.empty((R, 4), **f64), refreshed=None, counts=None)
+            g.betas_by_round[0] = swap.beta
+            if not use_slice:
+                g.da = pd.adapt_init(Tl, torch.as_tensor(0.1 if eps is None else eps, **f64).expand(Tl).contiguous())
+                g.log_eps = g.da[:, 0].clone()
+            return g
+
+        def explore(g, scan, ref):
+            """steps 1 and 2 of a scan for one leg: ℓπ and the swap potential of every replica under the leg's reference"""
+            rep2slot = torch.empty_like(g.swap.slot2rep)
+            rep2slot.scatter_(1, g.swap.slot2rep.long(), g.slots)
+            g.slot_w = rep2slot.t().contiguous().reshape(-1).long()                   # the ladder slot of walker r·n_chains + c
+            with pd.reference(ref):
+                if use_slice:
+                    so = pd.slice_step(g.theta_t, beta=g.swap.beta[g.slot_w], w=slice_w, p=slice_p, n_passes=n_passes, seed=seed, step=scan, chain0=g.chain0)
+                    g.lp, g.ll, acc = so["logpost"], so["loglike"], so["n_eval"]
+                else:
+                    g.lp, g.ll, dH, acc = pd.hmc_step(g.theta_t, beta=g.swap.beta[g.slot_w], eps=torch.exp(g.log_eps)[g.slot_w], n_leapfrog=n_leapfrog,
+                                                      inv_mass=inv_mass, seed=seed, step=scan, chain0=g.chain0)
+                if g.cold_last:
+                    g.refreshed = g.swap.slot2rep[:, g.T - 1].long() * Cn + chains
+                    _, fresh, lpt = pd.sample(seed, g.next_draw, Cn, theta=False)
+            if g.cold_last:
+                lp_f, _ = model.logpost_device(fresh, grad=False)
+                g.theta_t[:, g.refreshed] = fresh
+                g.lp[g.refreshed] = lp_f
+                g.ll[g.refreshed] = _finite_or_neg_inf(lp_f - lpt)
+                g.next_draw += Cn
+            g.acc_sum += torch.zeros(g.T, **f64).index_add_(0, g.slot_w, acc.double()) / Cn
+            if scan < n_adapt:
+                pd.adapt_step(g.da, dH, acc, scan + 1, group=g.slot_w.int(), want_eps=False)
+                g.log_eps = g.da[:, 1 if scan == n_adapt - 1 else 0].clone()          # the next scan's slots differ: ε is gathered by slot there
+
+        A = new_leg(T, 0, 0, 0, betas)
+        B = new_leg(Tv, T * Cn, VARIATIONAL_FIRST_DRAW, VARIATIONAL_SWAP_STEP, None)
+        ref, staging, active = pd.reference_table(), pd.reference_table(), None       # active: the table the second leg anneals from, None = the prior
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        mom = (torch.zeros(1, **f64), torch.zeros((1, D), **f64), torch.zeros((1, D), **f64))
+        mean_by_round = torch.full((R, D), float("nan"), **f64)
+        sd_by_round = torch.full((R, D), float("nan"), **f64)
+        bad_by_round = np.zeros(R, dtype=np.int64)
+        scan = 0
+        for r in range(1, R + 1):
+            for _ in range(2 ** r):
+                explore(A, scan, None)
+                explore(B, scan, active)
+                for g in (A, B):
+                    pd.moments(g.theta_t, group=torch.where(g.slot_w == 0, 0, -1).int(), G=1, out=mom, accumulate=True)
+                pd.reference_exchange(A.swap.slot2rep, A.theta_t, A.lp, A.ll, None, B.swap.slot2rep, B.theta_t, B.lp, B.ll, active)
+                for g in (A, B):
+                    if r == R:
+                        target = g.swap.slot2rep[:, 0].long() * Cn + chains
+                        g.rec_t[scan - (n_scans - n_keep)] = g.theta_t[:, target]
+                        g.rec_lp[scan - (n_scans - n_keep)] = g.lp[target]
+                    pd.pt_stats(g.ll, g.swap.slot2rep, g.swap.beta, g.pt)
+                    g.swap.swap_step(g.ll, g.step0 + scan)
+                scan += 1
+            fit = first_tuning_round - 1 <= r < R
+            if fit:
+                pd.reference_fit(staging, mom[0], mom[1][0], mom[2][0], inflate=inflate, bad=bad)
+            for t in mom:
+                t.zero_()
+            for g in (A, B):
+                if r == R:
+                    g.counts = g.pt["acc"][:, [0, 2, 5]].clone()
+                s = pd.pt_schedule(g.pt, g.swap.beta, adapt=r < R, reset=True, beta_out=g.swap.beta)
+                g.betas_by_round[r] = g.swap.beta
+                g.rejection_by_round[r - 1] = s["rejection"]
+                g.summary_by_round[r - 1] = s["summary"]
+            if fit:
+                bad_by_round[r - 1] = int(bad.item())      # pt_schedule has waited for the stream: the fit is done
+                if bad_by_round[r - 1] == 0:
+                    ref.copy_(staging)
+                    active = ref
+            if active is not None:
+                mean_by_round[r - 1], sd_by_round[r - 1] = pd.reference_moments(ref)
+        torch.cuda.synchronize(dev)
+
+        def result(g):
+            pairs = np.arange(g.T - 1)
+            attempts = np.array([(n_scans + 1 - (t % 2)) // 2 for t in pairs]) * Cn  # pair (t, t + 1) is tried in the scans of parity t % 2
+            explored = dict(slice_evals=(g.acc_sum / n_scans).cpu().numpy()) if use_slice else dict(hmc_acceptance=(g.acc_sum / n_scans).cpu().numpy(),
+                                                                                                 eps=torch.exp(g.log_eps).cpu().numpy())
+            summary = g.summary_by_round.cpu().numpy()
+            per_chain = g.pt["restarts"].cpu().numpy()
+            counts = g.counts.cpu().numpy().astype(np.int64)
+            return dict(**_recorded(model, g.rec_t, g.rec_lp), **explored, swap_acceptance=g.swap.accepted.cpu().numpy()[:g.T - 1] / np.maximum(attempts, 1),
+                        betas=g.swap.beta.cpu().numpy(),
+                        log_evidence=dict(fwd=float(summary[-1, 1]), rev=float(summary[-1, 2]), mean=float(summary[-1, 3]), n=counts[:, 0], n_fwd=counts[:, 1],
+                                          n_rev=counts[:, 2]),
+                        betas_by_round=g.betas_by_round.cpu().numpy(), rejection_by_round=g.rejection_by_round.cpu().numpy(),
+                        barrier_by_round=summary[:, 0].copy(), restarts=dict(total=int(per_chain.sum()), per_chain=per_chain))
+
+        out = result(A)
+        out.update(names=list(model.names), n_scans=n_scans,
+                   state=dict(theta_t=A.theta_t.cpu().numpy(), slot2rep=A.swap.slot2rep.cpu().numpy(),
+                              refreshed=None if A.refreshed is None else A.refreshed.cpu().numpy(), refreshed_first=A.next_draw - Cn if A.cold_last else None),
+                   variational=dict(**result(B), mean_by_round=mean_by_round.cpu().numpy(), sd_by_round=sd_by_round.cpu().numpy(), bad_by_round=bad_by_round))
+        return out
 
 
 def warmup_windows(n_warmup):

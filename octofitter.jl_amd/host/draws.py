@@ -22,6 +22,10 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     state = draws.pt_state(T, Cn)                           # parallel tempering between the scans: the zeroed state (acc, leg, restarts)
     draws.pt_stats(ll, slot2rep, beta, state)               # … a scan's swap probabilities, stepping-stone sums and tempered restarts, accumulated
     r = draws.pt_schedule(state, beta)                      # … a round's rejection rates, barrier Λ, log evidence and the re-placed ladder: dict
+    ref = draws.reference_table()                           # a variational tempering leg: the reference table, an empty device buffer
+    bad = draws.reference_fit(ref, count[0:1], mean[0], m2[0])      # … a mean-field normal on θ_t from one group's moments (reference_set: from μ, σ)
+    with draws.reference(ref): ...                          # … every call inside reads the table in place of the handle's priors
+    draws.reference_exchange(s2r_a, θ_a, lp_a, ll_a, None, s2r_b, θ_b, lp_b, ll_b, ref)      # … the two legs' target replicas trade places
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -29,6 +33,7 @@ has not been built: the draws have no NumPy fallback here (host/callers.py keeps
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import numpy as np
@@ -101,6 +106,12 @@ _SIGS = {
                                            C.c_void_p]),
     "octo_draws_pt_stats_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 7),
     "octo_draws_pt_schedule_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "octo_draws_reference_doubles": (C.c_int64, [C.c_int32]),
+    "octo_draws_reference_set_device": (C.c_int32, [C.c_void_p] * 6),
+    "octo_draws_reference_fit_device": (C.c_int32, [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 3),
+    "octo_draws_use_reference": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "octo_draws_reference_exchange_device": (C.c_int32, [C.c_void_p, C.c_int64] + [C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+                                             + [C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -663,6 +674,96 @@ class PriorDraws(companion.Handle):
                                                            rej.data_ptr(), summary.data_ptr(), self._stream(stream, dev)))
         self._keep = (state, beta, beta_out)
         return dict(beta=beta_out, rejection=rej, summary=summary, **dict(zip(PT_SUMMARY, summary)))
+
+    # ---- the variational reference of a tempering leg (include/octofitter_hip_draws.h, "The variational reference of a tempering leg"): no model needed
+    def reference_table(self):
+        """An empty reference table for this handle's D on its device: float64 [octo_draws_reference_doubles(D)]. Its first reference_set or
+        reference_fit must be clean (bad = 0): a coordinate never written is no prior."""
+        import torch
+        return torch.zeros(int(self.lib.octo_draws_reference_doubles(self.D)), dtype=torch.float64, device=self.device)
+
+    def _reference(self, ref, what, none_ok=False):
+        import torch
+        if ref is None and none_ok:
+            return None
+        if ref is None or ref.dtype != torch.float64 or ref.device != self.device or ref.ndim != 1 or not ref.is_contiguous() \
+                or ref.numel() != int(self.lib.octo_draws_reference_doubles(self.D)):
+            raise ValueError(f"{what}: ref must be the contiguous float64 tensor reference_table() makes, on {self.device}")
+        return ref
+
+    def reference_set(self, ref, mean, sd, bad=None, stream=None):
+        """The table of N(mean_d, sd_d) on θ_t written into `ref` (in place): mean, sd float64 [D]. A coordinate with a non-finite mean or sd, or
+        sd <= 0, keeps what it had. Returns the device tensor bad int32 [1], their number (bad=: written into it). Asynchronous on `stream`."""
+        import torch
+        self._reference(ref, "reference_set")
+        mu, sg = (device_vector(t, self.D, self.device, "reference_set") for t in (mean, sd))
+        bad = self._out(1, dtype=torch.int32) if bad is None else bad
+        self._check(self.lib.octo_draws_reference_set_device(self._h, mu.data_ptr(), sg.data_ptr(), ref.data_ptr(), bad.data_ptr(), self._stream(stream, self.device)))
+        self._keep = (ref, mu, sg, bad)
+        return bad
+
+    def reference_fit(self, ref, count, mean, m2, inflate=1.0, bad=None, stream=None):
+        """The table fitted to ONE group's moments (count [1], mean [D], m2 [D]: rows of moments' outputs), written into `ref` in place:
+        μ = mean, σ = inflate·√(M2/(n − 1)). With n < 2 every coordinate is bad and the table keeps what it had. Returns bad int32 [1]."""
+        import torch
+        self._reference(ref, "reference_fit")
+        for t, n in ((count, 1), (mean, self.D), (m2, self.D)):
+            if t.dtype != torch.float64 or t.device != self.device or t.numel() != n or not t.is_contiguous():
+                raise ValueError("reference_fit: count [1], mean [D] and m2 [D] must be contiguous float64 tensors on the handle's device")
+        bad = self._out(1, dtype=torch.int32) if bad is None else bad
+        self._check(self.lib.octo_draws_reference_fit_device(self._h, count.data_ptr(), mean.data_ptr(), m2.data_ptr(), float(inflate), ref.data_ptr(),
+                                                             bad.data_ptr(), self._stream(stream, self.device)))
+        self._keep = (ref, count, mean, m2, bad)
+        return bad
+
+    def reference_moments(self, ref):
+        """(μ [D], σ [D]) of the table `ref`: views of its last two parts."""
+        self._reference(ref, "reference_moments")
+        return ref[-2 * self.D:-self.D], ref[-self.D:]
+
+    def use_reference(self, ref):
+        """octo_draws_use_reference: from the next call on the handle reads `ref` in place of its priors; None restores them. The handle keeps
+        the tensor alive while it is active."""
+        self._reference(ref, "use_reference", none_ok=True)
+        self._check(self.lib.octo_draws_use_reference(self._h, ptr(ref)))
+        self._active_reference = ref
+
+    @contextlib.contextmanager
+    def reference(self, ref):
+        """with pd.reference(ref): every call inside reads the table `ref`; on leaving, what was active before is active again. None: the
+        handle's own priors (a leg that has no reference yet takes the same code path)."""
+        before = getattr(self, "_active_reference", None)
+        self.use_reference(ref)
+        try:
+            yield self
+        finally:
+            self.use_reference(before)
+
+    def reference_exchange(self, slot2rep_a, theta_a, lp_a, ll_a, ref_a, slot2rep_b, theta_b, lp_b, ll_b, ref_b, stream=None):
+        """The exchange of two legs' target replicas, in place: per leg slot2rep int32 [Cn, T], theta_t float64 [D, >= T·Cn] (rows contiguous), ℓπ
+        and the swap potential float64 [>= T·Cn] by replica, and its reference table (None: the handle's own prior). The two legs' Cn agree.
+        Asynchronous on `stream`."""
+        import torch
+        dev = self.device
+        legs = []
+        for s2r, th, lp, ll, ref, name in ((slot2rep_a, theta_a, lp_a, ll_a, ref_a, "a"), (slot2rep_b, theta_b, lp_b, ll_b, ref_b, "b")):
+            if s2r.dtype != torch.int32 or s2r.ndim != 2 or s2r.device != dev or not s2r.is_contiguous():
+                raise ValueError(f"reference_exchange: slot2rep_{name} must be a contiguous int32 [Cn, T] tensor on {dev}")
+            Cn, T = (int(n) for n in s2r.shape)
+            _, cols, ld = chain_matrix(th, self.D, dev, "reference_exchange", f"theta_{name}")
+            for t, what in ((lp, "lp"), (ll, "ll")):
+                if t.dtype != torch.float64 or t.device != dev or t.ndim != 1 or not t.is_contiguous() or t.numel() < T * Cn:
+                    raise ValueError(f"reference_exchange: {what}_{name} must be a contiguous float64 tensor of at least T·Cn values on {dev}")
+            if cols < T * Cn:
+                raise ValueError(f"reference_exchange: theta_{name} holds fewer than T·Cn columns")
+            legs.append((Cn, T, s2r, ld, th, lp, ll, self._reference(ref, "reference_exchange", none_ok=True)))
+        (Cn, T_a, s_a, ld_a, th_a, p_a, l_a, r_a), (Cn_b, T_b, s_b, ld_b, th_b, p_b, l_b, r_b) = legs
+        if Cn != Cn_b:
+            raise ValueError("reference_exchange: the two legs must hold the same number of chains")
+        self._check(self.lib.octo_draws_reference_exchange_device(self._h, Cn, T_a, s_a.data_ptr(), ld_a, th_a.data_ptr(), p_a.data_ptr(), l_a.data_ptr(), ptr(r_a),
+                                                                  T_b, s_b.data_ptr(), ld_b, th_b.data_ptr(), p_b.data_ptr(), l_b.data_ptr(), ptr(r_b),
+                                                                  self._stream(stream, dev)))
+        self._keep = tuple(x for leg in legs for x in leg[2:])
 
     def close(self):
         if getattr(self, "_h", None) and self.model is not None and not getattr(self.model.ln_like, "_ctx", None):
