@@ -220,6 +220,12 @@ int get_tasks(octo_ctx* ctx, const octo_dataset* ds, int64_t key, TaskTable** ou
             chunk = (rows_per_task + wpb - 1) / wpb;
         }
         const int64_t span = chunk * wpb;
+        bool even = n > 1;
+        {
+            double smin = INFINITY, smax = 0.0;
+            for (int64_t r = 1; r < n; ++r) { smin = std::min(smin, (double)ds->h_step[o][r]); smax = std::max(smax, (double)ds->h_step[o][r]); }
+            even = even && std::isfinite(smax) && smin > 0.0 && smax - smin <= 1.0e-7 * smax;
+        }
         for (int64_t r0 = 0; r0 < n; r0 += span) {
             Task t;
             std::memset(&t, 0, sizeof(t));
@@ -231,6 +237,9 @@ int get_tasks(octo_ctx* ctx, const octo_dataset* ds, int64_t key, TaskTable** ou
                 float f = (float)km;
                 if ((double)f < km) f = std::nextafterf(f, INFINITY);
                 t.key_max = std::isfinite(km) ? f : INFINITY;
+                // … and the table's common step where ALL its steps agree to 1e-7 relative (the extrapolated gap of kepler_warm_newton scales with the step
+                // cubed: 1e-7 moves it by under 1e-10 of itself), else 0: a table with one odd step keeps the warm loop it had in every task
+                t.dm_uniform = (even && std::isfinite(km) && km > 0.0) ? f : 0.0f;
             }
             tt.h_tasks.push_back(t);
             double a = 0.0, b = 0.0;
@@ -518,6 +527,7 @@ int32_t octo_ctx_create(octo_ctx** out, int32_t device_id) {
     if (const char* ev = std::getenv("OCTO_WIDE")) ctx->env_wide = std::atoi(ev);
     if (const char* ev = std::getenv("OCTO_FIN_FUSED")) ctx->env_no_fin_fused = std::atoi(ev) ? 0 : 1;
     if (const char* ev = std::getenv("OCTO_WARM")) { ctx->env_warm = std::atoi(ev); ctx->opt_warm = ctx->env_warm ? 1 : 0; }
+    if (const char* ev = std::getenv("OCTO_WARM_NEWTON")) ctx->env_warm_newton = std::atoi(ev) ? 1 : 0;
     if (const char* ev = std::getenv("OCTO_TILE_SORT")) ctx->tile_mode = std::min(std::max(std::atoi(ev), 0), 2);      // experiments: the default of OCTO_OPT_TILE_SORT
     if (const char* ev = std::getenv("OCTO_TILE_MIN_W")) ctx->tile_min_w = std::max<int64_t>(std::atoll(ev), 64);
     *out = ctx;
@@ -844,7 +854,7 @@ static int eval_impl(octo_ctx* ctx, const octo_dataset* ds, const double* d_elem
     a.n_obs = ds->n_obs; a.n_planets = ds->n_planets;
     for (int p = 0; p < ds->n_planets; ++p) { a.orbit_kind[p] = ds->planets[p].orbit_kind; a.has_mass[p] = ds->planets[p].has_mass; }
     a.elems = d_elems; a.nuis = d_nuis; a.ld = ld; a.W = W;
-    a.warm = (ctx->opt_warm && !ctx->opt_invariant) ? 1 : 0;
+    a.warm = (ctx->opt_warm && !ctx->opt_invariant) ? (1 | (ctx->env_warm_newton ? 2 : 0)) : 0;
     a.ws_in = a.ws_out = 1;
     if (ctx->stage_ws_in > 0) { a.ws_in = ctx->stage_ws_in; a.ws_out = ctx->stage_ws_out; }      // octo_eval's walker-major staging (k_small only)
     a.wc = ctx->d_wc; a.valid = ctx->d_valid; a.ldw = ctx->cap_w; a.sctab = ctx->d_sctab;

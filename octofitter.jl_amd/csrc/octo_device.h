@@ -135,6 +135,8 @@ constexpr float WARM_X_CAP = 0.06f;       // bound (b): |x| the rotation's polyn
 constexpr float WARM_E_MAX = 0.99f;       // above: bound (a) alone
 constexpr int WARM_LADDER = 8;            // candidate step bounds per table (DevObs::dm_ladder)
 constexpr int WARM_RESTART = 256;         // every WARM_RESTART-th row of a table starts cold
+constexpr float WARM_NEWTON_TOL = 4.0e-16f;      // Newton-only rows (kepler_warm_newton): τ² e/√(1 − e²) stays below this — twice the bound on the Newton step's truncation
+constexpr float WARM_NEWTON_CAP = 1.4e-8f;       // … and τ below this: the rotation through δ drops δ²/2 < 1e-16
 
 // The lane's bound on 1/D of the previous row (KWarm above): e the eccentricity, dm = |ΔM| of the wave's step bound. FP32 (v_log_f32 / v_exp_f32 are base 2),
 // once per lane per task. The ONE copy of the formula: k_main (warm_init, warm_last_init), the test hook k_kepler_warm and k_tile_sort's closed-form failure
@@ -364,8 +366,9 @@ __device__ __forceinline__ float markley_starter_f32(double frac, const PC& pc) 
 // INV_NR: Newton steps on 1/(1 − e cos E) (1 when it only feeds adjoints, 2 when it feeds a model value, -1 when nobody needs it).
 // FOURTH_ORDER: stop at δ4 — for a start within WARM_TOL of the root (the warm rows of k_main) δ4's error is already below the rounding
 // of the rotation that follows (tools/kepler_warm_proto.py: the same 1.1e-15 D-weighted maximum as δ5 over config 3's walkers; 1.4e-14 at four times the tolerance).
+// d_out: where a caller wants the correction δ itself (kepler_warm_newton's history), or null.
 template <int INV_NR, bool FOURTH_ORDER = false>
-__device__ __forceinline__ void kepler_correct(KSol& s, const PC& pc, double E1, double s1, double c1, double f0) {
+__device__ __forceinline__ void kepler_correct(KSol& s, const PC& pc, double E1, double s1, double c1, double f0, double* d_out = nullptr) {
     const double e = pc.e;
     // f2/2, f2/24, f3/6 of Markley's (21)-(27) from the loop-invariant e/2 and e/6 (f2 = e sin E1 itself is not needed)
     const double hf2 = pc.he * s1, q24 = hf2 * (1.0 / 12.0);
@@ -389,6 +392,7 @@ __device__ __forceinline__ void kepler_correct(KSol& s, const PC& pc, double E1,
         d5 = fma(-r4, fma(den5, d4, f0), d4);
     }
     s.E = E1 + d5;                                                   // eq. (29); dead code unless a caller reads it
+    if (d_out) *d_out = d5;
     // ---- sin/cos(E1 + δ5) by rotation; |δ5| < 5e-4: sin δ = δ(1 − δ²/6) (+1e-19), cos δ − 1 = δ²(−1/2 + δ²/24) (+1e-23)
     const double dd = d5 * d5;
     const double sd = d5 * fma(dd, OCTO_KT[18], 1.0);
@@ -510,6 +514,100 @@ __device__ __forceinline__ KSol kepler_solve_warm(double t, const PC& pc, const 
         kepler_correct<INV_NR>(s, pc, E1, s1, c1, f0);
     }
     }
+    st.sE = s.sE; st.cE = s.cE; st.invD = s.invD;
+    return s;
+}
+
+// NEWTON-ONLY WARM ROWS from an extrapolated predictor (evenly sampled tables: Task::dm_uniform). Everything kepler_solve_warm does after f0 — the fourth-order
+// correction with its own reciprocal, the rotation through δ4 with its polynomials, a second reciprocal for 1/D — is there because the second-order predictor
+// misses the root by up to WARM_TOL. At a constant step the miss c_j = (E_j − E_{j−1}) − dE2_j is smooth in j, and for the rows behind it is known: it is the
+// correction that was applied. Extrapolated from the last rows (c_pred = 3(c₁ − c₂) + c₃ from three, 4(c₁ + c₃) − 6c₂ − c₄ from four), it puts the start dE2 + c_pred within ~1e-8 of the root on most
+// rows (tests/warm_newton_model.py: 0.7-0.8 of config 3's wave-rows), and from there ONE Newton step δ = −f0/f1 is exact to rounding: its truncation is
+// δ²·(e sin E)/(2D) <= ½ δ² β_max, β_max = e/√(1 − e²), below WARM_NEWTON_TOL/2 for |δ| <= τ(e) = min(√(WARM_NEWTON_TOL/β_max), WARM_NEWTON_CAP); the rotation through δ
+// is two FMAs (δ²/2 < 1e-16) and 1/D is one Newton step on the reciprocal taken for δ (D differs from f1 by e s1 δ ~ 1e-8). The decision is WAVE-UNIFORM
+// and a posteriori, one out-of-line exit behind the straight-line Newton row (the triangle of kepler_solve_warm):
+//   cold          the a-priori test of kepler_solve_warm fails, or some lane has |δ| > WARM_TOL (stronger than the a-priori bound): the cold solve, history reset;
+//   fourth order  otherwise, some lane has |δ| > τ: kepler_correct<., true> from the same (s1, c1, f0) — the arithmetic of kepler_solve_warm's warm row from a
+//                 start at least as good — and c = c_pred + δ4 is recorded;
+//   Newton-only   otherwise; c = c_pred + δ is recorded.
+// The history is FP32 (it has to be good to ~1e-9 of a value below 1e-3, and δ is needed in FP32 for the compares anyway): one VGPR per value, and a wave-uniform
+// count of consecutive recorded rows — c_pred is exactly 0 until the history is full. Nothing here depends on the table being even: an uneven step only makes
+// c_pred a poor guess, which the |δ| tests see. A NaN lane (an invalid walker) passes both compares, as in kepler_solve_warm; its sums are discarded.
+#ifndef OCTO_WARM_NEWTON_DEPTH
+#define OCTO_WARM_NEWTON_DEPTH 4
+#endif
+constexpr int WARM_NEWTON_DEPTH = OCTO_WARM_NEWTON_DEPTH;      // values of c kept: 3 — c_pred = 3(c₁ − c₂) + c₃; 4 — 4(c₁ + c₃) − 6c₂ − c₄ (the choice)
+static_assert(WARM_NEWTON_DEPTH == 3 || WARM_NEWTON_DEPTH == 4, "kepler_warm_newton: three or four values of history");
+struct KWarmNewton {
+    float c[WARM_NEWTON_DEPTH];      // the last recorded c, latest first
+    float tau;                       // the lane's τ(e)
+    int n;                           // consecutive recorded rows, saturating at WARM_NEWTON_DEPTH (wave-uniform)
+};
+
+__device__ __forceinline__ void warm_newton_init(KWarmNewton& wn, float e) {
+    const float t = __builtin_amdgcn_sqrtf(WARM_NEWTON_TOL * __builtin_amdgcn_sqrtf(fmaf(-e, e, 1.0f)) * __builtin_amdgcn_rcpf(e));      // e = 0: +Inf; e >= 1 or NaN: NaN
+    wn.tau = fminf(t, WARM_NEWTON_CAP);      // (fminf returns the other operand for a NaN: the cap)
+#pragma unroll
+    for (int k = 0; k < WARM_NEWTON_DEPTH; ++k) wn.c[k] = 0.0f;
+    wn.n = 0;
+}
+
+template <int INV_NR>
+__device__ __forceinline__ KSol kepler_warm_newton(double t, const PC& pc, const SinCosTab& tab, KWarm& st, KWarmNewton& wn, double thr, double dm) {
+    static_assert(INV_NR == 1, "kepler_warm_newton: 1/(1 − e cos E) one Newton step from the reciprocal of f1 (the adjoints' bar)");
+    KSol s;
+    s.dt = t - pc.tp;
+    s.E = 0.0;
+    const bool apriori = __builtin_amdgcn_ballot_w64(st.invD >= thr) == 0;
+    const float gate = wn.n >= WARM_NEWTON_DEPTH ? 1.0f : 0.0f;      // (scalar)
+    float cp;
+    if constexpr (WARM_NEWTON_DEPTH == 3) cp = gate * fmaf(3.0f, wn.c[0] - wn.c[1], wn.c[2]);
+    else cp = gate * fmaf(4.0f, wn.c[0] + wn.c[2], fmaf(-6.0f, wn.c[1], -wn.c[3]));
+    const double dM = dm * pc.invP;
+    const double x = dM * st.invD;
+    const double z = x * st.invD;
+    const double dE = fma(-((pc.he * st.sE) * z), x, x) + (double)cp;
+    const double u = dE * dE;
+    const double sr = dE * fma(u, fma(u, fma(u, OCTO_KT[22], OCTO_KT[17]), OCTO_KT[18]), 1.0);
+    const double cm1 = u * fma(u, fma(u, fma(u, OCTO_KT[23], OCTO_KT[19]), OCTO_KT[20]), -0.5);
+    const double ds = fma(st.sE, cm1, st.cE * sr);
+    const double s1 = st.sE + ds;
+    const double c1 = fma(st.cE, cm1, fma(-st.sE, sr, st.cE));
+    const double f0 = fma(-pc.e, ds, dE - dM);
+    const double f1 = fma(-pc.e, c1, 1.0);
+    const double r1 = rcp_nr<1>(f1);
+    const double d = -f0 * r1;
+    const float df = (float)d;
+    // the Newton-only row, unconditionally
+    s.sE = fma(c1, d, s1);
+    s.cE = fma(-s1, d, c1);
+    s.invD = fma(fma(-fma(-pc.e, s.cE, 1.0), r1, 1.0), r1, r1);
+    float cn = cp + df;
+    int n = wn.n + 1;
+    // (the a-priori test first: the compiler then sends a row it rejects straight to the cold solve, AHEAD of the Newton row it would waste — measured against
+    // one exit on the two ballots together, which keeps the Newton row straight-line: 0.2732 against 0.2795 ms per step of config 3, parent 0.2810, same box)
+    const bool fast = apriori && __builtin_amdgcn_ballot_w64(fabsf(df) > wn.tau) == 0;
+    if (__builtin_expect(!fast, 0)) {
+        if (apriori && __builtin_amdgcn_ballot_w64(fabsf(df) > (float)WARM_TOL) == 0) {
+            double d4;
+            kepler_correct<INV_NR, true>(s, pc, 0.0, s1, c1, f0, &d4);
+            cn = cp + (float)d4;
+        } else {
+            const double uo = s.dt * pc.invP;
+            const double frac = uo - rint(uo);
+            const float E1f = markley_starter_f32(frac, pc);
+            const double E1 = (double)E1f;
+            double sc, cc;
+            sincos_table(E1f, tab, sc, cc);
+            kepler_correct<INV_NR>(s, pc, E1, sc, cc, fma(-pc.e, sc, fma(-frac, TWO_PI, E1)));
+            cn = 0.0f;
+            n = 0;
+        }
+    }
+#pragma unroll
+    for (int k = WARM_NEWTON_DEPTH - 1; k > 0; --k) wn.c[k] = wn.c[k - 1];
+    wn.c[0] = cn;
+    wn.n = n < WARM_NEWTON_DEPTH ? n : WARM_NEWTON_DEPTH;
     st.sE = s.sE; st.cE = s.cE; st.invD = s.invD;
     return s;
 }

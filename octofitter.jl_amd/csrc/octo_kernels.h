@@ -69,7 +69,9 @@ struct Task {
     int32_t obs, row0, nrows, chunk;   // chunk = rows per wave: the block's WPB waves split the task's nrows
     float key_max;                     // largest |2π Δt| of the task's rows, each wave's first row aside (+Inf for a non-finite step): a wave whose bound
                                        // covers it — and whose chunk is within WARM_RESTART — takes the warm loop WITHOUT the per-row test
-    int32_t pad[3];
+    float dm_uniform;                  // key_max again where every step of the TABLE agrees with every other to 1e-7 relative (an evenly sampled table), else 0: the task may take
+                                       // the Newton-only warm loop (octo_device.h: kepler_warm_newton). A routing rule only: no result depends on it
+    int32_t pad[2];
 };
 
 struct DevConsts {
@@ -83,7 +85,8 @@ struct EvalArgs {
     const int32_t* obs_range;     // [n_obs][2] first and one-past-last task of each observation (tasks are grouped by observation)
     const double* obs_const;      // [n_obs] Σ task_const over the observation's tasks, in task order
     int32_t n_obs, n_tasks, n_planets, n_hblocks;      // n_hblocks: k_small only — extra blocks per walker that compute the HGCA term
-    int32_t warm, fin_fused;                    // warm 1: k_main may take the warm-started row loop (octo_ctx option OCTO_OPT_WARM_START / _BATCH_INVARIANT);
+    int32_t warm, fin_fused;                    // warm bit 0: k_main may take the warm-started row loop (octo_ctx option OCTO_OPT_WARM_START / _BATCH_INVARIANT);
+                                                // bit 1 (only with bit 0): … and the Newton-only loop on evenly sampled tasks (OCTO_WARM_NEWTON=0 clears it)
                                                 // fin_fused 1: the launch has ONE task and k_main's blocks finish their own tile (fin_in_main): no partials, no k_finish
     int32_t task0, n_rblocks;                   // first task of this launch (k_main grid.y is relative to it); k_small: blocks per walker that take row tasks
     int32_t orbit_kind[MAXP];
@@ -484,10 +487,11 @@ struct WarmState { KWarm st[P]; double thr[P]; uint32_t key_hi; bool row_ok; };
 
 // WLAST (round 6, P >= 2): 1 — the LAST planet takes the warm step (octo_device.h: kepler_warm_step) from ws->st[P − 1], the others the cold solve;
 // 2 — the same behind a per-row test (ws->row_ok, wave-uniform): a rejected row re-solves the last planet cold and records that solution.
+// WARM 3 (P == 1): the Newton-only warm row (octo_device.h: kepler_warm_newton) with its own state wn; no per-row key test (the unchecked loop's tasks).
 template <int P, bool GRAD, bool NUIS, int KM, bool TAB, int WARM = 0, bool WCHECK = true, int WLAST = 0>
 __device__ __forceinline__ void astrom_row(AccArr<P, GRAD, NUIS, KM>& acc, LogProd& lp, const PC (&pc)[P],
                                            const AstromCoef<P>& co, double t, double y1, double y2, double c3, double c4, double c5,
-                                           const SinCosTab& tab, WarmState<P>* ws = nullptr, double dm = 0.0) {
+                                           const SinCosTab& tab, WarmState<P>* ws = nullptr, double dm = 0.0, KWarmNewton* wn = nullptr) {
     using L = Layout<P, GRAD, NUIS, KM>;
     // DEFER (k_main's mapping, lane = walker: round 6): every factor of an adjoint sum that is constant over the table's rows for one walker — the
     // planet's coefficient f_p, the jitter, the platescale in front of the northangle term — is applied ONCE per wave after the row loop
@@ -502,7 +506,8 @@ __device__ __forceinline__ void astrom_row(AccArr<P, GRAD, NUIS, KM>& acc, LogPr
     double ra_m, dec_m;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-        if constexpr (WARM != 0) s[p] = kepler_solve_warm<1, WARM == 1>(t, pc[p], tab, ws->st[p], ws->thr[p], dm, WCHECK ? ws->row_ok : true);
+        if constexpr (WARM == 3) s[p] = kepler_warm_newton<1>(t, pc[p], tab, ws->st[p], *wn, ws->thr[p], dm);
+        else if constexpr (WARM != 0) s[p] = kepler_solve_warm<1, WARM == 1>(t, pc[p], tab, ws->st[p], ws->thr[p], dm, WCHECK ? ws->row_ok : true);
         else if constexpr (WLAST != 0) { if (p == P - 1) s[p] = kepler_warm_step<1>(t, pc[p], ws->st[p], dm); else s[p] = kepler_solve<1, TAB>(t, pc[p], tab); }
         else s[p] = kepler_solve<1, TAB>(t, pc[p], tab);
         if constexpr (WLAST == 2) {
@@ -972,6 +977,17 @@ template <int P, bool GRAD, bool NUIS, int KM, bool FUSED>
 constexpr bool main_warm() {
     return OCTO_WARM && FUSED && P == 1 && !(KM & KM_ONEIL);
 }
+// The Newton-only warm loop (octo_device.h: kepler_warm_newton) in place of the astrometry branch's unchecked warm loop: the four-wave nuisance-free kernels of
+// RA/Dec [+ cor] tables — config 3's. Tasks the unchecked loop would take but whose steps are uneven go to the checked loop. Not the eight-wave kernel (held to
+// 80 registers), not the one-task kernel with the finish inside.
+#ifndef OCTO_WARM_NEWTON
+#define OCTO_WARM_NEWTON 1
+#endif
+template <int P, bool GRAD, bool NUIS, int KM, bool FUSED, int NWV, bool FINF>
+constexpr bool main_warm_newton() {
+    return OCTO_WARM_NEWTON && main_warm<P, GRAD, NUIS, KM, FUSED>() && !main_warm_plain<P, GRAD, NUIS, KM, FUSED>() && !NUIS && NWV == WPB && !FINF &&
+           (KM == KM_RADEC || KM == (KM_RADEC | KM_COR));
+}
 
 // Two and three planets (round 6): the LAST planet — the outer one in the usual order — starts from the previous row's solution. A warm/cold DIAMOND per planet ends the
 // interleaving of the two solves that a kernel at two waves per SIMD lives on (round 5: −3 %, −8 %; and a diamond around the whole row body costs five scalar
@@ -1249,7 +1265,28 @@ static __global__ __launch_bounds__(64 * NWV) void k_main(EvalArgs a) {
                     }
                     row_drain(A);      // the normal exit's spare prefetch sits in A: the wait names the tuple, so its registers stay allocated until it has landed
                 };
-                if (n_rows > 0) {
+                if constexpr (main_warm_newton<P, GRAD, NUIS, KM, FUSED, NWV, FINF>()) {
+                    // an evenly sampled task no row of which needs the key test: the Newton-only loop (same prefetch); every other task: the checked loop
+                    if (n_rows > 0) {
+                        if (warm_unchecked && (a.warm & 2) != 0 && tk.dm_uniform > 0.0f) {
+                            KWarmNewton wn;
+                            warm_newton_init(wn, pc[0].ef);
+                            auto nbody = [&](const RowRegs8& r) {
+                                astrom_row<P, GRAD, NUIS, KM, true, 3, false>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2), row_get(r, 3), row_get(r, 4),
+                                                                              row_get(r, 5), tab, &ws, row_get(r, 6), &wn);
+                            };
+                            RowRegs8 A = row_issue8(rows);
+                            for (int j = 0; j < n_rows; j += 2) {
+                                RowRegs8 B = row_wait_issue(A, rows + (int64_t)(j + 1 < n_rows ? j + 1 : j) * ROW_STRIDE);
+                                nbody(A);
+                                if (__builtin_expect(j + 1 >= n_rows, 0)) { row_drain(B); break; }
+                                A = row_wait_issue(B, rows + (int64_t)(j + 2 < n_rows ? j + 2 : j + 1) * ROW_STRIDE);
+                                nbody(B);
+                            }
+                            row_drain(A);
+                        } else wloop(std::true_type{});
+                    }
+                } else if (n_rows > 0) {
                     if (warm_unchecked) wloop(std::false_type{});
                     else wloop(std::true_type{});
                 }
