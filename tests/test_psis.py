@@ -10,6 +10,11 @@ with the float64 restatement. Bars:
                                 (computed here and printed; 7.4e-12 and 6.0e-13): the margin covers another summation order and the
                                 device's exp / log / log1p;
   invariance                    bitwise.
+The edge rows (psis_reference.EDGE_ROWS: a gather at every pass of the select and never, tails of 8 … 4096 = MAX_TAIL with m = 94 = MAX_GRID,
+tie blocks, sparse rows, offsets; above S = 120 001 against psis_row_hybrid) keep these bars. Only the rows built to gather late have their
+tail within 1e-2 … 1e-8 of the cut-off, where y = exp(x) − exp(x_c) cancels: there a field's bar is max(the bar above, 100 × the restatement's
+gap on that row), k̂'s capped at 1e-5, and tests/test_psis_reference.py shows on the reference alone that a tail wrong by one entry moves k̂
+by at least ten such bars.
 The observed maxima are printed (tools/psis_bench.py writes them to profiles/psis_throughput.txt).
 """
 import ctypes as C
@@ -38,9 +43,10 @@ def as_result(out, lw):
     return res
 
 
-def device_loo(pkg, ps, LL, pad=5, pad_w=3):
+def device_loo(pkg, ps, LL, pad=5, pad_w=3, weights=True):
     """The device call through the C ABI with ld = S + pad and ld_w = S + pad_w. The matrix's padding holds a FINITE value (read, it would
-    count: n is exact), the weights' padding a sentinel that must survive."""
+    count: n is exact), the weights' padding a sentinel that must survive. weights=False is the statistics-only call (d_lw = NULL): the
+    weights returned are then the untouched sentinel."""
     import torch
     R, S = LL.shape
     buf = np.full((R, S + pad), 50.0)
@@ -49,10 +55,11 @@ def device_loo(pkg, ps, LL, pad=5, pad_w=3):
     d_out = torch.full((ps_n_stats(pkg), R), 777.0, dtype=torch.float64, device="cuda")
     d_lw = torch.full((R, S + pad_w), 123.0, dtype=torch.float64, device="cuda")
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    st = ps.lib.octo_psis_loo_device(ps._h, d_ll.data_ptr(), S + pad, R, S, d_out.data_ptr(), d_lw.data_ptr(), S + pad_w, stream)
+    st = ps.lib.octo_psis_loo_device(ps._h, d_ll.data_ptr(), S + pad, R, S, d_out.data_ptr(), d_lw.data_ptr() if weights else None, S + pad_w if weights else 0, stream)
     assert st == pkg.capi.OCTO_OK, (st, ps.lib.octo_psis_last_error(ps._h))
     torch.cuda.synchronize()
     lw = d_lw.cpu().numpy()
+    assert weights or np.all(lw == 123.0)
     assert np.all(lw[:, S:] == 123.0)                                  # nothing written past S
     assert np.array_equal(bits(d_ll.cpu().numpy()), bits(buf))        # the input is untouched
     return as_result(d_out.cpu().numpy(), np.ascontiguousarray(lw[:, :S]))
@@ -204,6 +211,76 @@ def test_invariance_bitwise(pkg, ps):
             else:
                 os.environ[k] = v
     assert same_bits(host_loo(pkg, ps, big), b)
+
+
+@pytest.mark.parametrize("name", list(pr.EDGE_ROWS))
+def test_edge_rows_against_the_reference(pkg, ps, bars, name):
+    """The routes no case of the generator takes (psis_reference.EDGE_ROWS): tails of 8 … 4096 with and without sort padding, a gather at
+    every pass 0 … 7 and never, constant rows, tie blocks, few finite entries in a long row, values far from 0. What edge_case asserts on the
+    CPU (gather_pass among it) is the evidence that the row takes its route; the bars are the cases' — for the rows whose fit is
+    ill-conditioned by construction the per-row rule of psis_reference.edge_bars — and never the device's output."""
+    LL, ref, gather = pr.edge_case(name)
+    row_bars, gap = pr.edge_bars(name, bars)
+    print(f"{name}: S {LL.shape[1]}  n {ref['n'][0]:.0f}  gather_pass {gather}  tail_len {ref['tail_len'][0]:.0f}  k̂ {ref['pareto_k'][0]:.4f}  "
+          f"restatement's k̂ gap {gap['pareto_k']:.2e}")
+    got = device_loo(pkg, ps, LL)
+    check(name, got, ref, row_bars)
+    if name.startswith("const"):
+        assert got["pareto_k"][0] == np.inf and got["tail_len"][0] == 0
+    if name.startswith("dup10"):
+        # what test_ties asserts: equal values inside the tail got DIFFERENT weights, in index order — except where the smoothed value is
+        # capped at x = 0 (k̂ = 0.08: the top 3 of the 420 quantiles lie above the largest ratio), which both sides must cap alike
+        order = pr.tail_order(LL[0])
+        ties = [i for i in range(len(order) - 1) if LL[0][order[i]] == LL[0][order[i + 1]]]
+        assert len(order) == ref["tail_len"][0] < pr.tail_len(LL.shape[1]) and len(ties) == 9 * len(order) // 10
+        g, f = got["lw"][0][order], ref["lw"][0][order]
+        capped = f == ref["lw"].max()
+        assert np.array_equal(capped, g == got["lw"].max()) and 0 < capped.sum() <= 3 and np.all(capped[-capped.sum():])
+        for i in ties:
+            assert order[i] < order[i + 1] and ((g[i] < g[i + 1] and f[i] < f[i + 1]) or (capped[i] and capped[i + 1])), i
+
+
+@pytest.mark.parametrize("name", ["S130_R70", "never_tieblock", pr.LIMIT_ROW])
+def test_statistics_only_call_is_bit_identical(pkg, ps, name):
+    """d_lw = NULL changes what is stored, not what is computed: the six statistics keep their bits."""
+    LL = pr.case(name)[0] if name in pr.CASES else pr.edge_case(name)[0]
+    a, b = device_loo(pkg, ps, LL), device_loo(pkg, ps, LL, weights=False)
+    assert all(np.array_equal(bits(a[k]), bits(b[k])) for k in pr.FIELDS), name
+
+
+def test_limit_row_through_the_host_buffer_call(pkg, ps):
+    """S = octo_psis_max_samples() through octo_psis_loo: one row of 15 MB in the default 64 MiB device buffer, then through a staging buffer
+    of 1 MB — fifteen pieces, the last a short one — with the device call's bits both times."""
+    LL = pr.edge_case(pr.LIMIT_ROW)[0]
+    S = LL.shape[1]
+    assert S == ps.lib.octo_psis_max_samples() and (S * 8) % 1_000_000 != 0
+    a = device_loo(pkg, ps, LL)
+    assert same_bits(host_loo(pkg, ps, LL), a)
+    keep = os.environ.get("OCTO_PSIS_STAGE_BYTES")
+    os.environ["OCTO_PSIS_STAGE_BYTES"] = "1000000"
+    try:
+        small = pkg.Psis()
+        try:
+            assert same_bits(host_loo(pkg, small, LL), a)
+        finally:
+            small.close()
+    finally:
+        if keep is None:
+            os.environ.pop("OCTO_PSIS_STAGE_BYTES", None)
+        else:
+            os.environ["OCTO_PSIS_STAGE_BYTES"] = keep
+
+
+def test_late_gather_row_keeps_its_bits_in_a_matrix(pkg, ps):
+    """gather6 (the select gathers at pass 6) as row 0 and as row 69 of 70 rows of S = 20 000 whose other rows gather at pass 2, and alone."""
+    row = pr.edge_case("gather6")[0][0]
+    LL = pr.student_rows(20000, 70, 0.3, 30.0, 70)
+    LL[0], LL[69] = row, row
+    assert pr.gather_pass(LL[0]) == pr.gather_pass(LL[69]) == 6 and pr.gather_pass(LL[1]) == pr.gather_pass(LL[68]) == 2
+    a = device_loo(pkg, ps, LL)
+    one = device_loo(pkg, ps, row[None, :], pad=0, pad_w=0)
+    for r in (0, 69):
+        assert all(bits(one[k])[0] == bits(a[k])[r] for k in pr.FIELDS) and np.array_equal(bits(one["lw"][0]), bits(a["lw"][r])), r
 
 
 class TableModel:

@@ -136,11 +136,28 @@ def accuracy(pkg, lines):
             rest = {k: max(v, g[k]) for k, v in rest.items()}
             g = pr.gaps(tp.device_loo(pkg, ps, LL), ref)
             worst = {k: max(v, g[k]) for k, v in worst.items()}
+        # the edge rows (psis_reference.EDGE_ROWS): every select route, tails up to 4096, tie blocks, sparse rows, offsets
+        base = dict(pareto_k=100 * rest["pareto_k"], ess=100 * rest["ess"], elpd_loo=1e-11, lppd=1e-11, lw=1e-11)
+        erest, eworst, per_row = dict.fromkeys(rest, 0.0), dict.fromkeys(rest, 0.0), []
+        for name in pr.EDGE_ROWS:
+            LL, ref, gather = pr.edge_case(name)
+            row_bars, g = pr.edge_bars(name, base)
+            erest = {k: max(v, g[k]) for k, v in erest.items()}
+            d = pr.gaps(tp.device_loo(pkg, ps, LL), ref)
+            eworst = {k: max(v, d[k]) for k, v in eworst.items()}
+            if name in pr.ROUTE_ROWS:
+                per_row.append(f"    {name:8s} gather at pass {gather}, tail {ref['tail_len'][0]:.0f}, k̂ {ref['pareto_k'][0]:.3f}: restatement k̂ {g['pareto_k']:.3e}, device k̂ {d['pareto_k']:.3e}; bars "
+                               + ", ".join(f"{k} {v:.3e}" for k, v in row_bars.items()) + f"; one entry more or less in the tail moves k̂ by {pr.cut_sensitivity(name):.1e}")
     finally:
         ps.close()
     lines.append("  float64 restatement (NumPy): " + ", ".join(f"{k} {v:.3e}" for k, v in rest.items()))
     lines.append("  device                     : " + ", ".join(f"{k} {v:.3e}" for k, v in worst.items()))
     lines.append(f"  bars of the device         : pareto_k {100 * rest['pareto_k']:.3e} (absolute), ess {100 * rest['ess']:.3e} (relative), elpd_loo, lppd, lw 1e-11")
+    lines.append(f"the same over the {len(pr.EDGE_ROWS)} edge rows of tests/psis_reference.py (S up to {max(pr.edge_case(k)[0].shape[1] for k in pr.EDGE_ROWS)}; the hybrid reference above S = 120 001):")
+    lines.append("  float64 restatement (NumPy): " + ", ".join(f"{k} {v:.3e}" for k, v in erest.items()))
+    lines.append("  device                     : " + ", ".join(f"{k} {v:.3e}" for k, v in eworst.items()))
+    lines.append("  bars: the ones above, except on the rows whose tail lies within 1e-2 … 1e-8 of the cut-off (max(the bar above, 100 x the restatement's gap on that row), k̂'s capped at 1e-5):")
+    lines.extend(per_row)
 
 
 def main():
