@@ -528,6 +528,7 @@ int32_t octo_ctx_create(octo_ctx** out, int32_t device_id) {
     if (const char* ev = std::getenv("OCTO_FIN_FUSED")) ctx->env_no_fin_fused = std::atoi(ev) ? 0 : 1;
     if (const char* ev = std::getenv("OCTO_WARM")) { ctx->env_warm = std::atoi(ev); ctx->opt_warm = ctx->env_warm ? 1 : 0; }
     if (const char* ev = std::getenv("OCTO_WARM_NEWTON")) ctx->env_warm_newton = std::atoi(ev) ? 1 : 0;
+    if (const char* ev = std::getenv("OCTO_WARM_NEWTON_MID")) ctx->env_warm_newton_mid = std::atoi(ev) ? 1 : 0;
     if (const char* ev = std::getenv("OCTO_TILE_SORT")) ctx->tile_mode = std::min(std::max(std::atoi(ev), 0), 2);      // experiments: the default of OCTO_OPT_TILE_SORT
     if (const char* ev = std::getenv("OCTO_TILE_MIN_W")) ctx->tile_min_w = std::max<int64_t>(std::atoll(ev), 64);
     *out = ctx;
@@ -854,7 +855,7 @@ static int eval_impl(octo_ctx* ctx, const octo_dataset* ds, const double* d_elem
     a.n_obs = ds->n_obs; a.n_planets = ds->n_planets;
     for (int p = 0; p < ds->n_planets; ++p) { a.orbit_kind[p] = ds->planets[p].orbit_kind; a.has_mass[p] = ds->planets[p].has_mass; }
     a.elems = d_elems; a.nuis = d_nuis; a.ld = ld; a.W = W;
-    a.warm = (ctx->opt_warm && !ctx->opt_invariant) ? (1 | (ctx->env_warm_newton ? 2 : 0)) : 0;
+    a.warm = (ctx->opt_warm && !ctx->opt_invariant) ? (1 | (ctx->env_warm_newton ? 2 : 0) | (ctx->env_warm_newton_mid ? 4 : 0)) : 0;
     a.ws_in = a.ws_out = 1;
     if (ctx->stage_ws_in > 0) { a.ws_in = ctx->stage_ws_in; a.ws_out = ctx->stage_ws_out; }      // octo_eval's walker-major staging (k_small only)
     a.wc = ctx->d_wc; a.valid = ctx->d_valid; a.ldw = ctx->cap_w; a.sctab = ctx->d_sctab;

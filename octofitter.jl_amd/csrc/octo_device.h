@@ -137,6 +137,8 @@ constexpr int WARM_LADDER = 8;            // candidate step bounds per table (De
 constexpr int WARM_RESTART = 256;         // every WARM_RESTART-th row of a table starts cold
 constexpr float WARM_NEWTON_TOL = 4.0e-16f;      // Newton-only rows (kepler_warm_newton): τ² e/√(1 − e²) stays below this — twice the bound on the Newton step's truncation
 constexpr float WARM_NEWTON_CAP = 1.4e-8f;       // … and τ below this: the rotation through δ drops δ²/2 < 1e-16
+constexpr float WARM_NEWTON_MID_TOL = 2.0e-16f;  // the middle arm of kepler_warm_newton (one Halley step): κ(e) τ₂³ stays below this — the bound on the step's truncation
+constexpr float WARM_NEWTON_MID_CAP = 8.0e-6f;   // … and τ₂ below this: its rotation drops δ³/6 < 1e-16
 
 // The lane's bound on 1/D of the previous row (KWarm above): e the eccentricity, dm = |ΔM| of the wave's step bound. FP32 (v_log_f32 / v_exp_f32 are base 2),
 // once per lane per task. The ONE copy of the formula: k_main (warm_init, warm_last_init), the test hook k_kepler_warm and k_tile_sort's closed-form failure
@@ -527,8 +529,15 @@ __device__ __forceinline__ KSol kepler_solve_warm(double t, const PC& pc, const 
 // is two FMAs (δ²/2 < 1e-16) and 1/D is one Newton step on the reciprocal taken for δ (D differs from f1 by e s1 δ ~ 1e-8). The decision is WAVE-UNIFORM
 // and a posteriori, one out-of-line exit behind the straight-line Newton row (the triangle of kepler_solve_warm):
 //   cold          the a-priori test of kepler_solve_warm fails, or some lane has |δ| > WARM_TOL (stronger than the a-priori bound): the cold solve, history reset;
-//   fourth order  otherwise, some lane has |δ| > τ: kepler_correct<., true> from the same (s1, c1, f0) — the arithmetic of kepler_solve_warm's warm row from a
+//   fourth order  otherwise, some lane has |δ| > τ₂: kepler_correct<., true> from the same (s1, c1, f0) — the arithmetic of kepler_solve_warm's warm row from a
 //                 start at least as good — and c = c_pred + δ4 is recorded;
+//   middle        otherwise, some lane has |δ| > τ: ONE Halley step, as a series in the Newton δ with the reciprocal already taken — δh = δ − (q δ) δ,
+//                 q = f2/(2 f1) = (e/2 · s1)·r1 — whose truncation |a²/2 − b/6| |δ|³ (a = e sin E/D, b = e cos E/D) stays below WARM_NEWTON_MID_TOL for
+//                 |δ| <= τ₂(e) = min((WARM_NEWTON_MID_TOL/κ)^(1/3), WARM_NEWTON_MID_CAP), κ(e) = β_max²/2 + e/(6(1 − e)); the rotation keeps its δ² term (three more FMAs; δ³/6 < 1e-16)
+//                 and 1/D takes TWO Newton steps from r1 (D differs from f1 by ~e s1 δ <~ 5e-5 relative). No reciprocal instruction: 15 FP64 against the fourth-order
+//                 arm's 23 and two v_rcp_f64, on 0.88 of the rows that arm used to take (tests/warm_newton_mid_model.py: 0.176 of config 3's wave-rows).
+//                 c = c_pred + δh is recorded. OCTO_WARM_NEWTON_MID=0 (bit 2 of EvalArgs::warm clear) sets τ₂ = 0: the arm is never taken — a row with
+//                 every |δ| <= 0 has already passed as Newton-only — and the loop is the one without it, bit for bit;
 //   Newton-only   otherwise; c = c_pred + δ is recorded.
 // The history is FP32 (it has to be good to ~1e-9 of a value below 1e-3, and δ is needed in FP32 for the compares anyway): one VGPR per value, and a wave-uniform
 // count of consecutive recorded rows — c_pred is exactly 0 until the history is full. Nothing here depends on the table being even: an uneven step only makes
@@ -541,12 +550,18 @@ static_assert(WARM_NEWTON_DEPTH == 3 || WARM_NEWTON_DEPTH == 4, "kepler_warm_new
 struct KWarmNewton {
     float c[WARM_NEWTON_DEPTH];      // the last recorded c, latest first
     float tau;                       // the lane's τ(e)
+    float tau2;                      // the lane's τ₂(e) of the middle arm, or 0: the arm is off
     int n;                           // consecutive recorded rows, saturating at WARM_NEWTON_DEPTH (wave-uniform)
 };
 
-__device__ __forceinline__ void warm_newton_init(KWarmNewton& wn, float e) {
+// mid: the middle arm is on (wave-uniform: bit 2 of EvalArgs::warm)
+__device__ __forceinline__ void warm_newton_init(KWarmNewton& wn, float e, bool mid) {
     const float t = __builtin_amdgcn_sqrtf(WARM_NEWTON_TOL * __builtin_amdgcn_sqrtf(fmaf(-e, e, 1.0f)) * __builtin_amdgcn_rcpf(e));      // e = 0: +Inf; e >= 1 or NaN: NaN
     wn.tau = fminf(t, WARM_NEWTON_CAP);      // (fminf returns the other operand for a NaN: the cap)
+    // κ = ½ e²/(1 − e²) + e/(6(1 − e)); the cube root through v_log_f32 / v_exp_f32 (base 2). e = 0: κ = 0, +Inf; e = 1: κ = +Inf, 0 (as τ); e > 1 (κ < 0) or NaN: NaN
+    const float k = fmaf(0.5f * e * e, __builtin_amdgcn_rcpf(fmaf(-e, e, 1.0f)), (e * (1.0f / 6.0f)) * __builtin_amdgcn_rcpf(1.0f - e));
+    const float t2 = __builtin_amdgcn_exp2f((1.0f / 3.0f) * __builtin_amdgcn_logf(WARM_NEWTON_MID_TOL * __builtin_amdgcn_rcpf(k)));
+    wn.tau2 = mid ? fminf(t2, WARM_NEWTON_MID_CAP) : 0.0f;
 #pragma unroll
     for (int k = 0; k < WARM_NEWTON_DEPTH; ++k) wn.c[k] = 0.0f;
     wn.n = 0;
@@ -588,7 +603,18 @@ __device__ __forceinline__ KSol kepler_warm_newton(double t, const PC& pc, const
     // one exit on the two ballots together, which keeps the Newton row straight-line: 0.2732 against 0.2795 ms per step of config 3, parent 0.2810, same box)
     const bool fast = apriori && __builtin_amdgcn_ballot_w64(fabsf(df) > wn.tau) == 0;
     if (__builtin_expect(!fast, 0)) {
-        if (apriori && __builtin_amdgcn_ballot_w64(fabsf(df) > (float)WARM_TOL) == 0) {
+        if (apriori && __builtin_amdgcn_ballot_w64(fabsf(df) > wn.tau2) == 0) {
+            // the middle arm: one Halley step from the Newton δ and its reciprocal
+            const double q = (pc.he * s1) * r1;
+            const double dh = fma(-(q * d), d, d);
+            const double w = -0.5 * dh;
+            s.sE = fma(dh, fma(w, s1, c1), s1);
+            s.cE = fma(dh, fma(w, c1, -s1), c1);
+            const double D = fma(-pc.e, s.cE, 1.0);
+            const double r2 = fma(fma(-D, r1, 1.0), r1, r1);
+            s.invD = fma(fma(-D, r2, 1.0), r2, r2);
+            cn = cp + (float)dh;
+        } else if (apriori && __builtin_amdgcn_ballot_w64(fabsf(df) > (float)WARM_TOL) == 0) {
             double d4;
             kepler_correct<INV_NR, true>(s, pc, 0.0, s1, c1, f0, &d4);
             cn = cp + (float)d4;

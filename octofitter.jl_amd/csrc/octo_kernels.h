@@ -86,7 +86,8 @@ struct EvalArgs {
     const double* obs_const;      // [n_obs] Σ task_const over the observation's tasks, in task order
     int32_t n_obs, n_tasks, n_planets, n_hblocks;      // n_hblocks: k_small only — extra blocks per walker that compute the HGCA term
     int32_t warm, fin_fused;                    // warm bit 0: k_main may take the warm-started row loop (octo_ctx option OCTO_OPT_WARM_START / _BATCH_INVARIANT);
-                                                // bit 1 (only with bit 0): … and the Newton-only loop on evenly sampled tasks (OCTO_WARM_NEWTON=0 clears it)
+                                                // bit 1 (only with bit 0): … and the Newton-only loop on evenly sampled tasks (OCTO_WARM_NEWTON=0 clears it);
+                                                // bit 2: … with its middle arm (OCTO_WARM_NEWTON_MID=0 clears it: τ₂ = 0)
                                                 // fin_fused 1: the launch has ONE task and k_main's blocks finish their own tile (fin_in_main): no partials, no k_finish
     int32_t task0, n_rblocks;                   // first task of this launch (k_main grid.y is relative to it); k_small: blocks per walker that take row tasks
     int32_t orbit_kind[MAXP];
@@ -1270,7 +1271,7 @@ static __global__ __launch_bounds__(64 * NWV) void k_main(EvalArgs a) {
                     if (n_rows > 0) {
                         if (warm_unchecked && (a.warm & 2) != 0 && tk.dm_uniform > 0.0f) {
                             KWarmNewton wn;
-                            warm_newton_init(wn, pc[0].ef);
+                            warm_newton_init(wn, pc[0].ef, (a.warm & 4) != 0);
                             auto nbody = [&](const RowRegs8& r) {
                                 astrom_row<P, GRAD, NUIS, KM, true, 3, false>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2), row_get(r, 3), row_get(r, 4),
                                                                               row_get(r, 5), tab, &ws, row_get(r, 6), &wn);
