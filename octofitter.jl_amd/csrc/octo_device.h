@@ -431,6 +431,19 @@ __device__ __forceinline__ KSol kepler_solve(double t, const PC& pc, const SinCo
 // The warm step alone, UNCONDITIONAL (round 6: the two-planet kernels' "last planet always warm" loop): for a wave whose lanes all pass the a-priori test on
 // every row — 1/(1 − e) < thr: the bound holds at periastron itself — and whose task has no row beyond the wave's step bound, there is nothing to test
 // and nothing to fall back to: no ballot, no branch, the two planets' solves stay in one basic block.
+// The constants of the FIRST Horner step of the two rotation polynomials, fma(u, KT[22], KT[17]) and fma(u, KT[23], KT[19]): both operands are
+// wave-uniform (SGPRs), an instruction reads one SGPR pair, and the compiler copies the other into a VGPR pair on EVERY row (v_mov_b64 v, s). A row loop
+// that has two VGPR pairs to spare holds KT[17] and KT[19] there for its whole length (warm_pin: opaque, so that they are not rematerialised inside);
+// the operations, their operands and their order are the same — PIN false reads the constant table as before.
+struct WarmPin { double k17, k19; };
+__device__ __forceinline__ WarmPin warm_pin() {
+    WarmPin p{OCTO_KT[17], OCTO_KT[19]};
+    asm volatile("" : "+v"(p.k17), "+v"(p.k19));
+    return p;
+}
+template <bool PIN> __device__ __forceinline__ double warm_k17(const WarmPin* p) { if constexpr (PIN) return p->k17; else return OCTO_KT[17]; }
+template <bool PIN> __device__ __forceinline__ double warm_k19(const WarmPin* p) { if constexpr (PIN) return p->k19; else return OCTO_KT[19]; }
+
 template <int INV_NR>
 __device__ __forceinline__ KSol kepler_warm_step(double t, const PC& pc, KWarm& st, double dm) {
     static_assert(INV_NR >= 0, "the warm start needs 1/(1 − e cos E) of every row");
@@ -455,8 +468,9 @@ __device__ __forceinline__ KSol kepler_warm_step(double t, const PC& pc, KWarm& 
 #ifndef OCTO_WARM_TRI
 #define OCTO_WARM_TRI 1
 #endif
-template <int INV_NR, bool TRI = (OCTO_WARM_TRI != 0)>
-__device__ __forceinline__ KSol kepler_solve_warm(double t, const PC& pc, const SinCosTab& tab, KWarm& st, double thr, double dm, bool row_ok = true) {
+template <int INV_NR, bool TRI = (OCTO_WARM_TRI != 0), bool PIN = false>
+__device__ __forceinline__ KSol kepler_solve_warm(double t, const PC& pc, const SinCosTab& tab, KWarm& st, double thr, double dm, bool row_ok = true,
+                                                  const WarmPin* pin = nullptr) {
     static_assert(INV_NR >= 0, "the warm start needs 1/(1 − e cos E) of every row");
     KSol s;
     s.dt = t - pc.tp;
@@ -473,8 +487,8 @@ __device__ __forceinline__ KSol kepler_solve_warm(double t, const PC& pc, const 
         const double z = x * st.invD;
         const double dE = fma(-((pc.he * st.sE) * z), x, x);
         const double u = dE * dE;
-        const double sr = dE * fma(u, fma(u, fma(u, OCTO_KT[22], OCTO_KT[17]), OCTO_KT[18]), 1.0);
-        const double cm1 = u * fma(u, fma(u, fma(u, OCTO_KT[23], OCTO_KT[19]), OCTO_KT[20]), -0.5);
+        const double sr = dE * fma(u, fma(u, fma(u, OCTO_KT[22], warm_k17<PIN>(pin)), OCTO_KT[18]), 1.0);
+        const double cm1 = u * fma(u, fma(u, fma(u, OCTO_KT[23], warm_k19<PIN>(pin)), OCTO_KT[20]), -0.5);
         const double ds = fma(st.sE, cm1, st.cE * sr);
         s1 = st.sE + ds;
         c1 = fma(st.cE, cm1, fma(-st.sE, sr, st.cE));
@@ -499,8 +513,8 @@ __device__ __forceinline__ KSol kepler_solve_warm(double t, const PC& pc, const 
         const double z = x * st.invD;
         const double dE = fma(-((pc.he * st.sE) * z), x, x);
         const double u = dE * dE;
-        const double sr = dE * fma(u, fma(u, fma(u, OCTO_KT[22], OCTO_KT[17]), OCTO_KT[18]), 1.0);      // |dE| < 0.066 here (thr >= WARM_MIN_THR): dE⁹/9! < 7e-17
-        const double cm1 = u * fma(u, fma(u, fma(u, OCTO_KT[23], OCTO_KT[19]), OCTO_KT[20]), -0.5);
+        const double sr = dE * fma(u, fma(u, fma(u, OCTO_KT[22], warm_k17<PIN>(pin)), OCTO_KT[18]), 1.0);      // |dE| < 0.066 here (thr >= WARM_MIN_THR): dE⁹/9! < 7e-17
+        const double cm1 = u * fma(u, fma(u, fma(u, OCTO_KT[23], warm_k19<PIN>(pin)), OCTO_KT[20]), -0.5);
         const double ds = fma(st.sE, cm1, st.cE * sr);               // sin E1 − sin E, without cancellation
         s1 = st.sE + ds;
         c1 = fma(st.cE, cm1, fma(-st.sE, sr, st.cE));
@@ -548,7 +562,7 @@ __device__ __forceinline__ KSol kepler_solve_warm(double t, const PC& pc, const 
 constexpr int WARM_NEWTON_DEPTH = OCTO_WARM_NEWTON_DEPTH;      // values of c kept: 3 — c_pred = 3(c₁ − c₂) + c₃; 4 — 4(c₁ + c₃) − 6c₂ − c₄ (the choice)
 static_assert(WARM_NEWTON_DEPTH == 3 || WARM_NEWTON_DEPTH == 4, "kepler_warm_newton: three or four values of history");
 struct KWarmNewton {
-    float c[WARM_NEWTON_DEPTH];      // the last recorded c, latest first
+    float c[WARM_NEWTON_DEPTH];      // the last recorded c: latest first (depth 3), or a ring the row's phase indexes (depth 4: kepler_warm_newton)
     float tau;                       // the lane's τ(e)
     float tau2;                      // the lane's τ₂(e) of the middle arm, or 0: the arm is off
     int n;                           // consecutive recorded rows, saturating at WARM_NEWTON_DEPTH (wave-uniform)
@@ -567,24 +581,32 @@ __device__ __forceinline__ void warm_newton_init(KWarmNewton& wn, float e, bool 
     wn.n = 0;
 }
 
-template <int INV_NR>
-__device__ __forceinline__ KSol kepler_warm_newton(double t, const PC& pc, const SinCosTab& tab, KWarm& st, KWarmNewton& wn, double thr, double dm) {
+// PH: the row's phase in the loop's four-row trip (depth 4). The history is a RING: slot (i − PH) & 3 of wn.c plays c_i, the row records its c in the
+// slot of c₃, which falls out — slot (3 − PH) & 3, c₀ of phase PH + 1 — and nothing is shifted (the shift was two to four v_mov_b32 per row, at the
+// loop's back edge and exits). The caller steps PH by one per row, whatever arm the row took. Depth 3 keeps the shift and ignores PH.
+// pin: KT[17] and KT[19] in VGPRs for the whole loop (WarmPin).
+template <int INV_NR, int PH = 0>
+__device__ __forceinline__ KSol kepler_warm_newton(double t, const PC& pc, const SinCosTab& tab, KWarm& st, KWarmNewton& wn, double thr, double dm, const WarmPin& pin) {
     static_assert(INV_NR == 1, "kepler_warm_newton: 1/(1 − e cos E) one Newton step from the reciprocal of f1 (the adjoints' bar)");
+    static_assert(PH >= 0 && PH < 4, "kepler_warm_newton: four phases");
+    constexpr bool RING = WARM_NEWTON_DEPTH == 4;
+    constexpr int I0 = RING ? (0 - PH) & 3 : 0, I1 = RING ? (1 - PH) & 3 : 1, I2 = RING ? (2 - PH) & 3 : 2, I3 = (3 - PH) & 3;
     KSol s;
     s.dt = t - pc.tp;
     s.E = 0.0;
     const bool apriori = __builtin_amdgcn_ballot_w64(st.invD >= thr) == 0;
-    const float gate = wn.n >= WARM_NEWTON_DEPTH ? 1.0f : 0.0f;      // (scalar)
+    // 1 or 0, selected as BITS on the scalar unit (s_cselect_b32) and multiplied in from the SGPR: a float select went to the vector unit (v_cndmask_b32)
+    const float gate = __uint_as_float(wn.n >= WARM_NEWTON_DEPTH ? 0x3f800000u : 0u);
     float cp;
     if constexpr (WARM_NEWTON_DEPTH == 3) cp = gate * fmaf(3.0f, wn.c[0] - wn.c[1], wn.c[2]);
-    else cp = gate * fmaf(4.0f, wn.c[0] + wn.c[2], fmaf(-6.0f, wn.c[1], -wn.c[3]));
+    else cp = gate * fmaf(4.0f, wn.c[I0] + wn.c[I2], fmaf(-6.0f, wn.c[I1], -wn.c[I3]));
     const double dM = dm * pc.invP;
     const double x = dM * st.invD;
     const double z = x * st.invD;
     const double dE = fma(-((pc.he * st.sE) * z), x, x) + (double)cp;
     const double u = dE * dE;
-    const double sr = dE * fma(u, fma(u, fma(u, OCTO_KT[22], OCTO_KT[17]), OCTO_KT[18]), 1.0);
-    const double cm1 = u * fma(u, fma(u, fma(u, OCTO_KT[23], OCTO_KT[19]), OCTO_KT[20]), -0.5);
+    const double sr = dE * fma(u, fma(u, fma(u, OCTO_KT[22], pin.k17), OCTO_KT[18]), 1.0);
+    const double cm1 = u * fma(u, fma(u, fma(u, OCTO_KT[23], pin.k19), OCTO_KT[20]), -0.5);
     const double ds = fma(st.sE, cm1, st.cE * sr);
     const double s1 = st.sE + ds;
     const double c1 = fma(st.cE, cm1, fma(-st.sE, sr, st.cE));
@@ -630,9 +652,12 @@ __device__ __forceinline__ KSol kepler_warm_newton(double t, const PC& pc, const
             n = 0;
         }
     }
+    if constexpr (RING) wn.c[I3] = cn;
+    else {
 #pragma unroll
-    for (int k = WARM_NEWTON_DEPTH - 1; k > 0; --k) wn.c[k] = wn.c[k - 1];
-    wn.c[0] = cn;
+        for (int k = WARM_NEWTON_DEPTH - 1; k > 0; --k) wn.c[k] = wn.c[k - 1];
+        wn.c[0] = cn;
+    }
     wn.n = n < WARM_NEWTON_DEPTH ? n : WARM_NEWTON_DEPTH;
     st.sE = s.sE; st.cE = s.cE; st.invD = s.invD;
     return s;

@@ -484,12 +484,13 @@ __device__ __forceinline__ AstromCoef<P> astrom_coef(const double* __restrict__ 
 
 // The warm start's per-wave state (octo_device.h: KWarm): the previous row's solution and the lane's bound on 1/D, per planet.
 template <int P>
-struct WarmState { KWarm st[P]; double thr[P]; uint32_t key_hi; bool row_ok; };
+struct WarmState { KWarm st[P]; double thr[P]; uint32_t key_hi; bool row_ok; WarmPin pin; };      // pin: set by the loops that use it (main_warm_pin)
 
 // WLAST (round 6, P >= 2): 1 — the LAST planet takes the warm step (octo_device.h: kepler_warm_step) from ws->st[P − 1], the others the cold solve;
 // 2 — the same behind a per-row test (ws->row_ok, wave-uniform): a rejected row re-solves the last planet cold and records that solution.
 // WARM 3 (P == 1): the Newton-only warm row (octo_device.h: kepler_warm_newton) with its own state wn; no per-row key test (the unchecked loop's tasks).
-template <int P, bool GRAD, bool NUIS, int KM, bool TAB, int WARM = 0, bool WCHECK = true, int WLAST = 0>
+// WPH: that row's phase in the four-row trip. WPIN: the warm row reads two rotation constants from ws->pin (WARM 3 always does).
+template <int P, bool GRAD, bool NUIS, int KM, bool TAB, int WARM = 0, bool WCHECK = true, int WLAST = 0, int WPH = 0, bool WPIN = false>
 __device__ __forceinline__ void astrom_row(AccArr<P, GRAD, NUIS, KM>& acc, LogProd& lp, const PC (&pc)[P],
                                            const AstromCoef<P>& co, double t, double y1, double y2, double c3, double c4, double c5,
                                            const SinCosTab& tab, WarmState<P>* ws = nullptr, double dm = 0.0, KWarmNewton* wn = nullptr) {
@@ -507,8 +508,8 @@ __device__ __forceinline__ void astrom_row(AccArr<P, GRAD, NUIS, KM>& acc, LogPr
     double ra_m, dec_m;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-        if constexpr (WARM == 3) s[p] = kepler_warm_newton<1>(t, pc[p], tab, ws->st[p], *wn, ws->thr[p], dm);
-        else if constexpr (WARM != 0) s[p] = kepler_solve_warm<1, WARM == 1>(t, pc[p], tab, ws->st[p], ws->thr[p], dm, WCHECK ? ws->row_ok : true);
+        if constexpr (WARM == 3) s[p] = kepler_warm_newton<1, WPH>(t, pc[p], tab, ws->st[p], *wn, ws->thr[p], dm, ws->pin);
+        else if constexpr (WARM != 0) s[p] = kepler_solve_warm<1, WARM == 1, WPIN>(t, pc[p], tab, ws->st[p], ws->thr[p], dm, WCHECK ? ws->row_ok : true, &ws->pin);
         else if constexpr (WLAST != 0) { if (p == P - 1) s[p] = kepler_warm_step<1>(t, pc[p], ws->st[p], dm); else s[p] = kepler_solve<1, TAB>(t, pc[p], tab); }
         else s[p] = kepler_solve<1, TAB>(t, pc[p], tab);
         if constexpr (WLAST == 2) {
@@ -990,6 +991,20 @@ constexpr bool main_warm_newton() {
            (KM == KM_RADEC || KM == (KM_RADEC | KM_COR));
 }
 
+// Two rotation constants held in VGPRs over the astrometry branch's warm loops (octo_device.h: WarmPin) — the checked and the unchecked loop and the Newton-only
+// loop: the four-wave single-planet nuisance-free kernels, which have the two register pairs within their occupancy step (config 3's gradient kernel: 84 -> 88
+// VGPRs, five waves either way). Not the eight-wave kernels (held to 80), not k_main<…, FINF>, not P >= 2, and not the nuisance kernels: at the same
+// registers and waves the `nuis` workload ran 1 % SLOWER with them (0.3534 -> 0.3568 ms per step, same box, twice each way: DESIGN.md §7). Every kernel that
+// has the Newton-only loop is one of these.
+#ifndef OCTO_WARM_PIN
+#define OCTO_WARM_PIN 1
+#endif
+template <int P, bool GRAD, bool NUIS, int KM, bool FUSED, int NWV, bool FINF>
+constexpr bool main_warm_pin() {
+    return main_warm_newton<P, GRAD, NUIS, KM, FUSED, NWV, FINF>() ||
+           (OCTO_WARM_PIN && main_warm<P, GRAD, NUIS, KM, FUSED>() && !main_warm_plain<P, GRAD, NUIS, KM, FUSED>() && !NUIS && NWV == WPB && !FINF);
+}
+
 // Two and three planets (round 6): the LAST planet — the outer one in the usual order — starts from the previous row's solution. A warm/cold DIAMOND per planet ends the
 // interleaving of the two solves that a kernel at two waves per SIMD lives on (round 5: −3 %, −8 %; and a diamond around the whole row body costs five scalar
 // branches per row: −3 % where every row is warm). So the row body takes the warm step for that planet UNCONDITIONALLY, next to the other planet's cold solve
@@ -1250,10 +1265,12 @@ static __global__ __launch_bounds__(64 * NWV) void k_main(EvalArgs a) {
                     astrom_row<P, GRAD, NUIS, KM, true, WMODE, true>(acc, lp, pc, co, rw[0], rw[1], rw[2], rw[3], rw[4], rw[5], tab, &ws, rw[6]);
                 }
             } else if constexpr (main_warm<P, GRAD, NUIS, KM, FUSED>()) {
+                constexpr bool WPIN = main_warm_pin<P, GRAD, NUIS, KM, FUSED, NWV, FINF>();
+                if constexpr (WPIN) ws.pin = warm_pin();
                 auto wbody_t = [&](const RowRegs8& r, auto checked) {
                     if constexpr (decltype(checked)::value) ws.row_ok = warm_row_ok<P>(ws, r);
-                    astrom_row<P, GRAD, NUIS, KM, true, WMODE, decltype(checked)::value>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2), row_get(r, 3),
-                                                                                         row_get(r, 4), row_get(r, 5), tab, &ws, row_get(r, 6));
+                    astrom_row<P, GRAD, NUIS, KM, true, WMODE, decltype(checked)::value, 0, 0, WPIN>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2),
+                                                                                                     row_get(r, 3), row_get(r, 4), row_get(r, 5), tab, &ws, row_get(r, 6));
                 };
                 auto wloop = [&](auto checked) {
                     RowRegs8 A = row_issue8(rows);
@@ -1272,17 +1289,28 @@ static __global__ __launch_bounds__(64 * NWV) void k_main(EvalArgs a) {
                         if (warm_unchecked && (a.warm & 2) != 0 && tk.dm_uniform > 0.0f) {
                             KWarmNewton wn;
                             warm_newton_init(wn, pc[0].ef, (a.warm & 4) != 0);
-                            auto nbody = [&](const RowRegs8& r) {
-                                astrom_row<P, GRAD, NUIS, KM, true, 3, false>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2), row_get(r, 3), row_get(r, 4),
-                                                                              row_get(r, 5), tab, &ws, row_get(r, 6), &wn);
+                            auto nbody = [&](const RowRegs8& r, auto ph) {
+                                astrom_row<P, GRAD, NUIS, KM, true, 3, false, 0, decltype(ph)::value>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2),
+                                                                                                      row_get(r, 3), row_get(r, 4), row_get(r, 5), tab, &ws, row_get(r, 6), &wn);
                             };
+                            // FOUR rows per trip, one per phase of the history ring (kepler_warm_newton), through the same two SGPR buffers: one prefetch in
+                            // flight, waited for behind the loop. The chunk's remainder (n_rows mod 4, or a chunk shorter than four rows) is taken at the FRONT:
+                            // the first trip leaves its leading `skip` slots empty (their prefetches read row 0 again), every later trip is whole, and the loop
+                            // has ONE exit, at its foot — no tuple and no sum crosses an early exit. The ring has no origin, so the phase a row falls on
+                            // changes nothing: the history is empty until four rows have been recorded, whichever slot the first of them took.
+                            const int skip = (4 - (n_rows & 3)) & 3;
+                            auto row_at = [&](int k) { k -= skip; return rows + (int64_t)(k < 0 ? 0 : (k < n_rows ? k : n_rows - 1)) * ROW_STRIDE; };
                             RowRegs8 A = row_issue8(rows);
-                            for (int j = 0; j < n_rows; j += 2) {
-                                RowRegs8 B = row_wait_issue(A, rows + (int64_t)(j + 1 < n_rows ? j + 1 : j) * ROW_STRIDE);
-                                nbody(A);
-                                if (__builtin_expect(j + 1 >= n_rows, 0)) { row_drain(B); break; }
-                                A = row_wait_issue(B, rows + (int64_t)(j + 2 < n_rows ? j + 2 : j + 1) * ROW_STRIDE);
-                                nbody(B);
+                            for (int j = 0;; j += 4) {
+                                RowRegs8 B = row_wait_issue(A, row_at(j + 1));
+                                if (__builtin_expect(j >= skip, 1)) nbody(A, std::integral_constant<int, 0>{});
+                                A = row_wait_issue(B, row_at(j + 2));
+                                if (__builtin_expect(j + 1 >= skip, 1)) nbody(B, std::integral_constant<int, 1>{});
+                                B = row_wait_issue(A, row_at(j + 3));
+                                if (__builtin_expect(j + 2 >= skip, 1)) nbody(A, std::integral_constant<int, 2>{});
+                                A = row_wait_issue(B, row_at(j + 4));
+                                nbody(B, std::integral_constant<int, 3>{});
+                                if (j + 4 >= n_rows + skip) break;
                             }
                             row_drain(A);
                         } else wloop(std::true_type{});

@@ -34,6 +34,8 @@ __global__ __launch_bounds__(256) void k(double* out, double a, double b, long l
             if (OP == 13) x[i] = __builtin_amdgcn_rsq(x[i]);
             if (OP == 14) x[i] = __builtin_amdgcn_fract(x[i] * b);
             if (OP == 15) x[i] = fabs(x[i]) > b ? x[i] : a;    // cmp + cndmask x2
+            if (OP == 16) asm volatile("v_mov_b64 %0, %1" : "=v"(x[i]) : "v"(x[(i + 1) % NACC]));   // VGPR pair <- VGPR pair
+            if (OP == 17) asm volatile("v_mov_b64 %0, %1" : "=v"(x[i]) : "s"(b));                  // VGPR pair <- SGPR pair (a wave-uniform constant)
         }
     }
     long long t1 = clock64();
@@ -62,5 +64,6 @@ int main() {
     run<4>("v_mul_f64+v_rndne_f64", 1); run<14>("v_mul_f64+v_fract_f64", 1);
     run<5>("v_fma_f32", 0); run<12>("2x v_fma_f32 (pk?)", 1); run<6>("v_rcp_f32", 0); run<7>("v_sqrt_f32", 0); run<8>("v_log_f32", 0); run<9>("v_exp_f32", 0);
     run<10>("v_cvt_f32_f64+v_add_f32", 1); run<11>("v_cvt_f64_f32+v_add_f64", 1); run<15>("v_cmp_f64+2 cndmask", 2);
+    run<16>("v_mov_b64 v, v", 0); run<17>("v_mov_b64 v, s", 0);
     return 0;
 }
