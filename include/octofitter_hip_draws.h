@@ -64,6 +64,10 @@
  * functions in place of its own table, and the exchange of the two legs' target replicas, stated in full at their declaration
  * (tests/vref_reference.py restates them). No model, no random number.
  *
+ * The twelfth is derived variables (octo_draws_program_set … octo_draws_program_values_device): the straight-line arithmetic a variable block puts
+ * between θ and the kernel inputs, as an expression program that the device interprets forward and reverse in place of octo_model_logpost_device, under
+ * every function of the handle that needs ℓπ, stated in full at its declaration (tests/program_reference.py restates it). No random number.
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -637,6 +641,86 @@ int32_t octo_draws_use_reference(octo_draws* h, const double* d_ref);
 int32_t octo_draws_reference_exchange_device(octo_draws* h, int64_t Cn, int32_t T_a, const int32_t* d_slot2rep_a, int64_t ld_a, double* d_theta_a,
                                              double* d_lp_a, double* d_ll_a, const double* d_ref_a, int32_t T_b, const int32_t* d_slot2rep_b, int64_t ld_b,
                                              double* d_theta_b, double* d_lp_b, double* d_ll_b, const double* d_ref_b, void* hip_stream);
+
+/* ---- Derived variables: expression programs (the twelfth part). The reference's `@variables` block produces, next to the priors, a short
+ * straight-line list of arithmetic on θ evaluated in declaration order: a = cbrt(M·P²), e = h² + k², tp = τ·P·365.25 + t_ref. Such a list is
+ * DATA. A handle created with a context and WITHOUT a model takes one (octo_draws_program_set), and from then on every function of the handle
+ * that needs ℓπ — octo_draws_best, octo_draws_rejection, the HMC step, NUTS, the slice sampler, the L-BFGS, Pathfinder — evaluates
+ * octo_draws_program_logpost_device where a handle with a model evaluates octo_model_logpost_device. No generated code: an interpreter, forward
+ * and reverse, on the device (tests/program_reference.py restates it).
+ *
+ * Nodes. Node d < D is the natural parameter x_d = invlink_d(θ_t[d]) of the handle's prior d; node D + j is the result of op j. An operand
+ * index must be lower than the node's own index (declaration order is topological order); a node may have any number of consumers.
+ * Ops (IEEE / ocml routines, not the fast-math variants of the one-θ path): */
+#define OCTO_DRAWS_OP_CONST 0    /* value                                   */
+#define OCTO_DRAWS_OP_ADD   1    /* a + b                                   */
+#define OCTO_DRAWS_OP_SUB   2    /* a − b                                   */
+#define OCTO_DRAWS_OP_MUL   3    /* a·b                                     */
+#define OCTO_DRAWS_OP_DIV   4    /* a/b                                     */
+#define OCTO_DRAWS_OP_NEG   5    /* −a                                      */
+#define OCTO_DRAWS_OP_SQRT  6
+#define OCTO_DRAWS_OP_CBRT  7
+#define OCTO_DRAWS_OP_EXP   8
+#define OCTO_DRAWS_OP_LOG   9
+#define OCTO_DRAWS_OP_SIN   10
+#define OCTO_DRAWS_OP_COS   11
+#define OCTO_DRAWS_OP_ATAN2 12   /* atan2 with a = y, b = x: the reference's atan(y, x)  */
+#define OCTO_DRAWS_OP_POWC  13   /* pow of a and value                      */
+#define OCTO_DRAWS_OP_MULC  14   /* a·value                                 */
+#define OCTO_DRAWS_OP_ADDC  15   /* a + value                               */
+#define OCTO_DRAWS_N_OPS    16
+#define OCTO_DRAWS_PROGRAM_MAX_OPS 192   /* with D <= 64: D + n_ops <= 256 nodes, 128 KB of the 160 KB of LDS at 512 B a node */
+typedef struct octo_draws_op   { int32_t op, a, b, pad; double value; } octo_draws_op;    /* 24 bytes; operands an op does not read: 0 */
+/* Bindings: one per kernel input in the order octo_eval_device reads them, n_planets·OCTO_N_EL elements, then n_obs·OCTO_N_NUIS nuisances.
+ *   OCTO_DRAWS_BIND_NODE   the input is the value of `node`
+ *   OCTO_DRAWS_BIND_TPERI  only on the OCTO_EL_TP slot of a Campbell planet whose A, E, I, W, O and M slots are NODE bindings: the input is
+ *                          θ_at_epoch_to_tperi with node = the angle, value = theta_epoch and M, e, a, i, ω, Ω the planet's six bound nodes,
+ *                          in closed form with its gradient into all seven, with the constants of octo_consts_default. Flag
+ *                          OCTO_DRAWS_BIND_FLAG_TI in the upper half of `kind` says the planet is a Thiele-Innes planet — the dataset is
+ *                          opaque to this library, the caller knows — and is answered with OCTO_ENOTSUP. */
+#define OCTO_DRAWS_BIND_NODE  0
+#define OCTO_DRAWS_BIND_TPERI 1
+#define OCTO_DRAWS_BIND_FLAG_TI 65536
+typedef struct octo_draws_bind { int32_t kind, node; double value; } octo_draws_bind;  /* 16 bytes */
+/* Terms: terms[n_terms] are node indices whose values are added to ℓπ on the likelihood side of the split, as k_model_fwd treats the
+ * UnitLengthPrior of a UniformCircular pair (written in primitives here): they survive a healed prior and are tempered with ℓ.
+ *
+ * octo_draws_program_set copies ops, binds and terms to the device and validates on the host; ds (a dataset of n_planets planets and n_obs tables
+ * made with the handle's context) must outlive the program. It replaces a program already set and forgets the resume records of NUTS, the slice
+ * sampler and the L-BFGS. octo_draws_program_clear removes the program: the handle is a sampling-only handle again.
+ *   OCTO_EINVAL   NULL handle, ds or a NULL array with a non-zero count; a handle WITH a model, or without a context; n_planets < 1, n_obs < 0;
+ *                 n_binds != n_planets·OCTO_N_EL + n_obs·OCTO_N_NUIS; an unknown op ("op j: …"); an operand that is not an earlier node
+ *                 (forward reference); a binding of unknown kind or with a node out of range ("binding k: …"); a TPERI binding on a slot that
+ *                 is not OCTO_EL_TP, or whose planet has another of its seven as a non-NODE binding; a term index out of range ("term i: …")
+ *   OCTO_ENOTSUP  n_ops > OCTO_DRAWS_PROGRAM_MAX_OPS; a TPERI binding flagged Thiele-Innes; more LDS than the device has
+ *
+ * octo_draws_program_logpost_device: the signature and the contract of octo_model_logpost_device — d_theta_t [D][ld], W columns, d_lp [W],
+ * d_grad [D][ld] or NULL, asynchronous on hip_stream, elements beyond W in a row never written. Three steps on the stream, lane = walker, one
+ * wave a block, no host synchronisation and no allocation once the handle's work array (prog_work of csrc/draws/octo_draws_layout.h,
+ * (N + 2·D + 2·n_in + 7·P + 3)·ldw doubles at N = D + n_ops nodes, n_in inputs, P planets and ldw = W rounded up to 64) is large enough:
+ *   k_prog_fwd   x_d, dx_d/dθ_t and logpdf_with_trans of each prior in declaration order (the routines of the model callback, ALWAYS on the table
+ *                given to octo_draws_create, whatever octo_draws_use_reference has put in place); the ops in order, node values in LDS
+ *                [node][64] (with a gradient: streamed to the work array as well); the inputs; Σ terms in the order given
+ *   octo_eval_device   ℓ and ∂ℓ/∂inputs
+ *   k_prog_bwd   adjoints in LDS, zero but for the inputs' ∂ℓ/∂input (a TPERI input: times its closed-form gradient, into its seven nodes) and 1
+ *                for every term, in that order; the ops in reverse order, operand values read back from the work array; then
+ *                ∂/∂θ_t[d] = adjoint_d·dx_d/dθ_t + ∂prior_d/∂θ_t. No atomics: a lane owns its column, the order of accumulation is the program's.
+ * Semantics, those of octo_model_logpost_device: prior part = Σ logpdf_with_trans, −1.7976931348623157e308 with zero prior gradient in every
+ * coordinate if any term of it is not finite (the healing rule); −Inf if any θ_t entry is not finite; pp = prior part + Σ terms;
+ * lp = isfinite(pp) ? pp + ℓ : pp; NaN becomes −Inf; the gradient row of a walker is 0 wherever its lp is not finite. A domain error inside the
+ * program (log of a negative, e = h² + k² >= 1) is a NaN node: it reaches the likelihood as an invalid input, or pp as a NaN term, and costs
+ * THAT walker −Inf with zero gradient — never a status, never another walker: a lane's result depends on its own column alone, bit for bit.
+ * OCTO_EINVAL: NULL handle, no program, NULL d_theta_t or d_lp with W > 0, W < 0, ld < W, W > 2^30. W = 0 does nothing.
+ *
+ * octo_draws_program_values_device: d_out[k·ld_out + w] = the value of node nodes[k] (a HOST array of n indices, each 0 … N − 1; n <= 256) of
+ * walker w: the derived columns of a chain, and the forward sweep on its own. Elements beyond W in a row are not written.
+ * OCTO_EINVAL as above, and: n < 0 or > 256, a node out of range, ld_out < W. */
+int32_t octo_draws_program_set(octo_draws* h, const octo_dataset* ds, int32_t n_planets, int32_t n_obs, const octo_draws_op* ops, int32_t n_ops,
+                               const octo_draws_bind* binds, int32_t n_binds, const int32_t* terms, int32_t n_terms);
+int32_t octo_draws_program_clear(octo_draws* h);
+int32_t octo_draws_program_logpost_device(octo_draws* h, const double* d_theta_t, int64_t ld, int64_t W, double* d_lp, double* d_grad, void* hip_stream);
+int32_t octo_draws_program_values_device(octo_draws* h, const double* d_theta_t, int64_t ld, int64_t W, const int32_t* nodes, int32_t n, double* d_out,
+                                         int64_t ld_out, void* hip_stream);
 
 #ifdef __cplusplus
 }

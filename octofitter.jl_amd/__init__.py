@@ -19,6 +19,8 @@ from .host.tempering import TemperedSwap  # noqa: F401,E402
 from .host.ofti import OftiLinearSolver, ofti_linear_solve  # noqa: F401,E402
 from .host.priors import (Uniform, LogUniform, Normal, TruncatedNormal, truncated, Sine, UniformCircular,  # noqa: F401,E402
                           θ_at_epoch_to_tperi, variables)
+from .host import derived  # noqa: F401,E402
+from .host.derived import Derived  # noqa: F401,E402
 from .host.model import LogDensityModel  # noqa: F401,E402
 from .host.callers import (guess_starting_position, octofit_rejection, rejection_evaluate_likelihoods, pointwise_like,  # noqa: F401,E402
                            guess_starting_position_device, octofit_rejection_device, simulate_tables, posterior_predictive,

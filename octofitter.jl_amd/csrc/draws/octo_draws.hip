@@ -338,7 +338,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
         }
         if (release) (void)hipStreamDestroy(h->stream);
     }
-    for (void* p : std::initializer_list<void*>{h->own_priors, h->own_pc, h->own_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice})
+    for (void* p : std::initializer_list<void*>{h->own_priors, h->own_pc, h->own_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice, h->d_prog, h->d_prog_tab})
         (void)hipFree(p);
     delete h;
     return OCTO_OK;
@@ -346,7 +346,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
 
 int32_t octo_draws_detach(octo_draws* h) {
     if (!h) return OCTO_EINVAL;
-    h->ctx = nullptr; h->model = nullptr;
+    h->ctx = nullptr; h->model = nullptr; h->prog_ops = nullptr;
     return OCTO_OK;
 }
 
@@ -383,7 +383,7 @@ int32_t octo_draws_best(octo_draws* h, uint64_t seed, uint64_t first, int64_t N,
     for (int64_t done = 0; done < N; done += CHUNK) {
         const int64_t n = std::min(CHUNK, N - done);
         { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, k.tt, nullptr); if (rc) return rc; }
-        { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, k.tt, CHUNK, n, a.lp, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+        { int rc = logpost_at(h, st, true, k.tt, CHUNK, n, a.lp, nullptr); if (rc) return rc; }
         const int64_t nb = (n + SEL_SLAB - 1) / SEL_SLAB;
         hipLaunchKernelGGL(k_topk, dim3((unsigned)nb), dim3(TPB), 0, st, a.lp, (const uint64_t*)nullptr, first + (uint64_t)done, n, keep, (int64_t)1, k.clp, k.cix);
         hipLaunchKernelGGL(k_topk, dim3(1), dim3(TPB), 0, st, k.clp, k.cix, (uint64_t)0, (1 + nb) * keep, keep, (int64_t)0, k.clp, k.cix);
@@ -428,7 +428,7 @@ int32_t octo_draws_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64
     for (int64_t done = 0; done < N; done += CHUNK) {
         const int64_t n = std::min(CHUNK, N - done);
         { int rc = launch_draw(h, st, seed, first + (uint64_t)done, nullptr, n, CHUNK, nullptr, k.tt, k.lpt); if (rc) return rc; }
-        { int rc = main_call(h, octo_model_logpost_device(h->ctx, h->model, k.tt, CHUNK, n, a.lp + done, nullptr, (void*)st), "octo_model_logpost_device"); if (rc) return rc; }
+        { int rc = logpost_at(h, st, true, k.tt, CHUNK, n, a.lp + done, nullptr); if (rc) return rc; }
         hipLaunchKernelGGL(k_loglike, grid_of(n), dim3(TPB), 0, st, a.lp + done, k.lpt, n, a.ll + done, a.pmax + done / TPB);
         OCHK(h, hipGetLastError());
     }

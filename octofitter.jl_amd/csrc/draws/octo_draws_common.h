@@ -4,7 +4,8 @@
 // (SamplerHead), the per-lane preamble (Chain, chain_of) and the tempered target at a point (Target, target_at over prior_loop, tempered_energy,
 // dead_state). On the host: check_sampler_call, sampler_head, logpost_at (every octo_model_logpost_device call of the four units) and
 // run_rounds (the round driver of the L-BFGS and of NUTS).
-// Ten units include it (the tenth: octo_draws_vref.hip, the reference table of a variational tempering leg and the exchange of two legs' target
+// Eleven units include it (the eleventh: octo_draws_program.hip, the expression programs of derived variables, which logpost_at chooses over the model;
+// the tenth: octo_draws_vref.hip, the reference table of a variational tempering leg and the exchange of two legs' target
 // replicas, which take prior_loop and the handle's active table): octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
 // explorer), octo_draws_nuts.hip (the no-U-turn sampler), octo_draws_slice.hip (the slice sampler, which takes the samplers' head, preamble, target
 // and round driver without a gradient), octo_draws_lbfgs.hip (the multi-start L-BFGS), octo_draws_pathfinder.hip (Pathfinder
@@ -236,6 +237,14 @@ struct octo_draws : CompanionBase {
     double* d_slice = nullptr; int64_t cap_slice = 0;
     int64_t slice_W = 0, slice_ld = 0; int32_t slice_passes = 0, slice_p = 0, slice_shrink = 0;
     uint64_t slice_seed = 0, slice_step = 0, slice_chain0 = 0;
+    // the expression program (octo_draws_program.hip) of a handle without a model: the dataset it evaluates, its tables on the device in one
+    // allocation (prog_ops null: no program), its shape, and its work arrays, grown on demand
+    const octo_dataset* prog_ds = nullptr;
+    void* d_prog_tab = nullptr;
+    const octo_draws_op* prog_ops = nullptr; const octo_draws_bind* prog_binds = nullptr; const int32_t* prog_terms = nullptr;
+    int32_t prog_n_ops = 0, prog_n_in = 0, prog_n_el = 0, prog_n_terms = 0, prog_planets = 0;
+    double prog_k_yr = 0.0;
+    double* d_prog = nullptr; int64_t cap_prog = 0;
 };
 
 namespace {
@@ -258,8 +267,10 @@ int grow_to(octo_draws* h, double*& p, int64_t& cap, S& parts, F layout, A... ar
 }
 
 // The argument checks the functions share: who = the function's name, the rest of the message is the same in each.
+// ℓπ of the handle: its model's, or its expression program's
+inline bool has_target(const octo_draws* h) { return h->ctx && (h->model || h->prog_ops); }
 inline int check_model(octo_draws* h, const char* who) {
-    return h->model && h->ctx ? OCTO_OK : fail(h, OCTO_EINVAL, std::string(who) + ": the handle has no model (created without one, or detached)");
+    return has_target(h) ? OCTO_OK : fail(h, OCTO_EINVAL, std::string(who) + ": the handle has no model (created without one, or detached)");
 }
 inline int check_m(octo_draws* h, const char* who, int32_t m) {
     return m >= 1 && m <= OCTO_DRAWS_LBFGS_MAX_M ? OCTO_OK : fail(h, OCTO_EINVAL, std::string(who) + ": m must be 1 ... OCTO_DRAWS_LBFGS_MAX_M");
@@ -284,8 +295,10 @@ inline SamplerHead sampler_head(const octo_draws* h, bool has_model, uint64_t se
     return {h->d_priors, h->d_pc, d_beta, d_eps, d_inv_mass, eps, seed, step, chain0, W, ld, h->D, has_model ? 1 : 0, d_theta_t};
 }
 
-// ℓπ [W] and ∇ℓπ [D][ld] (or null) at the points `at` [D][ld] on the stream st; nothing to do on a handle without a model
+// ℓπ [W] and ∇ℓπ [D][ld] (or null) at the points `at` [D][ld] on the stream st; nothing to do on a handle without a model. The one place that
+// chooses between the model and the expression program.
 inline int logpost_at(octo_draws* h, hipStream_t st, bool has_model, const double* at, int64_t ld, int64_t W, double* lp, double* glp) {
+    if (has_model && h->prog_ops) return octo_draws_program_logpost_device(h, at, ld, W, lp, glp, (void*)st);
     return has_model ? main_call(h, octo_model_logpost_device(h->ctx, h->model, at, ld, W, lp, glp, (void*)st), "octo_model_logpost_device") : OCTO_OK;
 }
 

@@ -126,7 +126,7 @@ int32_t octo_draws_hmc_step_device(octo_draws* h, uint64_t seed, uint64_t step, 
                                    double* d_theta_prop, double* d_logpost, double* d_loglike, double* d_dH, int32_t* d_accepted, void* hip_stream) {
     if (!h) return OCTO_EINVAL;
     if (n_leapfrog < 1) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: n_leapfrog >= 1");
-    const bool has_model = h->model && h->ctx;
+    const bool has_model = has_target(h);
     if (int rc = check_sampler_call(h, "octo_draws_hmc_step_device", W, ld, d_eps, eps, has_model, d_logpost, d_loglike)) return rc;
     if (W == 0) return OCTO_OK;
     if (!d_theta_t || !d_accepted) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: d_theta_t and d_accepted are required");

@@ -141,6 +141,21 @@ inline RefTable ref_table(Carve& c, int64_t D, int64_t nc, int64_t icn) {
     return {c.take(REF_PRIOR_DOUBLES * D), c.take(nc * D), c.take(icn * D), c.take(D), c.take(D)};
 }
 
+// The work arrays of an expression program (octo_draws_program.hip), d_prog: (N + 2·D + 2·n_in + 7·P + 3)·ldw. N = D + n_ops nodes, n_in kernel
+// inputs, P planets, ldw = the batch rounded up to whole waves. The kernels take it by value: its members and their order are their argument layout.
+struct ProgWork {
+    double* vals;               // [N][ldw] node values of the forward sweep, what the reverse sweep reads its operands from
+    double *dx, *gpd;           // [D][ldw] dx_d/dθ_t · ∂(logpdf_with_trans of prior d)/∂θ_t
+    double *inputs, *g_in;      // [n_in][ldw] what octo_eval_device reads (elements, then nuisances) and its gradient
+    double* gtp;                // [P][7][ldw] a TPERI binding's ∂tp/∂(angle, a, e, i, ω, Ω, M)
+    double *pp, *ll;            // [ldw] prior part + terms · ℓ
+    int32_t* healed;            // [ldw] the prior was healed
+};
+inline ProgWork prog_work(Carve& c, int64_t D, int64_t N, int64_t n_in, int64_t P, int64_t ldw) {
+    return {c.take(N * ldw), c.take(D * ldw), c.take(D * ldw), c.take(n_in * ldw), c.take(n_in * ldw), c.take(7 * P * ldw), c.take(ldw), c.take(ldw),
+            c.take<int32_t>(ldw)};
+}
+
 // The convergence diagnostics of K rows (octo_draws_diag.hip), d_diag: 2K(P + S) + 10KM + 4K·T·(nblk + 1) + 5K. N draws of M = 2W split chains a row,
 // S = M·N used draws, P = the power of two the sort pads them to, T = the lags rounded up to whole blocks of 16, nblk = ⌈M/256⌉. The kernels take it
 // by value: its members and their order are their argument layout.

@@ -216,7 +216,7 @@ int32_t octo_draws_nuts_device(octo_draws* h, uint64_t seed, uint64_t step, uint
     if (!h) return OCTO_EINVAL;
     if (max_depth < 1 || max_depth > OCTO_DRAWS_NUTS_MAX_DEPTH) return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: max_depth must be 1 ... OCTO_DRAWS_NUTS_MAX_DEPTH");
     if (n_rounds < 0) return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: n_rounds >= 0");
-    const bool has_model = h->model && h->ctx;
+    const bool has_model = has_target(h);
     if (int rc = check_sampler_call(h, "octo_draws_nuts_device", W, ld, d_eps, eps, has_model, d_logpost, d_loglike)) return rc;
     if (resume && (h->nuts_depth != max_depth || h->nuts_W != W || h->nuts_ld != ld || h->nuts_seed != seed || h->nuts_step != step || h->nuts_chain0 != chain0))
         return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: resume needs a previous call with the same W, ld, max_depth, seed, step and chain0");

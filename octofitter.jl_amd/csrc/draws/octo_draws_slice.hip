@@ -215,7 +215,7 @@ int32_t octo_draws_slice_device(octo_draws* h, uint64_t seed, uint64_t step, uin
     if (max_shrink < 1 || max_shrink > OCTO_DRAWS_SLICE_MAX_SHRINK) return fail(h, OCTO_EINVAL, "octo_draws_slice_device: max_shrink must be 1 ... OCTO_DRAWS_SLICE_MAX_SHRINK");
     if (n_passes < 1 || n_passes > OCTO_DRAWS_SLICE_MAX_PASSES) return fail(h, OCTO_EINVAL, "octo_draws_slice_device: n_passes must be 1 ... OCTO_DRAWS_SLICE_MAX_PASSES");
     if (n_rounds < 0) return fail(h, OCTO_EINVAL, "octo_draws_slice_device: n_rounds >= 0");
-    const bool has_model = h->model && h->ctx;
+    const bool has_model = has_target(h);
     // the samplers' checks of the chains and of ℓπ outputs without a model; their step-size check has nothing to look at here (the width stands in the head's ε)
     if (int rc = check_sampler_call(h, "octo_draws_slice_device", W, ld, nullptr, 1.0, has_model, d_logpost, d_loglike)) return rc;
     if (resume && (h->slice_passes != n_passes || h->slice_p != p || h->slice_shrink != max_shrink || h->slice_W != W || h->slice_ld != ld || h->slice_seed != seed ||

@@ -154,10 +154,16 @@ def _finite_or_neg_inf(x):
     return torch.where(torch.isfinite(x), x, torch.full_like(x, -float("inf")))
 
 
-def _recorded(model, rec_t, rec_lp):
-    """What a sampler returns of its recorded rounds rec_t [n, D, n_chains] (θ_t) and rec_lp [n, n_chains]: samples, samples_t, logpost."""
+def _recorded(model, rec_t, rec_lp, pd):
+    """What a sampler returns of its recorded rounds rec_t [n, D, n_chains] (θ_t) and rec_lp [n, n_chains]: samples, samples_t, logpost; of a
+    model with Derived variables also derived: {name: [n, n_chains]}, each variable's column from the handle's program (PriorDraws.program_values)."""
     samples_t = rec_t.cpu().numpy()
-    return dict(samples=np.stack([model.invlink(x) for x in samples_t]), samples_t=samples_t, logpost=rec_lp.cpu().numpy())
+    out = dict(samples=np.stack([model.invlink(x) for x in samples_t]), samples_t=samples_t, logpost=rec_lp.cpu().numpy())
+    if getattr(model, "derived_names", None):
+        n, D, Cn = rec_t.shape
+        cols = pd.derived_columns(rec_t.permute(1, 0, 2).reshape(D, n * Cn).contiguous())
+        out["derived"] = {name: v.reshape(n, Cn).cpu().numpy() for name, v in cols.items()}
+    return out
 
 
 def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None, betas=None, inv_mass=None, seed=0, n_adapt=None, adapt="host",
@@ -258,7 +264,7 @@ def octofit_pt_device(model, n_temps, n_chains, n_rounds, n_leapfrog=4, eps=None
         pairs = np.arange(T - 1)
         attempts = np.array([(R + 1 - (t % 2)) // 2 for t in pairs]) * Cn            # pair (t, t + 1) is tried in the rounds of parity t % 2
         explored = dict(slice_evals=(acc_sum / R).cpu().numpy()) if use_slice else dict(hmc_acceptance=(acc_sum / R).cpu().numpy())
-        return dict(**_recorded(model, rec_t, rec_lp), **explored, swap_acceptance=swap.accepted.cpu().numpy()[:T - 1] / np.maximum(attempts, 1),
+        return dict(**_recorded(model, rec_t, rec_lp, pd), **explored, swap_acceptance=swap.accepted.cpu().numpy()[:T - 1] / np.maximum(attempts, 1),
                     **({} if use_slice else dict(eps=torch.exp(log_eps).cpu().numpy())), betas=swap.beta.cpu().numpy(), names=list(model.names),
                     state=dict(theta_t=theta_t.cpu().numpy(), slot2rep=swap.slot2rep.cpu().numpy(),
                                refreshed=None if refreshed is None else refreshed.cpu().numpy(), refreshed_first=next_draw - Cn if cold_last else None))
@@ -387,7 +393,7 @@ def octofit_pigeons_device(model, n_temps, n_chains, n_rounds, explorer="slice",
         summary = summary_by_round.cpu().numpy()
         per_chain = pt["restarts"].cpu().numpy()
         counts = counts.cpu().numpy().astype(np.int64)
-        return dict(**_recorded(model, rec_t, rec_lp), **explored, swap_acceptance=swap.accepted.cpu().numpy()[:T - 1] / np.maximum(attempts, 1),
+        return dict(**_recorded(model, rec_t, rec_lp, pd), **explored, swap_acceptance=swap.accepted.cpu().numpy()[:T - 1] / np.maximum(attempts, 1),
                     betas=swap.beta.cpu().numpy(), names=list(model.names),
                     state=dict(theta_t=theta_t.cpu().numpy(), slot2rep=swap.slot2rep.cpu().numpy(),
                                refreshed=None if refreshed is None else refreshed.cpu().numpy(), refreshed_first=next_draw - Cn if cold_last else None),
@@ -513,7 +519,7 @@ def _pigeons_two_legs(model, T, Tv, Cn, R, use_slice, n_leapfrog, eps, betas, in
             summary = g.summary_by_round.cpu().numpy()
             per_chain = g.pt["restarts"].cpu().numpy()
             counts = g.counts.cpu().numpy().astype(np.int64)
-            return dict(**_recorded(model, g.rec_t, g.rec_lp), **explored, swap_acceptance=g.swap.accepted.cpu().numpy()[:g.T - 1] / np.maximum(attempts, 1),
+            return dict(**_recorded(model, g.rec_t, g.rec_lp, pd), **explored, swap_acceptance=g.swap.accepted.cpu().numpy()[:g.T - 1] / np.maximum(attempts, 1),
                         betas=g.swap.beta.cpu().numpy(),
                         log_evidence=dict(fwd=float(summary[-1, 1]), rev=float(summary[-1, 2]), mean=float(summary[-1, 3]), n=counts[:, 0], n_fwd=counts[:, 1],
                                           n_rev=counts[:, 2]),
@@ -708,7 +714,7 @@ def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leap
         rhat = rhat_from_chain_moments(pd, cmean, cm2, ns)
         extra = _diagnosed(pd, rec_t) if diagnose else {}
         torch.cuda.synchronize(dev)
-        return dict(**_recorded(model, rec_t, rec_lp),
+        return dict(**_recorded(model, rec_t, rec_lp, pd),
                     accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
                     rhat=rhat.cpu().numpy(), names=list(model.names), state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns),
                     **{k: v.cpu().numpy() for k, v in extra.items()})
@@ -754,7 +760,7 @@ def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_d
         extra = _diagnosed(pd, rec_t) if diagnose else {}
         torch.cuda.synchronize(dev)
         tree = torch.cat([wu["tree"], tree]).cpu().numpy()
-        return dict(**_recorded(model, rec_t, rec_lp),
+        return dict(**_recorded(model, rec_t, rec_lp, pd),
                     accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
                     rhat=rhat.cpu().numpy(), depth=tree[:, 0], n_leapfrog=tree[:, 1], diverged=tree[:, 2].astype(np.int64), names=list(model.names),
                     state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns), **{k: v.cpu().numpy() for k, v in extra.items()})

@@ -21,6 +21,8 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     r, z = draws.ranks(rec)                                 # … the rank step alone: average ranks and normal scores, of rec's shape
     state = draws.pt_state(T, Cn)                           # parallel tempering between the scans: the zeroed state (acc, leg, restarts)
     draws.pt_stats(ll, slot2rep, beta, state)               # … a scan's swap probabilities, stepping-stone sums and tempered restarts, accumulated
+    lp, g = draws.program_logpost(θ_t)                      # a model with Derived variables: ℓπ and ∇ℓπ through its expression program
+    v = draws.program_values(θ_t, nodes)                    # … the values of chosen nodes [n, W]: the derived columns of a chain
     r = draws.pt_schedule(state, beta)                      # … a round's rejection rates, barrier Λ, log evidence and the re-placed ladder: dict
     ref = draws.reference_table()                           # a variational tempering leg: the reference table, an empty device buffer
     bad = draws.reference_fit(ref, count[0:1], mean[0], m2[0])      # … a mean-field normal on θ_t from one group's moments (reference_set: from μ, σ)
@@ -112,6 +114,10 @@ _SIGS = {
     "octo_draws_use_reference": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "octo_draws_reference_exchange_device": (C.c_int32, [C.c_void_p, C.c_int64] + [C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
                                              + [C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_void_p]),
+    "octo_draws_program_set": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "octo_draws_program_clear": (C.c_int32, [C.c_void_p]),
+    "octo_draws_program_logpost_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_program_values_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -218,26 +224,38 @@ def is_adapt_state(state, G, dev):
 
 
 class PriorDraws(companion.Handle):
-    """The handle of octo_draws_create. PriorDraws(model): for one LogDensityModel — its priors, its device model, its context.
+    """The handle of octo_draws_create. PriorDraws(model): for one LogDensityModel — its priors, its device model, its context; a model
+    with Derived variables has an expression program instead of a device model, and the handle is given that (octo_draws_program_set).
+    PriorDraws(model, program=(prog, binds)[, priors=[…]]): the model's context and dataset — and its priors unless others are given —
+    under a program of the caller's (host/derived.py: Program; binds [(kind, node, value)] one per kernel input) in place of its device model.
     PriorDraws(priors=[…], device=0): a list of host/priors.py priors and a context of its own — sampling only (no best / rejection)."""
 
     PREFIX = "octo_draws"
 
-    def __init__(self, model=None, priors=None, device=0):
-        if (model is None) == (priors is None):
-            raise ValueError("PriorDraws takes a LogDensityModel or a list of priors")
+    def __init__(self, model=None, priors=None, device=0, program=None):
+        if model is None and priors is None or (model is not None and priors is not None and program is None):
+            raise ValueError("PriorDraws takes a LogDensityModel or a list of priors (both only with a program)")
+        if program is not None and model is None:
+            raise ValueError("PriorDraws: a program needs a model, whose context and dataset it is evaluated on")
         self.model = model
         self._own_ctx = None
+        self.program = None
+        self._target = model is not None      # the handle has an ℓπ: a device model or a program
         self._open(load_library(), model.ln_like.device_index if model is not None else device)
-        if model is not None:
+        if model is not None and program is None and getattr(model, "program", None) is not None:
+            program = (model.program, model._binds)
+        if priors is None:
             self.D = int(model.D)
-            ctx, m, self._c_priors = model.ln_like._ctx, model._m, model._c_priors
+            self._c_priors = model._c_priors
         else:
             self.D = len(priors)
             self._c_priors = (capi.OctoPrior * max(self.D, 1))()
             for k, p in enumerate(priors):
                 self._c_priors[k].kind = p.kind
                 self._c_priors[k].p0, self._c_priors[k].p1, self._c_priors[k].lo, self._c_priors[k].hi = p.c_params()
+        if model is not None:
+            ctx, m = model.ln_like._ctx, (None if program is not None else model._m)
+        else:
             main = capi.load_library()
             ctx, m = C.c_void_p(), None
             st = main.octo_ctx_create(C.byref(ctx), self.device_index)
@@ -245,6 +263,50 @@ class PriorDraws(companion.Handle):
                 raise capi.OctoError(st, "octo_ctx_create")
             self._own_ctx = ctx
         self._created(self.lib.octo_draws_create(ctx, m, self._c_priors, self.D, self.device_index, C.byref(self._h)))
+        if program is not None:
+            self.program_set(*program)
+
+    # ---- derived variables (include/octofitter_hip_draws.h, "Derived variables"): a handle made from a model, without its device model
+    def program_set(self, prog, binds):
+        """octo_draws_program_set: from the next call on every function of the handle that needs ℓπ evaluates the program `prog`
+        (host/derived.py: Program) with the bindings binds [(kind, node, value)] on the model's dataset."""
+        fn = self.model.ln_like
+        arrays = prog.c_arrays(binds)
+        ops, n_ops, bs, n_binds, ts, n_terms = arrays
+        self._check(self.lib.octo_draws_program_set(self._h, fn._ds, fn.n_planets, fn.n_obs, C.cast(ops, C.c_void_p), n_ops, C.cast(bs, C.c_void_p), n_binds,
+                                                    C.cast(ts, C.c_void_p), n_terms))
+        self.program, self._target = prog, True
+
+    def program_clear(self):
+        """octo_draws_program_clear: the handle is a sampling-only handle again."""
+        self._check(self.lib.octo_draws_program_clear(self._h))
+        self.program, self._target = None, False
+
+    def program_logpost(self, theta_t, grad=True, out=None, stream=None):
+        """(ℓπ [W], ∇ℓπ [D, W] of theta_t's leading dimension, or None) of the W columns of theta_t (torch float64 [D, W] on the handle's
+        device, rows contiguous) through the program. out=(lp, grad): written in place. Asynchronous on `stream`."""
+        _, W, ld = chain_matrix(theta_t, self.D, self.device, "program_logpost")
+        lp, g = out if out is not None else (self._out(W), self._out(W, self.D, ld) if grad else None)
+        self._check(self.lib.octo_draws_program_logpost_device(self._h, theta_t.data_ptr(), ld, W, lp.data_ptr(), ptr(g), self._stream(stream, self.device)))
+        self._keep = (theta_t, lp, g)
+        return lp, g
+
+    def program_values(self, theta_t, nodes, stream=None):
+        """The values [n, W] of the nodes `nodes` (indices: d < D a natural parameter, D + j the result of op j) at the W columns of theta_t."""
+        _, W, ld = chain_matrix(theta_t, self.D, self.device, "program_values")
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        out = self._out(W, max(int(nodes.size), 1))[:nodes.size]
+        self._check(self.lib.octo_draws_program_values_device(self._h, theta_t.data_ptr(), ld, W, nodes.ctypes.data_as(C.c_void_p), int(nodes.size), out.data_ptr(),
+                                                              max(W, 1), self._stream(stream, self.device)))
+        self._keep = (theta_t, out)
+        return out
+
+    def derived_columns(self, theta_t):
+        """{name: [W] tensor} of the model's Derived variables at the columns of theta_t; {} for a model without any."""
+        names = getattr(self.model, "derived_names", None) if self.model is not None and self.program is not None else None
+        if not names:
+            return {}
+        return dict(zip(names, self.program_values(theta_t, self.model.derived_nodes)))
 
     @functools.cached_property
     def device(self):
@@ -324,7 +386,7 @@ class PriorDraws(companion.Handle):
         eps_w = device_vector(eps, W, dev, "eps") if per_chain else None
         be = device_vector(beta, W, dev, "beta")
         im = device_vector(inv_mass, self.D, dev, "inv_mass")
-        lp, ll = (self._out(W), self._out(W)) if self.model is not None else (None, None)
+        lp, ll = (self._out(W), self._out(W)) if self._target else (None, None)
         dH = self._out(W)
         acc = self._out(W, dtype=torch.int32)
         prop = self._out(W, self.D, ld) if want_proposal else None
@@ -351,7 +413,7 @@ class PriorDraws(companion.Handle):
         im = device_vector(inv_mass, self.D, dev, "inv_mass")
         if out is None:
             i32 = lambda n: self._out(n, dtype=torch.int32)      # noqa: E731
-            lp, ll = (self._out(W), self._out(W)) if self.model is not None else (None, None)
+            lp, ll = (self._out(W), self._out(W)) if self._target else (None, None)
             out = dict(logpost=lp, loglike=ll, log_accept=self._out(W), accepted=i32(W), depth=i32(W), n_leapfrog=i32(W), diverged=i32(W), n_active=i32(1))
         self._check(self.lib.octo_draws_nuts_device(self._h, int(seed), int(step), int(chain0), W, ld, theta_t.data_ptr(), ptr(be), ptr(eps_w),
                                                     0.0 if per_chain else float(eps), ptr(im), int(max_depth), int(n_rounds), 1 if resume else 0,
@@ -392,7 +454,7 @@ class PriorDraws(companion.Handle):
         be = device_vector(beta, W, dev, "beta")
         if out is None:
             i32 = lambda n: self._out(n, dtype=torch.int32)      # noqa: E731
-            lp, ll = (self._out(W), self._out(W)) if self.model is not None else (None, None)
+            lp, ll = (self._out(W), self._out(W)) if self._target else (None, None)
             out = dict(logpost=lp, loglike=ll, n_eval=i32(W), n_expand=i32(W), n_shrink=i32(W), n_stuck=i32(W), status=i32(W), n_active=i32(1))
         self._check(self.lib.octo_draws_slice_device(self._h, int(seed), int(step), int(chain0), W, ld, theta_t.data_ptr(), ptr(be), ptr(width),
                                                      0.0 if per_coordinate else float(w), int(p), int(n_passes), int(max_shrink), int(n_rounds), 1 if resume else 0,

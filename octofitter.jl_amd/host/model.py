@@ -18,7 +18,7 @@ import math
 
 import numpy as np
 
-from . import capi
+from . import capi, derived
 from .observations import normalizename
 from .priors import Prior, UniformCircular, θ_at_epoch_to_tperi
 from .system import BatchedLnLike, System, _BASIS, el_keys
@@ -48,8 +48,18 @@ class LogDensityModel:
         θex = dict(planets={pl.name: {k: 0.0 for k in (pl.variables or {})} for pl in system.planets})
         self.ln_like = BatchedLnLike(system, θex, device=device, consts=consts)
         fn = self.ln_like
+        self._m, self.program, self._pd = None, None, None
+        blocks = [sysvars] + [getattr(o, "variables", None) or {} for o in system.observations]
+        for pl in system.planets:
+            blocks += [pl.variables or {}] + [getattr(o, "variables", None) or {} for o in pl.observations]
+        has_derived = any(isinstance(v, derived.Derived) for b in blocks for v in b.values())
         try:
-            self._build(system, fn, sysvars)
+            if has_derived:
+                if consts is not None:
+                    raise NotImplementedError("a model with Derived variables uses the library's default constants (octo_consts_default)")
+                self._build_program(system, fn, sysvars)
+            else:
+                self._build(system, fn, sysvars)
         except Exception:
             fn.close()      # a model the library (or this classifier) refuses must not leak the context and dataset created for it
             raise
@@ -119,6 +129,96 @@ class LogDensityModel:
         self._m = C.c_void_p()
         fn._check(lib.octo_model_create(fn._ctx, fn._ds, pr, self.D, es, ns if nsrc else None, C.byref(self._m)), "octo_model_create")
 
+    def _build_program(self, system, fn, sysvars):
+        """A system with a Derived variable: no octo_model; the kernel inputs as an expression program (host/derived.py) that PriorDraws sets
+        on its handle. UniformCircular and θ_at_epoch_to_tperi are expanded here: an ATAN2 node (times domain/2π), the UnitLengthPrior term
+        in primitives, and a TPERI binding."""
+        prog = derived.Program(self.D)
+        self.derived_names, self.derived_nodes = [], []
+        angle = {}      # (scope, varname) of a UniformCircular -> its unscaled angle
+
+        def namespace(scope, prefix, block, sys_ns):
+            ns = derived.Namespace(prefix.rstrip("_") or "system")
+            for name, spec in block.items():
+                if isinstance(spec, Prior):
+                    ns._set(name, derived.theta(self._index[scope + (name,)]))
+                elif isinstance(spec, UniformCircular):
+                    ix, iy, dom = self._circ[scope + (name,)]
+                    x, y = derived.theta(ix), derived.theta(iy)
+                    angle[scope + (name,)] = ang = derived.atan(y, x)
+                    ns._set(name, ang * (dom * (1.0 / (2 * math.pi))))      # variables.jl:284
+                    prog.node(ns[name])
+                    prog.term(derived.unit_length(x, y))
+                elif isinstance(spec, derived.Derived):
+                    ns._set(name, spec.trace(ns, sys_ns if sys_ns is not None else ns))
+                    self.derived_names.append(prefix + name)
+                    self.derived_nodes.append(prog.node(ns[name]))
+                elif isinstance(spec, (int, float)):
+                    ns._set(name, derived.Sym.of(float(spec)))
+            return ns
+
+        sys_ns = namespace(("sys",), "", sysvars, None)
+        obs_ns = {id(obs): namespace(("sysobs", id(obs)), normalizename(obs.likelihoodname()) + "_", getattr(obs, "variables", None) or {}, sys_ns)
+                  for obs in system.observations}
+        pl_ns = {}
+        for pl in system.planets:
+            pl_ns[pl.name] = namespace(("pl", pl.name), pl.name + "_", pl.variables or {}, sys_ns)
+            for obs in pl.observations:
+                obs_ns[id(obs)] = namespace(("plobs", pl.name, id(obs)), f"{pl.name}_{normalizename(obs.likelihoodname())}_",
+                                            getattr(obs, "variables", None) or {}, sys_ns)
+        const = lambda v: (derived.BIND_NODE, prog.node(derived.Sym.of(float(v))), 0.0)      # noqa: E731
+        binds = []
+        for pl in system.planets:
+            pv, ns = pl.variables or {}, pl_ns[pl.name]
+            radvel, kep = _BASIS[pl.basis] == capi.ORBIT_RADVEL, _BASIS[pl.basis] == capi.ORBIT_KEP
+            for k, keys in enumerate(el_keys(pl.basis)):
+                hit = next(((pv, ns, ("pl", pl.name), key) for key in keys if key in pv), None) or \
+                    next(((sysvars, sys_ns, ("sys",), key) for key in keys if key in sysvars), None)
+                if hit is None:
+                    if k == capi.EL_MASS or (radvel and k in (capi.EL_I, capi.EL_O, capi.EL_PLX)) or (kep and k == capi.EL_PLX):
+                        binds.append(const(0.0))
+                        continue
+                    raise KeyError(f"planet {pl.name}: missing orbital element {keys[0]}")
+                block, bns, scope, key = hit
+                spec = block[key]
+                if isinstance(spec, θ_at_epoch_to_tperi):
+                    if scope + (spec.θ,) not in angle:
+                        raise KeyError(f"θ_at_epoch_to_tperi: `{spec.θ}` must be a UniformCircular variable of the same block")
+                    if self._circ[scope + (spec.θ,)][2] != 2 * math.pi:
+                        raise ValueError("θ_at_epoch_to_tperi expects θ ~ UniformCircular() (domain 2π)")
+                    ti = derived.BIND_FLAG_TI if _BASIS[pl.basis] == capi.ORBIT_THIELE_INNES else 0
+                    binds.append((derived.BIND_TPERI | ti, prog.node(angle[scope + (spec.θ,)]), spec.theta_epoch))
+                else:
+                    binds.append((derived.BIND_NODE, prog.node(bns[key]), 0.0))
+        for obs, ip, plname, key in fn.obs_entries:
+            ov, ns = getattr(obs, "variables", None) or {}, obs_ns[id(obs)]
+            if obs.kind == capi.HGCA:
+                for nm in ("pmra", "pmdec"):
+                    if nm not in sysvars:
+                        raise KeyError(f"HGCAInstantaneousObs requires the system variable `{nm}`")
+                    binds.append((derived.BIND_NODE, prog.node(sys_ns[nm]), 0.0))
+                binds.append(const(0.0))
+                continue
+            if obs.kind in capi.ASTROM_KINDS:
+                rows = (("jitter", 0.0), ("platescale", 1.0), ("northangle", 0.0))
+            else:
+                rows = (("offset", 0.0), ("jitter", 0.0), (getattr(obs, "trend_coef", None), 0.0))
+            for nm, dv in rows:
+                binds.append((derived.BIND_NODE, prog.node(ns[nm]), 0.0) if nm is not None and nm in ov else const(dv))
+        self.program, self._binds = prog, binds
+        pr = (capi.OctoPrior * self.D)()
+        for k, p in enumerate(self.priors):
+            pr[k].kind = p.kind
+            pr[k].p0, pr[k].p1, pr[k].lo, pr[k].hi = p.c_params()
+        self._c_priors = pr
+
+    def _handle(self):
+        """The PriorDraws handle a program model evaluates its callbacks through, made on first use."""
+        if self._pd is None:
+            from .draws import PriorDraws
+            self._pd = PriorDraws(self)
+        return self._pd
+
     # ------------------------------------------------------------------------------------------------ construction
     def _add_block(self, scope, prefix, block):
         for name, spec in block.items():
@@ -162,6 +262,13 @@ class LogDensityModel:
         single = θ_t.ndim == 1
         th = np.ascontiguousarray(θ_t.reshape(self.D, -1))
         W = th.shape[1]
+        if self.program is not None:
+            import torch
+            pd = self._handle()
+            lp, g = (t.cpu().numpy() if t is not None else None for t in pd.program_logpost(torch.as_tensor(th, device=pd.device), grad=grad))
+            if single:
+                return (lp[0], g[:, 0]) if grad else lp[0]
+            return (lp, g) if grad else lp
         lp = np.empty(W)
         g = np.empty_like(th) if grad else None
         fn._check(fn.lib.octo_model_logpost(fn._ctx, self._m, capi._dptr(th), W, W, capi._dptr(lp), capi._dptr(g)), "octo_model_logpost")
@@ -194,6 +301,8 @@ class LogDensityModel:
     def logpost_device(self, θ_t_tensor, grad=True, stream=None):
         """θ_t_tensor: torch float64 CUDA [D, W]. Returns (lp, grad) tensors; asynchronous."""
         import torch
+        if self.program is not None:
+            return self._handle().program_logpost(θ_t_tensor, grad=grad, stream=stream)
         fn = self.ln_like
         W = θ_t_tensor.shape[1]
         lp = torch.empty(W, dtype=torch.float64, device=θ_t_tensor.device)
@@ -224,6 +333,14 @@ class LogDensityModel:
         W = θ.shape[1]
         fn = self.ln_like
         n_el = fn.n_planets * capi.N_EL
+        if self.program is not None:
+            vals = self.program.evaluate(θ)
+            inputs = np.stack([vals[n] for _k, n, _v in self._binds])
+            for k, (kind, n, epoch) in enumerate(self._binds):
+                if kind & 0xFFFF == derived.BIND_TPERI:
+                    e_ = inputs[k - capi.EL_TP:k - capi.EL_TP + capi.N_EL]
+                    inputs[k] = _tperi(vals[n], epoch, e_[capi.EL_M], e_[capi.EL_E], e_[capi.EL_A], e_[capi.EL_I], e_[capi.EL_W], e_[capi.EL_O])
+            return inputs[:n_el], (inputs[n_el:] if len(self._binds) > n_el else None)
 
         def resolve(src, elems, p):
             kind, i0, i1, _flag, val = src
@@ -248,6 +365,9 @@ class LogDensityModel:
         return elems, nuis
 
     def close(self):
+        if getattr(self, "_pd", None) is not None:
+            self._pd.close()
+            self._pd = None
         if getattr(self, "_m", None):
             self.ln_like.lib.octo_model_destroy(self._m)
             self._m = None

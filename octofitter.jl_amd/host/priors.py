@@ -8,7 +8,8 @@ Host-side mirror of the reference's variable blocks for the STANDARD parameteris
 mirrors `@variables begin … end` (src/macros.jl) for the building blocks every reference test model uses:
 priors `~` (Uniform, LogUniform, Normal, truncated Normal, Sine, UniformCircular — src/variables.jl:279-299) and the
 derived `tp = θ_at_epoch_to_tperi(θ, epoch; M, e, a, i, ω, Ω)` (src/parameterizations.jl:6-69), plus constants.
-Arbitrary `Derived` Julia expressions are out of scope (they stay on the host in the reference).
+Deterministic `=` lines are `Derived(fn)` specs (host/derived.py): traced arithmetic on the variables declared before them, lowered to an
+expression program that the device interprets (include/octofitter_hip_draws.h, "Derived variables").
 
 The NumPy methods here (sample / link / invlink) are host conveniences of the mirror — `model.sample_priors`,
 `model.link` in the reference (src/logdensitymodel.jl:18-24); the hot path (invlink + log-prior + likelihood +
@@ -161,10 +162,11 @@ class θ_at_epoch_to_tperi:
 
 
 def variables(**kw) -> "OrderedDict":
-    """An ordered variable block: name -> Prior | UniformCircular | θ_at_epoch_to_tperi | number (constant)."""
+    """An ordered variable block: name -> Prior | UniformCircular | θ_at_epoch_to_tperi | Derived | number (constant)."""
+    from .derived import Derived
     out = OrderedDict()
     for k, v in kw.items():
-        if not isinstance(v, (Prior, UniformCircular, θ_at_epoch_to_tperi, int, float)):
+        if not isinstance(v, (Prior, UniformCircular, θ_at_epoch_to_tperi, Derived, int, float)):
             raise TypeError(f"variable {k}: {type(v).__name__} is not a standard-parameterisation building block")
         out[k] = v
     return out
