@@ -240,6 +240,8 @@ int get_tasks(octo_ctx* ctx, const octo_dataset* ds, int64_t key, TaskTable** ou
                 // … and the table's common step where ALL its steps agree to 1e-7 relative (the extrapolated gap of kepler_warm_newton scales with the step
                 // cubed: 1e-7 moves it by under 1e-10 of itself), else 0: a table with one odd step keeps the warm loop it had in every task
                 t.dm_uniform = (even && std::isfinite(km) && km > 0.0) ? f : 0.0f;
+                // … and the step itself where the table is EXACTLY even (octo_dataset_create: h_dm_exact): the Newton-only loop's variant without ΔM and t − tp in the row
+                t.dm_exact = t.dm_uniform > 0.0f ? ds->h_dm_exact[o] : 0.0;
             }
             tt.h_tasks.push_back(t);
             double a = 0.0, b = 0.0;
@@ -528,6 +530,7 @@ int32_t octo_ctx_create(octo_ctx** out, int32_t device_id) {
     if (const char* ev = std::getenv("OCTO_FIN_FUSED")) ctx->env_no_fin_fused = std::atoi(ev) ? 0 : 1;
     if (const char* ev = std::getenv("OCTO_WARM")) { ctx->env_warm = std::atoi(ev); ctx->opt_warm = ctx->env_warm ? 1 : 0; }
     if (const char* ev = std::getenv("OCTO_WARM_NEWTON")) ctx->env_warm_newton = std::atoi(ev) ? 1 : 0;
+    if (const char* ev = std::getenv("OCTO_WARM_EVEN")) ctx->env_warm_even = std::atoi(ev) <= 0 ? 0 : (std::atoi(ev) == 1 ? 1 : 2);
     if (const char* ev = std::getenv("OCTO_WARM_NEWTON_MID")) ctx->env_warm_newton_mid = std::atoi(ev) ? 1 : 0;
     if (const char* ev = std::getenv("OCTO_TILE_SORT")) ctx->tile_mode = std::min(std::max(std::atoi(ev), 0), 2);      // experiments: the default of OCTO_OPT_TILE_SORT
     if (const char* ev = std::getenv("OCTO_TILE_MIN_W")) ctx->tile_min_w = std::max<int64_t>(std::atoll(ev), 64);
@@ -641,7 +644,7 @@ int32_t octo_dataset_create(octo_ctx* ctx, const octo_obs_desc* obs, int32_t n_o
     ds->serial = g_dataset_serial.fetch_add(1);
     for (int p = 0; p < n_planets; ++p) ds->planets[p] = planets[p];
     auto bail = [&](int code, const std::string& msg) { octo_dataset_destroy(ds); return fail(ctx, code, msg); };
-    ds->h_obs.resize(n_obs); ds->h_rowconst_pre.resize(n_obs); ds->h_rowconst_raw.resize(n_obs); ds->h_step.resize(n_obs);
+    ds->h_obs.resize(n_obs); ds->h_rowconst_pre.resize(n_obs); ds->h_rowconst_raw.resize(n_obs); ds->h_step.resize(n_obs); ds->h_dm_exact.assign(n_obs, 0.0);
     for (int o = 0; o < n_obs; ++o) {
         const octo_obs_desc& d = obs[o];
         if (d.kind < 0 || d.kind >= OCTO_N_KINDS) return bail(OCTO_EINVAL, "octo_dataset_create: unknown observation kind");
@@ -750,11 +753,20 @@ int32_t octo_dataset_create(octo_ctx* ctx, const octo_obs_desc* obs, int32_t n_o
         // warm-started row loop multiplies by 1/P (octo_device.h: KWarm). Slot 7: the row's warm KEY — |that step|, or +Inf where the row must
         // start cold whatever the wave's bound is: row 0, every WARM_RESTART-th row (the chain of warm rows never sees E or M as numbers, so its
         // rounding accumulates until the next cold row: this bounds the chain whatever chunk the planner picks), a non-finite step.
-        double dm_max = 0.0;
+        // Task::dm_exact: every epoch difference, row 0 aside, is EXACT in FP64 (the error term of the subtraction is zero: always so for neighbours within a factor
+        // of two of each other, Sterbenz) and has the same bit pattern, positive — the epochs are then t_last − k·h exactly — and so has slot 6.
+        double dm_max = 0.0, dm_exact = 0.0;
+        bool exact = n > 1;
         std::vector<double> steps;
         steps.reserve((size_t)std::max<int64_t>(n, 1));
         for (int64_t r = 0; r < n; ++r) {
             const double dm = r > 0 ? TWO_PI * (d.epoch[r] - d.epoch[r - 1]) : 0.0;
+            if (r > 0) {
+                const double ta = d.epoch[r], tb = d.epoch[r - 1], h = ta - tb, h1 = d.epoch[1] - d.epoch[0];
+                const double bb = h - ta, err = (ta - (h - bb)) + (-tb - bb);     // TwoSum's error term of ta + (−tb)
+                if (r == 1) dm_exact = dm;
+                exact = exact && std::isfinite(dm) && h > 0.0 && err == 0.0 && std::memcmp(&h, &h1, sizeof(double)) == 0 && std::memcmp(&dm, &dm_exact, sizeof(double)) == 0;
+            }
             double key = std::fabs(dm);
             if (r > 0) { dm_max = std::max(dm_max, key); steps.push_back(key); }
             ds->h_step[o][r] = std::isfinite(key) ? key : INFINITY;
@@ -762,6 +774,7 @@ int32_t octo_dataset_create(octo_ctx* ctx, const octo_obs_desc* obs, int32_t n_o
             raw[(size_t)r * ROW_STRIDE + 6] = pre[(size_t)r * ROW_STRIDE + 6] = dm;
             raw[(size_t)r * ROW_STRIDE + 7] = pre[(size_t)r * ROW_STRIDE + 7] = key;
         }
+        ds->h_dm_exact[o] = exact ? dm_exact : 0.0;
         DevObs& h = ds->h_obs[o];
         h.kind = d.kind; h.planet = planet_obs ? d.planet : -1; h.has_cor = d.cor ? 1 : 0; h.dm_max = ctx->env_warm ? (float)(dm_max * 1.000001) : 0.0f; h.n = n;
         // The ladder of candidate bounds (DevObs::dm_ladder), preferred first: the 97 % quantile of the steps (the largest 3 % of a table's gaps
@@ -855,7 +868,7 @@ static int eval_impl(octo_ctx* ctx, const octo_dataset* ds, const double* d_elem
     a.n_obs = ds->n_obs; a.n_planets = ds->n_planets;
     for (int p = 0; p < ds->n_planets; ++p) { a.orbit_kind[p] = ds->planets[p].orbit_kind; a.has_mass[p] = ds->planets[p].has_mass; }
     a.elems = d_elems; a.nuis = d_nuis; a.ld = ld; a.W = W;
-    a.warm = (ctx->opt_warm && !ctx->opt_invariant) ? (1 | (ctx->env_warm_newton ? 2 : 0) | (ctx->env_warm_newton_mid ? 4 : 0)) : 0;
+    a.warm = (ctx->opt_warm && !ctx->opt_invariant) ? (1 | (ctx->env_warm_newton ? 2 : 0) | (ctx->env_warm_newton_mid ? 4 : 0) | (ctx->env_warm_even >= 1 ? 8 : 0) | (ctx->env_warm_even >= 2 ? 16 : 0)) : 0;
     a.ws_in = a.ws_out = 1;
     if (ctx->stage_ws_in > 0) { a.ws_in = ctx->stage_ws_in; a.ws_out = ctx->stage_ws_out; }      // octo_eval's walker-major staging (k_small only)
     a.wc = ctx->d_wc; a.valid = ctx->d_valid; a.ldw = ctx->cap_w; a.sctab = ctx->d_sctab;

@@ -585,14 +585,19 @@ __device__ __forceinline__ void warm_newton_init(KWarmNewton& wn, float e, bool 
 // slot of c₃, which falls out — slot (3 − PH) & 3, c₀ of phase PH + 1 — and nothing is shifted (the shift was two to four v_mov_b32 per row, at the
 // loop's back edge and exits). The caller steps PH by one per row, whatever arm the row took. Depth 3 keeps the shift and ignores PH.
 // pin: KT[17] and KT[19] in VGPRs for the whole loop (WarmPin).
-template <int INV_NR, int PH = 0>
+// HOIST (an exactly even table: Task::dm_exact): `dm` is the lane's ΔM = dm·(1/P) itself, formed once ahead of the loop from the operands the row would use —
+// the step's bit pattern is the same in every row, so the product is too, and no output bit moves.
+// NODT (the same tables): the row does not form t − tp; only the cold arm needs it (its own subtraction, the same operands), and KSol::dt is left 0 — the
+// caller's ∂/∂tp sum does without it (octo_kernels.h: astrom_row<…, WEVEN>).
+template <int INV_NR, int PH = 0, bool HOIST = false, bool NODT = false>
 __device__ __forceinline__ KSol kepler_warm_newton(double t, const PC& pc, const SinCosTab& tab, KWarm& st, KWarmNewton& wn, double thr, double dm, const WarmPin& pin) {
     static_assert(INV_NR == 1, "kepler_warm_newton: 1/(1 − e cos E) one Newton step from the reciprocal of f1 (the adjoints' bar)");
     static_assert(PH >= 0 && PH < 4, "kepler_warm_newton: four phases");
     constexpr bool RING = WARM_NEWTON_DEPTH == 4;
     constexpr int I0 = RING ? (0 - PH) & 3 : 0, I1 = RING ? (1 - PH) & 3 : 1, I2 = RING ? (2 - PH) & 3 : 2, I3 = (3 - PH) & 3;
     KSol s;
-    s.dt = t - pc.tp;
+    if constexpr (NODT) s.dt = 0.0;
+    else s.dt = t - pc.tp;
     s.E = 0.0;
     const bool apriori = __builtin_amdgcn_ballot_w64(st.invD >= thr) == 0;
     // 1 or 0, selected as BITS on the scalar unit (s_cselect_b32) and multiplied in from the SGPR: a float select went to the vector unit (v_cndmask_b32)
@@ -600,7 +605,9 @@ __device__ __forceinline__ KSol kepler_warm_newton(double t, const PC& pc, const
     float cp;
     if constexpr (WARM_NEWTON_DEPTH == 3) cp = gate * fmaf(3.0f, wn.c[0] - wn.c[1], wn.c[2]);
     else cp = gate * fmaf(4.0f, wn.c[I0] + wn.c[I2], fmaf(-6.0f, wn.c[I1], -wn.c[I3]));
-    const double dM = dm * pc.invP;
+    double dM;
+    if constexpr (HOIST) dM = dm;
+    else dM = dm * pc.invP;
     const double x = dM * st.invD;
     const double z = x * st.invD;
     const double dE = fma(-((pc.he * st.sE) * z), x, x) + (double)cp;
@@ -641,7 +648,10 @@ __device__ __forceinline__ KSol kepler_warm_newton(double t, const PC& pc, const
             kepler_correct<INV_NR, true>(s, pc, 0.0, s1, c1, f0, &d4);
             cn = cp + (float)d4;
         } else {
-            const double uo = s.dt * pc.invP;
+            double dtc;
+            if constexpr (NODT) dtc = t - pc.tp;
+            else dtc = s.dt;
+            const double uo = dtc * pc.invP;
             const double frac = uo - rint(uo);
             const float E1f = markley_starter_f32(frac, pc);
             const double E1 = (double)E1f;

@@ -53,6 +53,7 @@ struct octo_dataset {
     std::vector<DevObs> h_obs;
     std::vector<std::vector<double>> h_rowconst_pre, h_rowconst_raw;   // per obs, per row
     std::vector<std::vector<double>> h_step;                           // per obs, per row: |2π·(t − t of the previous row)| (0 in row 0, +Inf if not finite): Task::key_max
+    std::vector<double> h_dm_exact;                                    // per obs: slot 6 of its records where the table is exactly even (Task::dm_exact), else 0
     DevObs* d_obs = nullptr;
     std::vector<double*> d_bufs;
     octo_planet_desc planets[MAXP];
@@ -118,6 +119,8 @@ struct octo_ctx {
     int64_t env_small_blocks = 0, env_small_min_span = 0, env_stage_bytes = 0, env_chunk = 0, env_rounds = 0, env_rv_cost = 0, env_kind_all = 0, env_mainp_tpb = 0;
     int env_warm = 1;                           // OCTO_WARM=0: experiments and tests — datasets created by this context never take k_main's warm-started row loop (DevObs::dm_max = 0)
     int env_warm_newton = 1;                    // OCTO_WARM_NEWTON=0: evenly sampled tasks keep the warm loop without the Newton-only rows (octo_device.h: kepler_warm_newton) — tests and A/B
+    int env_warm_even = 2;                      // OCTO_WARM_EVEN=0: exactly even tasks (Task::dm_exact) keep the Newton-only loop every evenly sampled task has; 1: they take the
+                                                // hoisted ΔM but keep t − tp and the ∂/∂tp sum's FMA in the row (no output bit moves) — tests and A/B
     int env_warm_newton_mid = 1;                // OCTO_WARM_NEWTON_MID=0: … without the middle arm of those rows (one Halley step between the Newton-only and the fourth-order rows) — tests and A/B
     // ---- options (octo_ctx_set_option; include/octofitter_hip.h: OCTO_OPT_*)
     int opt_warm = 1;                           // OCTO_OPT_WARM_START: 0 = every launch of this context takes k_main's cold row loop

@@ -71,8 +71,11 @@ struct Task {
                                        // covers it — and whose chunk is within WARM_RESTART — takes the warm loop WITHOUT the per-row test
     float dm_uniform;                  // key_max again where every step of the TABLE agrees with every other to 1e-7 relative (an evenly sampled table), else 0: the task may take
                                        // the Newton-only warm loop (octo_device.h: kepler_warm_newton). A routing rule only: no result depends on it
-    int32_t pad[2];
+    double dm_exact;                   // the table's step 2π·Δt (slot 6 of its records) where the table is EXACTLY even — every epoch difference, row 0 aside, exact in FP64
+                                       // and the same bit pattern, hence slot 6 too — else 0: the Newton-only loop may hoist ΔM and sum ∂/∂tp without t − tp (k_main: the
+                                       // loop behind warm_newton_init). 50000 + j is; 50000 + j/3 is even to 1e-16 and is not
 };
+static_assert(sizeof(Task) == 32, "Task: eight dwords, two scalar loads");
 
 struct DevConsts {
     double k_yr, yd, au2m, sec2yr, mas_per_au_per_plx /* rad2as/pc2au */, mjup2msol;
@@ -88,6 +91,8 @@ struct EvalArgs {
     int32_t warm, fin_fused;                    // warm bit 0: k_main may take the warm-started row loop (octo_ctx option OCTO_OPT_WARM_START / _BATCH_INVARIANT);
                                                 // bit 1 (only with bit 0): … and the Newton-only loop on evenly sampled tasks (OCTO_WARM_NEWTON=0 clears it);
                                                 // bit 2: … with its middle arm (OCTO_WARM_NEWTON_MID=0 clears it: τ₂ = 0)
+                                                // bit 3: … and, on exactly even tasks (Task::dm_exact), with ΔM hoisted out of the row (OCTO_WARM_EVEN=0 clears it);
+                                                // bit 4 (only with bit 3): … and the ∂/∂tp sum by prefix, without t − tp in the row (OCTO_WARM_EVEN=1 clears it)
                                                 // fin_fused 1: the launch has ONE task and k_main's blocks finish their own tile (fin_in_main): no partials, no k_finish
     int32_t task0, n_rblocks;                   // first task of this launch (k_main grid.y is relative to it); k_small: blocks per walker that take row tasks
     int32_t orbit_kind[MAXP];
@@ -490,7 +495,10 @@ struct WarmState { KWarm st[P]; double thr[P]; uint32_t key_hi; bool row_ok; War
 // 2 — the same behind a per-row test (ws->row_ok, wave-uniform): a rejected row re-solves the last planet cold and records that solution.
 // WARM 3 (P == 1): the Newton-only warm row (octo_device.h: kepler_warm_newton) with its own state wn; no per-row key test (the unchecked loop's tasks).
 // WPH: that row's phase in the four-row trip. WPIN: the warm row reads two rotation constants from ws->pin (WARM 3 always does).
-template <int P, bool GRAD, bool NUIS, int KM, bool TAB, int WARM = 0, bool WCHECK = true, int WLAST = 0, int WPH = 0, bool WPIN = false>
+// WEVEN (WARM 3, a task with Task::dm_exact): 1 — `dm` is the lane's hoisted ΔM (kepler_warm_newton<…, HOIST>), every output bit the same; 2 — also, the row does not
+// form t − tp: the ∂/∂tp sum Σ Mb·(t − tp) is carried as the running sum of the INCLUSIVE prefixes of Σ Mb (one add in place of the FMA) and converted once behind
+// the loop (even_gt_finish below).
+template <int P, bool GRAD, bool NUIS, int KM, bool TAB, int WARM = 0, bool WCHECK = true, int WLAST = 0, int WPH = 0, bool WPIN = false, int WEVEN = 0>
 __device__ __forceinline__ void astrom_row(AccArr<P, GRAD, NUIS, KM>& acc, LogProd& lp, const PC (&pc)[P],
                                            const AstromCoef<P>& co, double t, double y1, double y2, double c3, double c4, double c5,
                                            const SinCosTab& tab, WarmState<P>* ws = nullptr, double dm = 0.0, KWarmNewton* wn = nullptr) {
@@ -508,7 +516,7 @@ __device__ __forceinline__ void astrom_row(AccArr<P, GRAD, NUIS, KM>& acc, LogPr
     double ra_m, dec_m;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-        if constexpr (WARM == 3) s[p] = kepler_warm_newton<1, WPH>(t, pc[p], tab, ws->st[p], *wn, ws->thr[p], dm, ws->pin);
+        if constexpr (WARM == 3) s[p] = kepler_warm_newton<1, WPH, (WEVEN >= 1), (WEVEN >= 2)>(t, pc[p], tab, ws->st[p], *wn, ws->thr[p], dm, ws->pin);
         else if constexpr (WARM != 0) s[p] = kepler_solve_warm<1, WARM == 1, WPIN>(t, pc[p], tab, ws->st[p], ws->thr[p], dm, WCHECK ? ws->row_ok : true, &ws->pin);
         else if constexpr (WLAST != 0) { if (p == P - 1) s[p] = kepler_warm_step<1>(t, pc[p], ws->st[p], dm); else s[p] = kepler_solve<1, TAB>(t, pc[p], tab); }
         else s[p] = kepler_solve<1, TAB>(t, pc[p], tab);
@@ -661,8 +669,22 @@ __device__ __forceinline__ void astrom_row(AccArr<P, GRAD, NUIS, KM>& acc, LogPr
             const double Mb = fma(ra_f, dra, de_f * dde) * s[p].invD;
             g[L::GE] = fma(Mb, s[p].sE, g[L::GE]);          // ∂E/∂e = sin E/(1 − e cos E); the rest of ē in k_finish
             g[L::GM] += Mb;
-            g[L::GT] = fma(Mb, s[p].dt, g[L::GT]);
+            if constexpr (WEVEN >= 2) g[L::GT] += g[L::GM];
+            else g[L::GT] = fma(Mb, s[p].dt, g[L::GT]);
         }
+    }
+}
+
+// Behind a loop of astrom_row<…, WEVEN = 2> rows (one wave's chunk of an exactly even table, P = 1): the rows' epochs are t_i = t_last − (n − 1 − i)·h exactly, GM = Σ Mb_i
+// and the loop left GG = Σ_i Σ_{k<=i} Mb_k in the GT slot, so Σ_i Mb_i (t_i − tp) = (t_last − tp + h)·GM − h·GG. Rows the loop skipped ran no body and are in neither sum.
+// A chunk of one row has h = 0 (there is no second epoch to take it from) and comes out as (t − tp)·Mb, the row's own product.
+template <int P, bool GRAD, bool NUIS, int KM>
+__device__ __forceinline__ void even_gt_finish(AccArr<P, GRAD, NUIS, KM>& acc, const PC (&pc)[P], double t_last, double h) {
+    using L = Layout<P, GRAD, NUIS, KM>;
+    static_assert(P == 1, "even_gt_finish: the single-planet Newton-only loop");
+    if constexpr (GRAD) {
+        double* g = &acc[L::OFF_PL];
+        g[L::GT] = fma(-h, g[L::GT], ((t_last - pc[0].tp) + h) * g[L::GM]);
     }
 }
 
@@ -991,6 +1013,16 @@ constexpr bool main_warm_newton() {
            (KM == KM_RADEC || KM == (KM_RADEC | KM_COR));
 }
 
+// The Newton-only loop's variant for exactly even tasks (Task::dm_exact; the loop behind warm_newton_init): 0 — none; 1 — ΔM hoisted out of the row (no output bit moves);
+// 2 — and the ∂/∂tp sum without t − tp in the row (the outputs that read that sum move in their last digits). Every kernel that has the Newton-only loop.
+#ifndef OCTO_WARM_EVEN
+#define OCTO_WARM_EVEN 2
+#endif
+template <int P, bool GRAD, bool NUIS, int KM, bool FUSED, int NWV, bool FINF>
+constexpr int main_warm_even() {
+    return main_warm_newton<P, GRAD, NUIS, KM, FUSED, NWV, FINF>() ? OCTO_WARM_EVEN : 0;
+}
+
 // Two rotation constants held in VGPRs over the astrometry branch's warm loops (octo_device.h: WarmPin) — the checked and the unchecked loop and the Newton-only
 // loop: the four-wave single-planet nuisance-free kernels, which have the two register pairs within their occupancy step (config 3's gradient kernel: 84 -> 88
 // VGPRs, five waves either way). Not the eight-wave kernels (held to 80), not k_main<…, FINF>, not P >= 2, and not the nuisance kernels: at the same
@@ -1289,10 +1321,6 @@ static __global__ __launch_bounds__(64 * NWV) void k_main(EvalArgs a) {
                         if (warm_unchecked && (a.warm & 2) != 0 && tk.dm_uniform > 0.0f) {
                             KWarmNewton wn;
                             warm_newton_init(wn, pc[0].ef, (a.warm & 4) != 0);
-                            auto nbody = [&](const RowRegs8& r, auto ph) {
-                                astrom_row<P, GRAD, NUIS, KM, true, 3, false, 0, decltype(ph)::value>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2),
-                                                                                                      row_get(r, 3), row_get(r, 4), row_get(r, 5), tab, &ws, row_get(r, 6), &wn);
-                            };
                             // FOUR rows per trip, one per phase of the history ring (kepler_warm_newton), through the same two SGPR buffers: one prefetch in
                             // flight, waited for behind the loop. The chunk's remainder (n_rows mod 4, or a chunk shorter than four rows) is taken at the FRONT:
                             // the first trip leaves its leading `skip` slots empty (their prefetches read row 0 again), every later trip is whole, and the loop
@@ -1300,19 +1328,50 @@ static __global__ __launch_bounds__(64 * NWV) void k_main(EvalArgs a) {
                             // changes nothing: the history is empty until four rows have been recorded, whichever slot the first of them took.
                             const int skip = (4 - (n_rows & 3)) & 3;
                             auto row_at = [&](int k) { k -= skip; return rows + (int64_t)(k < 0 ? 0 : (k < n_rows ? k : n_rows - 1)) * ROW_STRIDE; };
-                            RowRegs8 A = row_issue8(rows);
-                            for (int j = 0;; j += 4) {
-                                RowRegs8 B = row_wait_issue(A, row_at(j + 1));
-                                if (__builtin_expect(j >= skip, 1)) nbody(A, std::integral_constant<int, 0>{});
-                                A = row_wait_issue(B, row_at(j + 2));
-                                if (__builtin_expect(j + 1 >= skip, 1)) nbody(B, std::integral_constant<int, 1>{});
-                                B = row_wait_issue(A, row_at(j + 3));
-                                if (__builtin_expect(j + 2 >= skip, 1)) nbody(A, std::integral_constant<int, 2>{});
-                                A = row_wait_issue(B, row_at(j + 4));
-                                nbody(B, std::integral_constant<int, 3>{});
-                                if (j + 4 >= n_rows + skip) break;
-                            }
-                            row_drain(A);
+                            // even: 0 — the step from slot 6 of every record, ΔM = dm·(1/P) and t − tp in the row; 1, 2 — an exactly even task (Task::dm_exact): ΔM formed
+                            // HERE from the same two operands, and the records read without slots 6 and 7 (RowRegs, as the cold loop reads them); 2 — the ∂/∂tp sum by
+                            // prefix, converted behind the loop (astrom_row<…, WEVEN>, even_gt_finish)
+                            auto nloop = [&](auto even, auto issue) {
+                                constexpr int EV = decltype(even)::value;
+                                double dmh = 0.0;
+                                if constexpr (EV >= 1) dmh = tk.dm_exact * pc[0].invP;
+                                auto nbody = [&](const auto& r, auto ph) {
+                                    double dm;
+                                    if constexpr (EV >= 1) dm = dmh;
+                                    else dm = row_get(r, 6);
+                                    astrom_row<P, GRAD, NUIS, KM, true, 3, false, 0, decltype(ph)::value, false, EV>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2),
+                                                                                                                     row_get(r, 3), row_get(r, 4), row_get(r, 5), tab, &ws, dm, &wn);
+                                };
+                                auto A = issue(rows);
+                                for (int j = 0;; j += 4) {
+                                    auto B = row_wait_issue(A, row_at(j + 1));
+                                    if (__builtin_expect(j >= skip, 1)) nbody(A, std::integral_constant<int, 0>{});
+                                    A = row_wait_issue(B, row_at(j + 2));
+                                    if (__builtin_expect(j + 1 >= skip, 1)) nbody(B, std::integral_constant<int, 1>{});
+                                    B = row_wait_issue(A, row_at(j + 3));
+                                    if (__builtin_expect(j + 2 >= skip, 1)) nbody(A, std::integral_constant<int, 2>{});
+                                    A = row_wait_issue(B, row_at(j + 4));
+                                    nbody(B, std::integral_constant<int, 3>{});
+                                    if (j + 4 >= n_rows + skip) break;
+                                }
+                                row_drain(A);
+                                if constexpr (EV >= 2 && GRAD) {
+                                    // the wave's last epoch and the table's step, from the records themselves (the differences of an exactly even table are exact)
+                                    const double t_last = rows[(int64_t)(n_rows - 1) * ROW_STRIDE];
+                                    const double h = n_rows > 1 ? t_last - rows[(int64_t)(n_rows - 2) * ROW_STRIDE] : 0.0;
+                                    even_gt_finish<P, GRAD, NUIS, KM>(acc, pc, t_last, h);
+                                }
+                            };
+                            constexpr int WEV = main_warm_even<P, GRAD, NUIS, KM, FUSED, NWV, FINF>();
+                            // (a chunk of at most WARM_NEWTON_DEPTH rows never fills the history: it has no Newton-only row to make cheaper, and the prefix form of the ∂/∂tp
+                            // sum is badly conditioned on a chunk of two rows — tests/even_sum_model.py — so it keeps the rows every evenly sampled task has)
+                            if (WEV != 0 && (a.warm & 8) != 0 && tk.dm_exact != 0.0 && n_rows > WARM_NEWTON_DEPTH) {
+                                // (bit 4 clear: the hoisted ΔM alone. Only a gradient kernel compiles that loop a second time: a forward kernel has no ∂/∂tp sum)
+                                if constexpr (WEV >= 2 && GRAD) {
+                                    if ((a.warm & 16) != 0) nloop(std::integral_constant<int, 2>{}, [](crow_t q) { return row_issue(q); });
+                                    else nloop(std::integral_constant<int, 1>{}, [](crow_t q) { return row_issue(q); });
+                                } else if constexpr (WEV != 0) nloop(std::integral_constant<int, WEV>{}, [](crow_t q) { return row_issue(q); });
+                            } else nloop(std::integral_constant<int, 0>{}, [](crow_t q) { return row_issue8(q); });
                         } else wloop(std::true_type{});
                     }
                 } else if (n_rows > 0) {
