@@ -68,6 +68,13 @@
  * between θ and the kernel inputs, as an expression program that the device interprets forward and reverse in place of octo_model_logpost_device, under
  * every function of the handle that needs ℓπ, stated in full at its declaration (tests/program_reference.py restates it). No random number.
  *
+ * The thirteenth is nested sampling (octo_draws_cube_device … octo_draws_nested_move_device): the unit cube behind the prior draws and the hypercube
+ * transform out of it, the ordered cull of a live set with its evidence bookkeeping, and a constrained-prior slice move in the cube in lockstep rounds,
+ * stated in full at their declaration (tests/nested_reference.py restates them). Its two streams add
+ *   purpose 10: the survivor that seeds dead rank r of iteration `iter`, counter (r, 0, 10, iter), word 0
+ *   purpose 11: uniform number i of update j of live slot c at `iter`, counter (c, j·128 + i, 11, iter), word 0 (words 1 and 2 of i = 0: the interval's
+ *               position and the split of the steps)
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -721,6 +728,90 @@ int32_t octo_draws_program_clear(octo_draws* h);
 int32_t octo_draws_program_logpost_device(octo_draws* h, const double* d_theta_t, int64_t ld, int64_t W, double* d_lp, double* d_grad, void* hip_stream);
 int32_t octo_draws_program_values_device(octo_draws* h, const double* d_theta_t, int64_t ld, int64_t W, const int32_t* nodes, int32_t n, double* d_out,
                                          int64_t ld_out, void* hip_stream);
+
+/* ---- Nested sampling (the thirteenth part; Skilling 2006, "Nested sampling for general Bayesian computation"; the reference's fourth sampler is
+ * dynesty behind a hypercube prior transform, ext/OctofitterDynestyHypercubeTransformExt.jl): K live points in the unit cube (0, 1)^D, the B lowest
+ * likelihoods removed per iteration with their share of the prior volume, and B new points drawn from the prior restricted to ℓ > ℓ* by a
+ * coordinate-wise slice move in the cube (Neal 2003, Fig. 3 and Fig. 5). The likelihood at a point is the rejection driver's: ℓ = ℓπ − ℓprior_t,
+ * non-finite -> −Inf. All on DEVICE buffers, asynchronous on hip_stream: no host synchronisation, no graph capture, no floating-point atomic.
+ *
+ * THE CUBE. octo_draws_cube_device writes u[d][t] (d_u [D][ld], t < n) = the uniform of word d % 4 of counter (first + t, d / 4, 0, 0): the numbers
+ * octo_draws_sample_device feeds to the quantile. octo_draws_from_cube_device is the hypercube transform, every output optional: per coordinate, with
+ * the routines of octo_draws_sample_device in its order, θ = the prior's quantile of u (moved one ulp inside where it rounds onto a bound),
+ * θ_t = link(θ), and ℓprior_t accumulated in declaration order with the healing sentinel. from_cube(cube(seed, first, n)) is byte for byte
+ * octo_draws_sample_device(seed, first, n) in all three outputs. A draw with ANY coordinate not inside (0, 1) — 0, 1, beyond, NaN — has every output
+ * NaN (θ and θ_t in all D coordinates, ℓprior_t). The prior table is the handle's active one (octo_draws_use_reference applies).
+ * OCTO_EINVAL: NULL handle; n < 0, ld < n, n > 2^30; first + n overflowing; NULL d_u with something to do.
+ *
+ * THE CULL. octo_draws_nested_cull_device, one iteration's bookkeeping on K live points, 2 <= K <= OCTO_DRAWS_NESTED_MAX_LIVE.
+ *   Order     the live points ascending by (key, slot index), key = ℓ, or −Inf where ℓ is NaN or −Inf: a total order. Ranks r = 0 … B − 1 are the dead.
+ *   Volume    t_r = 1/(K − r). With logX the state's log volume on entry: logX_r = logX_{r−1} − t_r (logX_{−1} = logX), one subtraction per rank in
+ *             rank order; logwt_r = (key_r + logX_{r−1}) + log(−expm1(−t_r)).
+ *   Evidence  logZ <- logaddexp(logZ, logwt_r) for r = 0 … B − 1 in that order; logaddexp(a, b) = max(a, b) + log1p(exp(−|a − b|)), −Inf when both are.
+ *   State     d_state, 8 doubles in/out: [0] logZ · [1] logX = logX_{B−1} · [2] the floor ℓ* = key of rank B − 1 · [3] ℓmax = key of rank K − 1 (the
+ *             largest live ℓ, before and after the replacement) · [4] the remaining-evidence bound logaddexp(logZ, ℓmax + logX) − logZ, +Inf while
+ *             logZ = −Inf · [5] the number of dead so far · [6], [7] reserved, written 0. The initial state is (−Inf, 0, −Inf, −Inf, +Inf, 0, 0, 0).
+ *   Records   at columns dead_first + r of caller arrays of leading dimension ld_dead (each may be NULL): d_dead_u [D][ld_dead] the u column of rank
+ *             r, d_dead_loglike its key, d_dead_logvol logX_r, d_dead_logwt logwt_r. d_slot[r] = the live slot that held rank r.
+ *   replace = 1 (1 <= B <= K − 1): slot d_slot[r] receives the u column and the ℓ (its bits, not its key) of the survivor of rank
+ *             B + min(K − B − 1, ⌊v_r·(K − B)⌋), v_r = the uniform of word 0 of counter (r, 0, 10, iter). d_width[d] (or NULL) = max − min of
+ *             coordinate d over all K live points as they stood on entry (fmax / fmin: exact, order-free).
+ *   replace = 0 requires B = K: the final flush by the same rule; no seeds, d_width is not written, d_slot holds the whole order.
+ * Nothing is written beyond column K of the live arrays or outside the B dead records. Non-finite inputs never trap. No allocation once the handle's
+ * order array holds K doubles.
+ * OCTO_EINVAL: NULL handle; K out of range; ldK < K; NULL d_u_live, d_loglike_live or d_state; replace not 0 or 1; B out of range for `replace`;
+ * dead_first < 0 or dead_first + B > ld_dead; NULL d_slot.
+ *
+ * THE MOVE. octo_draws_nested_move_device, one constrained-prior transition of the B live slots named by d_slot (distinct), in place in d_u_live and
+ * d_loglike_live, in lockstep ROUNDS as octo_draws_slice_device: a round is one forward log-posterior call at the trial points of all B chains and one
+ * step of every chain's state machine. Chain = slot c = d_slot[w] at iteration `iter`. The floor ℓ* is read from d_state[2] on the device.
+ *   Inside     inside(y) for coordinate d: 0 < y < 1 and ℓ(u with coordinate d replaced by y) > ℓ*. A y not in (0, 1) is outside without an
+ *              evaluation and takes no round.
+ *   Updates    n_passes sweeps over the D coordinates; update j = pass·D + d changes coordinate d alone. x = the coordinate, w_d = d_width[d] or w.
+ *   Uniforms   v_i = word 0 of counter (c, j·128 + i, 11, iter); v′, v″ = words 1 and 2 of the counter of i = 0.
+ *   Interval   L = x − w_d·v′, R = L + w_d.
+ *   Stepping   m = max_steps: J = min(m − 1, ⌊m·v″⌋), Kr = m − 1 − J. While J > 0 and inside(L): L <- L − w_d, J <- J − 1 (n_step counts it). Then
+ *              while Kr > 0 and inside(R): R <- R + w_d, Kr <- Kr − 1. With m = 1 there is no stepping out.
+ *   Clip       L <- max(L, 0), R <- min(R, 1).
+ *   Shrink     for s = 0 … max_shrink − 1: x′ = L + v_{64+s}·(R − L) (n_shrink counts it). If inside(x′) the coordinate becomes x′ and the slot's ℓ
+ *              the ℓ evaluated there; the trial point keeps its transformed value: nothing is evaluated twice. Otherwise x′ < x sets L <- x′, else
+ *              R <- x′ (an x′ that rounded onto 0 or 1 among them, without a round).
+ *   Stuck      after max_shrink proposals the coordinate keeps its value and n_stuck counts it.
+ *   End        after n_passes·D updates the status is DONE; a DONE chain is FROZEN: its outputs and its slot keep their bits for the rest of the
+ *              call and across `resume`.
+ * A trial coordinate reaches θ_t by the hypercube transform's routine; the opening gathers the B columns and transforms all D coordinates of them by
+ * octo_draws_from_cube_device's launches. resume = 0 opens and makes n_rounds rounds; resume = 1 continues with n_rounds more: the same K, ldK, B, ld,
+ * max_steps, n_passes, max_shrink, seed and iter, and the other arguments as that call had and left them. Two calls of a and b rounds give the bits
+ * of one call of a + b. A chain's result depends only on its slot, iter and seed — never on B, ld, its position in d_slot or how the rounds were
+ * cut. No allocation once the handle's work array holds (3·D + 15)·ld doubles.
+ *   d_theta_t  [D][ld]  or NULL: θ_t of the B points as they stand
+ *   d_n_eval, d_n_step, d_n_shrink, d_n_stuck [B]  int32 or NULL: the rounds the chain took part in, the steps out, the proposals, the stuck updates
+ *   d_status   [B]      int32 or NULL: OCTO_DRAWS_NESTED_ACTIVE / _DONE
+ *   d_n_active [1]      int32 or NULL: the chains still ACTIVE after the call
+ * OCTO_EINVAL, each with a message: NULL handle; a handle with neither a model nor a program ("nested sampling needs a likelihood"); K out of range,
+ * ldK < K, NULL d_u_live, d_loglike_live or d_state; B outside 0 … K − 1 or ld < B; w not in (0, 1] with d_width NULL; max_steps outside
+ * 1 … OCTO_DRAWS_NESTED_MAX_STEPS; max_shrink outside 1 … OCTO_DRAWS_NESTED_MAX_SHRINK; n_passes outside 1 … OCTO_DRAWS_NESTED_MAX_PASSES;
+ * n_rounds < 0; a resume that does not match the call before it; NULL d_slot with B > 0. */
+#define OCTO_DRAWS_PURPOSE_NESTED_SEED 10
+#define OCTO_DRAWS_PURPOSE_NESTED_MOVE 11
+#define OCTO_DRAWS_NESTED_MAX_LIVE 4096
+#define OCTO_DRAWS_NESTED_MAX_STEPS 64
+#define OCTO_DRAWS_NESTED_MAX_SHRINK 64
+#define OCTO_DRAWS_NESTED_MAX_PASSES 1024
+#define OCTO_DRAWS_NESTED_ACTIVE 0
+#define OCTO_DRAWS_NESTED_DONE   1
+int32_t octo_draws_cube_device(octo_draws* h, uint64_t seed, uint64_t first, int64_t n, int64_t ld, double* d_u, void* hip_stream);
+int32_t octo_draws_from_cube_device(octo_draws* h, int64_t n, int64_t ld, const double* d_u, double* d_theta, double* d_theta_t, double* d_logprior_t,
+                                    void* hip_stream);
+int32_t octo_draws_nested_cull_device(octo_draws* h, uint64_t seed, uint64_t iter, int32_t K, int64_t ldK, double* d_u_live, double* d_loglike_live,
+                                      double* d_state, int32_t B, int32_t replace, int64_t dead_first, int64_t ld_dead, double* d_dead_u,
+                                      double* d_dead_loglike, double* d_dead_logvol, double* d_dead_logwt, int32_t* d_slot, double* d_width,
+                                      void* hip_stream);
+int32_t octo_draws_nested_move_device(octo_draws* h, uint64_t seed, uint64_t iter, int32_t K, int64_t ldK, double* d_u_live, double* d_loglike_live,
+                                      const double* d_state, int64_t B, int64_t ld, const int32_t* d_slot, const double* d_width, double w,
+                                      int32_t max_steps, int32_t n_passes, int32_t max_shrink, int32_t n_rounds, int32_t resume, double* d_theta_t,
+                                      int32_t* d_n_eval, int32_t* d_n_step, int32_t* d_n_shrink, int32_t* d_n_stuck, int32_t* d_status,
+                                      int32_t* d_n_active, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -31,17 +31,6 @@ __device__ __forceinline__ double rejection_uniform(uint64_t seed, uint64_t i) {
     return u01(r[0]);
 }
 
-struct DrawArgs {
-    const octo_prior* priors;      // [D]
-    const double* pc;              // [D][PRIOR_NC] constants of prior_density_lanes
-    const double* ic;              // [D][IC_N] constants of prior_quantile
-    const uint64_t* idx;           // [n] draw indices, or null: first + t
-    uint64_t seed, first;
-    int64_t n, ld;
-    int32_t D, d0;                 // this launch: coordinates d0 … d0 + 3 (d0 a multiple of 4)
-    double* theta; double* theta_t; double* lpt;
-};
-
 // One launch = one Philox block of four coordinates [d0, d0 + 4) ∩ [0, D); the host walks the blocks (launch_draw). A loop over the coordinates
 // INSIDE the kernel was tried first: the compiler hoists the ~230 polynomial coefficients of normcdfinv / exp / log / log1p / acos out of it into
 // registers (480 VGPRs + AGPRs, one wave per SIMD; held to 128 it spilled 348 of them). Without a loop there is nothing to hoist them out of.
@@ -51,33 +40,10 @@ __global__ __launch_bounds__(TPB) void k_draw(DrawArgs a) {
     const bool live = t < a.n;                        // no early exit: prior_density_lanes votes across the wave
     const int64_t tl = live ? t : a.n - 1;
     const uint64_t i = a.idx ? a.idx[tl] : a.first + (uint64_t)tl;
-    const bool want_t = a.theta_t != nullptr || a.lpt != nullptr;
-    double lp = 0.0;
-    bool healed = false;
-    if (a.lpt && a.d0 > 0) { lp = a.lpt[tl]; healed = lp == HEALED; }
     uint64_t r[4];
     philox4x64(a.seed, KEY1, i, (uint64_t)(a.d0 >> 2), OCTO_DRAWS_PURPOSE_PRIOR, 0, r);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int d = a.d0 + q;
-        if (d >= a.D) break;
-        const octo_prior pr = a.priors[d];
-        const PriorBounds B = prior_bounds(pr);
-        const double x = prior_quantile(pr, B, a.ic + IC_N * d, u01(r[q]));
-        if (a.theta && live) a.theta[(int64_t)d * a.ld + t] = x;
-        if (!want_t) continue;
-        const double y = prior_link_forward(B, x);
-        if (a.theta_t && live) a.theta_t[(int64_t)d * a.ld + t] = y;
-        if (a.lpt) {
-            // what the model callback does with this θ_t: x' = invlink(y), logpdf_with_trans at x', the healing rule (k_model_fwd)
-            double xv, xd, pv, pd;
-            prior_link_lanes(pr, y, xv, xd);
-            prior_density_lanes(pr, xv, xd, pv, pd, a.pc + PRIOR_NC * d);
-            healed = healed || !isfinite(pv);
-            lp += pv;
-        }
-    }
-    if (a.lpt && live) a.lpt[t] = healed ? HEALED : lp;
+    const double u[4] = {u01(r[0]), u01(r[1]), u01(r[2]), u01(r[3])};
+    draw_block(a, t, tl, live, u, false);      // octo_draws_common.h: shared with the hypercube transform
 }
 
 // ---- selection ---------------------------------------------------------------------------------------------------------------------------
@@ -338,7 +304,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
         }
         if (release) (void)hipStreamDestroy(h->stream);
     }
-    for (void* p : std::initializer_list<void*>{h->own_priors, h->own_pc, h->own_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice, h->d_prog, h->d_prog_tab})
+    for (void* p : std::initializer_list<void*>{h->own_priors, h->own_pc, h->own_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice, h->d_prog, h->d_prog_tab, h->d_ncull, h->d_nest})
         (void)hipFree(p);
     delete h;
     return OCTO_OK;

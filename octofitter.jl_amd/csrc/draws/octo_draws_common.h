@@ -12,6 +12,8 @@
 // on its paths), octo_draws_adapt.hip (the warm-up statistics of the explorer), octo_draws_diag.hip (the convergence diagnostics of stored draws) and
 // octo_draws_pt.hip (the tempering statistics between the scans, which take wave_sum and waves_total). Everything but the handle lives in an unnamed namespace,
 // one copy per unit. How the handle's work allocations are cut into their parts is octo_draws_layout.h.
+// The thirteenth part of the library, nested sampling (octo_draws_nested.hip), takes DrawArgs, cube_link and draw_block (what k_draw does after its Philox
+// call) beside the samplers' head, preamble, target and round driver.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
 
@@ -89,6 +91,55 @@ __device__ __forceinline__ double prior_link_forward(const PriorBounds& B, doubl
     if (B.fa) return log(x - B.a);
     if (B.fb) return log(B.b - x);
     return x;
+}
+
+// ---- a draw from its uniforms: what k_draw does after its Philox call, and the hypercube transform of nested sampling (octo_draws_nested.hip)
+struct DrawArgs {
+    const octo_prior* priors;      // [D]
+    const double* pc;              // [D][PRIOR_NC] constants of prior_density_lanes
+    const double* ic;              // [D][IC_N] constants of prior_quantile
+    const uint64_t* idx;           // [n] draw indices, or null: first + t
+    uint64_t seed, first;
+    int64_t n, ld;
+    int32_t D, d0;                 // this launch: coordinates d0 … d0 + 3 (d0 a multiple of 4)
+    double* theta; double* theta_t; double* lpt;
+};
+
+// θ = the quantile of u (one ulp inside a bound it rounds onto) and θ_t = its link: the one routine that takes a cube coordinate to θ_t
+__device__ __forceinline__ double cube_link(const octo_prior& pr, const PriorBounds& B, const double* __restrict__ ic, double u, double& x) {
+    x = prior_quantile(pr, B, ic, u);
+    return prior_link_forward(B, x);
+}
+
+// Coordinates [d0, d0 + 4) ∩ [0, D) of draw t from their uniforms u: quantile -> link -> density, logprior_t carried through a.lpt from launch to
+// launch in declaration order with the healing sentinel. Every lane of a wave calls it (prior_density_lanes votes), a lane beyond the batch as
+// tl = the last draw. bad: the draw's outputs are NaN (a cube point outside (0, 1); its u are then read as ½) — k_draw passes false.
+__device__ __forceinline__ void draw_block(const DrawArgs& a, int64_t t, int64_t tl, bool live, const double (&u)[4], bool bad) {
+    const bool want_t = a.theta_t != nullptr || a.lpt != nullptr;
+    double lp = 0.0;
+    bool healed = false;
+    if (a.lpt && a.d0 > 0) { lp = a.lpt[tl]; healed = lp == HEALED; }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int d = a.d0 + q;
+        if (d >= a.D) break;
+        const octo_prior pr = a.priors[d];
+        const PriorBounds B = prior_bounds(pr);
+        const double x = prior_quantile(pr, B, a.ic + IC_N * d, u[q]);
+        if (a.theta && live) a.theta[(int64_t)d * a.ld + t] = bad ? NAN : x;
+        if (!want_t) continue;
+        const double y = prior_link_forward(B, x);
+        if (a.theta_t && live) a.theta_t[(int64_t)d * a.ld + t] = bad ? NAN : y;
+        if (a.lpt) {
+            // what the model callback does with this θ_t: x' = invlink(y), logpdf_with_trans at x', the healing rule (k_model_fwd)
+            double xv, xd, pv, pd;
+            prior_link_lanes(pr, y, xv, xd);
+            prior_density_lanes(pr, xv, xd, pv, pd, a.pc + PRIOR_NC * d);
+            healed = healed || !isfinite(pv);
+            lp += pv;
+        }
+    }
+    if (a.lpt && live) a.lpt[t] = bad ? NAN : (healed ? HEALED : lp);
 }
 
 // ---- the cross-chain sums of the warm-up statistics, the diagnostics and the tempering statistics (octo_draws_adapt.hip, _diag.hip, _pt.hip)
@@ -245,6 +296,12 @@ struct octo_draws : CompanionBase {
     int32_t prog_n_ops = 0, prog_n_in = 0, prog_n_el = 0, prog_n_terms = 0, prog_planets = 0;
     double prog_k_yr = 0.0;
     double* d_prog = nullptr; int64_t cap_prog = 0;
+    // nested sampling (octo_draws_nested.hip), grown on demand: the order of a cull, and the state machines of a move in one allocation with the
+    // transition it was opened for (nest_passes = 0: nothing to resume)
+    double* d_ncull = nullptr; int64_t cap_ncull = 0;
+    double* d_nest = nullptr; int64_t cap_nest = 0;
+    int64_t nest_B = 0, nest_ld = 0, nest_ldK = 0; int32_t nest_K = 0, nest_passes = 0, nest_steps = 0, nest_shrink = 0;
+    uint64_t nest_seed = 0, nest_iter = 0;
 };
 
 namespace {

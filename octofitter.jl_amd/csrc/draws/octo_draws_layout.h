@@ -116,6 +116,26 @@ inline SliceWork slice_work(Carve& c, int64_t D, int64_t ld) {
             c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld)};
 }
 
+// The state machines of one constrained-prior move of nested sampling (octo_draws_nested.hip), d_nest: (3·D + 15)·ld. The kernels take it by value
+// (NestedArgs): its members and their order are their argument layout.
+struct NestedWork {
+    double *trial, *gpr, *u;                     // [D][ld] θ_t of the point of the next log-posterior call · ∇ℓprior_t (target_at's, not read) · the gathered cube columns (the opening's)
+    double *lp, *L, *R, *xp, *keep;              // [ld] ℓπ at the point of a launch · the interval of the update · the proposal x′ · θ_t of the coordinate as it stands
+    int32_t *status, *j, *phase, *s, *J, *Kr;    // [ld] OCTO_DRAWS_NESTED_* · the update number · what the launch's evaluation is · the shrink number · the steps left on either side
+    int32_t *n_eval, *n_step, *n_shrink, *n_stuck;      // [ld] the counts
+};
+inline NestedWork nested_work(Carve& c, int64_t D, int64_t ld) {
+    const int64_t plane = D * ld;
+    return {c.take(plane), c.take(plane), c.take(plane),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld),
+            c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld)};
+}
+
+// The order of one cull of nested sampling, d_ncull: K. order[r] = the live slot of rank r, ascending by (ℓ, slot).
+struct NestedCull { int32_t* order; };      // [K]
+inline NestedCull nested_cull(Carve& c, int64_t K) { return {c.take<int32_t>(K)}; }
+
 // The block partials of the grouped moments (octo_draws_adapt.hip), d_mom: nblk·G·(2K + 1). Per block of 256 chains and group: the number
 // of chains it holds · per row their sum and Σ(x − the block's mean)². sum and m2 of a (block, group) with cnt = 0 are never written or read.
 struct MomentsPartials { double *cnt, *sum, *m2; };      // [nblk][G] · [nblk][G][K] · [nblk][G][K]

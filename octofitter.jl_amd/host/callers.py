@@ -26,6 +26,10 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   L-BFGS iterate, the one with the best ELBO kept per path, draws from every path's fit, and PSIS importance resampling of their union
   (host/psis.py: Psis.loo on one row). Only the resampling is on the host.
 
+  octofit_nested_device: nested sampling, the reference's fourth sampler (dynesty behind a hypercube prior transform) — the live set in the unit cube,
+  the ordered cull with its evidence bookkeeping and the constrained-prior slice moves on the device (PriorDraws.cube / from_cube / nested_step);
+  the host reads the 8-double state once per iteration, and computes the information and the resampling from the dead records.
+
   pointwise_like_rows / waic: the pointwise log-likelihood at the grain model comparison needs — one column per DATUM (table row), not per
   table — and its WAIC / importance-sampling LOO sums, computed (and for waic reduced over the samples) on the device
   (host/pointwise.py: Pointwise).
@@ -1019,3 +1023,59 @@ def posterior_predictive(planets, elems, epochs, channels, summary=True, basis=N
             import torch
             torch.cuda.synchronize()      # device inputs ran on torch's current stream: the handle is destroyed below
         return res
+
+
+def octofit_nested_device(model, n_live=1024, batch=256, n_passes=4, max_steps=8, max_shrink=64, dlogz=0.01, max_iter=2000, n_samples=4096, seed=0):
+    """Nested sampling (the reference's fourth sampler: dynesty behind a hypercube prior transform) with the live set, the cull, the
+    constrained-prior moves and the evidence bookkeeping on the device (PriorDraws.cube / from_cube / nested_step / nested_cull). n_live prior
+    points of the unit cube are scored; every iteration removes the `batch` lowest and replaces them by slice moves in the cube from copies of
+    survivors (n_passes sweeps, stepping out up to max_steps widths of the live set's extent per coordinate), until the remaining-evidence bound
+    of the state falls below dlogz or after max_iter iterations; then the live set is flushed. The host reads the 8-double state once per
+    iteration and the count of active chains once per segment of rounds. The defaults are the project's own.
+    Returns dict(logz, logz_err = √(information/n_live), information, theta [D, n] (natural domain), theta_t [D, n], loglike [n], logwt [n] of
+    the n dead points in the order they died, weights [n] = exp(logwt − logz), samples [D, n_samples] (natural domain) and samples_t, equally
+    weighted by systematic resampling from one uniform of the counter generator (coordinate 0 of prior draw n_live of `seed`), ess, n_iter,
+    n_evals, n_stuck, names)."""
+    import torch
+    from .draws import PriorDraws
+    K, B, most = int(n_live), int(batch), int(max_iter)
+    if not 1 <= B <= K - 1 or most < 1 or int(n_samples) < 1:
+        raise ValueError("octofit_nested_device: 1 <= batch <= n_live - 1, max_iter >= 1, n_samples >= 1")
+    dev = torch.device("cuda", model.ln_like.device_index)
+    D = int(model.D)
+    with PriorDraws(model) as pd:
+        u = pd.cube(seed, 0, K)
+        _, tt, lpt = pd.from_cube(u, theta=False)
+        ll = _finite_or_neg_inf(model.logpost_device(tt, grad=False)[0] - lpt).contiguous()
+        state = pd.nested_state()
+        room = most * B + K
+        dead = dict(u=torch.empty((D, room), dtype=torch.float64, device=dev), loglike=torch.empty(room, dtype=torch.float64, device=dev),
+                    logvol=torch.empty(room, dtype=torch.float64, device=dev), logwt=torch.empty(room, dtype=torch.float64, device=dev))
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        n_iter = 0
+        while n_iter < most:
+            r = pd.nested_step(u, ll, state, B, max_steps=max_steps, n_passes=n_passes, max_shrink=max_shrink, seed=seed, iter=n_iter, dead=dead,
+                               dead_first=n_iter * B)
+            counts += torch.stack([r["n_eval"].sum(), r["n_stuck"].sum()])
+            n_iter += 1
+            if float(state.cpu()[4]) < float(dlogz):
+                break
+        pd.nested_cull(u, ll, state, K, replace=False, seed=seed, iter=n_iter, dead=dead, dead_first=n_iter * B)
+        n = n_iter * B + K
+        du = dead["u"][:, :n].contiguous()
+        theta, theta_t, _ = pd.from_cube(du, logprior_t=False)
+        v = float(pd.cube(seed, K, 1)[0, 0])
+        torch.cuda.synchronize(dev)
+        logz = float(state[0])
+        loglike, logwt = dead["loglike"][:n].cpu().numpy(), dead["logwt"][:n].cpu().numpy()
+        theta, theta_t = theta.cpu().numpy(), theta_t.cpu().numpy()
+        n_evals, n_stuck = (int(c) for c in counts.cpu())
+    with np.errstate(all="ignore"):
+        p = np.exp(logwt - logz)
+        ok = p > 0
+        information = float(np.sum(p[ok] * (loglike[ok] - logz)))
+    cum = np.cumsum(p)
+    pick = np.minimum(np.searchsorted(cum / cum[-1], (v + np.arange(int(n_samples))) / int(n_samples), side="left"), n - 1)
+    return dict(logz=logz, logz_err=float(np.sqrt(max(information, 0.0) / K)), information=information, theta=theta, theta_t=theta_t, loglike=loglike,
+                logwt=logwt, weights=p, samples=theta[:, pick], samples_t=theta_t[:, pick], ess=float(1.0 / np.sum((p / cum[-1]) ** 2)), n_iter=n_iter,
+                n_evals=n_evals + K, n_stuck=n_stuck, names=list(model.names))

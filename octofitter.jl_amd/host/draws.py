@@ -12,6 +12,8 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     φ, logq, logpost = draws.pathfinder_draw(θ_t, 256, seed=seed)      # [D, 256·W], [256·W], [256·W]: draws from every chain's kept fit
     lp, ll, log_accept, acc, depth, n_leapfrog, diverged = draws.nuts_step(θ_t, eps=0.1, max_depth=10, seed=seed, step=step)      # one NUTS transition
     r = draws.slice_step(θ_t, beta, w=10.0, p=3, n_passes=3, seed=seed, step=step)      # one slice-sampling transition (no gradient, no ε, no metric): dict
+    u = draws.cube(seed, first, n); θ, θ_t, lpt = draws.from_cube(u)      # the unit cube behind `sample` and the hypercube transform out of it: the same bytes
+    r = draws.nested_step(u_live, ll_live, state, B, seed=seed, iter=it)  # one iteration of nested sampling: cull the B lowest, move their slots (dict)
     count, mean, m2 = draws.moments(θ_t)                    # warm-up: pooled moments of the chains, [1], [1, D], [1, D] (or per group)
     draws.metric(count[0:1], mean[0], m2[0], inv_mass)      # … the diagonal metric they give, written into inv_mass [D]
     state = draws.adapt_init(1, 0.1)                        # … dual averaging of ε: the state [G, 4]
@@ -52,6 +54,11 @@ PURPOSE_SLICE = 9
 SLICE_MAX_DOUBLINGS, SLICE_MAX_SHRINK, SLICE_MAX_PASSES = 8, 64, 1024      # OCTO_DRAWS_SLICE_MAX_*
 SLICE_ACTIVE, SLICE_DONE, SLICE_DEAD = 0, 1, 2                            # OCTO_DRAWS_SLICE_*
 SLICE_OUTPUTS = ("logpost", "loglike", "n_eval", "n_expand", "n_shrink", "n_stuck", "status", "n_active")      # the outputs of octo_draws_slice_device, in order
+PURPOSE_NESTED_SEED, PURPOSE_NESTED_MOVE = 10, 11
+NESTED_MAX_LIVE, NESTED_MAX_STEPS, NESTED_MAX_SHRINK, NESTED_MAX_PASSES = 4096, 64, 64, 1024      # OCTO_DRAWS_NESTED_MAX_*
+NESTED_ACTIVE, NESTED_DONE = 0, 1                                                                  # OCTO_DRAWS_NESTED_*
+NESTED_STATE = ("logz", "logvol", "floor", "loglike_max", "remaining", "n_dead")                   # the entries of d_state [8], in order (two reserved)
+NESTED_MOVE_OUTPUTS = ("theta_t", "n_eval", "n_step", "n_shrink", "n_stuck", "status", "n_active")      # the outputs of octo_draws_nested_move_device, in order
 LBFGS_MAX_M = 8                    # OCTO_DRAWS_LBFGS_MAX_M
 LBFGS_ACTIVE, LBFGS_GTOL, LBFGS_FTOL, LBFGS_LINESEARCH, LBFGS_DEAD = 0, 1, 2, 3, 4      # OCTO_DRAWS_LBFGS_*
 PF_MAX_D = 64                      # OCTO_DRAWS_PF_MAX_D
@@ -118,6 +125,12 @@ _SIGS = {
     "octo_draws_program_clear": (C.c_int32, [C.c_void_p]),
     "octo_draws_program_logpost_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "octo_draws_program_values_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "octo_draws_cube_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "octo_draws_from_cube_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5),
+    "octo_draws_nested_cull_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_int64, C.c_int64] + [C.c_void_p] * 7),
+    "octo_draws_nested_move_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -480,6 +493,120 @@ class PriorDraws(companion.Handle):
             out = self.slice(theta_t, n_rounds=n, resume=out is not None, out=out, **args)
             done += n
         return out
+
+    # ---- nested sampling (include/octofitter_hip_draws.h, "Nested sampling")
+    def cube(self, seed, first, n, out=None, stream=None):
+        """octo_draws_cube_device: the uniforms u [D, n] of draws first … first + n − 1, what `sample` feeds to the quantile. out: a float64
+        [D, n] tensor with contiguous rows, written in place. Asynchronous on `stream`."""
+        n = int(n)
+        u = self._out(n, self.D) if out is None else out
+        _, n_u, ld = chain_matrix(u, self.D, self.device, "cube", "out")
+        if n_u != n:
+            raise ValueError(f"cube: out must hold {n} columns")
+        self._check(self.lib.octo_draws_cube_device(self._h, int(seed), int(first), n, ld, u.data_ptr(), self._stream(stream, self.device)))
+        self._keep = (u,)
+        return u
+
+    def from_cube(self, u, theta=True, theta_t=True, logprior_t=True, out=None, stream=None):
+        """octo_draws_from_cube_device, the hypercube transform of the columns of u [D, n]: (θ [D, n], θ_t [D, n], logprior_t [n]) as `sample`
+        returns them, of u's leading dimension; None for an output switched off. A column with a coordinate outside (0, 1) gives NaN.
+        out=(θ, θ_t, logprior_t): written in place (None: switched off); the matrices have u's shape and leading dimension."""
+        _, n, ld = chain_matrix(u, self.D, self.device, "from_cube", "u")
+        if out is not None:
+            th, tt, lp = out
+            for t, name in ((th, "theta"), (tt, "theta_t")):
+                if t is not None and chain_matrix(t, self.D, self.device, "from_cube", name) != (self.D, n, ld):
+                    raise ValueError(f"from_cube: {name} must have u's shape and leading dimension")
+        else:
+            th = self._out(n, self.D, ld) if theta else None
+            tt = self._out(n, self.D, ld) if theta_t else None
+            lp = self._out(n) if logprior_t else None
+        self._check(self.lib.octo_draws_from_cube_device(self._h, n, ld, u.data_ptr(), ptr(th), ptr(tt), ptr(lp), self._stream(stream, self.device)))
+        self._keep = (u,)
+        return th, tt, lp
+
+    def nested_state(self):
+        """The initial state of a nested-sampling run, float64 [8] on the device: NESTED_STATE names its entries."""
+        import torch
+        inf = float("inf")
+        return torch.tensor([-inf, 0.0, -inf, -inf, inf, 0.0, 0.0, 0.0], dtype=torch.float64, device=self.device)
+
+    def _live(self, u_live, loglike_live, state, what):
+        import torch
+        _, K, ldK = chain_matrix(u_live, self.D, self.device, what, "u_live")
+        for t, n, name in ((loglike_live, K, "loglike_live"), (state, 8, "state")):
+            if t.dtype != torch.float64 or t.device != self.device or t.shape != (n,) or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be a contiguous float64 [{n}] tensor on {self.device}")
+        return K, ldK
+
+    def nested_cull(self, u_live, loglike_live, state, B, replace=True, seed=0, iter=0, dead=None, dead_first=0, slot=None, width=None, stream=None):
+        """octo_draws_nested_cull_device: removes the B lowest of the K live points u_live [D, K], loglike_live [K] (both in place), updates
+        state [8] in place, and with replace copies a survivor into every dead slot. dead: None, or dict(u [D, n], loglike, logvol, logwt [n]) of
+        caller arrays that receive the records at columns dead_first … dead_first + B − 1. Returns (slot int32 [B], width [D] or None without
+        replace). Asynchronous on `stream`."""
+        import torch
+        K, ldK = self._live(u_live, loglike_live, state, "nested_cull")
+        B = int(B)
+        slot = self._out(max(B, 1), dtype=torch.int32) if slot is None else slot
+        if replace and width is None:
+            width = self._out(self.D)
+        ld_dead, dp = int(dead_first) + B, [None] * 4
+        if dead is not None:
+            _, _, ld_dead = chain_matrix(dead["u"], self.D, self.device, "nested_cull", "dead['u']")
+            if any(int(dead[k].numel()) < int(dead_first) + B for k in ("loglike", "logvol", "logwt")):
+                raise ValueError("nested_cull: the dead arrays hold fewer than dead_first + B records")
+            dp = [ptr(dead[k]) for k in ("u", "loglike", "logvol", "logwt")]
+        self._check(self.lib.octo_draws_nested_cull_device(self._h, int(seed), int(iter), K, ldK, u_live.data_ptr(), loglike_live.data_ptr(), state.data_ptr(), B,
+                                                           1 if replace else 0, int(dead_first), ld_dead, *dp, slot.data_ptr(), ptr(width) if replace else None,
+                                                           self._stream(stream, self.device)))
+        self._keep = (u_live, loglike_live, state, dead, slot, width)
+        return slot[:B], (width if replace else None)
+
+    def nested_move(self, u_live, loglike_live, state, slot, w=1.0, max_steps=8, n_passes=3, max_shrink=NESTED_MAX_SHRINK, n_rounds=0, resume=False, seed=0, iter=0,
+                    want_theta_t=False, out=None, stream=None):
+        """octo_draws_nested_move_device, the raw call: opens (resume=False) or continues (resume=True: the same arguments, and out= the dict
+        the opening call returned) one constrained-prior transition of the live slots `slot` (int32 [B]) under the floor state[2], in place in
+        u_live and loglike_live, and makes n_rounds rounds of it. w: the width in the cube, a number or one per coordinate [D].
+        Returns dict(theta_t [D, B] or None, n_eval, n_step, n_shrink, n_stuck, status int32 [B], n_active int32 [1]). Asynchronous on `stream`."""
+        import torch
+        dev = self.device
+        K, ldK = self._live(u_live, loglike_live, state, "nested_move")
+        if slot.dtype != torch.int32 or slot.device != dev or slot.ndim != 1 or not slot.is_contiguous():
+            raise ValueError(f"nested_move: slot must be a contiguous int32 [B] tensor on {dev}")
+        B = int(slot.numel())
+        per_coordinate = torch.is_tensor(w) or np.ndim(w) > 0
+        width = device_vector(w, self.D, dev, "w") if per_coordinate else None
+        if out is None:
+            i32 = lambda n: self._out(n, dtype=torch.int32)      # noqa: E731
+            out = dict(theta_t=self._out(B, self.D) if want_theta_t else None, n_eval=i32(B), n_step=i32(B), n_shrink=i32(B), n_stuck=i32(B), status=i32(B),
+                       n_active=i32(1))
+        ld = B if out["theta_t"] is None else chain_matrix(out["theta_t"], self.D, dev, "nested_move", "out['theta_t']")[2]
+        self._check(self.lib.octo_draws_nested_move_device(self._h, int(seed), int(iter), K, ldK, u_live.data_ptr(), loglike_live.data_ptr(), state.data_ptr(), B, ld,
+                                                           slot.data_ptr(), ptr(width), 0.0 if per_coordinate else float(w), int(max_steps), int(n_passes),
+                                                           int(max_shrink), int(n_rounds), 1 if resume else 0, *(ptr(out[k]) for k in NESTED_MOVE_OUTPUTS),
+                                                           self._stream(stream, dev)))
+        self._keep = (u_live, loglike_live, state, slot, width, out)
+        return out
+
+    def nested_step(self, u_live, loglike_live, state, B, w=None, max_steps=8, n_passes=3, max_shrink=NESTED_MAX_SHRINK, seed=0, iter=0, dead=None, dead_first=0,
+                    rounds_per_call=None, want_theta_t=False, stream=None):
+        """One iteration of nested sampling: one cull of the B lowest live points (nested_cull with replace), then the move of their slots in
+        segments of rounds_per_call rounds (default 2·n_passes·D) until no chain is active — after each segment the number of active chains is
+        read (a 4-byte copy, the only synchronisation). w: None = the cull's per-coordinate widths. The same bits however the rounds are cut.
+        Returns nested_move's dict, with slot and width."""
+        slot, width = self.nested_cull(u_live, loglike_live, state, B, replace=True, seed=seed, iter=iter, dead=dead, dead_first=dead_first, stream=stream)
+        updates = int(n_passes) * self.D
+        per_call = 2 * updates if rounds_per_call is None else int(rounds_per_call)
+        if per_call < 1:
+            raise ValueError("nested_step: rounds_per_call >= 1")
+        args = dict(w=width if w is None else w, max_steps=max_steps, n_passes=n_passes, max_shrink=max_shrink, seed=seed, iter=iter, stream=stream)
+        done, out = 0, None
+        most = updates * (int(max_steps) - 1 + int(max_shrink))      # what finishes every chain
+        while out is None or (done < most and int(out["n_active"].item()) > 0):
+            n = min(per_call, most - done)
+            out = self.nested_move(u_live, loglike_live, state, slot, n_rounds=n, resume=out is not None, want_theta_t=want_theta_t, out=out, **args)
+            done += n
+        return dict(out, slot=slot, width=width)
 
     def lbfgs_direction(self, cnt, head, S, Y, g, inv_mass=None, stream=None):
         """The two-loop recursion of every chain on its own history: d [D, W] = −H·g with H₀ = γ·diag(inv_mass). cnt, head: int32 [W] (stored
