@@ -813,6 +813,48 @@ int32_t octo_draws_nested_move_device(octo_draws* h, uint64_t seed, uint64_t ite
                                       int32_t* d_n_eval, int32_t* d_n_step, int32_t* d_n_shrink, int32_t* d_n_stuck, int32_t* d_status,
                                       int32_t* d_n_active, void* hip_stream);
 
+/* ---- The dense metric (the fourteenth part; the reference's octofit runs NUTS with a dense Euclidean metric, AdvancedHMC's DenseEuclideanMetric, and
+ * Stan's dense_e adapts it by the rule below): M⁻¹ = Σ = L·Lᵀ, L the lower Cholesky factor of a pooled covariance estimate of θ_t, PACKED by rows
+ * (row i at i(i+1)/2, D(D+1)/2 doubles). All on DEVICE buffers, asynchronous on hip_stream; no floating-point atomic, the same bits on every run.
+ *
+ * THE WHITENED TRANSITION. While a factor is set (octo_draws_use_metric) octo_draws_hmc_step_device, octo_draws_hmc_step and octo_draws_nuts_device
+ * simulate H = −E(θ_t) + ½pᵀΣp with p ~ N(0, Σ⁻¹), carried as the whitened momentum r = Lᵀp:
+ *   r ~ N(0, I): the draw is octo_draws_momentum_device with a NULL metric, bit for bit · K = ½Σ r_d²
+ *   kick   r += c·(Lᵀ∇E), ∇E the tempered gradient (∇ℓπ and ∇ℓprior_t mixed by β BEFORE the product) · drift  θ_t += ε·(L·r)
+ *   every turn test ρᵀΣp is the plain product ρ_r·r with ρ_r = Σ r over the subtree: NUTS's checkpoints, ρ and ρ_s hold whitened momenta, its endpoint
+ *   gradients hold Lᵀ∇E, and its tree logic, its counters and every output are those of the diagonal call. No work array grows.
+ * A leapfrog is two triangular products per chain, each summed over the coordinate index in ascending order by fma. With L = diag(√inv_mass) the
+ * transition is the diagonal one up to rounding. d_inv_mass must be NULL in those three calls while a factor is set (OCTO_EINVAL otherwise), and a
+ * NUTS `resume` needs the factor pointer of the call it resumes (OCTO_EINVAL otherwise). The factor is CALLER-owned and read by every such call: it
+ * must stay allocated and unchanged while a transition is open. octo_draws_momentum_device is unchanged; the L-BFGS, Pathfinder, the slice sampler,
+ * nested sampling and the tempering statistics do not read the factor.
+ *
+ * octo_draws_cov_device: the pooled co-moments of the W chains in d_x [K][ld], one group, 1 <= K <= OCTO_DRAWS_DENSE_MAX_D. A chain with any
+ * non-finite value is left out (octo_draws_moments_device's rule). d_count [1] = n, d_mean [K], d_m2 [K(K+1)/2] packed as L is:
+ * Σ_w (x_i − mean_i)(x_j − mean_j). Block partials of 256 chains, two-pass about the block's mean, merged in block order by Chan's formula (cross term
+ * d_i·d_j·n·n_b/(n + n_b)); with `accumulate` the result is then merged into what the three arrays hold (a held count of 0: replaced; a call without a
+ * valid chain: untouched). The partials are cov_partials of csrc/draws/octo_draws_layout.h, nblk·(1 + K + K(K+1)/2) doubles of the handle's
+ * moments allocation. OCTO_EINVAL: NULL handle; NULL d_count, d_mean or d_m2, NULL d_x with W > 0; K out of range; W < 0, ld < W, W > 2^24.
+ *
+ * octo_draws_metric_dense_device: Σ = M2/(n − 1); with `regularize` (n/(n + 5))·Σ + 1e-3·(5/(n + 5))·I, octo_draws_metric_device's constants. One
+ * wave factors it in LDS (left-looking, lane = row). d_info [1] = 0: d_chol was written. d_info = j + 1: pivot j was not finite and > 0 (n < 2: 1), and
+ * d_chol is UNTOUCHED. OCTO_EINVAL: NULL handle, a NULL array, K out of range.
+ *
+ * octo_draws_metric_apply_device: d_out [D][ld] = L·x (transpose = 0) or Lᵀ·x (transpose = 1) for the n columns of d_x [D][ld], D the handle's;
+ * d_out may be d_x. The routines of the samplers' dense kernels behind an entry point: θ_t = μ + L·z from whitened draws, z = Lᵀ… of a gradient.
+ * OCTO_EINVAL: NULL handle; D > OCTO_DRAWS_DENSE_MAX_D; n < 0, ld < n, n > 2^30; a NULL array with n > 0.
+ *
+ * octo_draws_use_metric: handle state, as octo_draws_use_reference. d_chol: the factor, D(D+1)/2 doubles, or NULL = back to the per-call diagonal
+ * metric. OCTO_EINVAL: NULL handle; D > OCTO_DRAWS_DENSE_MAX_D with a non-NULL factor. */
+#define OCTO_DRAWS_DENSE_MAX_D 64
+int32_t octo_draws_cov_device(octo_draws* h, int64_t W, int64_t ld, int32_t K, const double* d_x, int32_t accumulate, double* d_count, double* d_mean,
+                              double* d_m2, void* hip_stream);
+int32_t octo_draws_metric_dense_device(octo_draws* h, int32_t K, const double* d_count, const double* d_m2, int32_t regularize, double* d_chol,
+                                       int32_t* d_info, void* hip_stream);
+int32_t octo_draws_metric_apply_device(octo_draws* h, int64_t n, int64_t ld, const double* d_chol, int32_t transpose, const double* d_x, double* d_out,
+                                       void* hip_stream);
+int32_t octo_draws_use_metric(octo_draws* h, const double* d_chol);
+
 #ifdef __cplusplus
 }
 #endif

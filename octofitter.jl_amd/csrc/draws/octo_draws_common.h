@@ -4,6 +4,8 @@
 // (SamplerHead), the per-lane preamble (Chain, chain_of) and the tempered target at a point (Target, target_at over prior_loop, tempered_energy,
 // dead_state). On the host: check_sampler_call, sampler_head, logpost_at (every octo_model_logpost_device call of the four units) and
 // run_rounds (the round driver of the L-BFGS and of NUTS).
+// The fourteenth part, the dense metric (octo_draws_dense.hip: pooled covariance, its Cholesky factor, the products with it), adds metric_lower and
+// metric_lower_t to the metric and metric_gradient behind the target: the HMC step and NUTS reach a factor through these alone.
 // Eleven units include it (the eleventh: octo_draws_program.hip, the expression programs of derived variables, which logpost_at chooses over the model;
 // the tenth: octo_draws_vref.hip, the reference table of a variational tempering leg and the exchange of two legs' target
 // replicas, which take prior_loop and the handle's active table): octo_draws.hip (the draws and the two drivers that consume a batch of them), octo_draws_hmc.hip (the tempered HMC
@@ -195,6 +197,29 @@ __device__ __forceinline__ double prior_loop(const octo_prior* priors, const dou
 __device__ __forceinline__ double inv_mass_at(const double* inv_mass, int d) { return inv_mass ? inv_mass[d] : 1.0; }
 // the momentum p = z/√m⁻¹ of a standard normal z (a null metric takes z bit for bit)
 __device__ __forceinline__ double momentum_of(const double* inv_mass, int d, double z) { return inv_mass ? z / sqrt(inv_mass[d]) : z; }
+// The dense metric M⁻¹ = L·Lᵀ (octo_draws_use_metric): L lower-triangular, packed by rows (row i at i(i+1)/2), one factor for all chains — its
+// index is wave-uniform, so it comes through the scalar cache. x is one lane's column of a [D][ld] array at offset w; D <= OCTO_DRAWS_DENSE_MAX_D
+// is a run-time value and nothing of the column is kept in a private array: it is read again through the caches. put(i, v) receives the
+// products; every sum runs over the coordinate index in ascending order by fma, so a product has the same bits wherever it is formed.
+// (L·x)_i for i = D − 1 … 0: put may overwrite x_i (no later i reads it), which forms the product in place
+template <class Put>
+__device__ __forceinline__ void metric_lower(const double* __restrict__ L, int32_t D, const double* x, int64_t ld, int64_t w, Put put) {
+    for (int i = D - 1; i >= 0; --i) {
+        const double* __restrict__ row = L + (i * (i + 1) >> 1);
+        double s = 0.0;
+        for (int j = 0; j <= i; ++j) s = fma(row[j], x[(int64_t)j * ld + w], s);
+        put(i, s);
+    }
+}
+// (Lᵀ·x)_j for j = 0 … D − 1: put may overwrite x_j likewise
+template <class Put>
+__device__ __forceinline__ void metric_lower_t(const double* __restrict__ L, int32_t D, const double* x, int64_t ld, int64_t w, Put put) {
+    for (int j = 0; j < D; ++j) {
+        double s = 0.0;
+        for (int i = j; i < D; ++i) s = fma(L[(i * (i + 1) >> 1) + j], x[(int64_t)i * ld + w], s);
+        put(j, s);
+    }
+}
 
 // ---- the head of the two samplers' kernel arguments (HmcArgs, NutsArgs derive from it), filled by sampler_head
 struct SamplerHead {
@@ -241,6 +266,18 @@ __device__ __forceinline__ Target target_at(const SamplerHead& a, const Chain& c
     t.lpt = prior_loop(a.priors, a.pc, a.D, at, a.ld, c.w, c.wl, c.live, gpr, t.healed);
     t.beta = c.beta; t.has_model = a.has_model; t.lpi = lp; t.glp = glp; t.gpr = gpr;
     return t;
+}
+
+// ∇E of chain column w in the coordinates the momenta live in, for d = 0 … D − 1 in that order: body(d, o, g), o = d·ld + w. The diagonal metric
+// keeps p itself and g = ∇E_d. DENSE (the whitened momenta r = Lᵀp of a factor L): the mixed gradient tg.grad — ∇ℓπ and ∇ℓprior_t by β — goes to
+// the column gpr, whose ∇ℓprior_t is spent by then, and g = (Lᵀ∇E)_d is formed on it in place.
+template <bool DENSE, class Body>
+__device__ __forceinline__ void metric_gradient(const Target& tg, const double* chol, double* gpr, int32_t D, int64_t ld, int64_t w, Body body) {
+    if (DENSE) {
+        for (int d = 0; d < D; ++d) { const int64_t o = (int64_t)d * ld + w; gpr[o] = tg.grad(o); }
+        metric_lower_t(chol, D, gpr, ld, w, [&](int d, double g) { const int64_t o = (int64_t)d * ld + w; gpr[o] = g; body(d, o, g); });
+    } else
+        for (int d = 0; d < D; ++d) { const int64_t o = (int64_t)d * ld + w; body(d, o, tg.grad(o)); }
 }
 
 }  // namespace
@@ -302,6 +339,10 @@ struct octo_draws : CompanionBase {
     double* d_nest = nullptr; int64_t cap_nest = 0;
     int64_t nest_B = 0, nest_ld = 0, nest_ldK = 0; int32_t nest_K = 0, nest_passes = 0, nest_steps = 0, nest_shrink = 0;
     uint64_t nest_seed = 0, nest_iter = 0;
+    // the dense metric (octo_draws_dense.hip): the CALLER's packed factor L [D(D+1)/2] that the HMC step and NUTS read while it is set
+    // (octo_draws_use_metric; null: the per-call diagonal metric), and the one the open NUTS transition was started with
+    const double* d_metric = nullptr;
+    const double* nuts_metric = nullptr;
 };
 
 namespace {

@@ -7,6 +7,7 @@
 //   k_hmc_leap<OPEN>   the start point: prior value and derivative, E₀, K₀, the half kick and the drift.
 //   k_hmc_leap<STEP>   a point inside the trajectory: prior value and derivative at it, the whole kick and the drift.
 //   k_hmc_leap<LAST>   the end point: the half kick, H₁, the decision, the selection and every output.
+//   k_dense_hmc_leap<·>  the same three bodies with the handle's dense metric (octo_draws_use_metric): whitened momenta, two triangular products.
 // A step is ⌈D/4⌉ + 1 + n_leapfrog launches besides the n_leapfrog + 1 log-posterior calls; the host reads nothing.
 // From octo_draws_common.h: the head of HmcArgs and its filling, the lane's chain (chain_of), the target at a point (target_at), the metric
 // (inv_mass_at, momentum_of), the shared argument checks (check_sampler_call) and the log-posterior call (logpost_at).
@@ -44,34 +45,37 @@ struct HmcArgs : SamplerHead {
     HmcWork s;
     double *theta_prop, *o_lp, *o_ll, *o_dH;
     int32_t* o_acc;
+    const double* chol;            // the handle's dense factor L, packed; read by k_dense_hmc_leap alone
 };
 
 // Two loops over the coordinates. The first is target_at's prior_loop() (octo_draws_common.h, shared with the no-U-turn sampler): every
-// transcendental, and ∇ℓprior_t left in a.s.gpr. The second is arithmetic alone.
-template <int PHASE>
-__global__ __launch_bounds__(TPB) void k_hmc_leap(HmcArgs a) {
+// transcendental, and ∇ℓprior_t left in a.s.gpr. The second is arithmetic alone. DENSE: the handle's factor L is set and p holds the whitened
+// momenta r = Lᵀp ~ N(0, I) (a.inv_mass is null: K = ½Σr²); the kick takes Lᵀ∇E (metric_gradient) and the drift L·r, after the loop that made r½.
+template <int PHASE, bool DENSE>
+__device__ __forceinline__ void hmc_leap(const HmcArgs& a) {
     const Chain ch = chain_of(a);
     const int64_t w = ch.w, wl = ch.wl;
     const bool live = ch.live;
     const double beta = ch.beta, eps = ch.eps;
     const double* __restrict__ at = PHASE == HMC_OPEN ? a.theta_t : a.s.q;
     const Target tg = target_at(a, ch, at, a.s.lp, a.s.glp, a.s.gpr);
+    if (DENSE && !live) return;      // the products write the lane's own column
     const double lp = tg.lp(wl), lpt = tg.lpt;
     const double kick = PHASE == HMC_STEP ? eps : 0.5 * eps;
     double K = 0.0;
-    for (int d = 0; d < a.D; ++d) {
-        const int64_t o = (int64_t)d * a.ld + wl;
+    metric_gradient<DENSE>(tg, a.chol, a.s.gpr, a.D, a.ld, wl, [&](int d, int64_t o, double g) {
         const double im = inv_mass_at(a.inv_mass, d);
-        const double g = tg.grad(o);
         double pd = a.s.p[o];
         if (PHASE == HMC_OPEN) K += im * pd * pd;
         pd += kick * g;
         if (PHASE == HMC_LAST) K += im * pd * pd;
         else if (live) {
             a.s.p[o] = pd;
-            a.s.q[o] = at[o] + eps * (im * pd);
+            if (!DENSE) a.s.q[o] = at[o] + eps * (im * pd);
         }
-    }
+    });
+    if (DENSE && PHASE != HMC_LAST)
+        metric_lower(a.chol, a.D, a.s.p, a.ld, w, [&](int d, double v) { const int64_t o = (int64_t)d * a.ld + w; a.s.q[o] = at[o] + eps * v; });
     K *= 0.5;
     if (PHASE == HMC_OPEN && live) { a.s.lp0[w] = lp; a.s.lpt0[w] = lpt; a.s.K0[w] = K; }
     if (PHASE != HMC_LAST) return;
@@ -98,6 +102,11 @@ __global__ __launch_bounds__(TPB) void k_hmc_leap(HmcArgs a) {
     if (a.o_dH) a.o_dH[w] = dH;
     a.o_acc[w] = acc ? 1 : 0;
 }
+
+template <int PHASE>
+__global__ __launch_bounds__(TPB) void k_hmc_leap(HmcArgs a) { hmc_leap<PHASE, false>(a); }
+template <int PHASE>
+__global__ __launch_bounds__(TPB) void k_dense_hmc_leap(HmcArgs a) { hmc_leap<PHASE, true>(a); }
 
 void launch_momentum(hipStream_t st, uint64_t seed, uint64_t step, uint64_t chain0, int64_t n, int64_t ld, int32_t D, const double* d_inv_mass, double* d_p) {
     MomentumArgs m;
@@ -130,22 +139,24 @@ int32_t octo_draws_hmc_step_device(octo_draws* h, uint64_t seed, uint64_t step, 
     if (int rc = check_sampler_call(h, "octo_draws_hmc_step_device", W, ld, d_eps, eps, has_model, d_logpost, d_loglike)) return rc;
     if (W == 0) return OCTO_OK;
     if (!d_theta_t || !d_accepted) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: d_theta_t and d_accepted are required");
+    const bool dense = h->d_metric != nullptr;
+    if (dense && d_inv_mass) return fail(h, OCTO_EINVAL, "octo_draws_hmc_step_device: d_inv_mass must be NULL while a dense metric is set (octo_draws_use_metric)");
     OCHK(h, hipSetDevice(h->device));
     const hipStream_t st = stream_of(h, hip_stream);
     HmcArgs a{sampler_head(h, has_model, seed, step, chain0, W, ld, d_theta_t, d_beta, d_eps, eps, d_inv_mass)};
     if (int rc = grow_to(h, h->d_hmc, h->cap_hmc, a.s, hmc_work, (int64_t)h->D, ld)) return rc;
     double *lp = a.s.lp, *glp = a.s.glp;
     if (!has_model) { a.s.lp = nullptr; a.s.glp = nullptr; }
-    a.theta_prop = d_theta_prop; a.o_lp = d_logpost; a.o_ll = d_loglike; a.o_dH = d_dH; a.o_acc = d_accepted;
+    a.theta_prop = d_theta_prop; a.o_lp = d_logpost; a.o_ll = d_loglike; a.o_dH = d_dH; a.o_acc = d_accepted; a.chol = h->d_metric;
     const dim3 grid = grid_of(W), block(TPB);
     launch_momentum(st, seed, step, chain0, W, ld, h->D, d_inv_mass, a.s.p);
     OCHK(h, hipGetLastError());
     if (int rc = logpost_at(h, st, has_model, d_theta_t, ld, W, lp, glp)) return rc;
-    hipLaunchKernelGGL(k_hmc_leap<HMC_OPEN>, grid, block, 0, st, a);
+    hipLaunchKernelGGL(dense ? k_dense_hmc_leap<HMC_OPEN> : k_hmc_leap<HMC_OPEN>, grid, block, 0, st, a);
     for (int s = 1; s <= n_leapfrog; ++s) {
         if (int rc = logpost_at(h, st, has_model, a.s.q, ld, W, lp, glp)) return rc;
-        if (s < n_leapfrog) hipLaunchKernelGGL(k_hmc_leap<HMC_STEP>, grid, block, 0, st, a);
-        else hipLaunchKernelGGL(k_hmc_leap<HMC_LAST>, grid, block, 0, st, a);
+        if (s < n_leapfrog) hipLaunchKernelGGL(dense ? k_dense_hmc_leap<HMC_STEP> : k_hmc_leap<HMC_STEP>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(dense ? k_dense_hmc_leap<HMC_LAST> : k_hmc_leap<HMC_LAST>, grid, block, 0, st, a);
     }
     OCHK(h, hipGetLastError());
     return OCTO_OK;

@@ -143,6 +143,12 @@ inline MomentsPartials moments_partials(Carve& c, int64_t nblk, int64_t G, int64
     return {c.take(nblk * G), c.take(nblk * G * K), c.take(nblk * G * K)};
 }
 
+// The block partials of the pooled covariance (octo_draws_dense.hip), on d_mom as well: nblk·(1 + K + K(K+1)/2). Per block of 256 chains: the number
+// of chains it holds · per row their sum · per pair i >= j, packed by rows, Σ(x_i − the block's mean_i)(x_j − the block's mean_j). sum and m2 of a
+// block with cnt = 0 are never written or read.
+struct CovPartials { double *cnt, *sum, *m2; };      // [nblk] · [nblk][K] · [nblk][K(K+1)/2]
+inline CovPartials cov_partials(Carve& c, int64_t nblk, int64_t K) { return {c.take(nblk), c.take(nblk * K), c.take(nblk * (K * (K + 1) / 2))}; }
+
 // The block partials of the tempering statistics (octo_draws_pt.hip), on d_mom as well: 7·P·nblk. Per pair of neighbouring slots (P = T − 1) and
 // block of 256 chains: Σα · the forward stepping-stone terms' count, maximum and Σ exp(v − maximum) · the backward terms' three. Pair-major, so
 // that the merge reads a pair's blocks side by side; m of a (pair, block) without a term is −Inf and its s is 0. The kernels take it by value.

@@ -10,6 +10,8 @@
 //                  the checkpoint store or the turn tests, the merge and the tree's test where the subtree completes, the write-back where
 //                  the chain ends, and the opening half kick and drift of the next leaf.
 //   k_nuts_report  the outputs alone: a resumed call of no rounds.
+//   k_dense_nuts_open, k_dense_nuts_leaf   the same two bodies with the handle's dense metric (octo_draws_use_metric): whitened momenta and
+//                  gradients in every array of the tree, Lᵀ∇E after the gradient arrives and L·r½ before the drift.
 // The last launch of a call writes the outputs. The momenta are octo_draws_momentum_device's (purpose 2), the HMC step's.
 // From octo_draws_common.h, as the HMC step: the head of NutsArgs, chain_of, target_at, inv_mass_at, check_sampler_call; and run_rounds, the
 // round driver it shares with the L-BFGS (opening, rounds, report; the last launch writes the outputs).
@@ -26,6 +28,7 @@ struct NutsArgs : SamplerHead {
     NutsWork s;
     double *o_lp, *o_ll, *o_la;
     int32_t *o_acc, *o_depth, *o_nleaf, *o_div, *o_nact;
+    const double* chol;            // the handle's dense factor L, packed; read by k_dense_nuts_open and k_dense_nuts_leaf alone
 };
 
 __device__ __forceinline__ double log_add_exp(double x, double y) {
@@ -40,7 +43,9 @@ __device__ __forceinline__ double nuts_uniform(const NutsArgs& a, int64_t w, uin
     return u01(r[0]);
 }
 
-// the opening half kick and the drift of the next leaf, from the endpoint on the side v: p½ and q′ into pt and trial
+// the opening half kick and the drift of the next leaf, from the endpoint on the side v: p½ and q′ into pt and trial. DENSE: the endpoints hold
+// whitened momenta and gradients, so the kick is the same line, and the drift takes L·r½ once pt holds all of r½
+template <bool DENSE>
 __device__ __forceinline__ void next_leaf(const NutsArgs& a, int64_t w, int32_t v, double eps) {
     const double *qe = v > 0 ? a.s.qR : a.s.qL, *pe = v > 0 ? a.s.pR : a.s.pL, *ge = v > 0 ? a.s.gR : a.s.gL;
     const double hk = (double)v * (0.5 * eps), dr = (double)v * eps;
@@ -48,8 +53,9 @@ __device__ __forceinline__ void next_leaf(const NutsArgs& a, int64_t w, int32_t 
         const int64_t o = (int64_t)d * a.ld + w;
         const double ph = pe[o] + hk * ge[o];
         a.s.pt[o] = ph;
-        a.s.trial[o] = qe[o] + dr * (inv_mass_at(a.inv_mass, d) * ph);
+        if (!DENSE) a.s.trial[o] = qe[o] + dr * (inv_mass_at(a.inv_mass, d) * ph);
     }
+    if (DENSE) metric_lower(a.chol, a.D, a.s.pt, a.ld, w, [&](int d, double u) { const int64_t o = (int64_t)d * a.ld + w; a.s.trial[o] = qe[o] + dr * u; });
 }
 
 // a chain that has ended: θ_t takes the proposal if it moved, and the trial point is θ_t from now on
@@ -78,22 +84,23 @@ __device__ __forceinline__ void report(const NutsArgs& a, int64_t w) {
     if (a.o_nact && status == NUTS_BUILDING) atomicAdd(a.o_nact, 1);      // an integer count: order-free
 }
 
-__global__ __launch_bounds__(TPB) void k_nuts_open(NutsArgs a) {
+// DENSE in the two bodies below: the handle's factor L is set, and every momentum of the tree — the endpoints, ρ, ρ_s, the checkpoints — is the
+// whitened r = Lᵀp ~ N(0, I), every stored gradient Lᵀ∇E (metric_gradient). a.inv_mass is null, so K and the turn tests are the identity metric's.
+template <bool DENSE>
+__device__ __forceinline__ void nuts_open(const NutsArgs& a) {
     const Chain ch = chain_of(a);
     const Target tg = target_at(a, ch, a.theta_t, a.s.lp, a.s.glp, a.s.gpr);      // every lane: its prior_loop() votes across the wave
     if (!ch.live) return;
     const int64_t w = ch.w;
     const double beta = ch.beta, lp = tg.lp(w), lpt = tg.lpt;
     double K = 0.0;
-    for (int d = 0; d < a.D; ++d) {
-        const int64_t o = (int64_t)d * a.ld + w;
+    metric_gradient<DENSE>(tg, a.chol, a.s.gpr, a.D, a.ld, w, [&](int d, int64_t o, double g) {
         const double im = inv_mass_at(a.inv_mass, d);
-        const double g = tg.grad(o);
         const double p = a.s.pL[o], q = a.theta_t[o];      // the momenta were drawn into pL
         K += im * p * p;
         a.s.qL[o] = q; a.s.qR[o] = q; a.s.pR[o] = p; a.s.gL[o] = g; a.s.gR[o] = g;
         a.s.prop[o] = q; a.s.rho[o] = p;
-    }
+    });
     K *= 0.5;
     const double E0 = tempered_energy(beta, lp, lpt);
     const bool dead = dead_state(beta, E0, lp, lpt);
@@ -104,11 +111,12 @@ __global__ __launch_bounds__(TPB) void k_nuts_open(NutsArgs a) {
     const int32_t v = nuts_uniform(a, w, 0, OCTO_DRAWS_PURPOSE_NUTS_DIRECTION) < 0.5 ? 1 : -1;
     a.s.v[w] = v;
     if (dead) finish(a, w, false, lp, lpt);
-    else next_leaf(a, w, v, ch.eps);
+    else next_leaf<DENSE>(a, w, v, ch.eps);
     if (a.write_out) report(a, w);
 }
 
-__global__ __launch_bounds__(TPB) void k_nuts_leaf(NutsArgs a) {
+template <bool DENSE>
+__device__ __forceinline__ void nuts_leaf(const NutsArgs& a) {
     const Chain ch = chain_of(a);
     const Target tg = target_at(a, ch, a.s.trial, a.s.lp, a.s.glp, a.s.gpr);      // every lane: its prior_loop() votes across the wave; a frozen chain: at its θ_t, ignored
     if (!ch.live) return;
@@ -125,16 +133,14 @@ __global__ __launch_bounds__(TPB) void k_nuts_leaf(NutsArgs a) {
         double *ckp = a.s.ck_p + imax * plane, *ckr = a.s.ck_r + imax * plane;
         const double hk = (double)v * (0.5 * eps);
         double K = 0.0;
-        for (int d = 0; d < a.D; ++d) {
-            const int64_t o = (int64_t)d * a.ld + w;
+        metric_gradient<DENSE>(tg, a.chol, a.s.gpr, a.D, a.ld, w, [&](int d, int64_t o, double g) {
             const double im = inv_mass_at(a.inv_mass, d);
-            const double g = tg.grad(o);
             const double p = a.s.pt[o] + hk * g;
             K += im * p * p;
             const double rs = first ? p : a.s.rho_s[o] + p;
             qe[o] = a.s.trial[o]; pe[o] = p; ge[o] = g; a.s.rho_s[o] = rs;
             if (even) { ckp[o] = p; ckr[o] = rs; }
-        }
+        });
         K *= 0.5;
         const double E1 = tempered_energy(beta, lp, lpt);
         const double delta = (-E1 + K) - a.s.H0[w];
@@ -195,10 +201,15 @@ __global__ __launch_bounds__(TPB) void k_nuts_leaf(NutsArgs a) {
         if (status != NUTS_BUILDING) {
             a.s.status[w] = status;
             finish(a, w, a.s.sel[w] != 0, a.s.prop_lp[w], a.s.prop_lpt[w]);
-        } else next_leaf(a, w, a.s.v[w], eps);
+        } else next_leaf<DENSE>(a, w, a.s.v[w], eps);
     }
     if (a.write_out) report(a, w);
 }
+
+__global__ __launch_bounds__(TPB) void k_nuts_open(NutsArgs a) { nuts_open<false>(a); }
+__global__ __launch_bounds__(TPB) void k_nuts_leaf(NutsArgs a) { nuts_leaf<false>(a); }
+__global__ __launch_bounds__(TPB) void k_dense_nuts_open(NutsArgs a) { nuts_open<true>(a); }
+__global__ __launch_bounds__(TPB) void k_dense_nuts_leaf(NutsArgs a) { nuts_leaf<true>(a); }
 
 __global__ __launch_bounds__(TPB) void k_nuts_report(NutsArgs a) {
     const int64_t w = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -218,6 +229,10 @@ int32_t octo_draws_nuts_device(octo_draws* h, uint64_t seed, uint64_t step, uint
     if (n_rounds < 0) return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: n_rounds >= 0");
     const bool has_model = has_target(h);
     if (int rc = check_sampler_call(h, "octo_draws_nuts_device", W, ld, d_eps, eps, has_model, d_logpost, d_loglike)) return rc;
+    const bool dense = h->d_metric != nullptr;
+    if (dense && d_inv_mass) return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: d_inv_mass must be NULL while a dense metric is set (octo_draws_use_metric)");
+    if (resume && h->nuts_depth != 0 && h->nuts_metric != h->d_metric)
+        return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: resume needs the dense metric (octo_draws_use_metric) of the call it resumes");
     if (resume && (h->nuts_depth != max_depth || h->nuts_W != W || h->nuts_ld != ld || h->nuts_seed != seed || h->nuts_step != step || h->nuts_chain0 != chain0))
         return fail(h, OCTO_EINVAL, "octo_draws_nuts_device: resume needs a previous call with the same W, ld, max_depth, seed, step and chain0");
     if (W == 0) {
@@ -237,11 +252,13 @@ int32_t octo_draws_nuts_device(octo_draws* h, uint64_t seed, uint64_t step, uint
     double *lp = a.s.lp, *glp = a.s.glp;
     if (!has_model) { a.s.lp = nullptr; a.s.glp = nullptr; }
     a.o_lp = d_logpost; a.o_ll = d_loglike; a.o_la = d_log_accept; a.o_acc = d_accepted; a.o_depth = d_depth; a.o_nleaf = d_n_leapfrog; a.o_div = d_diverged;
-    a.o_nact = d_n_active;
+    a.o_nact = d_n_active; a.chol = h->d_metric;
     if (d_n_active) OCHK(h, hipMemsetAsync(d_n_active, 0, sizeof(int32_t), st));      // the last launch of the call counts into it
     if (!resume)
         if (int rc = octo_draws_momentum_device(h, seed, step, chain0, W, ld, d_inv_mass, a.s.pL, hip_stream)) return rc;
-    if (int rc = run_rounds(h, st, a, has_model, d_theta_t, lp, glp, n_rounds, resume != 0, k_nuts_open, k_nuts_leaf, k_nuts_report)) return rc;
+    if (int rc = run_rounds(h, st, a, has_model, d_theta_t, lp, glp, n_rounds, resume != 0, dense ? k_dense_nuts_open : k_nuts_open, dense ? k_dense_nuts_leaf : k_nuts_leaf,
+                            k_nuts_report)) return rc;
+    h->nuts_metric = h->d_metric;
     h->nuts_W = W; h->nuts_ld = ld; h->nuts_depth = max_depth; h->nuts_seed = seed; h->nuts_step = step; h->nuts_chain0 = chain0;
     return OCTO_OK;
 }

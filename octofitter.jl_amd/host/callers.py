@@ -571,7 +571,7 @@ def _tree_means(depth, n_leapfrog, diverged):
 
 
 def hmc_warmup(pd, theta_t, n_warmup, n_leapfrog=8, eps=0.1, inv_mass=None, target_accept=0.8, seed=0, step=0, chain0=0, gamma=0.05, t0=10.0, kappa=0.75,
-               record=None, max_depth=None):
+               record=None, max_depth=None, metric="diag"):
     """Warm-up of PriorDraws.hmc_step on the W chains of theta_t ([D, W] on the device, updated in place) at β = 1 — on a handle without a
     model: on the prior. n_warmup rounds on the schedule of warmup_windows; round r is one hmc_step with step number step + r and then
       * the dual-averaging update of ε from the round's mean acceptance probability (PriorDraws.adapt_step, one group, δ = target_accept);
@@ -584,9 +584,19 @@ def hmc_warmup(pd, theta_t, n_warmup, n_leapfrog=8, eps=0.1, inv_mass=None, targ
     max_depth: None, or the tree depth of PriorDraws.nuts_step, which then is the round's step (n_leapfrog is not used): its log_accept goes where
     dH went — min(1, exp(·)) of it is the transition's mean acceptance statistic — and the result gains tree [n_warmup, 3], per round the mean
     depth, the mean n_leapfrog and the number of divergences.
+    metric: "diag", or "dense": the rounds run under the dense metric L·Lᵀ (PriorDraws.use_metric, D <= DENSE_MAX_D), L starting at diag(√inv_mass);
+    inside a slow window the states enter the pooled co-moments (PriorDraws.cov) where the moments are, and at a window's last round
+    L <- metric_dense(regularize=True) of them, written only where the factorisation holds: otherwise the previous factor stays, decided on the
+    device. The dual averaging, the schedule and the restart of ε are the same. The result gains metric_chol [D, D] (lower), and inv_mass is
+    diag(L·Lᵀ); record gains cov's triples under mom_in / mom, and chol (packed) and info after a window's factorisation. On return the handle
+    is back on the metric it had.
     inv_mass: [D] (a copy is adapted) or None = 1. Returns dict(theta_t, eps (a [1] tensor), inv_mass [D], accept_stat [n_warmup], step (the
     next step number)), device tensors."""
     import torch
+    from .draws import pack_lower, unpack_lower
+    if metric not in ("diag", "dense"):
+        raise ValueError('hmc_warmup: metric must be "diag" or "dense"')
+    dense = metric == "dense"
     dev = theta_t.device
     D, W = int(theta_t.shape[0]), int(theta_t.shape[1])
     n = int(n_warmup)
@@ -603,11 +613,16 @@ def hmc_warmup(pd, theta_t, n_warmup, n_leapfrog=8, eps=0.1, inv_mass=None, targ
     accept_stat = torch.empty(n, dtype=torch.float64, device=dev)
     tree = None if max_depth is None else torch.empty((n, 3), dtype=torch.float64, device=dev)
     mom, in_window, k = None, False, 0
+    chol, before = None, getattr(pd, "_active_metric", None)
+    if dense:
+        chol = pack_lower(torch.diag(torch.sqrt(inv_mass)))
+        pd.use_metric(chol)
+    step_mass = None if dense else inv_mass
     for r in range(n):
         if max_depth is None:
-            _lp, _ll, dH, acc = pd.hmc_step(theta_t, eps=eps_w, n_leapfrog=n_leapfrog, inv_mass=inv_mass, seed=seed, step=step + r, chain0=chain0)
+            _lp, _ll, dH, acc = pd.hmc_step(theta_t, eps=eps_w, n_leapfrog=n_leapfrog, inv_mass=step_mass, seed=seed, step=step + r, chain0=chain0)
         else:
-            _lp, _ll, dH, acc, *counts = pd.nuts_step(theta_t, eps=eps_w, inv_mass=inv_mass, max_depth=max_depth, seed=seed, step=step + r, chain0=chain0)
+            _lp, _ll, dH, acc, *counts = pd.nuts_step(theta_t, eps=eps_w, inv_mass=step_mass, max_depth=max_depth, seed=seed, step=step + r, chain0=chain0)
             tree[r] = _tree_means(*counts)
         k += 1
         rec = None if record is None else dict(round=r, k=k, dH=dH, accepted=acc, theta_t=theta_t.clone(), state_in=state.clone(), use_average=r == n - 1,
@@ -616,19 +631,30 @@ def hmc_warmup(pd, theta_t, n_warmup, n_leapfrog=8, eps=0.1, inv_mass=None, targ
         accept_stat[r:r + 1] = a
         in_window = in_window or r in first
         if in_window:
-            mom = pd.moments(theta_t, out=mom, accumulate=r not in first)
+            mom = (pd.cov if dense else pd.moments)(theta_t, out=mom, accumulate=r not in first)
         if rec is not None:
             rec.update(state=state.clone(), accept_stat=a, eps_w=eps_w.clone(), in_window=in_window, first=r in first, last=r in last,
                        mom=tuple(t.clone() for t in mom) if in_window else None, inv_mass_in=inv_mass.clone())
             record.append(rec)
         if r in last:
-            pd.metric(mom[0], mom[1][0], mom[2][0], inv_mass, regularize=True)
+            if dense:
+                _, info = pd.metric_dense(mom[0], mom[2], chol, regularize=True)      # chol is written only where info = 0: nothing is read back
+                if rec is not None:
+                    rec.update(chol=chol.clone(), info=info)
+            else:
+                pd.metric(mom[0], mom[1][0], mom[2][0], inv_mass, regularize=True)
             pd.adapt_init(1, torch.exp(state[:, 1]), state=state)
             eps_w = torch.exp(state[:, 0]).expand(W).contiguous()
             in_window, k = False, 0
             if rec is not None:
                 rec.update(inv_mass=inv_mass.clone(), state_restart=state.clone())
+    if dense:
+        pd.use_metric(before)
+        L = unpack_lower(chol, D)
+        inv_mass = (L * L).sum(dim=1)
     out = dict(theta_t=theta_t, eps=eps_w[:1].clone() if W else torch.exp(state[:, 1]), inv_mass=inv_mass, accept_stat=accept_stat, step=step + n)
+    if dense:
+        out["metric_chol"] = L
     if tree is not None:
         out["tree"] = tree
     return out
@@ -677,7 +703,17 @@ def diagnose_draws_device(samples, device=0):
         return {k: v.cpu().numpy() for k, v in d.items()}
 
 
-def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leapfrog=8, target_accept=0.8, init=None, eps=0.1, seed=0, diagnose=False):
+def _sampling_metric(pd, wu, pack_lower):
+    """(the inv_mass of the sampling rounds, what the result gains) after hmc_warmup: a dense warm-up's factor is set on the handle (the rounds
+    then pass no inv_mass) and returned as metric_chol; the handle is closed by its driver, which ends the setting"""
+    if "metric_chol" not in wu:
+        return wu["inv_mass"], {}
+    pd.use_metric(pack_lower(wu["metric_chol"]))
+    return None, dict(metric_chol=wu["metric_chol"])
+
+
+def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leapfrog=8, target_accept=0.8, init=None, eps=0.1, seed=0, diagnose=False,
+                       metric="diag"):
     """The reference's main entry (octofit: Pathfinder start, then HMC with step-size and metric adaptation) with every piece on the device:
     n_chains chains at β = 1, static trajectories of n_leapfrog steps, a diagonal metric.
       starts    init [D, n_chains] in θ_t, or pathfinder_device(model, n_draws=n_chains, seed=seed)["theta_t"];
@@ -687,9 +723,11 @@ def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leap
                 running moments (PriorDraws.chain_moments); R̂ from two PriorDraws.moments calls at the end.
     Returns dict(samples [n_samples, D, n_chains] natural domain, samples_t the same as θ_t, logpost [n_samples, n_chains], accept_stat
     [n_warmup + n_samples] (the mean of min(1, exp(dH)) of each round), eps, inv_mass [D], rhat [D], names, state = dict(theta_t, step)), NumPy.
-    diagnose=True adds ess_bulk, ess_tail, rhat_rank and ess_basic [D] of samples_t (PriorDraws.diagnose; NaN with n_samples < 8)."""
+    diagnose=True adds ess_bulk, ess_tail, rhat_rank and ess_basic [D] of samples_t (PriorDraws.diagnose; NaN with n_samples < 8).
+    metric="dense": hmc_warmup(metric="dense") and the sampling rounds under the factor it ends with; the dict gains metric_chol [D, D] (lower),
+    and inv_mass is diag(L·Lᵀ)."""
     import torch
-    from .draws import PriorDraws
+    from .draws import PriorDraws, pack_lower
     Cn, nw, ns = int(n_chains), int(n_warmup), int(n_samples)
     if Cn < 2 or nw < 0 or ns < 1:
         raise ValueError("octofit_hmc_device: n_chains >= 2, n_warmup >= 0, n_samples >= 1")
@@ -702,15 +740,16 @@ def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leap
         raise ValueError(f"octofit_hmc_device: init must be [D = {D}, n_chains = {Cn}] in θ_t")
     with PriorDraws(model) as pd:
         inv_mass = _default_metric(pd, seed, dev, None)
-        wu = hmc_warmup(pd, theta_t, nw, n_leapfrog=n_leapfrog, eps=eps, inv_mass=inv_mass, target_accept=target_accept, seed=seed)
+        wu = hmc_warmup(pd, theta_t, nw, n_leapfrog=n_leapfrog, eps=eps, inv_mass=inv_mass, target_accept=target_accept, seed=seed, metric=metric)
         eps_w, inv_mass = wu["eps"].expand(Cn).contiguous(), wu["inv_mass"]
+        step_mass, dense = _sampling_metric(pd, wu, pack_lower)
         rec_t = torch.empty((ns, D, Cn), dtype=torch.float64, device=dev)
         rec_lp = torch.empty((ns, Cn), dtype=torch.float64, device=dev)
         acc_s = torch.empty(ns, dtype=torch.float64, device=dev)
         cmean, cm2 = torch.empty_like(theta_t), torch.empty_like(theta_t)
         state = pd.adapt_init(1, eps)      # never fed back: adapt_step is the reduction that gives the round's acceptance statistic
         for r in range(ns):
-            lp, _ll, dH, acc = pd.hmc_step(theta_t, eps=eps_w, n_leapfrog=n_leapfrog, inv_mass=inv_mass, seed=seed, step=nw + r)
+            lp, _ll, dH, acc = pd.hmc_step(theta_t, eps=eps_w, n_leapfrog=n_leapfrog, inv_mass=step_mass, seed=seed, step=nw + r)
             acc_s[r:r + 1] = pd.adapt_step(state, dH, acc, r + 1, delta=target_accept, want_eps=False)[0]
             rec_t[r] = theta_t
             rec_lp[r] = lp
@@ -721,18 +760,19 @@ def octofit_hmc_device(model, n_chains=1024, n_warmup=200, n_samples=200, n_leap
         return dict(**_recorded(model, rec_t, rec_lp, pd),
                     accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
                     rhat=rhat.cpu().numpy(), names=list(model.names), state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns),
-                    **{k: v.cpu().numpy() for k, v in extra.items()})
+                    **{k: v.cpu().numpy() for k, v in {**extra, **dense}.items()})
 
 
-def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_depth=10, target_accept=0.8, init=None, eps=0.1, seed=0, diagnose=False):
+def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_depth=10, target_accept=0.8, init=None, eps=0.1, seed=0, diagnose=False,
+                        metric="diag"):
     """octofit_hmc_device with the reference's own sampler: every round is one NUTS transition (PriorDraws.nuts_step: multinomial sampling, the
     generalised no-U-turn criterion, trees of depth <= max_depth) instead of a static trajectory. The starts, the metric, the warm-up
     (hmc_warmup(max_depth=max_depth)), the recording and R̂ are octofit_hmc_device's.
     Returns its dict — accept_stat is the mean over the chains of each transition's mean acceptance statistic — plus, per round of warm-up and
     sampling, depth and n_leapfrog [n_warmup + n_samples] (means over the chains) and diverged [n_warmup + n_samples] (counts); diagnose=True adds
-    octofit_hmc_device's four keys."""
+    octofit_hmc_device's four keys; metric="dense" as there: the reference's dense Euclidean metric."""
     import torch
-    from .draws import PriorDraws
+    from .draws import PriorDraws, pack_lower
     Cn, nw, ns = int(n_chains), int(n_warmup), int(n_samples)
     if Cn < 2 or nw < 0 or ns < 1:
         raise ValueError("octofit_nuts_device: n_chains >= 2, n_warmup >= 0, n_samples >= 1")
@@ -745,8 +785,9 @@ def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_d
         raise ValueError(f"octofit_nuts_device: init must be [D = {D}, n_chains = {Cn}] in θ_t")
     with PriorDraws(model) as pd:
         inv_mass = _default_metric(pd, seed, dev, None)
-        wu = hmc_warmup(pd, theta_t, nw, eps=eps, inv_mass=inv_mass, target_accept=target_accept, seed=seed, max_depth=max_depth)
+        wu = hmc_warmup(pd, theta_t, nw, eps=eps, inv_mass=inv_mass, target_accept=target_accept, seed=seed, max_depth=max_depth, metric=metric)
         eps_w, inv_mass = wu["eps"].expand(Cn).contiguous(), wu["inv_mass"]
+        step_mass, dense = _sampling_metric(pd, wu, pack_lower)
         rec_t = torch.empty((ns, D, Cn), dtype=torch.float64, device=dev)
         rec_lp = torch.empty((ns, Cn), dtype=torch.float64, device=dev)
         acc_s = torch.empty(ns, dtype=torch.float64, device=dev)
@@ -754,7 +795,7 @@ def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_d
         cmean, cm2 = torch.empty_like(theta_t), torch.empty_like(theta_t)
         state = pd.adapt_init(1, eps)      # never fed back: adapt_step is the reduction that gives the round's acceptance statistic
         for r in range(ns):
-            lp, _ll, la, acc, *counts = pd.nuts_step(theta_t, eps=eps_w, inv_mass=inv_mass, max_depth=max_depth, seed=seed, step=nw + r)
+            lp, _ll, la, acc, *counts = pd.nuts_step(theta_t, eps=eps_w, inv_mass=step_mass, max_depth=max_depth, seed=seed, step=nw + r)
             acc_s[r:r + 1] = pd.adapt_step(state, la, acc, r + 1, delta=target_accept, want_eps=False)[0]
             tree[r] = _tree_means(*counts)
             rec_t[r] = theta_t
@@ -767,7 +808,7 @@ def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_d
         return dict(**_recorded(model, rec_t, rec_lp, pd),
                     accept_stat=torch.cat([wu["accept_stat"], acc_s]).cpu().numpy(), eps=float(wu["eps"][0]), inv_mass=inv_mass.cpu().numpy(),
                     rhat=rhat.cpu().numpy(), depth=tree[:, 0], n_leapfrog=tree[:, 1], diverged=tree[:, 2].astype(np.int64), names=list(model.names),
-                    state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns), **{k: v.cpu().numpy() for k, v in extra.items()})
+                    state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns), **{k: v.cpu().numpy() for k, v in {**extra, **dense}.items()})
 
 
 def _optimizer_starts(pd, model, N, n_starts, seed, dev, inv_mass):

@@ -30,6 +30,10 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     bad = draws.reference_fit(ref, count[0:1], mean[0], m2[0])      # … a mean-field normal on θ_t from one group's moments (reference_set: from μ, σ)
     with draws.reference(ref): ...                          # … every call inside reads the table in place of the handle's priors
     draws.reference_exchange(s2r_a, θ_a, lp_a, ll_a, None, s2r_b, θ_b, lp_b, ll_b, ref)      # … the two legs' target replicas trade places
+    count, mean, m2 = draws.cov(θ_t)                        # the dense metric: pooled co-moments of the chains, [1], [D], [D(D+1)/2] packed by rows
+    chol, info = draws.metric_dense(count, m2, chol)        # … their regularised Cholesky factor L (M⁻¹ = L·Lᵀ), written only where it exists (info = 0)
+    y = draws.metric_apply(chol, x, transpose=False)        # … L·x or Lᵀ·x of the columns of x [D, n]
+    with draws.use_metric(chol): ...                        # … hmc_step and nuts inside run under L·Lᵀ and take no inv_mass (pack_lower, unpack_lower)
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -64,6 +68,7 @@ LBFGS_ACTIVE, LBFGS_GTOL, LBFGS_FTOL, LBFGS_LINESEARCH, LBFGS_DEAD = 0, 1, 2, 3,
 PF_MAX_D = 64                      # OCTO_DRAWS_PF_MAX_D
 PF_MAX_ELBO_DRAWS = 32             # OCTO_DRAWS_PF_MAX_ELBO_DRAWS
 MAX_GROUPS = 64                    # OCTO_DRAWS_MAX_GROUPS
+DENSE_MAX_D = 64                   # OCTO_DRAWS_DENSE_MAX_D
 DIAG_RHAT, DIAG_ESS_BULK, DIAG_ESS_TAIL, DIAG_RHAT_BASIC, DIAG_ESS_BASIC, DIAG_Q05, DIAG_Q50, DIAG_Q95, DIAG_N_STATS = range(9)      # OCTO_DRAWS_DIAG_*
 PT_ACC_COLUMNS = ("n", "A", "n_f", "m_f", "s_f", "n_b", "m_b", "s_b")      # the columns of d_acc [T − 1][8]
 PT_SUMMARY = ("barrier", "log_evidence_fwd", "log_evidence_rev", "log_evidence")      # the entries of d_summary, in order
@@ -131,6 +136,10 @@ _SIGS = {
                                                   C.c_int64, C.c_int64] + [C.c_void_p] * 7),
     "octo_draws_nested_move_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    "octo_draws_cov_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_metric_dense_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_metric_apply_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_use_metric": (C.c_int32, [C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -230,10 +239,41 @@ def group_ids(group, W, dev, what):
     return g
 
 
+def pack_lower(L):
+    """The packed factor [K(K+1)/2] (row i at i(i+1)/2, what octo_draws_use_metric reads) of the lower triangle of L [K, K]; what stands above
+    the diagonal is dropped."""
+    import torch
+    K = int(L.shape[0])
+    i, j = torch.tril_indices(K, K, device=L.device)
+    return L[i, j].contiguous()
+
+
+def unpack_lower(packed, K):
+    """The lower-triangular [K, K] matrix of a packed factor [K(K+1)/2], zeros above the diagonal."""
+    import torch
+    L = torch.zeros((K, K), dtype=packed.dtype, device=packed.device)
+    i, j = torch.tril_indices(K, K, device=packed.device)
+    L[i, j] = packed
+    return L
+
+
 def is_adapt_state(state, G, dev):
     """Whether `state` is a dual-averaging state: a contiguous float64 [G, 4] tensor on `dev`."""
     import torch
     return state.dtype == torch.float64 and state.device == dev and state.shape == (G, 4) and state.is_contiguous()
+
+
+class _MetricScope:
+    """What PriorDraws.use_metric returns: leaving it as a context manager returns the handle to the diagonal metric."""
+    def __init__(self, pd):
+        self._pd = pd
+
+    def __enter__(self):
+        return self._pd
+
+    def __exit__(self, *exc):
+        self._pd.use_metric(None)
+        return False
 
 
 class PriorDraws(companion.Handle):
@@ -729,6 +769,72 @@ class PriorDraws(companion.Handle):
                                                       self._stream(stream, self.device)))
         self._keep = (count, mean, m2, inv_mass)
         return inv_mass
+
+    # ---- the dense metric (include/octofitter_hip_draws.h, "The dense metric"): packed lower triangles, row i at i(i+1)/2 (pack_lower, unpack_lower)
+    def cov(self, x, out=None, accumulate=False, stream=None):
+        """Pooled co-moments of the chains in x [K, W], K <= DENSE_MAX_D (chains with a non-finite value are excluded): (count [1], mean [K],
+        m2 [K(K+1)/2] packed = Σ(x_i − mean_i)(x_j − mean_j)), device tensors. out=(count, mean, m2): write into these; with accumulate=True
+        Chan-merge this call's block into what they hold. Asynchronous on `stream`."""
+        K, W, ld = chain_matrix(x, None, self.device, "cov", "x")
+        P = K * (K + 1) // 2
+        if accumulate and out is None:
+            raise ValueError("cov: accumulate=True needs out=(count, mean, m2)")
+        if out is None:
+            cnt, mean, m2 = self._out(1), self._out(K), self._out(P)
+        else:
+            cnt, mean, m2 = out
+            if cnt.shape != (1,) or mean.shape != (K,) or m2.shape != (P,) or not (cnt.is_contiguous() and mean.is_contiguous() and m2.is_contiguous()):
+                raise ValueError(f"cov: out must be contiguous (count [1], mean [{K}], m2 [{P}])")
+        self._check(self.lib.octo_draws_cov_device(self._h, W, ld, K, x.data_ptr(), 1 if accumulate else 0, cnt.data_ptr(), mean.data_ptr(), m2.data_ptr(),
+                                                   self._stream(stream, self.device)))
+        self._keep = (x,)
+        return cnt, mean, m2
+
+    def metric_dense(self, count, m2, chol, regularize=True, info=None, stream=None):
+        """The packed Cholesky factor L of the covariance of cov's (count [1], m2 [K(K+1)/2]) into chol [K(K+1)/2] (written only where the
+        factorisation holds): M2/(n − 1), with regularize Stan's shrinkage towards 1e-3·I. Returns (chol, info int32 [1]): info = 0, or j + 1 where
+        pivot j was not finite and > 0 (n < 2: 1) and chol is untouched. Nothing is read back."""
+        import torch
+        P = int(m2.numel())
+        K = int((np.sqrt(8 * P + 1) - 1) / 2 + 0.5)
+        for t, n in ((count, 1), (m2, K * (K + 1) // 2), (chol, P)):
+            if t.dtype != torch.float64 or t.device != self.device or t.numel() != n or not t.is_contiguous():
+                raise ValueError("metric_dense: count [1], m2 [K(K+1)/2] and chol [K(K+1)/2] must be contiguous float64 tensors on the handle's device")
+        if info is None:
+            info = self._out(1, dtype=torch.int32)
+        self._check(self.lib.octo_draws_metric_dense_device(self._h, K, count.data_ptr(), m2.data_ptr(), 1 if regularize else 0, chol.data_ptr(),
+                                                            info.data_ptr(), self._stream(stream, self.device)))
+        self._keep = (count, m2, chol, info)
+        return chol, info
+
+    def metric_apply(self, chol, x, transpose=False, out=None, stream=None):
+        """L·x (transpose=False) or Lᵀ·x of the columns of x [D, n] with the packed factor chol [D(D+1)/2]; out: a tensor of x's layout, x itself
+        for the product in place, None for a new one. Returns out."""
+        import torch
+        dev = self.device
+        D = self.D
+        _, n, ld = chain_matrix(x, D, dev, "metric_apply", "x")
+        if chol.dtype != torch.float64 or chol.device != dev or chol.numel() != D * (D + 1) // 2 or not chol.is_contiguous():
+            raise ValueError("metric_apply: chol must be a contiguous float64 [D(D+1)/2] tensor on the handle's device")
+        if out is None:
+            out = self._out(n, D, ld)
+        elif chain_matrix(out, D, dev, "metric_apply", "out") != (D, n, ld):
+            raise ValueError("metric_apply: out must have x's shape and leading dimension")
+        self._check(self.lib.octo_draws_metric_apply_device(self._h, n, ld, chol.data_ptr(), 1 if transpose else 0, x.data_ptr(), out.data_ptr(),
+                                                            self._stream(stream, dev)))
+        self._keep = (chol, x, out)
+        return out
+
+    def use_metric(self, chol):
+        """octo_draws_use_metric: from the next call on hmc_step and nuts take the dense metric L·Lᵀ of the packed factor chol [D(D+1)/2] (and refuse
+        an inv_mass); None returns to the per-call diagonal metric. The handle keeps the tensor alive while it is set. Also a context manager:
+        `with pd.use_metric(chol): …` sets None on leaving."""
+        import torch
+        if chol is not None and (chol.dtype != torch.float64 or chol.device != self.device or chol.numel() != self.D * (self.D + 1) // 2 or not chol.is_contiguous()):
+            raise ValueError("use_metric: chol must be a contiguous float64 [D(D+1)/2] tensor on the handle's device, or None")
+        self._check(self.lib.octo_draws_use_metric(self._h, ptr(chol)))
+        self._active_metric = chol
+        return _MetricScope(self)
 
     def adapt_init(self, G, eps0, state=None, stream=None):
         """The dual-averaging state [G, 4] = (log ε, log ε̄, H̄, μ) started at eps0 (a number, or one value per group); state: written in place."""
