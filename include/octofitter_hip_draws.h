@@ -75,6 +75,15 @@
  *   purpose 11: uniform number i of update j of live slot c at `iter`, counter (c, j·128 + i, 11, iter), word 0 (words 1 and 2 of i = 0: the interval's
  *               position and the split of the steps)
  *
+ * The fourteenth is the dense metric of the HMC step and NUTS (octo_draws_cov_device … octo_draws_use_metric), stated at its declaration. No random number.
+ *
+ * The fifteenth is differential evolution (octo_draws_de_device): the gradient-free global search between the prior search and the local optimisers,
+ * a population climbing ℓπ in generations of one forward log-posterior call, stated in full at its declaration (tests/de_reference.py restates it).
+ * Its stream adds
+ *   purpose 12: block k of individual i at generation gen, counter (i, k, 12, gen) — k = 0: the three parent picks and j_rand (words 0 … 3) · k = 1: the
+ *               two adaptation tests and the two new values · k = 2 + d/4, word d % 4: the crossover uniform of coordinate d · k = 18 + d/4, word
+ *               d % 4: the bound-repair uniform of coordinate d (D <= 64: the blocks of the two do not meet)
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -854,6 +863,61 @@ int32_t octo_draws_metric_dense_device(octo_draws* h, int32_t K, const double* d
 int32_t octo_draws_metric_apply_device(octo_draws* h, int64_t n, int64_t ld, const double* d_chol, int32_t transpose, const double* d_x, double* d_out,
                                        void* hip_stream);
 int32_t octo_draws_use_metric(octo_draws* h, const double* d_chol);
+
+/* ---- Differential evolution (the fifteenth part; Storn & Price 1997, DE/rand/1/bin; the self-adaptation of Brest et al. 2006, "jDE"; the stage of the
+ * reference's initialisation between its prior search and Pathfinder, src/initialization.jl:188-289, which calls BlackBoxOptim's
+ * adaptive_de_rand_1_bin_radiuslimited — recalled, not read: that optimiser is steady-state on a host generator and its source is not in this tree.
+ * This is the same family made GENERATIONAL, so that the W trial points of a generation share one forward octo_model_logpost_device call). The
+ * function is stated in full so that a restatement elsewhere (tests/de_reference.py) and the device compute the same function.
+ *
+ * State      the population X = d_theta_t [D][ld] in θ_t, W individuals. f_i = ℓπ(X_i) — on a handle without a model ℓprior_t(X_i), with the
+ *            HMC step's ℓprior_t (the same routine, order and sentinel); a set expression program and a reference table in use apply as they do
+ *            to the slice sampler. A dead or non-finite point (the HMC step's dead states at β = 1, β = 0 without a model) has f = −Inf.
+ *            Per individual (F_i, CR_i): d_fcr, or F = OCTO_DRAWS_DE_F0 and CR = OCTO_DRAWS_DE_CR0 at the opening with d_fcr NULL.
+ * Uniforms   U(k, word) = the uniform of that word of counter (i, k, 12, gen), i the individual's index, gen = gen0 + g for generation g of the
+ *            call. Every ⌊U·n⌋ below is at most n − 1.
+ * A generation, for every individual i from the population and f as the generation before left them (the update is synchronous):
+ * Parameters F′ = U(1,0) < OCTO_DRAWS_DE_TAU_F ? OCTO_DRAWS_DE_F_LOW + OCTO_DRAWS_DE_F_SPAN·U(1,1) : F_i · CR′ = U(1,2) < OCTO_DRAWS_DE_TAU_CR ? U(1,3) : CR_i
+ * Neighbours n = W − 1 with radius = 0 (the whole population), otherwise n = min(max(2·radius, 3), W − 1). With h = ⌊n/2⌋, member
+ *            m_k = (i − h + k + (k >= h ? 1 : 0)) mod W for k = 0 … n − 1: distinct, none of them i.
+ * Parents    a = ⌊U(0,0)·n⌋ · b = ⌊U(0,1)·(n − 1)⌋, b += (b >= a) · c = ⌊U(0,2)·(n − 2)⌋, c += (c >= min(a, b)), then c += (c >= max(a, b)) ·
+ *            r1 = m_a, r2 = m_b, r3 = m_c.
+ * Trial      j_rand = ⌊U(0,3)·D⌋. Coordinate d CROSSES iff d = j_rand or U(2 + d/4, d % 4) < CR′: v_d = X[d][r3] + F′·(X[d][r1] − X[d][r2]), the
+ *            difference, the product and the sum each rounded by itself (no fused multiply-add). The others keep v_d = X[d][i].
+ * Bounds     with d_lo and d_hi: a crossing v_d < lo_d becomes lo_d + U(18 + d/4, d % 4)·(X[d][i] − lo_d), a crossing v_d > hi_d becomes
+ *            hi_d − U(18 + d/4, d % 4)·(hi_d − X[d][i]), each operation rounded by itself. A NaN stays NaN. The population is not clipped.
+ * Selection  f′ at v. The trial replaces the individual iff f′ > −Inf and f′ >= f_i: X_i, f_i, ℓ and ℓprior_t become the trial's (nothing is
+ *            evaluated twice), (F_i, CR_i) <- (F′, CR′), and n_accept_i counts it.
+ *
+ * On DEVICE buffers, asynchronous on hip_stream: no host synchronisation, no allocation once the handle's work array holds (5·D + 12)·ld doubles
+ * (octo_draws_de_work_doubles; it grows behind the handle's own stream), no graph capture, no floating-point atomic. A generation is the forward
+ * call and ONE launch: a lane decides its own selection and builds its next trial point from parents read as the selection leaves them, deciding
+ * each parent's selection again from that parent's f and f′; the population and the trial points are kept twice, one copy read and one written.
+ * resume = 0 opens — f of the population — and makes n_gen generations: n_gen + 1 log-posterior calls. resume = 1 continues the state the handle
+ * holds (d_theta_t and d_fcr are then written only): the same seed, W, ld, radius and bounds, and gen0 = the gen0 + n_gen of the call before it.
+ * Two calls of a and b generations give the bits of one call of a + b.
+ *   d_theta_t    [D][ld]  in/out: the population; columns W … ld − 1 are not touched
+ *   d_lo, d_hi   [D]      both or neither
+ *   d_fcr        [2][ld]  or NULL: F, then CR; read at the opening, written by every call
+ *   d_logpost, d_loglike [W]   or NULL: f and ℓ = f − ℓprior_t (−Inf where that is not finite) of the population as the call leaves it
+ *   d_n_accept   [W]      int32 or NULL: acceptances since the opening
+ *   d_best       [1]      int32 or NULL: the index of the highest finite f, ties to the lower index; −1 with none finite
+ *   d_best_logpost [1]    or NULL: the f of that individual (−Inf with none)
+ *   d_n_improved [1]      int32 or NULL: the acceptances of the last generation made (0 at the opening)
+ * OCTO_EINVAL: NULL handle; W < 4, ld < W, W > 2^30; radius < 0; n_gen < 0; one of d_lo, d_hi without the other; NULL d_theta_t; d_logpost or
+ * d_loglike on a handle without a model; resume without such a previous call. */
+#define OCTO_DRAWS_PURPOSE_DE 12
+#define OCTO_DRAWS_DE_TAU_F 0.1
+#define OCTO_DRAWS_DE_F_LOW 0.1
+#define OCTO_DRAWS_DE_F_SPAN 0.9
+#define OCTO_DRAWS_DE_TAU_CR 0.1
+#define OCTO_DRAWS_DE_F0 0.5
+#define OCTO_DRAWS_DE_CR0 0.9
+int32_t octo_draws_de_device(octo_draws* h, uint64_t seed, uint64_t gen0, int64_t W, int64_t ld, double* d_theta_t, const double* d_lo,
+                             const double* d_hi, int32_t radius, int32_t n_gen, int32_t resume, double* d_fcr, double* d_logpost, double* d_loglike,
+                             int32_t* d_n_accept, int32_t* d_best, double* d_best_logpost, int32_t* d_n_improved, void* hip_stream);
+/* Host only: the doubles of that work array at D coordinates and leading dimension ld, (5·D + 12)·ld; 0 with D < 1 or ld < 0. */
+int64_t octo_draws_de_work_doubles(int32_t D, int64_t ld);
 
 #ifdef __cplusplus
 }

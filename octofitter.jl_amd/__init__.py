@@ -25,7 +25,8 @@ from .host.model import LogDensityModel  # noqa: F401,E402
 from .host.callers import (guess_starting_position, octofit_rejection, rejection_evaluate_likelihoods, pointwise_like,  # noqa: F401,E402
                            guess_starting_position_device, octofit_rejection_device, simulate_tables, posterior_predictive,
                            pointwise_like_rows, waic, loo, octofit_pt_device, octofit_pigeons_device, optimize_starting_points_device, pathfinder_device,
-                           warmup_windows, hmc_warmup, octofit_hmc_device, octofit_nuts_device, diagnose_draws_device, octofit_nested_device)
+                           warmup_windows, hmc_warmup, octofit_hmc_device, octofit_nuts_device, diagnose_draws_device, octofit_nested_device,
+                           global_search_device, initialize_device)
 from .host.draws import PriorDraws  # noqa: F401,E402
 from .host import predict  # noqa: F401,E402
 from .host.predict import Predictor  # noqa: F401,E402

@@ -16,6 +16,8 @@
 // one copy per unit. How the handle's work allocations are cut into their parts is octo_draws_layout.h.
 // The thirteenth part of the library, nested sampling (octo_draws_nested.hip), takes DrawArgs, cube_link and draw_block (what k_draw does after its Philox
 // call) beside the samplers' head, preamble, target and round driver.
+// The fifteenth part, differential evolution (octo_draws_de.hip), takes the samplers' head, preamble, target, dead test and round driver as the slice
+// sampler does, one generation a run_rounds call of one round.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
 
@@ -343,6 +345,12 @@ struct octo_draws : CompanionBase {
     // (octo_draws_use_metric; null: the per-call diagonal metric), and the one the open NUTS transition was started with
     const double* d_metric = nullptr;
     const double* nuts_metric = nullptr;
+    // differential evolution (octo_draws_de.hip), grown on demand: the population, its trial points and their copies in one allocation with the
+    // search it was opened for (de_open = false: nothing to resume), the generation its trial points are built for and which copies are current
+    double* d_de = nullptr; int64_t cap_de = 0;
+    int64_t de_W = 0, de_ld = 0; int32_t de_radius = 0, de_flip = 0;
+    uint64_t de_seed = 0, de_gen = 0;
+    bool de_open = false, de_bounds = false;
 };
 
 namespace {

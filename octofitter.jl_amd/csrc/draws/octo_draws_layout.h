@@ -132,6 +132,24 @@ inline NestedWork nested_work(Carve& c, int64_t D, int64_t ld) {
             c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld)};
 }
 
+// The population of differential evolution (octo_draws_de.hip), d_de: (5·D + 12)·ld. The population and the trial points are kept twice: a
+// generation's launch reads one copy of each and writes the other, and so do the two [ld] arrays that other lanes read (f and ℓprior_t of the
+// trial). Which copy is current is the parity of the generations made since the opening; octo_draws_de_device hands the kernels the current
+// and the next one by name.
+struct DeWork {
+    double *pop0, *pop1, *trial0, *trial1, *gpr;      // [D][ld] X and the trial points V, twice · ∇ℓprior_t (target_at's, not read)
+    double *lp, *f0, *f1, *tlpt0, *tlpt1;             // [ld] ℓπ at the trial points of a launch · f of the population, twice · ℓprior_t of the trial points, twice
+    double *lpt, *F, *CR, *Ft, *CRt;                  // [ld] ℓprior_t of the population · (F_i, CR_i) · (F′, CR′) of the trial
+    int32_t *n_accept, *improved;                     // [ld] acceptances so far · the last generation accepted
+};
+inline DeWork de_work(Carve& c, int64_t D, int64_t ld) {
+    const int64_t plane = D * ld;
+    return {c.take(plane), c.take(plane), c.take(plane), c.take(plane), c.take(plane),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take(ld), c.take(ld), c.take(ld), c.take(ld), c.take(ld),
+            c.take<int32_t>(ld), c.take<int32_t>(ld)};
+}
+
 // The order of one cull of nested sampling, d_ncull: K. order[r] = the live slot of rank r, ascending by (ℓ, slot).
 struct NestedCull { int32_t* order; };      // [K]
 inline NestedCull nested_cull(Carve& c, int64_t K) { return {c.take<int32_t>(K)}; }

@@ -232,7 +232,7 @@ int32_t octo_draws_program_clear(octo_draws* h) {
     if (!h) return OCTO_EINVAL;
     h->prog_ops = nullptr; h->prog_binds = nullptr; h->prog_terms = nullptr; h->prog_ds = nullptr;
     h->prog_n_ops = h->prog_n_in = h->prog_n_el = h->prog_n_terms = h->prog_planets = 0;
-    h->nuts_depth = 0; h->slice_passes = 0; h->lbf_m = 0; h->pf_W = 0;      // a transition is never resumed on another target
+    h->nuts_depth = 0; h->slice_passes = 0; h->lbf_m = 0; h->pf_W = 0; h->de_open = false;      // a transition is never resumed on another target
     return OCTO_OK;
 }
 

@@ -140,7 +140,7 @@ int32_t octo_draws_use_reference(octo_draws* h, const double* d_ref) {
     } else {
         h->d_priors = h->own_priors; h->d_pc = h->own_pc; h->d_ic = h->own_ic;
     }
-    h->nuts_depth = 0; h->slice_passes = 0; h->lbf_m = 0;      // a transition is never resumed on another target
+    h->nuts_depth = 0; h->slice_passes = 0; h->lbf_m = 0; h->de_open = false;      // a transition is never resumed on another target
     return OCTO_OK;
 }
 

@@ -811,13 +811,22 @@ def octofit_nuts_device(model, n_chains=1024, n_warmup=200, n_samples=200, max_d
                     state=dict(theta_t=theta_t.cpu().numpy(), step=nw + ns), **{k: v.cpu().numpy() for k, v in {**extra, **dense}.items()})
 
 
-def _optimizer_starts(pd, model, N, n_starts, seed, dev, inv_mass):
+def _optimizer_starts(pd, model, N, n_starts, seed, dev, inv_mass, starts=None):
     """Where the two optimiser drivers start: (θ0 [D, n_starts] the best of prior draws 0 … N − 1, their ℓπ, inv_mass [D] on dev — by default
-    _default_metric —, theta_t = link(θ0) on dev)."""
+    _default_metric —, theta_t = link(θ0) on dev). starts: θ_t [D, n] (an array or a tensor) used in place of the best prior draws — θ0 is then
+    its inverse link and the ℓπ is the callback's there; N and n_starts are not looked at."""
     import torch
-    θ0, lp0, _ = pd.best(seed, N, keep=n_starts)
+    if starts is None:
+        θ0, lp0, _ = pd.best(seed, N, keep=n_starts)
+        theta_t = torch.as_tensor(model.link(θ0), dtype=torch.float64, device=dev).contiguous()
+    else:
+        theta_t = torch.as_tensor(starts, dtype=torch.float64, device=dev).clone().contiguous()
+        if theta_t.ndim != 2 or theta_t.shape[0] != pd.D or theta_t.shape[1] < 1:
+            raise ValueError(f"starts must be a [D = {pd.D}, n >= 1] array in θ_t")
+        θ0 = model.invlink(theta_t.cpu().numpy())
+        lp0 = model.logpost_device(theta_t, grad=True)[0].cpu().numpy()      # the call the optimisers open with
     inv_mass = _default_metric(pd, seed, dev, inv_mass)
-    return θ0, lp0, inv_mass, torch.as_tensor(model.link(θ0), dtype=torch.float64, device=dev).contiguous()
+    return θ0, lp0, inv_mass, theta_t
 
 
 def _run_segments(segment, max_rounds, rounds_per_call):
@@ -839,12 +848,13 @@ def _to_numpy_with_best(r):
     return out, int(np.argmax(np.where(np.isfinite(out["logpost"]), out["logpost"], -np.inf)))
 
 
-def optimize_starting_points_device(model, N=500_000, n_starts=64, seed=0, m=6, gtol=1e-6, ftol=0.0, max_rounds=1000, rounds_per_call=50, inv_mass=None):
+def optimize_starting_points_device(model, N=500_000, n_starts=64, seed=0, m=6, gtol=1e-6, ftol=0.0, max_rounds=1000, rounds_per_call=50, inv_mass=None,
+                                    starts=None):
     """MAP candidates from the best prior draws: the n_starts (<= 64) best of draws 0 … N − 1 of the counter stream `seed` (PriorDraws.best),
     each optimised by the batched L-BFGS of include/octofitter_hip_draws.h in θ_t, all chains in lockstep on the device. inv_mass, the
     scaling of the optimiser, defaults to the per-coordinate variance of prior draws 0 … 4095 in θ_t (the default of octofit_pt_device). The
     optimiser runs in segments of rounds_per_call rounds; the host reads the status between them and stops when no chain is active or after
-    max_rounds rounds.
+    max_rounds rounds. starts: θ_t [D, n] to start from in place of the best prior draws (global_search_device's individuals, say).
 
     Returns a dict in start order (best start first), NumPy: theta [D, n] natural domain, theta_t, logpost, start_logpost, status (LBFGS_* of
     host/draws.py), gnorm, iters, evals, inv_hess_diag [D, n] (the Pathfinder diagonal in θ_t: a natural inv_mass for hmc_step), best (the index of
@@ -855,7 +865,7 @@ def optimize_starting_points_device(model, N=500_000, n_starts=64, seed=0, m=6, 
         raise ValueError("optimize_starting_points_device: max_rounds >= 1, rounds_per_call >= 1")
     dev = torch.device("cuda", model.ln_like.device_index)
     with PriorDraws(model) as pd:
-        θ0, lp0, inv_mass, theta_t = _optimizer_starts(pd, model, N, n_starts, seed, dev, inv_mass)
+        θ0, lp0, inv_mass, theta_t = _optimizer_starts(pd, model, N, n_starts, seed, dev, inv_mass, starts)
         r = _run_segments(lambda n, resume: pd.lbfgs(theta_t, inv_mass=inv_mass, m=m, n_rounds=n, gtol=gtol, ftol=ftol, resume=resume, want_inv_hess_diag=True),
                           max_rounds, rounds_per_call)
         tt = theta_t.cpu().numpy()
@@ -863,14 +873,71 @@ def optimize_starting_points_device(model, N=500_000, n_starts=64, seed=0, m=6, 
         return dict(theta=model.invlink(tt), theta_t=tt, start_logpost=lp0, best=best, names=list(model.names), **out)
 
 
+def global_search_device(model, n_pop=1024, N=500_000, radius=8, max_gen=2000, gens_per_call=25, patience=100, ftol=1e-3, seed=0):
+    """The global stage of the reference's initialisation (src/initialization.jl:188-289, between its prior search and Pathfinder) on the device:
+    differential evolution (PriorDraws.de) on a population of n_pop points in θ_t. The population is prior draws 0 … n_pop − 1 of the counter
+    stream `seed`, with slots 0 … 63 overwritten by the 64 best of draws 0 … N − 1 (PriorDraws.best; fewer with n_pop or N below 64). The bounds
+    are the per-coordinate minimum and maximum of θ_t over prior draws 0 … 4095 and over the population. The search runs in segments of
+    gens_per_call generations; the host reads the best ℓπ between them (8 bytes, the only synchronisation) and stops when it has not risen by
+    ftol over the last `patience` generations, or after max_gen generations.
+
+    Returns a dict, NumPy: theta [D, n_pop] natural domain, theta_t, logpost [n_pop], best (the index of the highest ℓπ), best_logpost, history
+    (the best ℓπ at the opening and after every segment), generations (after each of them), n_gen, n_accept [n_pop], lo, hi, names."""
+    import torch
+    from .draws import MAX_KEEP, PriorDraws
+    if n_pop < 4 or max_gen < 0 or gens_per_call < 1 or patience < 1:
+        raise ValueError("global_search_device: n_pop >= 4, max_gen >= 0, gens_per_call >= 1, patience >= 1")
+    dev = torch.device("cuda", model.ln_like.device_index)
+    with PriorDraws(model) as pd:
+        theta_t = pd.sample(seed, 0, n_pop, theta=False, logprior_t=False)[1]
+        keep = min(MAX_KEEP, int(n_pop), int(N))
+        if keep > 0:
+            θ0, _lp0, _ = pd.best(seed, N, keep=keep)
+            theta_t[:, :keep] = torch.as_tensor(model.link(θ0), dtype=torch.float64, device=dev)
+        cloud = pd.sample(seed, 0, 4096, theta=False, logprior_t=False)[1]
+        lo = torch.minimum(cloud.min(dim=1).values, theta_t.min(dim=1).values)
+        hi = torch.maximum(cloud.max(dim=1).values, theta_t.max(dim=1).values)
+        args = dict(lo=lo, hi=hi, radius=radius, seed=seed)
+        out = pd.de(theta_t, n_gen=0, **args)
+        history, generations, done = [float(out["best_logpost"].item())], [0], 0
+        while done < max_gen:
+            n = min(int(gens_per_call), int(max_gen) - done)
+            out = pd.de(theta_t, n_gen=n, gen0=done, resume=True, out=out, **args)
+            done += n
+            history.append(float(out["best_logpost"].item()))      # the one read of a segment
+            generations.append(done)
+            back = next((h for h, g in zip(reversed(history), reversed(generations)) if g <= done - patience), None)
+            if back is not None and not history[-1] - back >= ftol:
+                break
+        tt = theta_t.cpu().numpy()
+        return dict(theta=model.invlink(tt), theta_t=tt, logpost=out["logpost"].cpu().numpy(), best=int(out["best"].item()), best_logpost=history[-1],
+                    history=np.array(history), generations=np.array(generations), n_gen=done, n_accept=out["n_accept"].cpu().numpy(),
+                    lo=lo.cpu().numpy(), hi=hi.cpu().numpy(), names=list(model.names))
+
+
+def initialize_device(model, n_starts=64, n_pop=1024, N=500_000, radius=8, max_gen=2000, gens_per_call=25, patience=100, search_ftol=1e-3, seed=0, m=6,
+                      gtol=1e-6, ftol=0.0, max_rounds=1000, rounds_per_call=50, inv_mass=None):
+    """The reference's initialisation up to its local stage, on the device throughout: global_search_device, then the n_starts individuals of the
+    highest ℓπ (best first, ties to the lower index) as the starts of optimize_starting_points_device. Returns that function's dict — its
+    start_logpost is the individuals' ℓπ — with the search's outputs under `search`, and search_index [n_starts]: the individual each start was."""
+    search = global_search_device(model, n_pop=n_pop, N=N, radius=radius, max_gen=max_gen, gens_per_call=gens_per_call, patience=patience, ftol=search_ftol,
+                                  seed=seed)
+    lp = np.where(np.isfinite(search["logpost"]), search["logpost"], -np.inf)
+    order = np.argsort(-lp, kind="stable")[:max(1, min(int(n_starts), lp.size))]
+    r = optimize_starting_points_device(model, seed=seed, m=m, gtol=gtol, ftol=ftol, max_rounds=max_rounds, rounds_per_call=rounds_per_call, inv_mass=inv_mass,
+                                        starts=np.ascontiguousarray(search["theta_t"][:, order]))
+    return dict(r, search=search, search_index=order)
+
+
 def pathfinder_device(model, N=500_000, n_paths=64, n_draws=1000, n_draws_per_path=256, n_elbo=5, seed=0, m=6, gtol=1e-6, ftol=0.0, max_rounds=1000,
-                      rounds_per_call=50, inv_mass=None):
+                      rounds_per_call=50, inv_mass=None, starts=None):
     """Multi-path Pathfinder (Zhang et al. 2022; stage 3 of the reference's initialisation, src/initialization.jl:188-289) on the device:
     the starts and the default inv_mass of optimize_starting_points_device (path p starts from the p-th best of draws 0 … N − 1 and owns
     chain p of the counter stream `seed`), PriorDraws.pathfinder in segments of rounds_per_call rounds until no chain is active or after
     max_rounds, then n_draws_per_path draws from every path's kept fit (PriorDraws.pathfinder_draw). The log ratios r = ℓπ − log q over the
     union of the draws of paths with a fit (non-finite: −Inf) are Pareto-smoothed by Psis.loo on the one row ll = −r, and n_draws are
-    resampled with replacement from the smoothed weights on the host: NumPy Generator(Philox(key=seed)), inverse CDF.
+    resampled with replacement from the smoothed weights on the host: NumPy Generator(Philox(key=seed)), inverse CDF. starts: θ_t [D, n] to
+    start the paths from in place of the best prior draws.
 
     Returns a dict, NumPy: theta [D, n_draws] natural domain, theta_t, logpost [n_draws], path [n_draws] (the start index of each draw),
     pareto_k, log_ratios and log_weights (over the n_paths·n_draws_per_path draws, draw j of path p at j·n_paths + p), per path elbo,
@@ -883,7 +950,7 @@ def pathfinder_device(model, N=500_000, n_paths=64, n_draws=1000, n_draws_per_pa
         raise ValueError("pathfinder_device: max_rounds, rounds_per_call, n_draws, n_draws_per_path >= 1")
     dev = torch.device("cuda", model.ln_like.device_index)
     with PriorDraws(model) as pd:
-        θ0, lp0, inv_mass, theta_t = _optimizer_starts(pd, model, N, n_paths, seed, dev, inv_mass)
+        θ0, lp0, inv_mass, theta_t = _optimizer_starts(pd, model, N, n_paths, seed, dev, inv_mass, starts)
         r = _run_segments(lambda n, resume: pd.pathfinder(theta_t, inv_mass=inv_mass, m=m, n_rounds=n, gtol=gtol, ftol=ftol, resume=resume,
                                                           want_inv_hess_diag=True, seed=seed, n_elbo=n_elbo), max_rounds, rounds_per_call)
         if not bool((r["elbo_iter"] >= 0).any()):

@@ -34,6 +34,7 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     chol, info = draws.metric_dense(count, m2, chol)        # … their regularised Cholesky factor L (M⁻¹ = L·Lᵀ), written only where it exists (info = 0)
     y = draws.metric_apply(chol, x, transpose=False)        # … L·x or Lᵀ·x of the columns of x [D, n]
     with draws.use_metric(chol): ...                        # … hmc_step and nuts inside run under L·Lᵀ and take no inv_mass (pack_lower, unpack_lower)
+    r = draws.de_step(θ_t, lo, hi, radius=8, n_gen=200, seed=seed)      # differential evolution: 200 generations of the population θ_t, updated in place (dict)
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -69,6 +70,9 @@ PF_MAX_D = 64                      # OCTO_DRAWS_PF_MAX_D
 PF_MAX_ELBO_DRAWS = 32             # OCTO_DRAWS_PF_MAX_ELBO_DRAWS
 MAX_GROUPS = 64                    # OCTO_DRAWS_MAX_GROUPS
 DENSE_MAX_D = 64                   # OCTO_DRAWS_DENSE_MAX_D
+PURPOSE_DE = 12
+DE_TAU_F, DE_F_LOW, DE_F_SPAN, DE_TAU_CR, DE_F0, DE_CR0 = 0.1, 0.1, 0.9, 0.1, 0.5, 0.9      # OCTO_DRAWS_DE_*
+DE_OUTPUTS = ("fcr", "logpost", "loglike", "n_accept", "best", "best_logpost", "n_improved")      # the outputs of octo_draws_de_device, in order
 DIAG_RHAT, DIAG_ESS_BULK, DIAG_ESS_TAIL, DIAG_RHAT_BASIC, DIAG_ESS_BASIC, DIAG_Q05, DIAG_Q50, DIAG_Q95, DIAG_N_STATS = range(9)      # OCTO_DRAWS_DIAG_*
 PT_ACC_COLUMNS = ("n", "A", "n_f", "m_f", "s_f", "n_b", "m_b", "s_b")      # the columns of d_acc [T − 1][8]
 PT_SUMMARY = ("barrier", "log_evidence_fwd", "log_evidence_rev", "log_evidence")      # the entries of d_summary, in order
@@ -140,6 +144,9 @@ _SIGS = {
     "octo_draws_metric_dense_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "octo_draws_metric_apply_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "octo_draws_use_metric": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "octo_draws_de_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+                             + [C.c_void_p] * 8),
+    "octo_draws_de_work_doubles": (C.c_int64, [C.c_int32, C.c_int64]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -531,6 +538,56 @@ class PriorDraws(companion.Handle):
         while out is None or (done < most and int(out["n_active"].item()) > 0):
             n = min(per_call, most - done)
             out = self.slice(theta_t, n_rounds=n, resume=out is not None, out=out, **args)
+            done += n
+        return out
+
+    # ---- differential evolution (include/octofitter_hip_draws.h, "Differential evolution")
+    def de(self, theta_t, lo=None, hi=None, radius=8, n_gen=0, gen0=0, seed=0, resume=False, fcr=None, out=None, stream=None):
+        """octo_draws_de_device, the raw call: opens (resume=False) or continues (resume=True: the same seed, radius and bounds, gen0 = the
+        generations made so far, and out= the dict the opening call returned) a differential-evolution search on the population theta_t
+        (torch float64 [D, W >= 4] on the handle's device, rows contiguous, updated in place) and makes n_gen generations of it, one forward
+        evaluation per individual each. lo, hi: the bounds in θ_t [D], both or neither; radius: the ring neighbourhood the parents come from,
+        0 = the whole population; fcr: a float64 [2, W] tensor with theta_t's leading dimension holding (F, CR) per individual, read at the
+        opening and written by every call (default: one is made, opened at F = 0.5, CR = 0.9; False: none, the pairs stay in the handle).
+        Returns dict(fcr, logpost, loglike (None on a handle made from priors alone), n_accept int32 [W], best int32 [1], best_logpost [1],
+        n_improved int32 [1]), device tensors. Asynchronous on `stream`."""
+        import torch
+        dev = self.device
+        _, W, ld = chain_matrix(theta_t, self.D, dev, "de")
+        if (lo is None) != (hi is None):
+            raise ValueError("de: lo and hi, both or neither")
+        lo_t, hi_t = device_vector(lo, self.D, dev, "lo"), device_vector(hi, self.D, dev, "hi")
+        if out is None:
+            i32 = lambda n: self._out(n, dtype=torch.int32)      # noqa: E731
+            lp, ll = (self._out(W), self._out(W)) if self._target else (None, None)
+            pair = fcr
+            if fcr is None:      # the library's opening values, in a pair the caller can read
+                pair = self._out(W, 2, ld)
+                pair[0].fill_(DE_F0)
+                pair[1].fill_(DE_CR0)
+            elif fcr is False:
+                pair = None
+            out = dict(fcr=pair, logpost=lp, loglike=ll, n_accept=i32(W), best=i32(1), best_logpost=self._out(1), n_improved=i32(1))
+        if out["fcr"] is not None and chain_matrix(out["fcr"], 2, dev, "de", "fcr")[1:] != (W, ld):
+            raise ValueError("de: fcr must be a float64 [2, W] tensor with theta_t's leading dimension")
+        self._check(self.lib.octo_draws_de_device(self._h, int(seed), int(gen0), W, ld, theta_t.data_ptr(), ptr(lo_t), ptr(hi_t), int(radius), int(n_gen),
+                                                  1 if resume else 0, *(ptr(out[k]) for k in DE_OUTPUTS), self._stream(stream, dev)))
+        self._keep = (theta_t, lo_t, hi_t, out)
+        return out
+
+    def de_step(self, theta_t, lo=None, hi=None, radius=8, n_gen=100, gen0=0, seed=0, fcr=None, gens_per_call=None, stream=None):
+        """n_gen generations of differential evolution on the population theta_t from its opening, in calls of gens_per_call generations
+        (default: all in one). No value is read between the calls; the same bits however the generations are cut. Returns de()'s dict."""
+        n_gen = int(n_gen)
+        per_call = max(n_gen, 1) if gens_per_call is None else int(gens_per_call)
+        if per_call < 1:
+            raise ValueError("de_step: gens_per_call >= 1")
+        args = dict(lo=lo, hi=hi, radius=radius, seed=seed, stream=stream)
+        out = self.de(theta_t, n_gen=0, gen0=gen0, fcr=fcr, **args)
+        done = 0
+        while done < n_gen:
+            n = min(per_call, n_gen - done)
+            out = self.de(theta_t, n_gen=n, gen0=int(gen0) + done, resume=True, out=out, **args)
             done += n
         return out
 
