@@ -364,34 +364,48 @@ bool small_eligible(const octo_ctx* ctx, const octo_dataset* ds, int64_t W, bool
 // point of the call sequence, so a rerun of the same calls makes the same decisions: results stay bit-reproducible run to run.
 constexpr int TILE_PROBE_EVERY = 64;
 constexpr double TILE_COLD_ROW_US = 27.0 * 2.15e-3;      // a cold row costs ~27 more VALU instructions than a warm one, 2.15 ns of a SIMD's issue each (tools/ubench.hip)
+constexpr double TILE_THETA_ROW_US = 10.0e-3;            // a wave-row of a slow tile in the θ-loop against today's loop, MEASURED: config 3 sorted, 12.0 µs per step between the loop on and off
+                                                         // x 1 024 SIMDs / (123 tiles x 1e4 rows) (profiles/warm_theta_ab.txt); the middle rows a sorted batch no longer takes are in that figure
 constexpr double TILE_LAUNCH_US = 6.5;                   // the kernel (4-5 µs at 1e4 walkers) + one dependent launch on the stream + the gathers through perm (profiles/r6_tile_trace.txt)
+
+// the θ-loop is offered (bit 5 of EvalArgs::warm): it is a copy of the Newton-only loop's exactly even variant with the ∂/∂tp sum by prefix, and off wherever that is
+static bool theta_on(const octo_ctx* ctx) { return ctx->env_warm_theta && ctx->env_warm_newton && ctx->env_warm_even >= 2; }
 
 // read the pending probe: wait for its launch, sum the segments' two numbers, decide
 static int tile_settle(octo_ctx* ctx, const octo_dataset* ds) {
     HIPCHK(ctx, hipEventSynchronize(ctx->ev_tile));
-    double d = 0.0;
-    for (int k = 0; k < ctx->tile_pending_segs; ++k) d += (double)ctx->h_tile_stats[2 * k] - (double)ctx->h_tile_stats[2 * k + 1];
-    ctx->tile_last_saving_us = d * (double)ds->tile_rows * TILE_COLD_ROW_US / (4.0 * (double)ctx->n_cus);
+    double d = 0.0, q_given = 0.0, q_sorted = 0.0;
+    for (int k = 0; k < ctx->tile_pending_segs; ++k) {
+        const float* sg = ctx->h_tile_stats + TILE_NSTAT * k;
+        d += (double)sg[0] - (double)sg[1];
+        q_given += (double)sg[2]; q_sorted += (double)sg[3];
+    }
+    ctx->tile_theta_given = (int64_t)q_given; ctx->tile_theta_sorted = (int64_t)q_sorted;
+    // the θ-loop's share: the tiles the sort makes slow, on the rows of the tables that loop takes (the exactly even ones: tile_theta_rows)
+    const double theta_rows = ctx->tile_pending_theta ? (q_sorted - q_given) * (double)ds->tile_theta_rows * TILE_THETA_ROW_US : 0.0;
+    ctx->tile_last_saving_us = (d * (double)ds->tile_rows * TILE_COLD_ROW_US + theta_rows) / (4.0 * (double)ctx->n_cus);
     ctx->tile_on = ctx->tile_last_saving_us > 1.3 * TILE_LAUNCH_US;
     ctx->tile_pending = false;
     return OCTO_OK;
 }
 
-int tile_prepare(octo_ctx* ctx, const octo_dataset* ds, EvalArgs& a, hipStream_t st) {
+int tile_prepare(octo_ctx* ctx, const octo_dataset* ds, EvalArgs& a, hipStream_t st, bool theta_kernel) {
     a.perm = nullptr;
     const int kp = ds->n_planets - 1;      // the planet whose severity is the key: the one planet, or the last of two (main_warm_last)
     if (!a.warm || ctx->tile_mode == 0 || a.W < ctx->tile_min_w || !(ds->tile_dm_ref > 0.0f) || ds->n_planets > 2 ||
         ds->planets[kp].orbit_kind == OCTO_ORBIT_THIELE_INNES)      // (a ThieleInnesOrbit's period needs its constructor: left as drawn)
         return OCTO_OK;
     bool probe = false, sort_now = ctx->tile_mode == 1;
+    // the launch is a kernel that has the θ-loop, the loop is on and the dataset has rows for it: the key orders the never-failing lanes and the probe counts slow tiles
+    const bool theta = theta_kernel && (a.warm & 32) != 0 && ds->tile_theta_rows > 0;
     // Two planets: only when forced (mode 1). Their launches are ONE round of blocks (two per CU), which lasts as long as its slowest block: the tiles
     // that collect the severe lanes keep the launch at their duration whatever the others gain (measured with the per-wave criterion the loop started with:
     // 155.2 µs as drawn, 156.8 sorted, the sort's own 3.8 µs included — profiles/r6_cfg4_warm_last.txt), and with the per-row test the loop has now ~5 % of
     // config 4's wave-rows are cold as drawn: nothing left for a sort to collect (profiles/r6_cfg4_dyn.txt).
     if (ctx->tile_mode == 2 && ds->n_planets > 1) return OCTO_OK;
     if (ctx->tile_mode == 2) {
-        if (ctx->tile_ds != ds->serial || ctx->tile_W != a.W) {      // another dataset or batch size: start over (a pending probe of the old shape is dropped)
-            ctx->tile_ds = ds->serial; ctx->tile_W = a.W; ctx->tile_seq = 0; ctx->tile_on = false; ctx->tile_pending = false;
+        if (ctx->tile_ds != ds->serial || ctx->tile_W != a.W || ctx->tile_theta != theta) {      // another dataset or batch size: start over (a pending probe of the old shape is dropped)
+            ctx->tile_ds = ds->serial; ctx->tile_W = a.W; ctx->tile_theta = theta; ctx->tile_seq = 0; ctx->tile_on = false; ctx->tile_pending = false;
         }
         if (ctx->tile_pending) { int rcd = tile_settle(ctx, ds); if (rcd) return rcd; }
         probe = (ctx->tile_seq % TILE_PROBE_EVERY) == 0;
@@ -403,10 +417,10 @@ int tile_prepare(octo_ctx* ctx, const octo_dataset* ds, EvalArgs& a, hipStream_t
     const int n_seg = (int)((a.W + TILE_SEG - 1) / TILE_SEG);
     int rc = grow(ctx, ctx->d_perm, ctx->cap_perm, a.W);
     if (rc) return rc;
-    if (2 * (int64_t)n_seg > ctx->cap_tile_stats) {
+    if (TILE_NSTAT * (int64_t)n_seg > ctx->cap_tile_stats) {
         if (ctx->h_tile_stats) ctx->retired_host.push_back((void*)ctx->h_tile_stats);
         ctx->h_tile_stats = nullptr; ctx->cap_tile_stats = 0;
-        const int64_t n = 2 * (int64_t)n_seg + 64;
+        const int64_t n = TILE_NSTAT * (int64_t)n_seg + 64;
         HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tile_stats, sizeof(float) * (size_t)n, hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent));
         ctx->cap_tile_stats = n;
     }
@@ -414,11 +428,11 @@ int tile_prepare(octo_ctx* ctx, const octo_dataset* ds, EvalArgs& a, hipStream_t
     TileArgs ta;
     ta.elems = a.elems; ta.ld = a.ld; ta.W = a.W; ta.perm = ctx->d_perm; ta.stats = probe ? ctx->h_tile_stats : nullptr;
     ta.dm_ref = ds->tile_dm_ref; ta.inv_k_yr = (float)(1.0 / ctx->consts.kepler_year_to_julian_day);
-    ta.planet = kp; ta.pad = 0;
+    ta.planet = kp; ta.theta = theta ? 1 : 0;
     hipLaunchKernelGGL(k_tile_sort, dim3((unsigned)n_seg), dim3(TILE_TPB), 0, st, ta);
     if (probe) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_tile, st));
-        ctx->tile_pending = true; ctx->tile_pending_segs = n_seg; ctx->tile_probes += 1;
+        ctx->tile_pending = true; ctx->tile_pending_segs = n_seg; ctx->tile_pending_theta = ta.theta != 0; ctx->tile_probes += 1;
         if (ctx->tile_seq == 1) {
             // The FIRST probe of a (dataset, batch size) is read at once (one host wait, once per shape), so that the decision already holds for the
             // evaluation it was taken on: the same inputs then give the same bits on every call of a context's life — later probes (read one
@@ -532,7 +546,8 @@ int32_t octo_ctx_create(octo_ctx** out, int32_t device_id) {
     if (const char* ev = std::getenv("OCTO_WARM_NEWTON")) ctx->env_warm_newton = std::atoi(ev) ? 1 : 0;
     if (const char* ev = std::getenv("OCTO_WARM_EVEN")) ctx->env_warm_even = std::atoi(ev) <= 0 ? 0 : (std::atoi(ev) == 1 ? 1 : 2);
     if (const char* ev = std::getenv("OCTO_WARM_NEWTON_MID")) ctx->env_warm_newton_mid = std::atoi(ev) ? 1 : 0;
-    if (const char* ev = std::getenv("OCTO_TILE_SORT")) ctx->tile_mode = std::min(std::max(std::atoi(ev), 0), 2);      // experiments: the default of OCTO_OPT_TILE_SORT
+    if (const char* ev = std::getenv("OCTO_WARM_THETA")) ctx->env_warm_theta = std::atoi(ev) ? 1 : 0;
+    if (const char* ev = std::getenv("OCTO_TILE_SORT"))ctx->tile_mode = std::min(std::max(std::atoi(ev), 0), 2);      // experiments: the default of OCTO_OPT_TILE_SORT
     if (const char* ev = std::getenv("OCTO_TILE_MIN_W")) ctx->tile_min_w = std::max<int64_t>(std::atoll(ev), 64);
     *out = ctx;
     return OCTO_OK;
@@ -816,6 +831,7 @@ int32_t octo_dataset_create(octo_ctx* ctx, const octo_obs_desc* obs, int32_t n_o
             const DevObs& h = ds->h_obs[o];
             if (h.kind == OCTO_HGCA || !(h.dm_ladder[0] > 0.0f)) continue;
             ds->tile_rows += h.n;
+            if (h.kind == OCTO_ASTROM_RADEC && ds->h_dm_exact[o] != 0.0) ds->tile_theta_rows += h.n;
             if (h.n > best) { best = h.n; ds->tile_dm_ref = h.dm_ladder[0]; }
         }
     }
@@ -868,7 +884,8 @@ static int eval_impl(octo_ctx* ctx, const octo_dataset* ds, const double* d_elem
     a.n_obs = ds->n_obs; a.n_planets = ds->n_planets;
     for (int p = 0; p < ds->n_planets; ++p) { a.orbit_kind[p] = ds->planets[p].orbit_kind; a.has_mass[p] = ds->planets[p].has_mass; }
     a.elems = d_elems; a.nuis = d_nuis; a.ld = ld; a.W = W;
-    a.warm = (ctx->opt_warm && !ctx->opt_invariant) ? (1 | (ctx->env_warm_newton ? 2 : 0) | (ctx->env_warm_newton_mid ? 4 : 0) | (ctx->env_warm_even >= 1 ? 8 : 0) | (ctx->env_warm_even >= 2 ? 16 : 0)) : 0;
+    a.warm = (ctx->opt_warm && !ctx->opt_invariant) ? (1 | (ctx->env_warm_newton ? 2 : 0) | (ctx->env_warm_newton_mid ? 4 : 0) | (ctx->env_warm_even >= 1 ? 8 : 0) | (ctx->env_warm_even >= 2 ? 16 : 0) |
+                                                         (theta_on(ctx) ? 32 : 0)) : 0;
     a.ws_in = a.ws_out = 1;
     if (ctx->stage_ws_in > 0) { a.ws_in = ctx->stage_ws_in; a.ws_out = ctx->stage_ws_out; }      // octo_eval's walker-major staging (k_small only)
     a.wc = ctx->d_wc; a.valid = ctx->d_valid; a.ldw = ctx->cap_w; a.sctab = ctx->d_sctab;
@@ -1199,6 +1216,14 @@ int32_t octo_debug_tile_state(octo_ctx* ctx, int64_t* sorted_launches, int64_t* 
     if (probes) *probes = ctx->tile_probes;
     if (on) *on = ctx->tile_on ? 1 : 0;
     if (last_saving_us) *last_saving_us = ctx->tile_last_saving_us;
+    return OCTO_OK;
+}
+
+// … and what the last probe counted for the θ-loop: the tiles all of whose walkers are slow, in the order given and sorted (octo_tile.h).
+int32_t octo_debug_tile_theta(octo_ctx* ctx, int64_t* tiles_given, int64_t* tiles_sorted) {
+    if (!ctx) return OCTO_EINVAL;
+    if (tiles_given) *tiles_given = ctx->tile_theta_given;
+    if (tiles_sorted) *tiles_sorted = ctx->tile_theta_sorted;
     return OCTO_OK;
 }
 

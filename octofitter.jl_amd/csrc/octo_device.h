@@ -673,4 +673,131 @@ __device__ __forceinline__ KSol kepler_warm_newton(double t, const PC& pc, const
     return s;
 }
 
+// THE WHOLE STEP EXTRAPOLATED (a tile of slow walkers on an exactly even table: k_main's θ-loop). kepler_warm_newton's start is the analytic second-order
+// predictor (x, z, he·sE, ·z, an FMA) plus the FP32 extrapolation of its miss c, joined by a conversion and an add, and δ is converted, added and compared
+// in FP32 to be recorded and tested. Once four rows of history exist the step θ_j = E_j − E_{j−1} itself can be extrapolated, in FP64:
+//   dE = 4(θ₁ + θ₃) − 6θ₂ − θ₄ (three instructions),   θ = dE + δ recorded (one),   |δ| tested in FP64 (one).
+// Everything behind dE is kepler_warm_newton's: the rotation with the pinned constants, f0 = dE − ΔM − e·ds with the hoisted ΔM, f1, one reciprocal, δ, the
+// two-FMA tail with one Newton step on 1/D, and the exits in the same order — a-priori reject -> cold; every |δ| <= τ -> stay; <= τ₂ -> middle; <= WARM_TOL ->
+// fourth order; else cold — whose accuracy bounds depend on |δ| alone, not on where dE came from. Each non-cold arm records θ = dE + the correction it applied.
+// WHY THE A-PRIORI COMPARE STAYS: the rotation's polynomials are exact for |dE| < 0.066 only, and |δ| bounds the guess minus the TRUTH, not the guess. The
+// a-priori test (1/D of the previous row below thr) bounds the TRUE step, |x| < 0.063 (KWarm above). Every θ in the ring is the step of an accepted row, so
+// |dE| <= (8 + 6 + 1)·0.063 < 0.95 whatever the lanes did, and on that range the polynomials' truncation (dE⁹/9!, dE¹⁰/10!) is below 2e-6: δ is the guess
+// minus the truth to 2e-6. A guess beyond 0.066 misses a true step below 0.063 by more than 3e-3, shows |δ| > 2e-3 > WARM_TOL and goes cold; an accepted
+// row therefore had its guess in range. Without the compare the true step is unbounded, the ring's entries with it, and a wrapped δ proves nothing.
+// The extrapolation error of θ goes like x⁵ where c's goes like x⁷: one fast lane spoils the wave, so the loop is for tiles whose lanes are ALL slow
+// (k_main: every valid lane's ΔM/(1 − e) below WARM_THETA_X0, decided per wave from its own 64 lanes — a routing constant, no accuracy depends on it).
+// START-UP: while fewer than four steps are recorded (after a chain start or a cold row) the row is kepler_solve_warm's warm step with d_out, out of line
+// behind one wave-uniform scalar test; it records its total step dE2 + δ4. The ring is phase-indexed like kepler_warm_newton's: one write per row, no shifts.
+#ifndef OCTO_WARM_THETA_X0
+#define OCTO_WARM_THETA_X0 0.012f
+#endif
+constexpr float WARM_THETA_X0 = OCTO_WARM_THETA_X0;
+constexpr int WARM_THETA_DEPTH = 4;
+struct KWarmTheta {
+    double th[WARM_THETA_DEPTH];     // the last four steps θ: a ring the row's phase indexes
+    double tau;                      // the lane's τ(e), FP64: the straight-line row compares δ as it is
+    float tau2;                      // the lane's τ₂(e) of the middle arm, or 0: the arm is off (read out of line only)
+    int n;                           // consecutive recorded rows, saturating at WARM_THETA_DEPTH (wave-uniform)
+};
+
+__device__ __forceinline__ void warm_theta_init(KWarmTheta& wt, float e, bool mid) {
+    KWarmNewton wn;
+    warm_newton_init(wn, e, mid);      // the ONE copy of τ(e) and τ₂(e)
+    wt.tau = (double)wn.tau; wt.tau2 = wn.tau2;
+#pragma unroll
+    for (int k = 0; k < WARM_THETA_DEPTH; ++k) wt.th[k] = 0.0;
+    wt.n = 0;
+}
+
+// dm: the lane's hoisted ΔM (an exactly even table). NODT as in kepler_warm_newton.
+template <int INV_NR, int PH = 0, bool NODT = false>
+__device__ __forceinline__ KSol kepler_warm_theta(double t, const PC& pc, const SinCosTab& tab, KWarm& st, KWarmTheta& wt, double thr, double dM, const WarmPin& pin) {
+    static_assert(INV_NR == 1, "kepler_warm_theta: 1/(1 − e cos E) one Newton step from the reciprocal of f1 (the adjoints' bar)");
+    static_assert(PH >= 0 && PH < 4, "kepler_warm_theta: four phases");
+    constexpr int I0 = (0 - PH) & 3, I1 = (1 - PH) & 3, I2 = (2 - PH) & 3, I3 = (3 - PH) & 3;
+    KSol s;
+    if constexpr (NODT) s.dt = 0.0;
+    else s.dt = t - pc.tp;
+    s.E = 0.0;
+    const bool apriori = __builtin_amdgcn_ballot_w64(st.invD >= thr) == 0;
+    bool cold = false;
+    double thn = 0.0;
+    int n = WARM_THETA_DEPTH;
+    if (__builtin_expect(wt.n < WARM_THETA_DEPTH, 0)) {
+        // start-up: the second-order predictor and the fourth-order correction (kepler_solve_warm's warm row)
+        cold = !apriori;
+        if (apriori) {
+            const double x = dM * st.invD;
+            const double z = x * st.invD;
+            const double dE = fma(-((pc.he * st.sE) * z), x, x);
+            const double u = dE * dE;
+            const double sr = dE * fma(u, fma(u, fma(u, OCTO_KT[22], pin.k17), OCTO_KT[18]), 1.0);
+            const double cm1 = u * fma(u, fma(u, fma(u, OCTO_KT[23], pin.k19), OCTO_KT[20]), -0.5);
+            const double ds = fma(st.sE, cm1, st.cE * sr);
+            const double s1 = st.sE + ds;
+            const double c1 = fma(st.cE, cm1, fma(-st.sE, sr, st.cE));
+            const double f0 = fma(-pc.e, ds, dE - dM);
+            double d4;
+            kepler_correct<INV_NR, true>(s, pc, 0.0, s1, c1, f0, &d4);
+            thn = dE + d4;
+            n = wt.n + 1;
+        }
+    } else {
+        const double dE = fma(4.0, wt.th[I0] + wt.th[I2], fma(-6.0, wt.th[I1], -wt.th[I3]));
+        const double u = dE * dE;
+        const double sr = dE * fma(u, fma(u, fma(u, OCTO_KT[22], pin.k17), OCTO_KT[18]), 1.0);
+        const double cm1 = u * fma(u, fma(u, fma(u, OCTO_KT[23], pin.k19), OCTO_KT[20]), -0.5);
+        const double ds = fma(st.sE, cm1, st.cE * sr);
+        const double s1 = st.sE + ds;
+        const double c1 = fma(st.cE, cm1, fma(-st.sE, sr, st.cE));
+        const double f0 = fma(-pc.e, ds, dE - dM);
+        const double f1 = fma(-pc.e, c1, 1.0);
+        const double r1 = rcp_nr<1>(f1);
+        const double d = -f0 * r1;
+        // the Newton-only row, unconditionally
+        s.sE = fma(c1, d, s1);
+        s.cE = fma(-s1, d, c1);
+        s.invD = fma(fma(-fma(-pc.e, s.cE, 1.0), r1, 1.0), r1, r1);
+        thn = dE + d;
+        // (a NaN lane — an invalid walker — passes every compare, as in kepler_warm_newton; k_main sends no such tile here)
+        const bool fast = apriori && __builtin_amdgcn_ballot_w64(fabs(d) > wt.tau) == 0;
+        if (__builtin_expect(!fast, 0)) {
+            if (apriori && __builtin_amdgcn_ballot_w64(fabs(d) > (double)wt.tau2) == 0) {
+                // the middle arm: one Halley step from the Newton δ and its reciprocal (kepler_warm_newton's)
+                const double q = (pc.he * s1) * r1;
+                const double dh = fma(-(q * d), d, d);
+                const double w = -0.5 * dh;
+                s.sE = fma(dh, fma(w, s1, c1), s1);
+                s.cE = fma(dh, fma(w, c1, -s1), c1);
+                const double D = fma(-pc.e, s.cE, 1.0);
+                const double r2 = fma(fma(-D, r1, 1.0), r1, r1);
+                s.invD = fma(fma(-D, r2, 1.0), r2, r2);
+                thn = dE + dh;
+            } else if (apriori && __builtin_amdgcn_ballot_w64(fabs(d) > WARM_TOL) == 0) {
+                double d4;
+                kepler_correct<INV_NR, true>(s, pc, 0.0, s1, c1, f0, &d4);
+                thn = dE + d4;
+            } else cold = true;
+        }
+    }
+    if (__builtin_expect(cold, 0)) {
+        double dtc;
+        if constexpr (NODT) dtc = t - pc.tp;
+        else dtc = s.dt;
+        const double uo = dtc * pc.invP;
+        const double frac = uo - rint(uo);
+        const float E1f = markley_starter_f32(frac, pc);
+        const double E1 = (double)E1f;
+        double sc, cc;
+        sincos_table(E1f, tab, sc, cc);
+        kepler_correct<INV_NR>(s, pc, E1, sc, cc, fma(-pc.e, sc, fma(-frac, TWO_PI, E1)));
+        n = 0;
+    }
+    wt.th[I3] = thn;
+    wt.n = n;
+    st.sE = s.sE; st.cE = s.cE; st.invD = s.invD;
+    return s;
+}
+
 }  // namespace octo

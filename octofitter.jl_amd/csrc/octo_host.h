@@ -59,6 +59,7 @@ struct octo_dataset {
     octo_planet_desc planets[MAXP];
     float tile_dm_ref = 0.0f;            // reference step of the walker-tile sort (octo_tile.h): the preferred rung of the largest table's ladder; 0: none
     int64_t tile_rows = 0;               // rows of the tables that have a ladder (what a homogeneous tile saves cold rows on)
+    int64_t tile_theta_rows = 0;         // … of them, rows of the exactly even RA/Dec tables: what a tile of slow walkers takes the θ-loop on (octo_device.h: kepler_warm_theta)
     uint64_t serial = 0;                 // process-unique id: the contexts key their task-table caches by it (the dataset itself
                                          // is immutable after octo_dataset_create, so contexts may share it without locking)
 };
@@ -122,6 +123,8 @@ struct octo_ctx {
     int env_warm_even = 2;                      // OCTO_WARM_EVEN=0: exactly even tasks (Task::dm_exact) keep the Newton-only loop every evenly sampled task has; 1: they take the
                                                 // hoisted ΔM but keep t − tp and the ∂/∂tp sum's FMA in the row (no output bit moves) — tests and A/B
     int env_warm_newton_mid = 1;                // OCTO_WARM_NEWTON_MID=0: … without the middle arm of those rows (one Halley step between the Newton-only and the fourth-order rows) — tests and A/B
+    int env_warm_theta = 1;                     // OCTO_WARM_THETA=0: tiles of slow walkers keep the Newton-only loop on exactly even tasks (octo_device.h: kepler_warm_theta), and the tile
+                                                // sort is priced without them — every result the one without the θ-loop, byte for byte. Tests and A/B
     // ---- options (octo_ctx_set_option; include/octofitter_hip.h: OCTO_OPT_*)
     int opt_warm = 1;                           // OCTO_OPT_WARM_START: 0 = every launch of this context takes k_main's cold row loop
     int opt_invariant = 0;                      // OCTO_OPT_BATCH_INVARIANT: results independent of the batch's size and composition (cold loop, no tile sort,
@@ -134,6 +137,9 @@ struct octo_ctx {
     hipEvent_t ev_tile = nullptr;
     bool tile_on = false, tile_pending = false;
     int tile_pending_segs = 0;
+    bool tile_theta = false;                                      // the current (dataset, batch size) is keyed for the θ-loop: part of what a decision holds for
+    bool tile_pending_theta = false;                              // the pending probe keyed and counted for the θ-loop (TileArgs::theta)
+    int64_t tile_theta_given = 0, tile_theta_sorted = 0;          // the last probe: tiles that qualify for the θ-loop, as given | sorted
     int64_t tile_seq = 0, tile_W = 0, tile_sorted_launches = 0, tile_probes = 0;
     uint64_t tile_ds = 0;
     double tile_last_saving_us = 0.0;
@@ -203,7 +209,7 @@ int get_tasks(octo_ctx* ctx, const octo_dataset* ds, int64_t key, TaskTable** ou
 int64_t plan_key(const octo_ctx* ctx, int64_t W, int64_t n_rows, int blocks_per_cu, bool* wide = nullptr, int blocks8_per_cu = 0);
 int busy(octo_ctx* ctx, const char* what);      // OCTO_EINVAL while an octo_eval_begin of this context is outstanding
 bool small_eligible(const octo_ctx* ctx, const octo_dataset* ds, int64_t W, bool model = false);
-int tile_prepare(octo_ctx* ctx, const octo_dataset* ds, EvalArgs& a, hipStream_t st);      // octo_tile.h: sets a.perm (or leaves it null)
+int tile_prepare(octo_ctx* ctx, const octo_dataset* ds, EvalArgs& a, hipStream_t st, bool theta_kernel);      // octo_tile.h: sets a.perm (or leaves it null)
 
 // Launch of one evaluation for a dataset with P planets (octo_launch.h; instantiated in octo_inst_p<P>.hip).
 template <int P>

@@ -93,6 +93,7 @@ struct EvalArgs {
                                                 // bit 2: … with its middle arm (OCTO_WARM_NEWTON_MID=0 clears it: τ₂ = 0)
                                                 // bit 3: … and, on exactly even tasks (Task::dm_exact), with ΔM hoisted out of the row (OCTO_WARM_EVEN=0 clears it);
                                                 // bit 4 (only with bit 3): … and the ∂/∂tp sum by prefix, without t − tp in the row (OCTO_WARM_EVEN=1 clears it)
+                                                // bit 5 (only with bit 4): … and tiles whose lanes are all slow extrapolate the whole step (kepler_warm_theta; OCTO_WARM_THETA=0 clears it)
                                                 // fin_fused 1: the launch has ONE task and k_main's blocks finish their own tile (fin_in_main): no partials, no k_finish
     int32_t task0, n_rblocks;                   // first task of this launch (k_main grid.y is relative to it); k_small: blocks per walker that take row tasks
     int32_t orbit_kind[MAXP];
@@ -494,14 +495,15 @@ struct WarmState { KWarm st[P]; double thr[P]; uint32_t key_hi; bool row_ok; War
 // WLAST (round 6, P >= 2): 1 — the LAST planet takes the warm step (octo_device.h: kepler_warm_step) from ws->st[P − 1], the others the cold solve;
 // 2 — the same behind a per-row test (ws->row_ok, wave-uniform): a rejected row re-solves the last planet cold and records that solution.
 // WARM 3 (P == 1): the Newton-only warm row (octo_device.h: kepler_warm_newton) with its own state wn; no per-row key test (the unchecked loop's tasks).
-// WPH: that row's phase in the four-row trip. WPIN: the warm row reads two rotation constants from ws->pin (WARM 3 always does).
+// WARM 4 (P == 1, an exactly even task, WEVEN >= 1): the θ row (octo_device.h: kepler_warm_theta) with its own state wt — a tile of slow walkers.
+// WPH: that row's phase in the four-row trip. WPIN: the warm row reads two rotation constants from ws->pin (WARM 3 and 4 always do).
 // WEVEN (WARM 3, a task with Task::dm_exact): 1 — `dm` is the lane's hoisted ΔM (kepler_warm_newton<…, HOIST>), every output bit the same; 2 — also, the row does not
 // form t − tp: the ∂/∂tp sum Σ Mb·(t − tp) is carried as the running sum of the INCLUSIVE prefixes of Σ Mb (one add in place of the FMA) and converted once behind
 // the loop (even_gt_finish below).
 template <int P, bool GRAD, bool NUIS, int KM, bool TAB, int WARM = 0, bool WCHECK = true, int WLAST = 0, int WPH = 0, bool WPIN = false, int WEVEN = 0>
 __device__ __forceinline__ void astrom_row(AccArr<P, GRAD, NUIS, KM>& acc, LogProd& lp, const PC (&pc)[P],
                                            const AstromCoef<P>& co, double t, double y1, double y2, double c3, double c4, double c5,
-                                           const SinCosTab& tab, WarmState<P>* ws = nullptr, double dm = 0.0, KWarmNewton* wn = nullptr) {
+                                           const SinCosTab& tab, WarmState<P>* ws = nullptr, double dm = 0.0, KWarmNewton* wn = nullptr, KWarmTheta* wt = nullptr) {
     using L = Layout<P, GRAD, NUIS, KM>;
     // DEFER (k_main's mapping, lane = walker: round 6): every factor of an adjoint sum that is constant over the table's rows for one walker — the
     // planet's coefficient f_p, the jitter, the platescale in front of the northangle term — is applied ONCE per wave after the row loop
@@ -516,7 +518,8 @@ __device__ __forceinline__ void astrom_row(AccArr<P, GRAD, NUIS, KM>& acc, LogPr
     double ra_m, dec_m;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-        if constexpr (WARM == 3) s[p] = kepler_warm_newton<1, WPH, (WEVEN >= 1), (WEVEN >= 2)>(t, pc[p], tab, ws->st[p], *wn, ws->thr[p], dm, ws->pin);
+        if constexpr (WARM == 4) s[p] = kepler_warm_theta<1, WPH, (WEVEN >= 2)>(t, pc[p], tab, ws->st[p], *wt, ws->thr[p], dm, ws->pin);
+        else if constexpr (WARM == 3) s[p] = kepler_warm_newton<1, WPH, (WEVEN >= 1), (WEVEN >= 2)>(t, pc[p], tab, ws->st[p], *wn, ws->thr[p], dm, ws->pin);
         else if constexpr (WARM != 0) s[p] = kepler_solve_warm<1, WARM == 1, WPIN>(t, pc[p], tab, ws->st[p], ws->thr[p], dm, WCHECK ? ws->row_ok : true, &ws->pin);
         else if constexpr (WLAST != 0) { if (p == P - 1) s[p] = kepler_warm_step<1>(t, pc[p], ws->st[p], dm); else s[p] = kepler_solve<1, TAB>(t, pc[p], tab); }
         else s[p] = kepler_solve<1, TAB>(t, pc[p], tab);
@@ -1331,16 +1334,22 @@ static __global__ __launch_bounds__(64 * NWV) void k_main(EvalArgs a) {
                             // even: 0 — the step from slot 6 of every record, ΔM = dm·(1/P) and t − tp in the row; 1, 2 — an exactly even task (Task::dm_exact): ΔM formed
                             // HERE from the same two operands, and the records read without slots 6 and 7 (RowRegs, as the cold loop reads them); 2 — the ∂/∂tp sum by
                             // prefix, converted behind the loop (astrom_row<…, WEVEN>, even_gt_finish)
-                            auto nloop = [&](auto even, auto issue) {
+                            // theta (an exactly even task only): the tile's lanes are all slow — the rows extrapolate the whole step (kepler_warm_theta) from a history wt of
+                            // their own; the trips, the prefetch and the sums are the same
+                            auto nloop = [&](auto even, auto issue, auto theta) {
                                 constexpr int EV = decltype(even)::value;
+                                constexpr bool TH = decltype(theta)::value;
+                                static_assert(!TH || EV >= 1, "the θ row takes the hoisted ΔM");
                                 double dmh = 0.0;
                                 if constexpr (EV >= 1) dmh = tk.dm_exact * pc[0].invP;
+                                KWarmTheta wt;
+                                if constexpr (TH) warm_theta_init(wt, pc[0].ef, (a.warm & 4) != 0);
                                 auto nbody = [&](const auto& r, auto ph) {
                                     double dm;
                                     if constexpr (EV >= 1) dm = dmh;
                                     else dm = row_get(r, 6);
-                                    astrom_row<P, GRAD, NUIS, KM, true, 3, false, 0, decltype(ph)::value, false, EV>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2),
-                                                                                                                     row_get(r, 3), row_get(r, 4), row_get(r, 5), tab, &ws, dm, &wn);
+                                    astrom_row<P, GRAD, NUIS, KM, true, (TH ? 4 : 3), false, 0, decltype(ph)::value, false, EV>(acc, lp, pc, co, row_get(r, 0), row_get(r, 1), row_get(r, 2),
+                                                                                                                     row_get(r, 3), row_get(r, 4), row_get(r, 5), tab, &ws, dm, &wn, &wt);
                                 };
                                 auto A = issue(rows);
                                 for (int j = 0;; j += 4) {
@@ -1366,12 +1375,28 @@ static __global__ __launch_bounds__(64 * NWV) void k_main(EvalArgs a) {
                             // (a chunk of at most WARM_NEWTON_DEPTH rows never fills the history: it has no Newton-only row to make cheaper, and the prefix form of the ∂/∂tp
                             // sum is badly conditioned on a chunk of two rows — tests/even_sum_model.py — so it keeps the rows every evenly sampled task has)
                             if (WEV != 0 && (a.warm & 8) != 0 && tk.dm_exact != 0.0 && n_rows > WARM_NEWTON_DEPTH) {
+                                // The θ-loop (bit 5, and only next to bit 4: forward and gradient kernels then take it on the same tiles): this wave's own 64 lanes all slow —
+                                // every lane's ΔM/(1 − e) below WARM_THETA_X0, in FP32 from the values the row uses; a NaN or an invalid e fails the compare and keeps the
+                                // tile on the loop it has today (tail lanes repeat the last walker). No other tile enters the decision. Only in a SORTED launch (a.perm): there the
+                                // last bits already follow the tiles' composition, and as drawn hardly a tile of a prior's batch qualifies (none of config 3's) — so an unsorted
+                                // evaluation, every batch below the sort's 2 048 walkers among them, keeps the Newton-only loop and returns what it returned, byte for byte.
+                                bool slow = false;
+                                if constexpr (WEV >= 2) {
+                                    if ((a.warm & 48) == 48 && a.perm != nullptr) {
+                                        const float xs = fabsf((float)(tk.dm_exact * pc[0].invP)) * __builtin_amdgcn_rcpf(pc[0].omef);
+                                        const bool ok = xs < WARM_THETA_X0 && pc[0].ef >= 0.0f && pc[0].ef < 1.0f;
+                                        slow = __builtin_amdgcn_ballot_w64(!ok) == 0;
+                                    }
+                                }
                                 // (bit 4 clear: the hoisted ΔM alone. Only a gradient kernel compiles that loop a second time: a forward kernel has no ∂/∂tp sum)
-                                if constexpr (WEV >= 2 && GRAD) {
-                                    if ((a.warm & 16) != 0) nloop(std::integral_constant<int, 2>{}, [](crow_t q) { return row_issue(q); });
-                                    else nloop(std::integral_constant<int, 1>{}, [](crow_t q) { return row_issue(q); });
-                                } else if constexpr (WEV != 0) nloop(std::integral_constant<int, WEV>{}, [](crow_t q) { return row_issue(q); });
-                            } else nloop(std::integral_constant<int, 0>{}, [](crow_t q) { return row_issue8(q); });
+                                if constexpr (WEV >= 2) {
+                                    if (slow) nloop(std::integral_constant<int, 2>{}, [](crow_t q) { return row_issue(q); }, std::true_type{});
+                                    else if constexpr (GRAD) {
+                                        if ((a.warm & 16) != 0) nloop(std::integral_constant<int, 2>{}, [](crow_t q) { return row_issue(q); }, std::false_type{});
+                                        else nloop(std::integral_constant<int, 1>{}, [](crow_t q) { return row_issue(q); }, std::false_type{});
+                                    } else nloop(std::integral_constant<int, 2>{}, [](crow_t q) { return row_issue(q); }, std::false_type{});
+                                } else if constexpr (WEV != 0) nloop(std::integral_constant<int, WEV>{}, [](crow_t q) { return row_issue(q); }, std::false_type{});
+                            } else nloop(std::integral_constant<int, 0>{}, [](crow_t q) { return row_issue8(q); }, std::false_type{});
                         } else wloop(std::true_type{});
                     }
                 } else if (n_rows > 0) {

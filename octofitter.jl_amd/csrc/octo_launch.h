@@ -199,7 +199,9 @@ int launch_all(octo_ctx* ctx, const octo_dataset* cds, EvalArgs& a, const SmallM
         if (a.n_tasks > 0) {      // (a dataset without rows — an HGCA table alone, empty tables — is k_finish's closed forms only)
             // walker tiles made homogeneous for the warm-started loop (octo_tile.h): one sort launch ahead of k_main when it pays
             if constexpr (!MAINP && ((P == 1 && main_warm<P, true, NUIS, KM, true>()) || main_warm_last<P, true, NUIS, KM, true>())) {
-                rc = tile_prepare(ctx, ds, a, st);
+                // (the θ-loop's share of the key and the price: only where the launch is a kernel that has that loop)
+                constexpr bool THETA_K = P == 1 && main_warm_even<P, GRAD, NUIS, KM, true, WPB, false>() >= 2;
+                rc = tile_prepare(ctx, ds, a, st, THETA_K && !wide && a.n_tasks > 1);
                 if (rc) return rc;
             }
             rc = timing_begin();

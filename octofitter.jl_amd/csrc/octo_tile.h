@@ -14,6 +14,13 @@
 // sorted order (tools/warm_rates.py: the closed form agrees with a row-by-row simulation to the third digit). The host compares the difference
 // × rows × the cost of a cold row with the cost of this launch (octo_api.hip: tile_decide) — config 3 gains 3.5 µs for a 4.5 µs launch and
 // stays as drawn; a batch with a ~ LogU(0.3, 100) AU goes from every wave cold to a fifth of them.
+//
+// THE θ-LOOP'S KEY. k_main's θ-loop (octo_device.h: kepler_warm_theta) takes a tile only if ALL its lanes are slow, x = ΔM/(1 − e) < WARM_THETA_X0, and the
+// Newton-only share of every tile rises when lanes of like x sit together — but the lanes that never fail the a-priori test, most of a batch, were ONE
+// bucket, left as drawn. With TileArgs::theta set they are ordered by x (FP32) into TILE_XK classes half an octave wide, one class boundary exactly at
+// WARM_THETA_X0, AHEAD of the p-ordered classes and the veto classes, which keep their meaning and their order (so the sorted cold share does not move).
+// The probe also counts, per segment, the tiles that qualify as given and as sorted (stats slots 2 and 3). With theta clear the key, the permutation and
+// the first two stats are what they were.
 #pragma once
 #include "octo_kernels.h"
 
@@ -27,17 +34,19 @@ constexpr int TILE_TPB = 1024;                     // threads per block
 constexpr int TILE_SEG = TILE_TPB * TILE_WPT;      // walkers per segment = per block. Measured / simulated (tools/warm_rates.py): segments of 1 024 leave
                                                    // 20.7 % of wide_prior's wave-rows cold, 2 048 20.0 %, 4 096 19.9 % (the whole batch: 19.9 %) — and the
                                                    // kernel, whose blocks each run on ONE CU, takes 8.9 µs at four walkers per thread
-constexpr int TILE_K = 32;            // severity buckets
+constexpr int TILE_XK = 17;           // classes of x = ΔM/(1 − e) for the lanes that never fail (one class when TileArgs::theta is clear)
+constexpr int TILE_K = 48;            // severity buckets: TILE_XK never-failing | 24 log-spaced classes of p | 7 veto classes
+constexpr int TILE_NSTAT = 4;         // floats per segment: expected cold wave-rows per row as given | sorted, tiles that qualify for the θ-loop as given | sorted
 
 struct TileArgs {
     const double* elems;      // [9][ld]: a, e, …, M of the one planet
     int64_t ld, W;
     int32_t* perm;            // [W]: perm[sorted position] = walker
-    float* stats;             // [2·n_segments] mapped pinned: expected cold wave-rows per row, as given | sorted
+    float* stats;             // [TILE_NSTAT·n_segments] mapped pinned: expected cold wave-rows per row, as given | sorted; tiles that qualify for the θ-loop, as given | sorted
     float dm_ref;             // the dataset's reference step 2π·Δt [rad·day]: the preferred rung of its main table's ladder
     float inv_k_yr;
     int32_t planet;           // the planet whose severity is the key (0; two planets: the last one — the planet the two-planet kernels start warm)
-    int32_t pad;
+    int32_t theta;            // the θ-loop is on: order the never-failing lanes by ΔM/(1 − e)
 };
 
 __device__ __forceinline__ float wave_excl_scan(float x, int lane, float& total) {
@@ -57,22 +66,24 @@ static __global__ __launch_bounds__(TILE_TPB) void k_tile_sort(TileArgs a) {
     __shared__ uint16_t goff[TILE_K * WAVE];                                     // [bucket][group of 16 threads] exclusive prefix over the groups
     __shared__ uint16_t bbase[TILE_K + 1];
     __shared__ float slq[TILE_SEG];                                              // log2(1 − p) at the SORTED positions
-    __shared__ float red[2 * (TILE_TPB / WAVE)];
+    __shared__ float red[TILE_NSTAT * (TILE_TPB / WAVE)];
+    __shared__ uint8_t sq[TILE_SEG];                                             // 1: the walker at this SORTED position is slow (qualifies for the θ-loop)
     const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t >> 6;
     const int64_t seg0 = (int64_t)blockIdx.x * TILE_SEG;
     const int n_seg = (int)(a.W - seg0 < TILE_SEG ? a.W - seg0 : TILE_SEG);
     {
         uint4* z = reinterpret_cast<uint4*>(cnt);
-        z[t] = make_uint4(0, 0, 0, 0); z[t + TILE_TPB] = make_uint4(0, 0, 0, 0);
+        static_assert(TILE_K * TILE_TPB == 3 * 16 * TILE_TPB, "three uint4 per thread clear the counts");
+        z[t] = make_uint4(0, 0, 0, 0); z[t + TILE_TPB] = make_uint4(0, 0, 0, 0); z[t + 2 * TILE_TPB] = make_uint4(0, 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < TILE_WPT; ++i) slq[TILE_WPT * t + i] = 0.0f;
+        for (int i = 0; i < TILE_WPT; ++i) { slq[TILE_WPT * t + i] = 0.0f; sq[TILE_WPT * t + i] = 1; }      // (positions beyond the segment's end stay neutral)
     }
     // ---- severity of my walkers
-    int bk[TILE_WPT]; float lq[TILE_WPT];
+    int bk[TILE_WPT]; float lq[TILE_WPT]; bool slow[TILE_WPT];
 #pragma unroll
     for (int i = 0; i < TILE_WPT; ++i) {
         const int k = TILE_WPT * t + i;
-        bk[i] = -1; lq[i] = 0.0f;
+        bk[i] = -1; lq[i] = 0.0f; slow[i] = true;
         if (k >= n_seg) continue;
         const int64_t w = seg0 + k;
         const double* el = a.elems + (int64_t)a.planet * OCTO_N_EL * a.ld + w;
@@ -83,12 +94,17 @@ static __global__ __launch_bounds__(TILE_TPB) void k_tile_sort(TileArgs a) {
         int b; float p;
         if (!(dM <= WARM_DM_VETO) || !(e >= 0.0f) || !(e < 1.0f)) {      // vetoes every rung the reference step stands for (or invalid / NaN): last, fastest at the very end
             const float x = __builtin_amdgcn_logf(dM * (1.0f / WARM_DM_VETO)) * 2.0f;
-            b = 25 + (x >= 0.0f ? (x < 6.0f ? (int)x : 6) : (x < 0.0f ? 0 : 6));
+            b = TILE_XK + 24 + (x >= 0.0f ? (x < 6.0f ? (int)x : 6) : (x < 0.0f ? 0 : 6));
             p = 1.0f;
         } else {
             const float thr = warm_thr(e, dM);      // the bound k_main tests against: >= 2 here (dM <= WARM_DM_VETO)
             const float g = 1.0f - __builtin_amdgcn_rcpf(thr);
-            if (e <= g) { b = 0; p = 0.0f; }
+            if (e <= g) {
+                // never fails: by x in half octaves around WARM_THETA_X0 — classes 0-7 below it, 8-16 at or above
+                const float xs = dM * __builtin_amdgcn_rcpf(1.0f - e);
+                const float xc = fminf(fmaxf(floorf(fmaf(2.0f, __builtin_amdgcn_logf(xs * (1.0f / WARM_THETA_X0)), 8.0f)), 0.0f), (float)(TILE_XK - 1));
+                b = a.theta ? (int)xc : 0; p = 0.0f;
+            }
             else {
                 const float c = g * __builtin_amdgcn_rcpf(e);      // in (1/2, 1): thr >= 2 here
                 // acos(c) = √(1 − c)·(a0 + a1 c + a2 c² + a3 c³) on [0, 1], |error| <= 5e-5 rad (Abramowitz & Stegun 4.4.45); the error enters p through
@@ -97,10 +113,12 @@ static __global__ __launch_bounds__(TILE_TPB) void k_tile_sort(TileArgs a) {
                 const float s0 = __builtin_amdgcn_sqrtf(fmaxf(fmaf(-c, c, 1.0f), 0.0f));
                 p = fminf(fmaxf((E0 - e * s0) * 0.318309886f, 0.0f), 1.0f);
                 const float x = (__builtin_amdgcn_logf(fmaxf(p, 1e-30f)) + 17.0f) * (24.0f / 17.0f);
-                b = 1 + (x > 0.0f ? (x < 23.0f ? (int)x : 23) : 0);
+                b = TILE_XK + (x > 0.0f ? (x < 23.0f ? (int)x : 23) : 0);
             }
         }
         bk[i] = b;
+        // k_main's rule for the θ-loop, from this kernel's FP32 period: a valid e and ΔM/(1 − e) below WARM_THETA_X0 (a NaN fails)
+        slow[i] = e >= 0.0f && e < 1.0f && dM * __builtin_amdgcn_rcpf(1.0f - e) < WARM_THETA_X0;
         lq[i] = p < 1.0f ? __builtin_amdgcn_logf(1.0f - p) : -INFINITY;
     }
     __syncthreads();
@@ -109,7 +127,7 @@ static __global__ __launch_bounds__(TILE_TPB) void k_tile_sort(TileArgs a) {
         if (bk[i] >= 0) cnt[bk[i] * TILE_TPB + t] += 1;      // my own byte: no other thread writes it
     __syncthreads();
     // ---- per bucket: exclusive prefix over the 1 024 thread counts = (prefix over the 64 groups of 16 threads) + (prefix within the group, written
-    // back over the counts as bytes: a group holds at most 64 walkers). Wave w takes buckets 2w and 2w + 1; lane l takes group l.
+    // back over the counts as bytes: a group holds at most 64 walkers). Wave w takes buckets 3w … 3w + 2; lane l takes group l.
 #pragma unroll
     for (int q = 0; q < TILE_K / (TILE_TPB / WAVE); ++q) {
         const int b = wv * (TILE_K / (TILE_TPB / WAVE)) + q;
@@ -154,27 +172,40 @@ static __global__ __launch_bounds__(TILE_TPB) void k_tile_sort(TileArgs a) {
         const int pos = (int)bbase[bk[i]] + (int)goff[bk[i] * WAVE + (t >> 4)] + (int)cnt[bk[i] * TILE_TPB + t] + rank;
         a.perm[seg0 + pos] = (int32_t)(seg0 + TILE_WPT * t + i);
         slq[pos] = lq[i];
+        sq[pos] = slow[i] ? 1 : 0;
     }
     if (!a.stats) return;      // (block-uniform: a kernel argument) not a probe: the permutation is all that was asked for
     __syncthreads();
     // ---- expected cold wave-rows per row: Σ_tiles (1 − Π (1 − p)), as given and sorted. A tile = LPT consecutive threads.
     constexpr int LPT = WAVE / TILE_WPT;
-    float s_id = 0.0f, s_so = 0.0f;
+    float s_id = 0.0f, s_so = 0.0f, f_id = 0.0f, f_so = 0.0f;      // f: walkers of the tile that are NOT slow (small counts: exact)
 #pragma unroll
-    for (int i = 0; i < TILE_WPT; ++i) { s_id += lq[i]; s_so += slq[TILE_WPT * t + i]; }
+    for (int i = 0; i < TILE_WPT; ++i) {
+        s_id += lq[i]; s_so += slq[TILE_WPT * t + i];
+        f_id += slow[i] ? 0.0f : 1.0f; f_so += sq[TILE_WPT * t + i] ? 0.0f : 1.0f;
+    }
 #pragma unroll
-    for (int d = 1; d < LPT; d <<= 1) { s_id += __shfl_xor(s_id, d, WAVE); s_so += __shfl_xor(s_so, d, WAVE); }
+    for (int d = 1; d < LPT; d <<= 1) {
+        s_id += __shfl_xor(s_id, d, WAVE); s_so += __shfl_xor(s_so, d, WAVE);
+        f_id += __shfl_xor(f_id, d, WAVE); f_so += __shfl_xor(f_so, d, WAVE);
+    }
     const bool head = (lane & (LPT - 1)) == 0 && TILE_WPT * t < n_seg;
     float c_id = head ? 1.0f - __builtin_amdgcn_exp2f(s_id) : 0.0f;
     float c_so = head ? 1.0f - __builtin_amdgcn_exp2f(s_so) : 0.0f;
+    float q_id = head && f_id == 0.0f ? 1.0f : 0.0f;
+    float q_so = head && f_so == 0.0f ? 1.0f : 0.0f;
 #pragma unroll
-    for (int d = LPT; d < WAVE; d <<= 1) { c_id += __shfl_xor(c_id, d, WAVE); c_so += __shfl_xor(c_so, d, WAVE); }
-    if (lane == 0) { red[2 * wv] = c_id; red[2 * wv + 1] = c_so; }
+    for (int d = LPT; d < WAVE; d <<= 1) {
+        c_id += __shfl_xor(c_id, d, WAVE); c_so += __shfl_xor(c_so, d, WAVE);
+        q_id += __shfl_xor(q_id, d, WAVE); q_so += __shfl_xor(q_so, d, WAVE);
+    }
+    if (lane == 0) { red[TILE_NSTAT * wv] = c_id; red[TILE_NSTAT * wv + 1] = c_so; red[TILE_NSTAT * wv + 2] = q_id; red[TILE_NSTAT * wv + 3] = q_so; }
     __syncthreads();
     if (t == 0) {
-        float x = 0.0f, y = 0.0f;
-        for (int k = 0; k < TILE_TPB / WAVE; ++k) { x += red[2 * k]; y += red[2 * k + 1]; }
-        a.stats[2 * blockIdx.x] = x; a.stats[2 * blockIdx.x + 1] = y;
+        float x = 0.0f, y = 0.0f, u = 0.0f, v = 0.0f;
+        for (int k = 0; k < TILE_TPB / WAVE; ++k) { x += red[TILE_NSTAT * k]; y += red[TILE_NSTAT * k + 1]; u += red[TILE_NSTAT * k + 2]; v += red[TILE_NSTAT * k + 3]; }
+        float* o = a.stats + TILE_NSTAT * blockIdx.x;
+        o[0] = x; o[1] = y; o[2] = u; o[3] = v;
     }
 }
 #endif      // OCTO_API_TU
