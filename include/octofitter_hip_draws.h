@@ -84,6 +84,11 @@
  *               two adaptation tests and the two new values · k = 2 + d/4, word d % 4: the crossover uniform of coordinate d · k = 18 + d/4, word
  *               d % 4: the bound-repair uniform of coordinate d (D <= 64: the blocks of the two do not meet)
  *
+ * The sixteenth is the OFTI rejection sampler (octo_draws_ofti_set … octo_draws_ofti_rejection): prior draws scored by the marginal likelihood of
+ * ofti_linear_solve, the rejection step, and for every survivor a draw of the Thiele-Innes constants from their conditional normal with its Campbell
+ * elements, stated in full at their declaration (tests/ofti_draws_reference.py restates them). Its stream adds
+ *   purpose 13: the four standard normals of draw i's Thiele-Innes constants, counter (i, 0, 13, 0), words 0 … 3
+ *
  * Not thread-safe: a handle uses its context (scratch, stream ordering), so the rule of the main header holds — one host
  * thread at a time per context, the handle's calls included.
  */
@@ -918,6 +923,71 @@ int32_t octo_draws_de_device(octo_draws* h, uint64_t seed, uint64_t gen0, int64_
                              int32_t* d_n_accept, int32_t* d_best, double* d_best_logpost, int32_t* d_n_improved, void* hip_stream);
 /* Host only: the doubles of that work array at D coordinates and leading dimension ld, (5·D + 12)·ld; 0 with D < 1 or ld < 0. */
 int64_t octo_draws_de_work_doubles(int32_t D, int64_t ld);
+
+/* ---- The sixteenth: the OFTI rejection sampler (examples/ofti_rejection_sampling.jl:78-108 of the reference): prior draws of (e, a, tp, M, plx), each
+ * scored by the marginal likelihood of ofti_linear_solve (octo_ofti_eval_device of the main library), accepted with probability exp(ℓ − max ℓ), and every
+ * survivor turned into an orbit: a draw of the Thiele-Innes constants from their conditional normal and the Campbell elements of that draw. The functions
+ * are stated in full so that a restatement elsewhere (tests/ofti_draws_reference.py) and the device compute the same function.
+ *
+ * octo_draws_ofti_set: the handle must have D = 5 priors in the order (e, a, tp or τ, M, plx) and a context; it needs no model. The call creates an
+ * octo_ofti of its own on the handle's context (octo_ofti_create: its input checks, its status and its message are passed through) and uploads the rows
+ * of the table for k_oftis_post with the weights octo_ofti_create forms: det = σ_ra²σ_dec²(1 − ρ²), w_rr = σ_dec²/det, w_dd = σ_ra²/det,
+ * w_rd = −ρσ_raσ_dec/det, p = w_rr·ra + w_rd·dec, q = w_dd·dec + w_rd·ra; λ = 1/σ_ABFG².
+ *   tp_mode 0   the third coordinate is tp [MJD]
+ *   tp_mode 1   the third coordinate is τ, tp = fma(τ, P_d, t_ref) with P_d = k_yr·sqrt(a·a·a/M), k_yr = consts->kepler_year_to_julian_day
+ * consts (NULL: octo_consts_default) must be what the CONTEXT holds (octo_consts_set): the context's kernels form the period from theirs. The main
+ * header has no call that reads a context's constants back, so this cannot be checked here: with other constants the draws are SCORED at one period
+ * and their tp (tp_mode 1), P_d and M_dyn are formed at another, silently.
+ * A second call replaces the first (one that fails past its argument checks leaves nothing set). octo_draws_ofti_clear undoes the call (no-op when nothing is set); octo_draws_destroy and octo_draws_detach release
+ * the OFTI state first.
+ * OCTO_EINVAL: NULL handle; D != 5; a handle without a context (detached); tp_mode outside 0, 1; t_ref not finite with tp_mode 1; and what
+ * octo_ofti_create refuses. */
+#define OCTO_DRAWS_PURPOSE_OFTI 13
+#define OCTO_DRAWS_OFTI_N_OUT 16
+int32_t octo_draws_ofti_set(octo_draws* h, const double* epochs, const double* ra, const double* dec, const double* sigma_ra, const double* sigma_dec,
+                            const double* cor /*NULL = 0*/, int64_t n_epochs, double sigma_abfg, int32_t tp_mode, double t_ref,
+                            const octo_consts* consts /*NULL = octo_consts_default*/);
+int32_t octo_draws_ofti_clear(octo_draws* h);
+
+/* θ (natural domain, d_theta [5][ld]: octo_draws_sample_device's) to the nl of octo_ofti_eval_device, d_nl [5][ld]: rows 0, 1, 3, 4 are copied, row 2 is tp
+ * by the handle's tp_mode. Asynchronous on hip_stream. OCTO_EINVAL: NULL handle; nothing set; n < 0, ld < n; a NULL array with n > 0. */
+int32_t octo_draws_ofti_nl_device(octo_draws* h, int64_t n, int64_t ld, const double* d_theta, double* d_nl, void* hip_stream);
+
+/* The posterior draw of n parameter sets, lane = draw (k_oftis_post), asynchronous on hip_stream. Per draw with index i = d_index[k] and nl = column k:
+ *   sums     the 13 sums of the normal equations over the rows of the table IN ROW ORDER by fma, from x = cos E − e, y = √(1 − e²)·sin E of the cold
+ *            Kepler solve (Markley's starter and fifth-order correction with the half-angle polynomial sin/cos: octo_device.h, kepler_solve<-1, false>):
+ *            Σw·xx, Σw·xy, Σw·yy for w = w_rr, w_dd, w_rd; Σx·q, Σy·q, Σx·p, Σy·p.
+ *   solve    S = DᵀWD + λI in the order (A, B, F, G), its Cholesky factor L (S = L·Lᵀ), μ = S⁻¹b and ℓ, operation for operation as octo_ofti_eval_device's
+ *            finishing kernel forms them; ℓ = −Inf by its rule: an element not finite, e outside [0, 1), a <= 0, M <= 0, S not positive definite, ℓ not finite.
+ *   normals  z_k = normcdfinv(uniform of word k of Philox(key, counter (i, 0, 13, 0))), k = 0 … 3: octo_draws_momentum_device's routines.
+ *   draw     x = μ + L⁻ᵀz by back substitution from k = 3: a function of (seed, i, nl) alone.
+ *   elements with u+v = ((A + G)² + (B − F)²)/2 and u−v = ((A − G)² + (B + F)²)/2 — u = (A² + B² + F² + G²)/2, v = AG − BF, without their cancellation —
+ *            s₊ = √(u+v), s₋ = √(u−v): α = (s₊ + s₋)/√2 [mas] · cos i = (s₊ − s₋)/(s₊ + s₋) · ω + Ω = atan2(B − F, A + G) · ω − Ω = atan2(−B − F, A − G) ·
+ *            ω and Ω their half sum and half difference, folded by (ω, Ω) -> (ω ± π, Ω ± π) to Ω ∈ [0, π) and then ω by 2π to [0, 2π) · a_ti = α/plx [AU] ·
+ *            P_d = k_yr·sqrt(a·a·a/M) [d] · M_dyn = M·a_ti³/a³, the total mass at which an orbit of semi-major axis a_ti has the period the solve used.
+ *            The convention is the main library's: dec = A·X + F·Y, ra = B·X + G·Y, and its Campbell planet at (a_ti, e, i, ω, Ω, tp, M_dyn, plx) is its
+ *            Thiele-Innes planet at the draw.
+ *   d_out    [OCTO_DRAWS_OFTI_N_OUT][ld]: rows 0-3 the draw (A, B, F, G) · 4-7 μ · 8 α · 9 a_ti · 10 i · 11 ω · 12 Ω · 13 P_d · 14 M_dyn · 15 ℓ.
+ *            A draw with ℓ = −Inf has NaN in rows 0-14. No lane reads another lane's data: an invalid draw leaves its neighbours their bits.
+ * OCTO_EINVAL: NULL handle; nothing set; n < 0, ld < n; a NULL array with n > 0. */
+int32_t octo_draws_ofti_posterior_device(octo_draws* h, uint64_t seed, int64_t n, int64_t ld, const uint64_t* d_index /*[n]*/, const double* d_nl /*[5][ld]*/,
+                                         double* d_out /*[OCTO_DRAWS_OFTI_N_OUT][ld]*/, void* hip_stream);
+
+/* The twin of octo_draws_rejection on the OFTI likelihood: HOST outputs, blocking, on the handle's stream. Pass 1, in chunks of 2^18 draws: the prior
+ * draws (purpose 0), their nl, octo_ofti_eval_device without the means, ℓ (not finite -> −Inf) kept for all N at 8 bytes a draw. Pass 2 is
+ * octo_draws_rejection's, the same kernels: draw i accepted iff ℓ_i != −Inf and its purpose-1 uniform is below exp(ℓ_i − max ℓ); accepted draws in
+ * draw-index order. θ of the stored draws is regenerated from the counter, then their nl and their posterior draw as above.
+ * Row 15 of post_out is octo_draws_ofti_posterior_device's OWN ℓ, not the ℓ that decided acceptance: the two kernels solve Kepler's equation with
+ * different sin/cos routines and sum the rows in different orders, so they agree to rounding (1e-9·max(1, |ℓ|) is the tested bar) and not bit for bit;
+ * *max_logml is pass 1's. In principle a draw that pass 1 accepts at the very edge of validity (S barely positive definite) can come back invalid
+ * from the posterior kernel, with NaN in rows 0-14 and ℓ = −Inf: a caller should drop such a column.
+ * At most `cap` are stored (cap = 0: count only; the arrays may then be NULL); *n_accepted is the full count, *max_logml (or NULL) the maximum.
+ *   theta_out [5][cap] · nl_out [5][cap] · post_out [OCTO_DRAWS_OFTI_N_OUT][cap] · index_out [cap]
+ * OCTO_EINVAL: NULL handle; nothing set; N < 1, first + N overflowing; cap < 0, NULL n_accepted, a NULL array with cap > 0; with the reference's message
+ * when every ℓ is −Inf. OCTO_ENOMEM: the work group (10·2^18 + N + 2⌈N/256⌉ + 2 + 29·min(cap, N) doubles) could not be allocated; the handle stays usable. */
+int32_t octo_draws_ofti_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64_t N, int64_t cap, double* theta_out /*[5][cap]*/,
+                                  double* nl_out /*[5][cap]*/, double* post_out /*[16][cap]*/, uint64_t* index_out /*[cap]*/, int64_t* n_accepted,
+                                  double* max_logml);
 
 #ifdef __cplusplus
 }

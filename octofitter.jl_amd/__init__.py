@@ -26,7 +26,7 @@ from .host.callers import (guess_starting_position, octofit_rejection, rejection
                            guess_starting_position_device, octofit_rejection_device, simulate_tables, posterior_predictive,
                            pointwise_like_rows, waic, loo, octofit_pt_device, octofit_pigeons_device, optimize_starting_points_device, pathfinder_device,
                            warmup_windows, hmc_warmup, octofit_hmc_device, octofit_nuts_device, diagnose_draws_device, octofit_nested_device,
-                           global_search_device, initialize_device)
+                           global_search_device, initialize_device, octofit_ofti_device)
 from .host.draws import PriorDraws  # noqa: F401,E402
 from .host import predict  # noqa: F401,E402
 from .host.predict import Predictor  # noqa: F401,E402

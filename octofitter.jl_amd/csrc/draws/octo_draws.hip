@@ -231,6 +231,39 @@ double normcdf_host(double z) { return 0.5 * std::erfc(-z * 0.707106781186547524
 
 }  // namespace
 
+// ---- what the OFTI driver (octo_draws_ofti.hip) takes from this unit, declared in octo_draws_common.h: the draw launches and pass 2 of the
+// rejection — the kernels of octo_draws_rejection, launched as it launches them
+int draws_launch_draw(octo_draws* h, hipStream_t st, uint64_t seed, uint64_t first, const uint64_t* d_idx, int64_t n, int64_t ld, double* d_theta) {
+    return launch_draw(h, st, seed, first, d_idx, n, ld, d_theta, nullptr, nullptr);
+}
+
+// The two halves of pass 2, written once for octo_draws_rejection and the OFTI driver (a caller sizes its outputs between them). The maximum of the
+// block maxima, on the host too, and the refusal when every ℓ is −Inf:
+int draws_max_pass(octo_draws* h, hipStream_t st, const double* pmax, int64_t N, double* d_max, double* mx_out) {
+    hipLaunchKernelGGL(k_max, dim3(1), dim3(TPB), 0, st, pmax, (N + TPB - 1) / TPB, d_max);
+    OCHK(h, hipGetLastError());
+    double mx = 0.0;
+    OCHK(h, hipMemcpyAsync(&mx, d_max, sizeof(double), hipMemcpyDeviceToHost, st));
+    OCHK(h, hipStreamSynchronize(st));
+    if (mx_out) *mx_out = mx;
+    if (!std::isfinite(mx))      // sampling.jl:194-197
+        return fail(h, OCTO_EINVAL, "All " + std::to_string(N) + " prior samples produced non-finite log-likelihoods. Check your model and priors.");
+    return OCTO_OK;
+}
+
+// flags -> block counts -> offsets -> ordered scatter of at most `room` accepted draws, and the full count
+int draws_accept_pass(octo_draws* h, hipStream_t st, const double* ll, const double* lp, int64_t N, const double* d_max, uint64_t seed, uint64_t first,
+                      int64_t* cnt, int64_t room, uint64_t* o_ix, double* o_ll, double* o_lp, int64_t* total_out) {
+    const int64_t nblk = (N + TPB - 1) / TPB;
+    hipLaunchKernelGGL(k_count, grid_of(N), dim3(TPB), 0, st, ll, N, d_max, seed, first, cnt);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(TPB), 0, st, cnt, nblk);
+    hipLaunchKernelGGL(k_scatter, grid_of(N), dim3(TPB), 0, st, ll, lp, N, d_max, seed, first, cnt, room, o_ix, o_ll, o_lp);
+    OCHK(h, hipGetLastError());
+    OCHK(h, hipMemcpyAsync(total_out, cnt + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    OCHK(h, hipStreamSynchronize(st));
+    return OCTO_OK;
+}
+
 extern "C" {
 
 int32_t octo_draws_create(octo_ctx* ctx, octo_model* model, const octo_prior* priors, int32_t D, int32_t device_id, octo_draws** out) {
@@ -291,6 +324,7 @@ int32_t octo_draws_create(octo_ctx* ctx, octo_model* model, const octo_prior* pr
 int32_t octo_draws_destroy(octo_draws* h) {
     if (!h) return OCTO_OK;
     (void)hipSetDevice(h->device);
+    (void)octo_draws_ofti_clear(h);      // the OFTI state first: its octo_ofti lives on the context
     if (h->stream) {
         (void)hipStreamSynchronize(h->stream);
         // The context orders a change of stream with an event recorded on the stream of its PREVIOUS call: it must not be left naming a stream
@@ -304,7 +338,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
         }
         if (release) (void)hipStreamDestroy(h->stream);
     }
-    for (void* p : std::initializer_list<void*>{h->own_priors, h->own_pc, h->own_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice, h->d_prog, h->d_prog_tab, h->d_ncull, h->d_nest, h->d_de})
+    for (void* p : std::initializer_list<void*>{h->own_priors, h->own_pc, h->own_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice, h->d_prog, h->d_prog_tab, h->d_ncull, h->d_nest, h->d_de, h->d_oftis, h->d_oftis_rows})
         (void)hipFree(p);
     delete h;
     return OCTO_OK;
@@ -312,6 +346,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
 
 int32_t octo_draws_detach(octo_draws* h) {
     if (!h) return OCTO_EINVAL;
+    (void)octo_draws_ofti_clear(h);
     h->ctx = nullptr; h->model = nullptr; h->prog_ops = nullptr;
     return OCTO_OK;
 }
@@ -389,7 +424,6 @@ int32_t octo_draws_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64
     { int rc = ensure_chunk(h, k); if (rc) return rc; }
     { int rc = ensure_draw_arrays(h, N, a); if (rc) return rc; }
     const hipStream_t st = h->stream;
-    const int64_t nblk = (N + TPB - 1) / TPB;
     // pass 1: ll of every draw, chunk by chunk (chunk boundaries are block boundaries), and its maximum
     for (int64_t done = 0; done < N; done += CHUNK) {
         const int64_t n = std::min(CHUNK, N - done);
@@ -398,25 +432,13 @@ int32_t octo_draws_rejection(octo_draws* h, uint64_t seed, uint64_t first, int64
         hipLaunchKernelGGL(k_loglike, grid_of(n), dim3(TPB), 0, st, a.lp + done, k.lpt, n, a.ll + done, a.pmax + done / TPB);
         OCHK(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_max, dim3(1), dim3(TPB), 0, st, a.pmax, nblk, k.max);
-    OCHK(h, hipGetLastError());
-    double mx = 0.0;
-    OCHK(h, hipMemcpyAsync(&mx, k.max, sizeof(double), hipMemcpyDeviceToHost, st));
-    OCHK(h, hipStreamSynchronize(st));
-    if (max_loglike) *max_loglike = mx;
     *n_accepted = 0;
-    if (!std::isfinite(mx))      // sampling.jl:194-197
-        return fail(h, OCTO_EINVAL, "All " + std::to_string(N) + " prior samples produced non-finite log-likelihoods. Check your model and priors.");
+    { int rc = draws_max_pass(h, st, a.pmax, N, k.max, max_loglike); if (rc) return rc; }
     // pass 2: flags -> block counts -> offsets -> ordered scatter
     { int rc = ensure_outputs(h, std::max<int64_t>(std::min(cap, N), 1), o); if (rc) return rc; }
     const int64_t room = std::min(cap, N);
-    hipLaunchKernelGGL(k_count, grid_of(N), dim3(TPB), 0, st, a.ll, N, k.max, seed, first, a.cnt);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(TPB), 0, st, a.cnt, nblk);
-    hipLaunchKernelGGL(k_scatter, grid_of(N), dim3(TPB), 0, st, a.ll, a.lp, N, k.max, seed, first, a.cnt, room, o.ix, o.ll, o.lp);
-    OCHK(h, hipGetLastError());
     int64_t total = 0;
-    OCHK(h, hipMemcpyAsync(&total, a.cnt + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    OCHK(h, hipStreamSynchronize(st));
+    { int rc = draws_accept_pass(h, st, a.ll, a.lp, N, k.max, seed, first, a.cnt, room, o.ix, o.ll, o.lp, &total); if (rc) return rc; }
     *n_accepted = total;
     const int64_t ns = std::min(total, room);
     if (ns == 0) return OCTO_OK;

@@ -18,6 +18,8 @@
 // call) beside the samplers' head, preamble, target and round driver.
 // The fifteenth part, differential evolution (octo_draws_de.hip), takes the samplers' head, preamble, target, dead test and round driver as the slice
 // sampler does, one generation a run_rounds call of one round.
+// The sixteenth part, the OFTI rejection sampler (octo_draws_ofti.hip), takes the generator, the handle and grow_to, and from octo_draws.hip the draw
+// launches and the rejection's second pass (draws_launch_draw, draws_max_pass, draws_accept_pass below).
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
 
@@ -351,7 +353,25 @@ struct octo_draws : CompanionBase {
     int64_t de_W = 0, de_ld = 0; int32_t de_radius = 0, de_flip = 0;
     uint64_t de_seed = 0, de_gen = 0;
     bool de_open = false, de_bounds = false;
+    // the OFTI rejection sampler (octo_draws_ofti.hip) while octo_draws_ofti_set holds (ofti null: not set): the main library's handle on the table,
+    // the table's rows for k_oftis_post with the scalars octo_ofti_create forms beside them, how the third coordinate is read, and the driver's work
+    // group, grown on demand
+    octo_ofti* ofti = nullptr;
+    double* d_oftis_rows = nullptr; int64_t cap_oftis_rows = 0;
+    int32_t oftis_n_rows = 0, oftis_tp_mode = 0;
+    double oftis_t_ref = 0.0, oftis_k_yr = 0.0, oftis_lambda = 0.0, oftis_data_quad = 0.0, oftis_log_det_data_cov = 0.0, oftis_log_det_prior_inv = 0.0,
+           oftis_n_log2pi = 0.0;
+    double* d_oftis = nullptr; int64_t cap_oftis = 0;
 };
+
+// What octo_draws_ofti.hip takes from octo_draws.hip (defined there, not exported): k_draw's launches into θ alone, and the two halves of pass 2 of the
+// rejection on ℓ [N] with its block maxima, the code octo_draws_rejection itself runs — draws_max_pass: k_max, the maximum on the host, the refusal when
+// every ℓ is −Inf; draws_accept_pass: k_count, k_scan, k_scatter and the full count.
+#define OCTO_DRAWS_INTERNAL __attribute__((visibility("hidden")))
+OCTO_DRAWS_INTERNAL int draws_launch_draw(octo_draws* h, hipStream_t st, uint64_t seed, uint64_t first, const uint64_t* d_idx, int64_t n, int64_t ld, double* d_theta);
+OCTO_DRAWS_INTERNAL int draws_max_pass(octo_draws* h, hipStream_t st, const double* pmax, int64_t N, double* d_max, double* mx_out);
+OCTO_DRAWS_INTERNAL int draws_accept_pass(octo_draws* h, hipStream_t st, const double* ll, const double* lp, int64_t N, const double* d_max, uint64_t seed,
+                                          uint64_t first, int64_t* cnt, int64_t room, uint64_t* o_ix, double* o_ll, double* o_lp, int64_t* total_out);
 
 namespace {
 

@@ -150,6 +150,26 @@ inline DeWork de_work(Carve& c, int64_t D, int64_t ld) {
             c.take<int32_t>(ld), c.take<int32_t>(ld)};
 }
 
+// The OFTI rejection sampler (octo_draws_ofti.hip). The rows of the table for k_oftis_post, d_oftis_rows: 8·n_rows — a row record of the main
+// library, {t, w_rr, w_dd, w_rd, p, q, 0, 0}.
+struct OftiRows { double* rows; };      // [n_rows][8]
+inline OftiRows ofti_rows(Carve& c, int64_t n_rows) { return {c.take(8 * n_rows)}; }
+
+// The work group of one octo_draws_ofti_rejection call, d_oftis: 10·chunk + N + 2·nblk + 2 + 29·room. Per chunk θ and nl (regenerated, never kept for
+// all N); ℓ of all N draws at 8 bytes a draw, the block maxima, the block counts with their total, the maximum; for the `room` stored draws their
+// index, ℓ (twice: k_scatter writes two columns), θ, nl and the posterior rows.
+struct OftiWork {
+    double *theta, *nl;                   // [5][chunk]
+    double *ll, *pmax; int64_t* cnt;      // [N] · [nblk] · [nblk + 1]
+    double* max;                          // [1]
+    uint64_t* ix; double *oll, *olp;      // [room]
+    double *otheta, *onl, *post;          // [5][room] · [5][room] · [16][room]
+};
+inline OftiWork ofti_work(Carve& c, int64_t chunk, int64_t N, int64_t nblk, int64_t room) {
+    return {c.take(5 * chunk), c.take(5 * chunk), c.take(N), c.take(nblk), c.take<int64_t>(nblk + 1), c.take(1),
+            c.take<uint64_t>(room), c.take(room), c.take(room), c.take(5 * room), c.take(5 * room), c.take(16 * room)};
+}
+
 // The order of one cull of nested sampling, d_ncull: K. order[r] = the live slot of rank r, ascending by (ℓ, slot).
 struct NestedCull { int32_t* order; };      // [K]
 inline NestedCull nested_cull(Carve& c, int64_t K) { return {c.take<int32_t>(K)}; }

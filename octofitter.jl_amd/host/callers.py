@@ -9,6 +9,9 @@ host, re-expressed on the LogDensityModel mirror so that every likelihood evalua
   guess_starting_position_device / octofit_rejection_device: the same two drivers with the draws, the link, the argmax and the
   accept / compaction step on the device too (host/draws.py: PriorDraws) — only the winners / the accepted chain cross PCIe.
 
+  octofit_ofti_device: the OFTI rejection sampler (examples/ofti_rejection_sampling.jl:78-108) — prior draws, the marginal likelihood, the rejection
+  step, the Thiele-Innes draw of every survivor and its Campbell elements on the device (PriorDraws.ofti_set / ofti_rejection).
+
   octofit_pt_device: parallel tempering with a tempered HMC explorer, fresh prior draws at β = 0 and the swap step all on the device
   (PriorDraws.hmc_step, host/tempering.py: TemperedSwap) — the device-resident twin of julia/OctofitterHIP.jl: octofit_pigeons_hip.
   octofit_pigeons_device: that driver in Pigeons' rounds — the ladder re-placed from the communication barrier, the log evidence and the tempered
@@ -142,6 +145,42 @@ def octofit_rejection_device(model, draws=100_000, seed=0):
     return dict(samples=r["samples"], loglike=r["loglike"], logpost=r["logpost"], draws=int(draws), n_accepted=r["n_accepted"],
                 acceptance_rate=r["n_accepted"] / draws, names=list(model.names), accept=accept, all_loglike=None,
                 index=r["index"], max_loglike=r["max_loglike"])
+
+
+def octofit_ofti_device(epochs, ra, dec, σ_ra, σ_dec, cor, σ_ABFG, priors, draws=1_000_000, seed=0, t_ref=None, cap=None, device=0):
+    """The reference's OFTI rejection sampler (examples/ofti_rejection_sampling.jl:78-108) in one call, on the device: `draws` prior draws of
+    (e, a, tp | τ, M, plx), each scored by the marginal likelihood of ofti_linear_solve, accepted with probability exp(ℓ − max ℓ), and for every
+    accepted draw the Thiele-Innes constants drawn from their conditional normal and turned into Campbell elements (PriorDraws.ofti_rejection).
+    priors: a variables(e=…, a=…, tp=… or τ=…, M=…, plx=…) block of host/priors.py; τ (the orbit fraction at t_ref) needs t_ref [MJD].
+    Returns a dict of NumPy columns over the accepted draws, in draw-index order: the five drawn parameters (e, a, tp or τ, M, plx), tp, the 16
+    rows of draws.OFTI_OUTPUTS by name (A, B, F, G, their means, alpha [mas], a_ti [AU], i, ω, Ω, P_d, M_dyn, logml), index, and the scalars
+    n_accepted, max_logml, draws, acceptance_rate. (a_ti, e, i, ω, Ω, tp, M_dyn, plx) are the elements posterior_predictive and Predictor take:
+    `a` is the semi-major axis the period of the solve was made from, a_ti the one the drawn constants have — the linear model leaves the scale of
+    the orbit free — and M_dyn is the total mass at which an orbit of semi-major axis a_ti has that period."""
+    from . import capi
+    from .draws import OFTI_OUTPUTS, PriorDraws
+    names = list(priors)
+    third = "τ" if "τ" in names else "tp"
+    if names != ["e", "a", third, "M", "plx"]:
+        raise ValueError("octofit_ofti_device: priors must be variables(e=…, a=…, tp=… or τ=…, M=…, plx=…), in that order")
+    if third == "τ" and t_ref is None:
+        raise ValueError("octofit_ofti_device: a τ prior needs t_ref")
+    with PriorDraws(priors=[priors[n] for n in names], device=device) as pd:
+        pd.ofti_set(epochs, ra, dec, σ_ra, σ_dec, cor, σ_ABFG, tp_mode=int(third == "τ"), t_ref=0.0 if t_ref is None else float(t_ref))
+        try:
+            r = pd.ofti_rejection(seed, draws, cap=cap)
+        except capi.OctoError as e:
+            if e.status == capi.OCTO_EINVAL and "non-finite log-likelihoods" in str(e):
+                raise RuntimeError(str(e).split(": ", 1)[1]) from None
+            raise
+    if r["n_accepted"] == 0:
+        raise RuntimeError(f"No samples were accepted out of {draws} draws. The posterior may be extremely concentrated relative "
+                           "to the prior. Consider increasing `draws` or using a different sampler.")
+    out = {n: r["theta"][k] for k, n in enumerate(names)}
+    out["tp"] = r["nl"][2]
+    out.update({n: r["post"][k] for k, n in enumerate(OFTI_OUTPUTS)})
+    out.update(index=r["index"], n_accepted=r["n_accepted"], max_logml=r["max_logml"], draws=int(draws), acceptance_rate=r["n_accepted"] / int(draws))
+    return out
 
 
 def _default_metric(pd, seed, dev, inv_mass):

@@ -35,6 +35,8 @@ ctypes binding of the companion C ABI in include/octofitter_hip_draws.h (lib/lib
     y = draws.metric_apply(chol, x, transpose=False)        # … L·x or Lᵀ·x of the columns of x [D, n]
     with draws.use_metric(chol): ...                        # … hmc_step and nuts inside run under L·Lᵀ and take no inv_mass (pack_lower, unpack_lower)
     r = draws.de_step(θ_t, lo, hi, radius=8, n_gen=200, seed=seed)      # differential evolution: 200 generations of the population θ_t, updated in place (dict)
+    pd = PriorDraws(priors=[e, a, τ, M, plx]); pd.ofti_set(epochs, ra, dec, σ_ra, σ_dec, cor, σ_ABFG, tp_mode=1, t_ref=50000.0)
+    r = pd.ofti_rejection(seed, 1_000_000)                  # OFTI: prior draws -> accepted orbits, dict(theta, nl, post [16, n], index, n_accepted, max_logml)
 
 Draw i of a seed is a pure function of (seed, i): Philox4x64-10 with key (seed, "octodraw") and counter (i, d // 4, purpose, 0)
 — the same number whatever call, batch or chunk produces it. Like capi.py this is plumbing that FAILS LOUDLY when the library
@@ -73,6 +75,9 @@ DENSE_MAX_D = 64                   # OCTO_DRAWS_DENSE_MAX_D
 PURPOSE_DE = 12
 DE_TAU_F, DE_F_LOW, DE_F_SPAN, DE_TAU_CR, DE_F0, DE_CR0 = 0.1, 0.1, 0.9, 0.1, 0.5, 0.9      # OCTO_DRAWS_DE_*
 DE_OUTPUTS = ("fcr", "logpost", "loglike", "n_accept", "best", "best_logpost", "n_improved")      # the outputs of octo_draws_de_device, in order
+PURPOSE_OFTI = 13
+OFTI_N_OUT = 16                    # OCTO_DRAWS_OFTI_N_OUT
+OFTI_OUTPUTS = ("A", "B", "F", "G", "A_mean", "B_mean", "F_mean", "G_mean", "alpha", "a_ti", "i", "ω", "Ω", "P_d", "M_dyn", "logml")      # the rows of d_out, in order
 DIAG_RHAT, DIAG_ESS_BULK, DIAG_ESS_TAIL, DIAG_RHAT_BASIC, DIAG_ESS_BASIC, DIAG_Q05, DIAG_Q50, DIAG_Q95, DIAG_N_STATS = range(9)      # OCTO_DRAWS_DIAG_*
 PT_ACC_COLUMNS = ("n", "A", "n_f", "m_f", "s_f", "n_b", "m_b", "s_b")      # the columns of d_acc [T − 1][8]
 PT_SUMMARY = ("barrier", "log_evidence_fwd", "log_evidence_rev", "log_evidence")      # the entries of d_summary, in order
@@ -147,6 +152,12 @@ _SIGS = {
     "octo_draws_de_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
                              + [C.c_void_p] * 8),
     "octo_draws_de_work_doubles": (C.c_int64, [C.c_int32, C.c_int64]),
+    "octo_draws_ofti_set": (C.c_int32, [C.c_void_p] + [capi.c_double_p] * 6 + [C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_void_p]),
+    "octo_draws_ofti_clear": (C.c_int32, [C.c_void_p]),
+    "octo_draws_ofti_nl_device": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_ofti_posterior_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "octo_draws_ofti_rejection": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, capi.c_double_p, capi.c_double_p, capi.c_double_p,
+                                              c_uint64_p, C.POINTER(C.c_int64), capi.c_double_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -422,6 +433,63 @@ class PriorDraws(companion.Handle):
         ns = min(int(n_acc.value), cap)
         return dict(samples=np.ascontiguousarray(th[:, :ns]), loglike=ll[:ns].copy(), logpost=lp[:ns].copy(), index=ix[:ns].copy(),
                     n_accepted=int(n_acc.value), max_loglike=float(mx.value))
+
+    # ---- the OFTI rejection sampler (include/octofitter_hip_draws.h, "The sixteenth"): a handle of five priors (e, a, tp or τ, M, plx)
+    def ofti_set(self, epochs, ra, dec, σ_ra, σ_dec, cor, σ_ABFG, tp_mode=0, t_ref=0.0, consts=None):
+        """octo_draws_ofti_set: the RA/Dec table (host arrays; cor None = 0) and σ_ABFG of the OFTI likelihood. tp_mode 1: the third prior is τ and
+        tp = t_ref + τ·P_d. consts: a capi.OctoConsts, what the context holds (None: the defaults)."""
+        cols = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in (epochs, ra, dec, σ_ra, σ_dec)]
+        n = cols[0].size
+        if any(c.size != n for c in cols):
+            raise ValueError("ofti_set: the columns must have one length")
+        cc = None if cor is None else np.ascontiguousarray(cor, dtype=np.float64).reshape(-1)
+        if cc is not None and cc.size != n:
+            raise ValueError("ofti_set: cor must have the columns' length")
+        self._check(self.lib.octo_draws_ofti_set(self._h, *[capi._dptr(c) for c in cols], capi._dptr(cc), n, float(σ_ABFG), int(tp_mode), float(t_ref),
+                                                 None if consts is None else C.cast(C.pointer(consts), C.c_void_p)))
+
+    def ofti_clear(self):
+        """octo_draws_ofti_clear"""
+        self._check(self.lib.octo_draws_ofti_clear(self._h))
+
+    def ofti_nl(self, theta, stream=None):
+        """nl [5, n] (e, a, tp, M, plx: what octo_ofti_eval_device reads) of θ [5, n] in the natural domain (`sample`'s). Asynchronous on `stream`."""
+        _, n, ld = chain_matrix(theta, 5, self.device, "ofti_nl", "theta")
+        nl = self._out(n, 5, ld)
+        self._check(self.lib.octo_draws_ofti_nl_device(self._h, n, ld, theta.data_ptr(), nl.data_ptr(), self._stream(stream, self.device)))
+        self._keep = (theta, nl)
+        return nl
+
+    def ofti_posterior(self, seed, index, nl, stream=None):
+        """The posterior rows [OFTI_N_OUT, n] (OFTI_OUTPUTS) of the parameter sets nl [5, n] with the draw indices `index` (uint64 values, n of them):
+        the Thiele-Innes draw, its mean, its Campbell elements, ℓ. Asynchronous on `stream`."""
+        import torch
+        _, n, ld = chain_matrix(nl, 5, self.device, "ofti_posterior", "nl")
+        ix = torch.as_tensor(np.ascontiguousarray(index, dtype=np.uint64).view(np.int64), device=self.device).contiguous()
+        if ix.shape != (n,):
+            raise ValueError(f"ofti_posterior: index takes {n} values")
+        out = self._out(n, OFTI_N_OUT, ld)
+        self._check(self.lib.octo_draws_ofti_posterior_device(self._h, int(seed), n, ld, ix.data_ptr(), nl.data_ptr(), out.data_ptr(), self._stream(stream, self.device)))
+        self._keep = (ix, nl, out)
+        return out
+
+    def ofti_rejection(self, seed, N, cap=None, first=0):
+        """Rejection sampling on the OFTI likelihood over draws first … first + N − 1: the accepted draws in draw-index order, at most `cap` of them
+        stored (default: all). dict(theta [5, n_stored], nl [5, n_stored], post [OFTI_N_OUT, n_stored], index, n_accepted, max_logml)."""
+        N = int(N)
+        n_acc, mx = C.c_int64(0), C.c_double(0.0)
+        room = min(N, max(65536, N // 16)) if cap is None else int(cap)
+        while True:
+            w = max(room, 1)
+            th, nl, post, ix = np.empty((5, w)), np.empty((5, w)), np.empty((OFTI_N_OUT, w)), np.empty(w, dtype=np.uint64)
+            self._check(self.lib.octo_draws_ofti_rejection(self._h, int(seed), int(first), N, room, capi._dptr(th), capi._dptr(nl), capi._dptr(post), _u64ptr(ix),
+                                                           C.byref(n_acc), C.byref(mx)))
+            if cap is not None or n_acc.value <= room:
+                break
+            room = int(n_acc.value)                    # more accepted than the first guess held: once more with room for all
+        ns = min(int(n_acc.value), room)
+        return dict(theta=np.ascontiguousarray(th[:, :ns]), nl=np.ascontiguousarray(nl[:, :ns]), post=np.ascontiguousarray(post[:, :ns]), index=ix[:ns].copy(),
+                    n_accepted=int(n_acc.value), max_logml=float(mx.value))
 
     def momentum(self, seed, step, n, inv_mass=None, chain0=0, stream=None):
         """The momenta p [D, n] of chains chain0 … chain0 + n − 1 at `step`: standard normals of the counter generator over √inv_mass."""
