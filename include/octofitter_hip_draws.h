@@ -989,6 +989,75 @@ int32_t octo_draws_ofti_rejection(octo_draws* h, uint64_t seed, uint64_t first, 
                                   double* nl_out /*[5][cap]*/, double* post_out /*[16][cap]*/, uint64_t* index_out /*[cap]*/, int64_t* n_accepted,
                                   double* max_logml);
 
+/* ---- The seventeenth: along-scan absolute astrometry — the Hipparcos intermediate astrometric data and Gaia's per-transit epoch astrometry: one
+ * along-scan coordinate per transit, a scan direction and design columns the caller builds (parallax factors, reference epochs: the library knows
+ * nothing of them). The functions are stated in full so that a restatement elsewhere (tests/scan_reference.py) and the device compute the same function.
+ *
+ * Table      n rows, 1 <= n <= 65536. Row i: epoch t_i [MJD], scan direction (u_i, v_i) along α* and δ, measurement y_i [mas], σ_i > 0 [mas] and
+ *            K design coefficients c_i[0 … K − 1], 0 <= K <= OCTO_DRAWS_SCAN_MAX_K; c is [K][n].
+ * Walker     the main ABI's element rows elems[(p·9 + k)·ld + w], the linear parameters β[k·ld + w], the jitter s[w] (NULL: 0), the planets'
+ *            descriptors (1 <= n_planets <= OCTO_MAX_PLANETS) and the constants (NULL: octo_consts_default, what the program route uses).
+ * Model      R_p(t) = f_p·(raoff_p(t), decoff_p(t)) [mas], f_p = −mass_p·mjup2msol/M_p (0 with has_mass = 0): the reflex rule of the HGCA term,
+ *            q_star = −m_p/M_tot·q_planet. raoff and decoff are the orbit constructor and the projection of the main library on the COLD Kepler solve
+ *            (the companion libraries' rule). OCTO_ORBIT_VISUAL_KEP and OCTO_ORBIT_THIELE_INNES planets contribute, the others contribute 0.
+ *              η_i = Σ_k c_i[k]·β_k + Σ_p (u_i·R_p,α(t_i) + v_i·R_p,δ(t_i))      r_i = y_i − η_i      w_i = 1/(σ_i² + s²)
+ *              ℓ   = Σ_i (−½·w_i·r_i² + ½·log w_i − ½·log 2π)
+ * Gradient   reverse mode: ∂ℓ/∂elems [P·9][ld] through the constructor (the adjoint rules of the main library's finish), ∂ℓ/∂β_k = Σ_i w_i r_i c_i[k],
+ *            ∂ℓ/∂s = s·Σ_i (w_i² r_i² − w_i).
+ * Invalid    a non-finite input, an element outside the main library's domain, s < 0, a non-finite β (or ℓ): ℓ = −Inf and a zero gradient for that
+ *            walker; never a status, never another walker's bits.
+ * Marginal   OCTO_DRAWS_SCAN_MARGINAL: β integrated out under a flat prior. A = Σ_i w_i c_i c_iᵀ, b = Σ_i w_i c_i (y_i − reflex_i), β̂ = A⁻¹b by Cholesky
+ *            per walker, ℓ_marg = ℓ(β̂) + (K/2)·log 2π − ½·log det A; ∂ℓ_marg/∂elems = the sampled adjoints at β̂;
+ *            ∂ℓ_marg/∂s = s·Σ(w_i² r̂_i² − w_i) + s·Σ w_i² c_iᵀA⁻¹c_i. d_beta and d_g_beta are not used; d_beta_hat [K][ld] (or NULL) receives β̂.
+ *            Two Kepler solves per (row, planet): one pass for A and b, one at β̂.
+ * Order      the rows are cut into tasks of OCTO_DRAWS_SCAN_ROWS rows, whatever W is; a task adds its rows in row order by fma, the tasks are added in
+ *            task order. No atomics: a walker's ℓ and gradient depend on its own column alone, bit for bit, in any batch and with any ld.
+ *
+ * octo_draws_scan_set copies the table to the device; it needs neither a model nor a context. A second call replaces the first;
+ * octo_draws_scan_clear removes it (no-op when nothing is set). Both drop a binding. With K > 0 the table must have full column rank: CᵀΣ⁻¹C must be
+ * positive definite (w_i > 0 for every s, so that is a property of the table alone), also where only the sampled mode will be used.
+ * OCTO_EINVAL: NULL handle; a NULL array (c may be NULL with K = 0); n or K or n_planets out of range; σ <= 0; a non-finite entry; an unknown
+ * orbit kind; CᵀΣ⁻¹C not positive definite. */
+#define OCTO_DRAWS_SCAN_MAX_K 6
+#define OCTO_DRAWS_SCAN_ROWS 8
+#define OCTO_DRAWS_SCAN_SAMPLED 0
+#define OCTO_DRAWS_SCAN_MARGINAL 1
+int32_t octo_draws_scan_set(octo_draws* h, const octo_planet_desc* planets, int32_t n_planets, const octo_consts* consts /*NULL = octo_consts_default*/,
+                            const double* t, const double* u, const double* v, const double* y, const double* sigma, const double* c /*[K][n]*/, int32_t K,
+                            int64_t n);
+int32_t octo_draws_scan_clear(octo_draws* h);
+
+/* ℓ [W] and the gradients of W walkers on DEVICE buffers, asynchronous on hip_stream: no host synchronisation, no allocation once the handle's work
+ * array holds (⌈n/OCTO_DRAWS_SCAN_ROWS⌉·n_sums + 28)·ldw doubles, ldw = W rounded up to whole waves, n_sums = 9 + 10·n_planets (marginal: at least 27).
+ * Every gradient output may be NULL; with all of them NULL no adjoint is formed. accumulate = 1 ADDS ℓ into d_ll and the element adjoints into
+ * d_g_elems (an invalid walker adds −Inf and 0); d_g_beta [K][ld], d_g_jitter [W] and d_beta_hat [K][ld] are always stored. accumulate = 0 stores
+ * 0 + the value, so that accumulating into zeroed outputs gives the same bits.
+ * OCTO_EINVAL: NULL handle; no table; mode outside 0, 1; marginal mode with K = 0; W < 0, ld < W; NULL d_elems or d_ll, or NULL d_beta in sampled mode
+ * with K > 0, with W > 0. */
+int32_t octo_draws_scan_eval_device(octo_draws* h, int32_t mode, const double* d_elems, int64_t ld, int64_t W, const double* d_beta, const double* d_jitter,
+                                    double* d_ll, double* d_g_elems, double* d_g_beta, double* d_g_jitter, double* d_beta_hat, int32_t accumulate,
+                                    void* hip_stream);
+/* The twin on HOST buffers, blocking, through the handle's staging on its own stream; accumulate = 0. */
+int32_t octo_draws_scan_eval(octo_draws* h, int32_t mode, const double* elems, int64_t ld, int64_t W, const double* beta, const double* jitter, double* ll,
+                             double* g_elems, double* g_beta, double* g_jitter, double* beta_hat);
+
+/* The model values η [n][ld_out] of W walkers (d_beta NULL: the reflex part alone), asynchronous on hip_stream: for posterior-predictive residuals.
+ * An invalid walker's column is not defined. OCTO_EINVAL: NULL handle; no table; W < 0, ld < W, ld_out < W; NULL d_elems or d_eta with W > 0. */
+int32_t octo_draws_scan_values_device(octo_draws* h, const double* d_elems, int64_t ld, int64_t W, const double* d_beta, double* d_eta /*[n][ld_out]*/,
+                                      int64_t ld_out, void* hip_stream);
+
+/* The table as a term of the handle's expression program: from the next call on octo_draws_program_logpost_device — and through it every function of
+ * the handle that needs ℓπ — adds ℓ_scan to the likelihood that octo_eval_device returns (it is tempered with it and survives a healed prior) and its
+ * adjoints to the inputs' gradient. binds names the nodes the table reads, OCTO_DRAWS_BIND_NODE only (a constant is a CONST node): in sampled mode
+ * n_binds = K + 1, the β nodes in column order and then the jitter node; in marginal mode n_binds = 1, the jitter node. The planets' elements are the
+ * program's own element rows. The bound nodes become input rows behind the program's own, so with nothing bound no launch and no work array differs.
+ * octo_draws_program_set, octo_draws_program_clear, octo_draws_scan_set and octo_draws_scan_clear drop the binding; octo_draws_scan_unbind is a no-op
+ * when nothing is bound. A transition that was open is never resumed across a change of the binding.
+ * OCTO_EINVAL: NULL handle; no table; no program, or one whose n_planets is not the table's; mode outside 0, 1; marginal mode with K = 0; n_binds not as
+ * above; a binding that is not a NODE or whose node is out of range. */
+int32_t octo_draws_scan_bind(octo_draws* h, int32_t mode, const octo_draws_bind* binds, int32_t n_binds);
+int32_t octo_draws_scan_unbind(octo_draws* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@
 // sampler does, one generation a run_rounds call of one round.
 // The sixteenth part, the OFTI rejection sampler (octo_draws_ofti.hip), takes the generator, the handle and grow_to, and from octo_draws.hip the draw
 // launches and the rejection's second pass (draws_launch_draw, draws_max_pass, draws_accept_pass below).
+// The seventeenth part, along-scan absolute astrometry (octo_draws_scan.hip), takes the handle, grow_to and the argument checks; the expression program
+// calls its draws_scan_accumulate (below) between octo_eval_device and k_prog_bwd while a table is bound.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
 
@@ -362,6 +364,17 @@ struct octo_draws : CompanionBase {
     double oftis_t_ref = 0.0, oftis_k_yr = 0.0, oftis_lambda = 0.0, oftis_data_quad = 0.0, oftis_log_det_data_cov = 0.0, oftis_log_det_prior_inv = 0.0,
            oftis_n_log2pi = 0.0;
     double* d_oftis = nullptr; int64_t cap_oftis = 0;
+    // along-scan absolute astrometry (octo_draws_scan.hip) while octo_draws_scan_set holds (scan_n = 0: not set): the table's rows on the device, its
+    // shape, the planets' descriptors and the constants of the orbit constructor, the work array (grown on demand), the device side of the host-buffer
+    // twin, and the binding to the expression program (scan_bound = 0: none; otherwise 1 + mode): the program's bindings with the bound nodes appended
+    double* d_scan_rows = nullptr; int64_t cap_scan_rows = 0;
+    int32_t scan_n = 0, scan_K = 0, scan_P = 0;
+    int32_t scan_kind[OCTO_MAX_PLANETS] = {}, scan_mass[OCTO_MAX_PLANETS] = {};
+    octo_consts scan_consts = {};
+    double* d_scan = nullptr; int64_t cap_scan = 0;
+    double* d_scan_hst = nullptr; int64_t cap_scan_hst = 0;
+    int32_t scan_bound = 0, scan_n_bind = 0;
+    double* d_scan_binds = nullptr; int64_t cap_scan_binds = 0;
 };
 
 // What octo_draws_ofti.hip takes from octo_draws.hip (defined there, not exported): k_draw's launches into θ alone, and the two halves of pass 2 of the
@@ -372,6 +385,10 @@ OCTO_DRAWS_INTERNAL int draws_launch_draw(octo_draws* h, hipStream_t st, uint64_
 OCTO_DRAWS_INTERNAL int draws_max_pass(octo_draws* h, hipStream_t st, const double* pmax, int64_t N, double* d_max, double* mx_out);
 OCTO_DRAWS_INTERNAL int draws_accept_pass(octo_draws* h, hipStream_t st, const double* ll, const double* lp, int64_t N, const double* d_max, uint64_t seed,
                                           uint64_t first, int64_t* cnt, int64_t room, uint64_t* o_ix, double* o_ll, double* o_lp, int64_t* total_out);
+
+// What octo_draws_program.hip takes from octo_draws_scan.hip (defined there, not exported): ℓ_scan of the bound table added into ll [W] and its element
+// adjoints into g_in (null: no gradient), the bound rows' adjoints stored behind the program's n_in rows; inputs and g_in are [rows][ldw].
+OCTO_DRAWS_INTERNAL int draws_scan_accumulate(octo_draws* h, hipStream_t st, const double* inputs, double* g_in, double* ll, int64_t ldw, int64_t W, int32_t n_in);
 
 namespace {
 

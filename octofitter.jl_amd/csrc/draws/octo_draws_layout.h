@@ -220,6 +220,26 @@ inline ProgWork prog_work(Carve& c, int64_t D, int64_t N, int64_t n_in, int64_t 
             c.take<int32_t>(ldw)};
 }
 
+// Along-scan absolute astrometry (octo_draws_scan.hip), d_scan: (n_tasks·n_sums + 28)·ldw. The partial sums of every task of SCAN_ROWS table rows,
+// task-major, and the marginal mode's per-walker solve. n_sums = 9 + 10·P: ℓ, the jitter sum, the marginal mode's Σw²cᵀA⁻¹c, six β sums, ten adjoint
+// sums a planet (U1 … U6, GE, GM, GT, GC of the main library's finish); the marginal mode's first pass keeps A (21, packed by rows) and b (6) in the same
+// rows, so there n_sums = max(9 + 10·P, 27). The kernels take it by value.
+struct ScanWork {
+    double* part;      // [n_tasks][n_sums][ldw]
+    double* marg;      // [28][ldw] β̂ [6] · A⁻¹ packed by rows [21] · log det A
+};
+inline ScanWork scan_work(Carve& c, int64_t n_tasks, int64_t n_sums, int64_t ldw) { return {c.take(n_tasks * n_sums * ldw), c.take(28 * ldw)}; }
+
+// The device side of octo_draws_scan_eval, d_scan_hst: (2·P·9 + 3·K + 3)·ld
+struct ScanStaging {
+    double *elems, *g_elems;           // [P·9][ld]
+    double *beta, *g_beta, *beta_hat;  // [K][ld]
+    double *jitter, *g_jitter, *ll;    // [ld]
+};
+inline ScanStaging scan_staging(Carve& c, int64_t P, int64_t K, int64_t ld) {
+    return {c.take(9 * P * ld), c.take(9 * P * ld), c.take(K * ld), c.take(K * ld), c.take(K * ld), c.take(ld), c.take(ld), c.take(ld)};
+}
+
 // The convergence diagnostics of K rows (octo_draws_diag.hip), d_diag: 2K(P + S) + 10KM + 4K·T·(nblk + 1) + 5K. N draws of M = 2W split chains a row,
 // S = M·N used draws, P = the power of two the sort pads them to, T = the lags rounded up to whole blocks of 16, nblk = ⌈M/256⌉. The kernels take it
 // by value: its members and their order are their argument layout.

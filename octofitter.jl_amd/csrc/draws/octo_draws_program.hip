@@ -221,6 +221,9 @@ ProgArgs program_args(const octo_draws* h, const double* d_theta_t, int64_t ld, 
     a.priors = h->own_priors; a.pc = h->own_pc; a.ops = h->prog_ops; a.binds = h->prog_binds; a.terms = h->prog_terms;
     a.D = h->D; a.n_ops = h->prog_n_ops; a.n_in = h->prog_n_in; a.n_terms = h->prog_n_terms;
     a.theta_t = d_theta_t; a.ld = ld; a.W = W; a.ldw = ldw; a.k_yr = h->prog_k_yr;
+    if (h->scan_bound) {      // a bound scan table (octo_draws_scan.hip): the nodes it reads are input rows behind the program's own
+        a.binds = (const octo_draws_bind*)h->d_scan_binds; a.n_in += h->scan_n_bind;
+    }
     return a;
 }
 
@@ -232,6 +235,7 @@ int32_t octo_draws_program_clear(octo_draws* h) {
     if (!h) return OCTO_EINVAL;
     h->prog_ops = nullptr; h->prog_binds = nullptr; h->prog_terms = nullptr; h->prog_ds = nullptr;
     h->prog_n_ops = h->prog_n_in = h->prog_n_el = h->prog_n_terms = h->prog_planets = 0;
+    h->scan_bound = 0; h->scan_n_bind = 0;      // a bound scan table names this program's nodes
     h->nuts_depth = 0; h->slice_passes = 0; h->lbf_m = 0; h->pf_W = 0; h->de_open = false;      // a transition is never resumed on another target
     return OCTO_OK;
 }
@@ -313,7 +317,7 @@ int32_t octo_draws_program_logpost_device(octo_draws* h, const double* d_theta_t
     const hipStream_t st = stream_of(h, hip_stream);
     const int64_t ldw = (W + WAVE - 1) / WAVE * WAVE;
     ProgArgs a = program_args(h, d_theta_t, ld, W, ldw);
-    if (int rc = grow_to(h, h->d_prog, h->cap_prog, a.k, prog_work, (int64_t)h->D, (int64_t)(h->D + h->prog_n_ops), (int64_t)h->prog_n_in, (int64_t)h->prog_planets, ldw)) return rc;
+    if (int rc = grow_to(h, h->d_prog, h->cap_prog, a.k, prog_work, (int64_t)h->D, (int64_t)(h->D + h->prog_n_ops), (int64_t)a.n_in, (int64_t)h->prog_planets, ldw)) return rc;
     a.lp_out = d_lp; a.grad_out = d_grad;
     const dim3 grid((unsigned)(ldw / WAVE)), block(WAVE);
     const size_t lds = prog_lds(h);
@@ -323,6 +327,8 @@ int32_t octo_draws_program_logpost_device(octo_draws* h, const double* d_theta_t
     const int n_el = h->prog_n_el, n_nu = h->prog_n_in - n_el;
     if (int rc = main_call(h, octo_eval_device(h->ctx, h->prog_ds, a.k.inputs, n_nu ? a.k.inputs + (int64_t)n_el * ldw : nullptr, ldw, W, a.k.ll,
                                                d_grad ? a.k.g_in : nullptr, d_grad && n_nu ? a.k.g_in + (int64_t)n_el * ldw : nullptr, (void*)st), "octo_eval_device")) return rc;
+    if (h->scan_bound)      // ℓ_scan into ℓ, its adjoints into g_in: on the likelihood side of the split, ahead of the reverse sweep
+        if (int rc = draws_scan_accumulate(h, st, a.k.inputs, d_grad ? a.k.g_in : nullptr, a.k.ll, ldw, W, h->prog_n_in)) return rc;
     hipLaunchKernelGGL(k_prog_bwd, grid, block, d_grad ? lds : 0, st, a);
     OCHK(h, hipGetLastError());
     return OCTO_OK;

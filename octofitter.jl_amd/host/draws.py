@@ -77,6 +77,10 @@ DE_TAU_F, DE_F_LOW, DE_F_SPAN, DE_TAU_CR, DE_F0, DE_CR0 = 0.1, 0.1, 0.9, 0.1, 0.
 DE_OUTPUTS = ("fcr", "logpost", "loglike", "n_accept", "best", "best_logpost", "n_improved")      # the outputs of octo_draws_de_device, in order
 PURPOSE_OFTI = 13
 OFTI_N_OUT = 16                    # OCTO_DRAWS_OFTI_N_OUT
+SCAN_MAX_K = 6                     # OCTO_DRAWS_SCAN_MAX_K
+SCAN_ROWS = 8                      # OCTO_DRAWS_SCAN_ROWS: the rows of a task
+SCAN_SAMPLED, SCAN_MARGINAL = 0, 1
+SCAN_MODES = {"sampled": SCAN_SAMPLED, "marginal": SCAN_MARGINAL}
 OFTI_OUTPUTS = ("A", "B", "F", "G", "A_mean", "B_mean", "F_mean", "G_mean", "alpha", "a_ti", "i", "ω", "Ω", "P_d", "M_dyn", "logml")      # the rows of d_out, in order
 DIAG_RHAT, DIAG_ESS_BULK, DIAG_ESS_TAIL, DIAG_RHAT_BASIC, DIAG_ESS_BASIC, DIAG_Q05, DIAG_Q50, DIAG_Q95, DIAG_N_STATS = range(9)      # OCTO_DRAWS_DIAG_*
 PT_ACC_COLUMNS = ("n", "A", "n_f", "m_f", "s_f", "n_b", "m_b", "s_b")      # the columns of d_acc [T − 1][8]
@@ -158,6 +162,13 @@ _SIGS = {
     "octo_draws_ofti_posterior_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "octo_draws_ofti_rejection": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, capi.c_double_p, capi.c_double_p, capi.c_double_p,
                                               c_uint64_p, C.POINTER(C.c_int64), capi.c_double_p]),
+    "octo_draws_scan_set": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + [capi.c_double_p] * 6 + [C.c_int32, C.c_int64]),
+    "octo_draws_scan_clear": (C.c_int32, [C.c_void_p]),
+    "octo_draws_scan_eval_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]),
+    "octo_draws_scan_eval": (C.c_int32, [C.c_void_p, C.c_int32, capi.c_double_p, C.c_int64, C.c_int64] + [capi.c_double_p] * 7),
+    "octo_draws_scan_values_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "octo_draws_scan_bind": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "octo_draws_scan_unbind": (C.c_int32, [C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -334,8 +345,16 @@ class PriorDraws(companion.Handle):
                 raise capi.OctoError(st, "octo_ctx_create")
             self._own_ctx = ctx
         self._created(self.lib.octo_draws_create(ctx, m, self._c_priors, self.D, self.device_index, C.byref(self._h)))
+        self.scan_shape = None      # (n, K, P) of the scan table while one is set
         if program is not None:
             self.program_set(*program)
+            scan = getattr(model, "_scan", None)
+            if scan is not None and program[0] is getattr(model, "program", None):      # the model's along-scan observation: a term of its program
+                obs, nodes = scan
+                t = obs.table
+                self.scan_set([(d["orbit_kind"], d["has_mass"]) for d in model.ln_like.planet_desc], t["epoch"], t["u"], t["v"], t["y"], t["sigma"],
+                              obs.columns if obs.columns.shape[0] else None)
+                self.scan_bind(nodes, obs.mode)
 
     # ---- derived variables (include/octofitter_hip_draws.h, "Derived variables"): a handle made from a model, without its device model
     def program_set(self, prog, binds):
@@ -490,6 +509,100 @@ class PriorDraws(companion.Handle):
         ns = min(int(n_acc.value), room)
         return dict(theta=np.ascontiguousarray(th[:, :ns]), nl=np.ascontiguousarray(nl[:, :ns]), post=np.ascontiguousarray(post[:, :ns]), index=ix[:ns].copy(),
                     n_accepted=int(n_acc.value), max_logml=float(mx.value))
+
+    # ---- along-scan absolute astrometry (include/octofitter_hip_draws.h, "The seventeenth"): any handle; the binding needs a program
+    def scan_set(self, planets, t, u, v, y, sigma, columns=None, consts=None):
+        """octo_draws_scan_set: the scan table (host arrays of one length n; columns [K, n] or None) for the planets [(orbit_kind, has_mass)].
+        consts: a capi.OctoConsts (None: the defaults)."""
+        cols = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in (t, u, v, y, sigma)]
+        n = cols[0].size
+        if any(c.size != n for c in cols):
+            raise ValueError("scan_set: the columns must have one length")
+        cm = np.zeros((0, n)) if columns is None else np.ascontiguousarray(columns, dtype=np.float64).reshape(-1, n)
+        K = int(cm.shape[0])
+        desc = (capi.OctoPlanetDesc * max(len(planets), 1))(*[capi.OctoPlanetDesc(int(k), int(bool(m))) for k, m in planets])
+        self._check(self.lib.octo_draws_scan_set(self._h, C.cast(desc, C.c_void_p), len(planets), None if consts is None else C.cast(C.pointer(consts), C.c_void_p),
+                                                 *[capi._dptr(c) for c in cols], capi._dptr(cm if K else None), K, n))
+        self.scan_shape = (n, K, len(planets))
+
+    def scan_clear(self):
+        """octo_draws_scan_clear"""
+        self._check(self.lib.octo_draws_scan_clear(self._h))
+        self.scan_shape = None
+
+    def scan_eval(self, elems, beta=None, jitter=None, mode="sampled", grad=True, accumulate=False, out=None, stream=None):
+        """ℓ and its gradients of the W columns of elems (torch float64 [P·9, W] on the handle's device, rows contiguous; beta [K, W] with the same
+        row distance, jitter [W] or None = 0): dict(ll [W], g_elems [P·9, W], g_beta [K, W] (sampled), g_jitter [W], beta_hat [K, W] (marginal));
+        the gradients None with grad=False. accumulate: ll and g_elems are ADDED into out["ll"] and out["g_elems"]. Asynchronous on `stream`."""
+        n, K, P = self.scan_shape
+        _, W, ld = chain_matrix(elems, P * capi.N_EL, self.device, "scan_eval", "elems")
+        m = SCAN_MODES[mode]
+        if beta is not None and K:
+            _, Wb, ldb = chain_matrix(beta, K, self.device, "scan_eval", "beta")
+            if Wb != W or (K > 1 and W and ldb != ld):
+                raise ValueError("scan_eval: beta must have elems' width and row distance")
+        out = dict(out or {})
+        if "ll" not in out:
+            if accumulate:
+                raise ValueError("scan_eval: accumulate needs out['ll']")
+            out["ll"] = self._out(W)
+        if grad:
+            out.setdefault("g_elems", self._out(W, P * capi.N_EL, ld))
+            out.setdefault("g_jitter", self._out(W))
+            if m == SCAN_SAMPLED and K:
+                out.setdefault("g_beta", self._out(W, K, ld))
+        if m == SCAN_MARGINAL:
+            out.setdefault("beta_hat", self._out(W, K, ld))
+        self._check(self.lib.octo_draws_scan_eval_device(self._h, m, elems.data_ptr(), ld, W, ptr(beta) if K else None, ptr(jitter), out["ll"].data_ptr(),
+                                                         ptr(out.get("g_elems")), ptr(out.get("g_beta")), ptr(out.get("g_jitter")), ptr(out.get("beta_hat")),
+                                                         int(bool(accumulate)), self._stream(stream, self.device)))
+        self._keep = (elems, beta, jitter, out)
+        return out
+
+    def scan_eval_host(self, elems, beta=None, jitter=None, mode="sampled", grad=True):
+        """octo_draws_scan_eval: the same on NumPy arrays (elems [P·9, W], beta [K, W], jitter [W]), blocking."""
+        n, K, P = self.scan_shape
+        m = SCAN_MODES[mode]
+        elems = np.ascontiguousarray(elems, dtype=np.float64).reshape(P * capi.N_EL, -1)
+        W = elems.shape[1]
+        beta = None if beta is None or not K else np.ascontiguousarray(beta, dtype=np.float64).reshape(K, W)
+        jitter = None if jitter is None else np.ascontiguousarray(jitter, dtype=np.float64).reshape(W)
+        out = dict(ll=np.empty(W))
+        if grad:
+            out.update(g_elems=np.empty((P * capi.N_EL, W)), g_jitter=np.empty(W))
+            if m == SCAN_SAMPLED and K:
+                out["g_beta"] = np.empty((K, W))
+        if m == SCAN_MARGINAL:
+            out["beta_hat"] = np.empty((K, W))
+        self._check(self.lib.octo_draws_scan_eval(self._h, m, capi._dptr(elems), W, W, capi._dptr(beta), capi._dptr(jitter), capi._dptr(out["ll"]),
+                                                  capi._dptr(out.get("g_elems")), capi._dptr(out.get("g_beta")), capi._dptr(out.get("g_jitter")),
+                                                  capi._dptr(out.get("beta_hat"))))
+        return out
+
+    def scan_values(self, elems, beta=None, stream=None):
+        """The model values η [n, W] at the W columns of elems (beta None: the reflex part alone). Asynchronous on `stream`."""
+        n, K, P = self.scan_shape
+        _, W, ld = chain_matrix(elems, P * capi.N_EL, self.device, "scan_values", "elems")
+        if beta is not None and K:
+            _, Wb, ldb = chain_matrix(beta, K, self.device, "scan_values", "beta")
+            if Wb != W or (K > 1 and W and ldb != ld):
+                raise ValueError("scan_values: beta must have elems' width and row distance")
+        eta = self._out(W, n)
+        self._check(self.lib.octo_draws_scan_values_device(self._h, elems.data_ptr(), ld, W, ptr(beta) if K else None, eta.data_ptr(), max(W, 1),
+                                                           self._stream(stream, self.device)))
+        self._keep = (elems, beta, eta)
+        return eta
+
+    def scan_bind(self, nodes, mode="sampled"):
+        """octo_draws_scan_bind: the table becomes a term of the handle's program. nodes: the program's node indices of the β parameters in
+        column order and then of the jitter (sampled), or of the jitter alone (marginal)."""
+        from . import derived
+        bs = (derived.OctoDrawsBind * max(len(nodes), 1))(*[derived.OctoDrawsBind(derived.BIND_NODE, int(k), 0.0) for k in nodes])
+        self._check(self.lib.octo_draws_scan_bind(self._h, SCAN_MODES[mode], C.cast(bs, C.c_void_p), len(nodes)))
+
+    def scan_unbind(self):
+        """octo_draws_scan_unbind"""
+        self._check(self.lib.octo_draws_scan_unbind(self._h))
 
     def momentum(self, seed, step, n, inv_mass=None, chain0=0, stream=None):
         """The momenta p [D, n] of chains chain0 … chain0 + n − 1 at `step`: standard normals of the counter generator over √inv_mass."""

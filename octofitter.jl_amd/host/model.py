@@ -53,10 +53,11 @@ class LogDensityModel:
         for pl in system.planets:
             blocks += [pl.variables or {}] + [getattr(o, "variables", None) or {} for o in pl.observations]
         has_derived = any(isinstance(v, derived.Derived) for b in blocks for v in b.values())
+        self._scan = None      # (AlongScanAstromObs, its program nodes) of a system with along-scan absolute astrometry
         try:
-            if has_derived:
+            if has_derived or fn.scan_obs:      # the scan table is a term of the expression program: such a model always has one
                 if consts is not None:
-                    raise NotImplementedError("a model with Derived variables uses the library's default constants (octo_consts_default)")
+                    raise NotImplementedError("a model with Derived variables or along-scan astrometry uses the library's default constants (octo_consts_default)")
                 self._build_program(system, fn, sysvars)
             else:
                 self._build(system, fn, sysvars)
@@ -205,6 +206,15 @@ class LogDensityModel:
                 rows = (("offset", 0.0), ("jitter", 0.0), (getattr(obs, "trend_coef", None), 0.0))
             for nm, dv in rows:
                 binds.append((derived.BIND_NODE, prog.node(ns[nm]), 0.0) if nm is not None and nm in ov else const(dv))
+        if fn.scan_obs:
+            if len(fn.scan_obs) > 1:
+                raise NotImplementedError("one AlongScanAstromObs a system: the draws handle holds one scan table")
+            obs = fn.scan_obs[0]
+            ov, ns = obs.variables, obs_ns[id(obs)]
+            if obs.mode == "sampled" and len(obs.beta_variables) != obs.columns.shape[0]:
+                raise KeyError(f"AlongScanAstromObs {obs.name!r}: variables must name its {obs.columns.shape[0]} β parameters in column order")
+            jitter = prog.node(ns["jitter"]) if "jitter" in ov else const(0.0)[1]
+            self._scan = (obs, [prog.node(ns[nm]) for nm in obs.beta_variables] + [jitter])
         self.program, self._binds = prog, binds
         pr = (capi.OctoPrior * self.D)()
         for k, p in enumerate(self.priors):

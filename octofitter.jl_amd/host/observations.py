@@ -312,3 +312,71 @@ class HGCAInstantaneousObs(AbstractObs):
 
 
 HGCAInstantaneousLikelihood = HGCAInstantaneousObs
+
+
+class AlongScanAstromObs(AbstractObs):
+    """Along-scan absolute astrometry of the primary (include/octofitter_hip_draws.h, "The seventeenth"): one along-scan coordinate y [mas] per
+    transit at epoch t [MJD] with scan direction (u, v) along α* and δ, uncertainty sigma [mas] and K <= 6 design columns [K, n] of a linear model
+    Σ_k columns[k]·β_k beside the star's reflex motion. A system-level observation. `variables` (a `variables(...)` block: priors, Derived,
+    constants) names the β parameters in column order, and an optional `jitter`; a Derived may hand a column the system's own variable, as the
+    parallax column `plx=Derived(lambda obs, system: system.plx)`. mode "sampled": the β are parameters of the model; "marginal": they are integrated
+    out under a flat prior and only `jitter` may be given. It is evaluated by the draws library's
+    expression-program route, not by the main library's dataset: BatchedLnLike leaves it out of the dataset."""
+    kind = None
+    nuisance_names = ()
+    MODES = ("sampled", "marginal")
+
+    def __init__(self, t, u, v, y, sigma, columns=None, *, mode="sampled", variables=None, name="AlongScan"):
+        cols = [np.asarray(c, dtype=np.float64).reshape(-1) for c in (t, u, v, y, sigma)]
+        n = cols[0].size
+        if n < 1 or any(c.size != n for c in cols):
+            raise ValueError("The columns in the input data do not all have the same length")
+        cm = np.zeros((0, n)) if columns is None else np.asarray(columns, dtype=np.float64).reshape(-1, n)
+        if cm.shape[0] > 6:
+            raise ValueError("AlongScanAstromObs: at most 6 design columns")
+        if mode not in self.MODES:
+            raise ValueError(f"AlongScanAstromObs: mode must be one of {self.MODES}")
+        if mode == "marginal" and cm.shape[0] == 0:
+            raise ValueError("AlongScanAstromObs: the marginal mode needs design columns")
+        if np.any(~(cols[4] > 0)) or not all(np.all(np.isfinite(c)) for c in cols + [cm]):
+            raise ValueError("AlongScanAstromObs: sigma must be > 0 and every entry finite")
+        _warn_epoch_range(cols[0])
+        variables = dict(variables or {})
+        n_beta = cm.shape[0] if mode == "sampled" else 0
+        self.beta_variables = tuple(k for k in variables if k != "jitter")
+        if variables and len(self.beta_variables) != n_beta:      # none at all: a table only, for PriorDraws.scan_set; a model needs them
+            raise ValueError(f"AlongScanAstromObs: variables names the {n_beta} β parameters in column order and an optional `jitter`")
+        self.table = dict(epoch=cols[0], u=cols[1], v=cols[2], y=cols[3], sigma=cols[4])
+        self.columns = cm
+        self.mode = mode
+        self.variables = variables
+        self.name = name
+
+    def __len__(self):
+        return len(self.table["epoch"])
+
+
+_J2000_MJD, _JULIAN_YEAR = 51544.5, 365.25
+
+
+def hipparcos_iad_obs(epoch_yr, parf, cpsi, spsi, res, sres, plx, pmra, pmdec, ref_epoch=1991.25, **kw):
+    """The Hipparcos intermediate astrometric data of one star (van Leeuwen 2007: the fields EPOCH as a decimal year, PARF, CPSI, SPSI, RES, SRES) and
+    its catalogue solution (ϖ, μα*, μδ) as an AlongScanAstromObs. The catalogue's model is added back onto the residuals,
+    y_i = RES_i + PARF_i·ϖ + CPSI_i·Δt_i·μα* + SPSI_i·Δt_i·μδ with Δt_i = EPOCH_i − ref_epoch [yr], so that the five columns
+    (CPSI, SPSI, PARF, CPSI·Δt, SPSI·Δt) fit (Δα*, Δδ, ϖ, μα*, μδ) afresh beside the companions' reflex motion; (u, v) = (CPSI, SPSI).
+    It only builds columns. The conventions are recalled, not read from the reference's hipparcos.jl."""
+    epoch_yr, parf, cpsi, spsi, res, sres = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (epoch_yr, parf, cpsi, spsi, res, sres))
+    dt = epoch_yr - ref_epoch
+    y = res + parf * plx + cpsi * dt * pmra + spsi * dt * pmdec
+    t = (epoch_yr - 2000.0) * _JULIAN_YEAR + _J2000_MJD
+    return AlongScanAstromObs(t, cpsi, spsi, y, sres, np.stack([cpsi, spsi, parf, cpsi * dt, spsi * dt]), **{"name": "HipparcosIAD", **kw})
+
+
+def gaia_epoch_obs(t_mjd, scan_angle, parallax_factor_al, centroid_al, sigma_al, ref_epoch_mjd, **kw):
+    """Gaia per-transit epoch astrometry as an AlongScanAstromObs: the along-scan centroid [mas] at scan position angle ψ [rad, from north through
+    east], (u, v) = (sin ψ, cos ψ), and the same five columns (u, v, parallax factor, u·Δt, v·Δt) ↔ (Δα*, Δδ, ϖ, μα*, μδ), Δt in Julian years from
+    ref_epoch_mjd. It only builds columns. The conventions are recalled, not read from the reference's gaia-dr4.jl."""
+    t, psi, pf, y, s = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (t_mjd, scan_angle, parallax_factor_al, centroid_al, sigma_al))
+    u, v = np.sin(psi), np.cos(psi)
+    dt = (t - ref_epoch_mjd) / _JULIAN_YEAR
+    return AlongScanAstromObs(t, u, v, y, s, np.stack([u, v, pf, u * dt, v * dt]), **{"name": "GaiaEpochAstrom", **kw})

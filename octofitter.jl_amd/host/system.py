@@ -25,7 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .observations import AbstractObs, normalizename
+from .observations import AbstractObs, AlongScanAstromObs, normalizename
 
 _EL_KEYS = (("a",), ("e",), ("i",), ("ω", "w", "omega"), ("Ω", "O", "Omega"), ("tp",), ("M",), ("plx",), ("mass",))
 # ThieleInnesOrbit(; e, tp, M, plx, A, B, F, G): the constants [mas] travel in the rows of a, i, ω, Ω (include/octofitter_hip.h)
@@ -82,7 +82,10 @@ class BatchedLnLike:
         self.all_epochs = []
         self.epoch_start_index_mapping = {}
         j = 1
-        for obs in system.observations:
+        # along-scan absolute astrometry is a term of the draws library's expression program, not a table of the dataset: left out here
+        self.scan_obs = [obs for obs in system.observations if isinstance(obs, AlongScanAstromObs)]
+        dataset_obs = [obs for obs in system.observations if not isinstance(obs, AlongScanAstromObs)]
+        for obs in dataset_obs:
             self.epoch_start_index_mapping[id(obs)] = j
             j += len(obs)
             self.all_epochs.extend(obs.table["epoch"].tolist())
@@ -95,10 +98,10 @@ class BatchedLnLike:
         self.obs_entries = []   # (obs, planet_index or -1, planet_name or None, θ_obs key)
         for ip, pl in enumerate(system.planets):
             for obs in pl.observations:
-                if obs.kind in (capi.RV_ABS, capi.RV_ABS_MARG, capi.HGCA):
+                if obs.kind in (capi.RV_ABS, capi.RV_ABS_MARG, capi.HGCA) or isinstance(obs, AlongScanAstromObs):
                     raise ValueError(f"{type(obs).__name__} is a system-level observation")
                 self.obs_entries.append((obs, ip, pl.name, normalizename(obs.likelihoodname())))
-        for obs in system.observations:
+        for obs in dataset_obs:
             if obs.kind not in (capi.RV_ABS, capi.RV_ABS_MARG, capi.HGCA):
                 raise ValueError(f"{type(obs).__name__} must be attached to a planet")
             self.obs_entries.append((obs, -1, None, normalizename(obs.likelihoodname())))
