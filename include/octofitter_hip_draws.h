@@ -1058,6 +1058,77 @@ int32_t octo_draws_scan_values_device(octo_draws* h, const double* d_elems, int6
 int32_t octo_draws_scan_bind(octo_draws* h, int32_t mode, const octo_draws_bind* binds, int32_t n_binds);
 int32_t octo_draws_scan_unbind(octo_draws* h);
 
+/* ---- The eighteenth: the catalogue proper-motion anomaly ("pma") from refitted scans — the reference's HGCAObs: the star is simulated at every Hipparcos
+ * and Gaia scan, each mission's linear model is refitted, and the fitted proper motions are compared with the catalogue under its covariance. The scan
+ * geometry and the weights do not depend on the walker, so each refit is a FIXED linear map of the reflex rows, which the host folds into the projector L:
+ * the library knows nothing of missions, reference epochs or parallax factors. The functions are stated in full so that a restatement elsewhere
+ * (tests/pma_reference.py) and the device compute the same function. The table is held beside the scan table of the seventeenth part, independent of it.
+ *
+ * Table      n rows, 1 <= n <= 65536. Row i: epoch t_i [MJD] and scan direction (u_i, v_i) along α* and δ. A projector L [Q][n], 1 <= Q <=
+ *            OCTO_DRAWS_PMA_MAX_Q; catalogue values d [Q]; a symmetric positive-definite covariance Σ [Q][Q]; a constant design H [Q][K] for K linear
+ *            walker parameters γ, 0 <= K <= OCTO_DRAWS_PMA_MAX_K (H may be NULL with K = 0); the planets' descriptors and the constants, as for
+ *            octo_draws_scan_set. Everything is in the units of L's rows: mas/yr for the HGCA.
+ * Model      ρ_i = Σ_p f_p·(u_i·raoff_p(t_i) + v_i·decoff_p(t_i)), f_p = −mass_p·mjup2msol/M_p: the scan part's reflex rule, word for word —
+ *            OCTO_ORBIT_VISUAL_KEP and OCTO_ORBIT_THIELE_INNES planets with a mass contribute, the others contribute 0; the companions' COLD Kepler solve
+ *            and the main library's constructor and projection.   z_q = Σ_i L[q][i]·ρ_i      m = z + H·γ      r = d − m
+ * Sampled    OCTO_DRAWS_PMA_SAMPLED: ℓ = −½·rᵀΣ⁻¹r − ½·log det(2πΣ). Reverse mode: λ = Σ⁻¹r, ∂ℓ/∂γ = Hᵀλ, the adjoint of ρ_i is g_i = Σ_q L[q][i]·λ_q,
+ *            and from g_i each planet's ten sums go through the main library's finish to ∂ℓ/∂elems [P·9][ld].
+ * Marginal   OCTO_DRAWS_PMA_MARGINAL: γ integrated out under a flat prior; needs K > 0 and N = HᵀΣ⁻¹H positive definite. P_m = Σ⁻¹ − Σ⁻¹H·N⁻¹·HᵀΣ⁻¹,
+ *            r = d − z, ℓ_marg = −½·rᵀP_m r − ½·log det(2πΣ) + (K/2)·log 2π − ½·log det N, λ = P_m r; γ̂ = N⁻¹HᵀΣ⁻¹r [K][ld] is an output.
+ * Matrices   Σ⁻¹, P_m, N⁻¹HᵀΣ⁻¹ and both constants are made once, on the host, in octo_draws_pma_set by Cholesky factors (csrc/draws/
+ *            octo_draws_pma_host.h; a pivot must exceed 1e-12 of its diagonal entry); the device only applies Q × Q and K × Q matrices. There is no jitter:
+ *            a fit with inflated errors passes an inflated Σ.
+ * Invalid    a non-finite input, an element outside the main library's domain, a non-finite γ (or ℓ): ℓ = −Inf and a zero gradient for that walker;
+ *            never a status, never another walker's bits. γ̂ of an invalid walker is not defined.
+ * Order      the rows are cut into tasks of OCTO_DRAWS_SCAN_ROWS rows, whatever W is; a task adds its planets into ρ_i in planet order and its rows
+ *            into z_q in row order by fma, the tasks are added in task order, the q and k sums run in index order. No atomics: a walker's outputs depend on
+ *            its own column alone, bit for bit, in any batch and with any ld.
+ *
+ * octo_draws_pma_set copies the table to the device; it needs neither a model nor a context. A second call replaces the first; octo_draws_pma_clear
+ * removes it (no-op when nothing is set). Both drop a binding. A rank-deficient H is not refused here: that is the marginal mode's condition, answered at
+ * eval and bind.
+ * OCTO_EINVAL: NULL handle; a NULL array (H may be NULL with K = 0); n, Q, K or n_planets out of range; a non-finite entry; an unknown orbit kind; Σ not
+ * symmetric (beyond 1e-12·√(Σ_ii Σ_jj)) or not positive definite. */
+#define OCTO_DRAWS_PMA_MAX_Q 8
+#define OCTO_DRAWS_PMA_MAX_K 4
+#define OCTO_DRAWS_PMA_SAMPLED 0
+#define OCTO_DRAWS_PMA_MARGINAL 1
+int32_t octo_draws_pma_set(octo_draws* h, const octo_planet_desc* planets, int32_t n_planets, const octo_consts* consts /*NULL = octo_consts_default*/,
+                           const double* t, const double* u, const double* v, const double* L /*[Q][n]*/, int32_t Q, const double* d /*[Q]*/,
+                           const double* cov /*[Q][Q]*/, const double* H /*[Q][K]*/, int32_t K, int64_t n);
+int32_t octo_draws_pma_clear(octo_draws* h);
+
+/* ℓ [W] and the gradients of W walkers on DEVICE buffers, asynchronous on hip_stream: no host synchronisation, no allocation once the handle's work
+ * array holds (⌈n/OCTO_DRAWS_SCAN_ROWS⌉·n_sums + 9)·ldw doubles, ldw = W rounded up to whole waves, n_sums = max(8, 10·n_planets). d_gamma, d_g_gamma and
+ * d_gamma_hat are [K][ld]. Every gradient output may be NULL; with d_g_elems NULL only the two forward kernels run (∂ℓ/∂γ and γ̂ come from them).
+ * accumulate = 1 ADDS ℓ into d_ll and the element adjoints into d_g_elems (an invalid walker adds −Inf and 0); d_g_gamma and d_gamma_hat are always
+ * stored. accumulate = 0 stores 0 + the value, so that accumulating into zeroed outputs gives the same bits.
+ * OCTO_EINVAL: NULL handle; no table; mode outside 0, 1; marginal mode with K = 0 or with HᵀΣ⁻¹H not positive definite; W < 0, ld < W; NULL d_elems or
+ * d_ll, or NULL d_gamma in sampled mode with K > 0, with W > 0. */
+int32_t octo_draws_pma_eval_device(octo_draws* h, int32_t mode, const double* d_elems, int64_t ld, int64_t W, const double* d_gamma, double* d_ll,
+                                   double* d_g_elems, double* d_g_gamma, double* d_gamma_hat, int32_t accumulate, void* hip_stream);
+/* The twin on HOST buffers, blocking, through the handle's staging ((2·P·9 + 3·K + 1)·ld doubles) on its own stream; accumulate = 0. */
+int32_t octo_draws_pma_eval(octo_draws* h, int32_t mode, const double* elems, int64_t ld, int64_t W, const double* gamma, double* ll, double* g_elems,
+                            double* g_gamma, double* gamma_hat);
+
+/* The model's catalogue values m = z + H·γ [Q][ld_out] of W walkers (d_gamma NULL: z alone), asynchronous on hip_stream: for posterior-predictive checks
+ * against the catalogue. An invalid walker's column is not defined. OCTO_EINVAL: NULL handle; no table; W < 0, ld < W, ld_out < W; NULL d_elems or d_m
+ * with W > 0. */
+int32_t octo_draws_pma_values_device(octo_draws* h, const double* d_elems, int64_t ld, int64_t W, const double* d_gamma, double* d_m /*[Q][ld_out]*/,
+                                     int64_t ld_out, void* hip_stream);
+
+/* The table as a term of the handle's expression program, exactly as octo_draws_scan_bind: ℓ_pma is added to the likelihood that octo_eval_device returns
+ * (it is tempered with it and survives a healed prior) and its adjoints to the inputs' gradient. binds names the γ nodes in column order,
+ * OCTO_DRAWS_BIND_NODE only: n_binds = K in sampled mode, 0 in marginal mode (binds may then be NULL). The bound nodes become input rows behind the
+ * program's own, so with nothing bound no launch and no work array differs. octo_draws_program_set, octo_draws_program_clear, octo_draws_pma_set and
+ * octo_draws_pma_clear drop the binding; octo_draws_pma_unbind is a no-op when nothing is bound. A transition that was open is never resumed across a
+ * change of the binding. ONE bound table a handle: with a scan table bound octo_draws_pma_bind answers OCTO_ENOTSUP, and so does octo_draws_scan_bind
+ * with a catalogue table bound.
+ * OCTO_EINVAL: NULL handle; no table; no program, or one whose n_planets is not the table's; mode outside 0, 1; marginal mode with K = 0 or a rank-
+ * deficient H; n_binds not as above; a binding that is not a NODE or whose node is out of range. */
+int32_t octo_draws_pma_bind(octo_draws* h, int32_t mode, const octo_draws_bind* binds, int32_t n_binds);
+int32_t octo_draws_pma_unbind(octo_draws* h);
+
 #ifdef __cplusplus
 }
 #endif

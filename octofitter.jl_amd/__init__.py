@@ -12,6 +12,7 @@ from .host.observations import (  # noqa: F401
     PlanetRelAstromObs, PlanetRelAstromLikelihood, StarAbsoluteRVObs, StarAbsoluteRVLikelihood,
     MarginalizedStarAbsoluteRVObs, PlanetRelativeRVObs, PlanetRelativeRVLikelihood, ObsPriorAstromONeil2019,
     HGCAInstantaneousObs, HGCAInstantaneousLikelihood, AlongScanAstromObs, hipparcos_iad_obs, gaia_epoch_obs,
+    CatalogueFitObs, hgca_obs, HGCAObs,
 )
 from .host.system import Planet, System, make_ln_like, BatchedLnLike, accelerate, not_on_device  # noqa: F401
 from .host.sharding import shard_range, ShardedLnLike  # noqa: F401,E402

@@ -22,6 +22,8 @@
 // launches and the rejection's second pass (draws_launch_draw, draws_max_pass, draws_accept_pass below).
 // The seventeenth part, along-scan absolute astrometry (octo_draws_scan.hip), takes the handle, grow_to and the argument checks; the expression program
 // calls its draws_scan_accumulate (below) between octo_eval_device and k_prog_bwd while a table is bound.
+// The eighteenth part, the catalogue proper-motion anomaly (octo_draws_pma.hip), takes the same and hands the program draws_pma_accumulate; its table
+// algebra is octo_draws_pma_host.h.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
 
@@ -35,6 +37,7 @@
 
 #include "octo_companion_host.h"
 #include "octo_draws_layout.h"
+#include "octo_draws_pma_host.h"
 #include "octo_model.h"
 #include "octofitter_hip_draws.h"
 
@@ -375,6 +378,18 @@ struct octo_draws : CompanionBase {
     double* d_scan_hst = nullptr; int64_t cap_scan_hst = 0;
     int32_t scan_bound = 0, scan_n_bind = 0;
     double* d_scan_binds = nullptr; int64_t cap_scan_binds = 0;
+    // the catalogue proper-motion anomaly (octo_draws_pma.hip) while octo_draws_pma_set holds (pma_n = 0: not set): the rows {t, u, v, 0, L[0 … 7]} on the
+    // device, the shape, the host-made matrices of both modes, the planets' descriptors and constants, the work array, the device side of the host-buffer
+    // twin, and the binding to the expression program as for the scan table (pma_bound = 0: none; otherwise 1 + mode). One bound table a handle.
+    double* d_pma_rows = nullptr; int64_t cap_pma_rows = 0;
+    int32_t pma_n = 0, pma_Q = 0, pma_K = 0, pma_P = 0;
+    PmaTable pma_tab = {};
+    int32_t pma_kind[OCTO_MAX_PLANETS] = {}, pma_mass[OCTO_MAX_PLANETS] = {};
+    octo_consts pma_consts = {};
+    double* d_pma = nullptr; int64_t cap_pma = 0;
+    double* d_pma_hst = nullptr; int64_t cap_pma_hst = 0;
+    int32_t pma_bound = 0, pma_n_bind = 0;
+    double* d_pma_binds = nullptr; int64_t cap_pma_binds = 0;
 };
 
 // What octo_draws_ofti.hip takes from octo_draws.hip (defined there, not exported): k_draw's launches into θ alone, and the two halves of pass 2 of the
@@ -389,6 +404,8 @@ OCTO_DRAWS_INTERNAL int draws_accept_pass(octo_draws* h, hipStream_t st, const d
 // What octo_draws_program.hip takes from octo_draws_scan.hip (defined there, not exported): ℓ_scan of the bound table added into ll [W] and its element
 // adjoints into g_in (null: no gradient), the bound rows' adjoints stored behind the program's n_in rows; inputs and g_in are [rows][ldw].
 OCTO_DRAWS_INTERNAL int draws_scan_accumulate(octo_draws* h, hipStream_t st, const double* inputs, double* g_in, double* ll, int64_t ldw, int64_t W, int32_t n_in);
+// … and from octo_draws_pma.hip, the same for the bound catalogue table: ℓ_pma into ll, the element adjoints into g_in, ∂ℓ/∂γ stored behind the n_in rows
+OCTO_DRAWS_INTERNAL int draws_pma_accumulate(octo_draws* h, hipStream_t st, const double* inputs, double* g_in, double* ll, int64_t ldw, int64_t W, int32_t n_in);
 
 namespace {
 

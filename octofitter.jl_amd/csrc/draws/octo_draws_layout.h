@@ -240,6 +240,27 @@ inline ScanStaging scan_staging(Carve& c, int64_t P, int64_t K, int64_t ld) {
     return {c.take(9 * P * ld), c.take(9 * P * ld), c.take(K * ld), c.take(K * ld), c.take(K * ld), c.take(ld), c.take(ld), c.take(ld)};
 }
 
+// The catalogue proper-motion anomaly (octo_draws_pma.hip), d_pma: (n_tasks·n_sums + 9)·ldw, n_sums = max(8, 10·P). The partial sums of every task of
+// SCAN_ROWS table rows, task-major: first the Q sums z_q of k_pma_rows, which k_pma_close consumes, then in the same rows the ten adjoint sums a planet
+// of k_pma_adj (U1 … U6, GE, GM, GT, GC of the main library's finish). λ = M·r of every walker (0 behind Q, and for an invalid walker) and its validity
+// (1 or 0) stay between k_pma_close and the adjoint kernels. The kernels take it by value.
+struct PmaWork {
+    double* part;      // [n_tasks][n_sums][ldw]
+    double* lam;       // [8][ldw]
+    double* ok;        // [ldw]
+};
+inline PmaWork pma_work(Carve& c, int64_t n_tasks, int64_t n_sums, int64_t ldw) { return {c.take(n_tasks * n_sums * ldw), c.take(8 * ldw), c.take(ldw)}; }
+
+// The device side of octo_draws_pma_eval, d_pma_hst: (2·P·9 + 3·K + 1)·ld
+struct PmaStaging {
+    double *elems, *g_elems;               // [P·9][ld]
+    double *gamma, *g_gamma, *gamma_hat;   // [K][ld]
+    double* ll;                            // [ld]
+};
+inline PmaStaging pma_staging(Carve& c, int64_t P, int64_t K, int64_t ld) {
+    return {c.take(9 * P * ld), c.take(9 * P * ld), c.take(K * ld), c.take(K * ld), c.take(K * ld), c.take(ld)};
+}
+
 // The convergence diagnostics of K rows (octo_draws_diag.hip), d_diag: 2K(P + S) + 10KM + 4K·T·(nblk + 1) + 5K. N draws of M = 2W split chains a row,
 // S = M·N used draws, P = the power of two the sort pads them to, T = the lags rounded up to whole blocks of 16, nblk = ⌈M/256⌉. The kernels take it
 // by value: its members and their order are their argument layout.

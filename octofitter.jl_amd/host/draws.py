@@ -81,6 +81,10 @@ SCAN_MAX_K = 6                     # OCTO_DRAWS_SCAN_MAX_K
 SCAN_ROWS = 8                      # OCTO_DRAWS_SCAN_ROWS: the rows of a task
 SCAN_SAMPLED, SCAN_MARGINAL = 0, 1
 SCAN_MODES = {"sampled": SCAN_SAMPLED, "marginal": SCAN_MARGINAL}
+PMA_MAX_Q = 8                      # OCTO_DRAWS_PMA_MAX_Q: catalogue values of a table
+PMA_MAX_K = 4                      # OCTO_DRAWS_PMA_MAX_K: its linear parameters γ
+PMA_SAMPLED, PMA_MARGINAL = 0, 1
+PMA_MODES = {"sampled": PMA_SAMPLED, "marginal": PMA_MARGINAL}
 OFTI_OUTPUTS = ("A", "B", "F", "G", "A_mean", "B_mean", "F_mean", "G_mean", "alpha", "a_ti", "i", "ω", "Ω", "P_d", "M_dyn", "logml")      # the rows of d_out, in order
 DIAG_RHAT, DIAG_ESS_BULK, DIAG_ESS_TAIL, DIAG_RHAT_BASIC, DIAG_ESS_BASIC, DIAG_Q05, DIAG_Q50, DIAG_Q95, DIAG_N_STATS = range(9)      # OCTO_DRAWS_DIAG_*
 PT_ACC_COLUMNS = ("n", "A", "n_f", "m_f", "s_f", "n_b", "m_b", "s_b")      # the columns of d_acc [T − 1][8]
@@ -169,6 +173,13 @@ _SIGS = {
     "octo_draws_scan_values_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "octo_draws_scan_bind": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "octo_draws_scan_unbind": (C.c_int32, [C.c_void_p]),
+    "octo_draws_pma_set": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + [capi.c_double_p] * 4 + [C.c_int32] + [capi.c_double_p] * 3 + [C.c_int32, C.c_int64]),
+    "octo_draws_pma_clear": (C.c_int32, [C.c_void_p]),
+    "octo_draws_pma_eval_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]),
+    "octo_draws_pma_eval": (C.c_int32, [C.c_void_p, C.c_int32, capi.c_double_p, C.c_int64, C.c_int64] + [capi.c_double_p] * 5),
+    "octo_draws_pma_values_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "octo_draws_pma_bind": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "octo_draws_pma_unbind": (C.c_int32, [C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -346,6 +357,7 @@ class PriorDraws(companion.Handle):
             self._own_ctx = ctx
         self._created(self.lib.octo_draws_create(ctx, m, self._c_priors, self.D, self.device_index, C.byref(self._h)))
         self.scan_shape = None      # (n, K, P) of the scan table while one is set
+        self.pma_shape = None       # (n, Q, K, P) of the catalogue table while one is set
         if program is not None:
             self.program_set(*program)
             scan = getattr(model, "_scan", None)
@@ -355,6 +367,11 @@ class PriorDraws(companion.Handle):
                 self.scan_set([(d["orbit_kind"], d["has_mass"]) for d in model.ln_like.planet_desc], t["epoch"], t["u"], t["v"], t["y"], t["sigma"],
                               obs.columns if obs.columns.shape[0] else None)
                 self.scan_bind(nodes, obs.mode)
+            pma = getattr(model, "_pma", None)
+            if pma is not None and program[0] is getattr(model, "program", None):      # the model's catalogue fit: a term of its program
+                obs, nodes = pma
+                self.pma_set([(d["orbit_kind"], d["has_mass"]) for d in model.ln_like.planet_desc], obs.t, obs.u, obs.v, obs.L, obs.d, obs.cov, obs.H)
+                self.pma_bind(nodes, obs.mode)
 
     # ---- derived variables (include/octofitter_hip_draws.h, "Derived variables"): a handle made from a model, without its device model
     def program_set(self, prog, binds):
@@ -603,6 +620,102 @@ class PriorDraws(companion.Handle):
     def scan_unbind(self):
         """octo_draws_scan_unbind"""
         self._check(self.lib.octo_draws_scan_unbind(self._h))
+
+    # ---- the catalogue proper-motion anomaly (include/octofitter_hip_draws.h, "The eighteenth"): any handle; the binding needs a program
+    def pma_set(self, planets, t, u, v, L, d, cov, H=None, consts=None):
+        """octo_draws_pma_set: the table (host arrays: t, u, v of one length n; the projector L [Q, n]; the catalogue values d [Q]; their covariance
+        cov [Q, Q]; the constant design H [Q, K] or None) for the planets [(orbit_kind, has_mass)]. consts: a capi.OctoConsts (None: the defaults)."""
+        cols = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in (t, u, v)]
+        n = cols[0].size
+        if any(c.size != n for c in cols):
+            raise ValueError("pma_set: t, u and v must have one length")
+        Lm = np.ascontiguousarray(L, dtype=np.float64).reshape(-1, n)
+        Q = int(Lm.shape[0])
+        dv = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
+        cm = np.ascontiguousarray(cov, dtype=np.float64)
+        Hm = np.zeros((Q, 0)) if H is None else np.ascontiguousarray(H, dtype=np.float64).reshape(Q, -1)
+        K = int(Hm.shape[1])
+        if dv.size != Q or cm.shape != (Q, Q):
+            raise ValueError("pma_set: L [Q, n], d [Q] and cov [Q, Q] must agree on Q")
+        desc = (capi.OctoPlanetDesc * max(len(planets), 1))(*[capi.OctoPlanetDesc(int(k), int(bool(m))) for k, m in planets])
+        self._check(self.lib.octo_draws_pma_set(self._h, C.cast(desc, C.c_void_p), len(planets), None if consts is None else C.cast(C.pointer(consts), C.c_void_p),
+                                                *[capi._dptr(c) for c in cols], capi._dptr(Lm), Q, capi._dptr(dv), capi._dptr(cm), capi._dptr(Hm if K else None), K, n))
+        self.pma_shape = (n, Q, K, len(planets))
+
+    def pma_clear(self):
+        """octo_draws_pma_clear"""
+        self._check(self.lib.octo_draws_pma_clear(self._h))
+        self.pma_shape = None
+
+    def pma_eval(self, elems, gamma=None, mode="sampled", grad=True, accumulate=False, out=None, stream=None):
+        """ℓ and its gradients of the W columns of elems (torch float64 [P·9, W] on the handle's device, rows contiguous; gamma [K, W] with the same
+        row distance): dict(ll [W], g_elems [P·9, W], g_gamma [K, W] (sampled), gamma_hat [K, W] (marginal)); with grad=False no g_elems and only the
+        two forward kernels run. accumulate: ll and g_elems are ADDED into out["ll"] and out["g_elems"]. Asynchronous on `stream`."""
+        n, Q, K, P = self.pma_shape
+        _, W, ld = chain_matrix(elems, P * capi.N_EL, self.device, "pma_eval", "elems")
+        m = PMA_MODES[mode]
+        if gamma is not None and K:
+            _, Wg, ldg = chain_matrix(gamma, K, self.device, "pma_eval", "gamma")
+            if Wg != W or (K > 1 and W and ldg != ld):
+                raise ValueError("pma_eval: gamma must have elems' width and row distance")
+        out = dict(out or {})
+        if "ll" not in out:
+            if accumulate:
+                raise ValueError("pma_eval: accumulate needs out['ll']")
+            out["ll"] = self._out(W)
+        if grad:
+            out.setdefault("g_elems", self._out(W, P * capi.N_EL, ld))
+        if m == PMA_SAMPLED and K:
+            out.setdefault("g_gamma", self._out(W, K, ld))
+        if m == PMA_MARGINAL:
+            out.setdefault("gamma_hat", self._out(W, K, ld))
+        self._check(self.lib.octo_draws_pma_eval_device(self._h, m, elems.data_ptr(), ld, W, ptr(gamma) if K else None, out["ll"].data_ptr(), ptr(out.get("g_elems")),
+                                                        ptr(out.get("g_gamma")), ptr(out.get("gamma_hat")), int(bool(accumulate)), self._stream(stream, self.device)))
+        self._keep = (elems, gamma, out)
+        return out
+
+    def pma_eval_host(self, elems, gamma=None, mode="sampled", grad=True):
+        """octo_draws_pma_eval: the same on NumPy arrays (elems [P·9, W], gamma [K, W]), blocking."""
+        n, Q, K, P = self.pma_shape
+        m = PMA_MODES[mode]
+        elems = np.ascontiguousarray(elems, dtype=np.float64).reshape(P * capi.N_EL, -1)
+        W = elems.shape[1]
+        gamma = None if gamma is None or not K else np.ascontiguousarray(gamma, dtype=np.float64).reshape(K, W)
+        out = dict(ll=np.empty(W))
+        if grad:
+            out["g_elems"] = np.empty((P * capi.N_EL, W))
+        if m == PMA_SAMPLED and K:
+            out["g_gamma"] = np.empty((K, W))
+        if m == PMA_MARGINAL:
+            out["gamma_hat"] = np.empty((K, W))
+        self._check(self.lib.octo_draws_pma_eval(self._h, m, capi._dptr(elems), W, W, capi._dptr(gamma), capi._dptr(out["ll"]), capi._dptr(out.get("g_elems")),
+                                                 capi._dptr(out.get("g_gamma")), capi._dptr(out.get("gamma_hat"))))
+        return out
+
+    def pma_values(self, elems, gamma=None, stream=None):
+        """The model's catalogue values m = z + H·γ [Q, W] at the W columns of elems (gamma None: z alone). Asynchronous on `stream`."""
+        n, Q, K, P = self.pma_shape
+        _, W, ld = chain_matrix(elems, P * capi.N_EL, self.device, "pma_values", "elems")
+        if gamma is not None and K:
+            _, Wg, ldg = chain_matrix(gamma, K, self.device, "pma_values", "gamma")
+            if Wg != W or (K > 1 and W and ldg != ld):
+                raise ValueError("pma_values: gamma must have elems' width and row distance")
+        m = self._out(W, Q)
+        self._check(self.lib.octo_draws_pma_values_device(self._h, elems.data_ptr(), ld, W, ptr(gamma) if K else None, m.data_ptr(), max(W, 1),
+                                                          self._stream(stream, self.device)))
+        self._keep = (elems, gamma, m)
+        return m
+
+    def pma_bind(self, nodes, mode="sampled"):
+        """octo_draws_pma_bind: the table becomes a term of the handle's program. nodes: the program's node indices of the γ parameters in column
+        order (sampled), or none (marginal)."""
+        from . import derived
+        bs = (derived.OctoDrawsBind * max(len(nodes), 1))(*[derived.OctoDrawsBind(derived.BIND_NODE, int(k), 0.0) for k in nodes])
+        self._check(self.lib.octo_draws_pma_bind(self._h, PMA_MODES[mode], C.cast(bs, C.c_void_p), len(nodes)))
+
+    def pma_unbind(self):
+        """octo_draws_pma_unbind"""
+        self._check(self.lib.octo_draws_pma_unbind(self._h))
 
     def momentum(self, seed, step, n, inv_mass=None, chain0=0, stream=None):
         """The momenta p [D, n] of chains chain0 … chain0 + n − 1 at `step`: standard normals of the counter generator over √inv_mass."""

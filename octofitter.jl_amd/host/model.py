@@ -54,10 +54,11 @@ class LogDensityModel:
             blocks += [pl.variables or {}] + [getattr(o, "variables", None) or {} for o in pl.observations]
         has_derived = any(isinstance(v, derived.Derived) for b in blocks for v in b.values())
         self._scan = None      # (AlongScanAstromObs, its program nodes) of a system with along-scan absolute astrometry
+        self._pma = None       # (CatalogueFitObs, its program nodes) of a system with a catalogue fit on refitted scans
         try:
-            if has_derived or fn.scan_obs:      # the scan table is a term of the expression program: such a model always has one
+            if has_derived or fn.scan_obs or fn.pma_obs:      # a scan or catalogue table is a term of the expression program: such a model always has one
                 if consts is not None:
-                    raise NotImplementedError("a model with Derived variables or along-scan astrometry uses the library's default constants (octo_consts_default)")
+                    raise NotImplementedError("a model with Derived variables, along-scan astrometry or a catalogue fit uses the library's default constants (octo_consts_default)")
                 self._build_program(system, fn, sysvars)
             else:
                 self._build(system, fn, sysvars)
@@ -215,6 +216,14 @@ class LogDensityModel:
                 raise KeyError(f"AlongScanAstromObs {obs.name!r}: variables must name its {obs.columns.shape[0]} β parameters in column order")
             jitter = prog.node(ns["jitter"]) if "jitter" in ov else const(0.0)[1]
             self._scan = (obs, [prog.node(ns[nm]) for nm in obs.beta_variables] + [jitter])
+        if fn.pma_obs:
+            if len(fn.pma_obs) > 1:
+                raise NotImplementedError("one CatalogueFitObs a system: the draws handle holds one catalogue table")
+            obs = fn.pma_obs[0]
+            ns = obs_ns[id(obs)]
+            if obs.mode == "sampled" and len(obs.gamma_variables) != obs.H.shape[1]:
+                raise KeyError(f"CatalogueFitObs {obs.name!r}: variables must name its {obs.H.shape[1]} γ parameters in column order")
+            self._pma = (obs, [prog.node(ns[nm]) for nm in obs.gamma_variables])
         self.program, self._binds = prog, binds
         pr = (capi.OctoPrior * self.D)()
         for k, p in enumerate(self.priors):

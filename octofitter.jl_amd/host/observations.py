@@ -380,3 +380,111 @@ def gaia_epoch_obs(t_mjd, scan_angle, parallax_factor_al, centroid_al, sigma_al,
     u, v = np.sin(psi), np.cos(psi)
     dt = (t - ref_epoch_mjd) / _JULIAN_YEAR
     return AlongScanAstromObs(t, u, v, y, s, np.stack([u, v, pf, u * dt, v * dt]), **{"name": "GaiaEpochAstrom", **kw})
+
+
+class CatalogueFitObs(AbstractObs):
+    """A catalogue of parameters REFITTED from the star's simulated scans (include/octofitter_hip_draws.h, "The eighteenth"): the star's reflex
+    ρ_i along the scan direction (u_i, v_i) at every epoch t_i [MJD] of a scan table, Q <= 8 fixed linear maps of the reflex rows z = L·ρ (L [Q, n]:
+    each mission's refitted linear model, built by the host), compared with the catalogue values d [Q] under their covariance cov [Q, Q];
+    m = z + H·γ with a constant design H [Q, K], K <= 4, for linear parameters γ. A system-level observation. `variables` (a `variables(...)` block:
+    priors, Derived, constants) names the γ in column order. mode "sampled": the γ are parameters of the model; "marginal": they are integrated out
+    under a flat prior and `variables` stays empty. It is evaluated by the draws library's expression-program route, not by the main library's
+    dataset: BatchedLnLike leaves it out of the dataset. One such observation a system, and not beside an AlongScanAstromObs."""
+    kind = None
+    nuisance_names = ()
+    MODES = ("sampled", "marginal")
+
+    def __init__(self, t, u, v, L, d, cov, H=None, *, mode="sampled", variables=None, name="CatalogueFit"):
+        cols = [np.asarray(c, dtype=np.float64).reshape(-1) for c in (t, u, v)]
+        n = cols[0].size
+        if n < 1 or any(c.size != n for c in cols):
+            raise ValueError("The columns in the input data do not all have the same length")
+        Lm = np.asarray(L, dtype=np.float64).reshape(-1, n)
+        Q = Lm.shape[0]
+        dv, cm = np.asarray(d, dtype=np.float64).reshape(-1), np.asarray(cov, dtype=np.float64)
+        Hm = np.zeros((Q, 0)) if H is None else np.asarray(H, dtype=np.float64).reshape(Q, -1)
+        if not 1 <= Q <= 8 or dv.size != Q or cm.shape != (Q, Q):
+            raise ValueError("CatalogueFitObs: L [Q, n], d [Q] and cov [Q, Q] with 1 <= Q <= 8")
+        if Hm.shape[1] > 4:
+            raise ValueError("CatalogueFitObs: at most 4 linear parameters")
+        if mode not in self.MODES:
+            raise ValueError(f"CatalogueFitObs: mode must be one of {self.MODES}")
+        if mode == "marginal" and Hm.shape[1] == 0:
+            raise ValueError("CatalogueFitObs: the marginal mode needs a design H")
+        if not all(np.all(np.isfinite(c)) for c in cols + [Lm, dv, cm, Hm]):
+            raise ValueError("CatalogueFitObs: every entry must be finite")
+        if not np.allclose(cm, cm.T, rtol=1e-12, atol=0.0) or np.any(np.linalg.eigvalsh(0.5 * (cm + cm.T)) <= 0.0):
+            raise ValueError("CatalogueFitObs: cov must be symmetric positive definite")
+        _warn_epoch_range(cols[0])
+        variables = dict(variables or {})
+        n_gamma = Hm.shape[1] if mode == "sampled" else 0
+        self.gamma_variables = tuple(variables)
+        if variables and len(self.gamma_variables) != n_gamma:      # none at all: a table only, for PriorDraws.pma_set; a model needs them
+            raise ValueError(f"CatalogueFitObs: variables names the {n_gamma} γ parameters in column order")
+        self.t, self.u, self.v = cols
+        self.table = dict(epoch=cols[0], u=cols[1], v=cols[2])
+        self.L, self.d, self.cov, self.H = Lm, dv, 0.5 * (cm + cm.T), Hm
+        self.mode = mode
+        self.variables = variables
+        self.name = name
+
+    def __len__(self):
+        return len(self.t)
+
+
+def mission_refit(t_mjd, u, v, pf, sigma=None):
+    """(F [5, n], t_ref [MJD]) of one mission's scans: F = (CᵀWC)⁻¹CᵀW maps along-scan positions to the weighted least-squares five-parameter
+    solution (Δα*, Δδ, ϖ, μα*, μδ) of C = [u, v, pf, u·τ, v·τ], τ = (t − t_ref)/365.25 from the weighted mean epoch t_ref, w = 1/σ² (None: equal)."""
+    t, u, v, pf = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (t_mjd, u, v, pf))
+    w = np.ones_like(t) if sigma is None else 1.0 / np.asarray(sigma, dtype=np.float64).reshape(-1) ** 2
+    t_ref = float(np.sum(w * t) / np.sum(w))
+    tau = (t - t_ref) / _JULIAN_YEAR
+    sw = np.sqrt(w)
+    C = np.stack([u, v, pf, u * tau, v * tau], axis=1)
+    if np.linalg.matrix_rank(C * sw[:, None]) < 5:
+        raise ValueError("mission_refit: the scans do not determine a five-parameter solution")
+    F = np.linalg.pinv(C * sw[:, None]) * sw[None, :]      # the least-squares solution operator of the weighted problem
+    return F, t_ref
+
+
+def hgca_obs(hgca, hip, gaia, *, factor=1, mode="sampled", variables=None, name="HGCA"):
+    """The Hipparcos-Gaia Catalog of Accelerations against proper motions REFITTED from the star's simulated scans — the reference's default HGCAObs —
+    as a CatalogueFitObs. `hgca` is the catalogue row mapping HGCAInstantaneousObs takes. hip = (epoch_yr, cpsi, spsi, sres, parf): the scans of the
+    Hipparcos intermediate astrometric data, (u, v) = (CPSI, SPSI); gaia = (t_mjd, scan_angle, parallax_factor_al[, sigma_al]): Gaia's scans at
+    position angle ψ [rad, from north through east], (u, v) = (sin ψ, cos ψ), equal weights without sigma_al.
+    Per mission mission_refit gives F [5, n_m] about the weighted mean epoch t_ref. The six outputs are (μα*_H, μδ_H, μα*_HG, μδ_HG, μα*_G, μδ_G) [mas/yr]:
+    L[μ_H] = F_H[μ] on the Hipparcos rows and 0 on Gaia's, L[μ_G] likewise, and
+    L[μα*_HG] = ((F_G[Δα*] + τ_G·F_G[μα*]) − (F_H[Δα*] + τ_H·F_H[μα*]))/(epoch_ra_gaia − epoch_ra_hip), τ_m = epoch_ra_m − t_ref,m in Julian years: each
+    mission's fitted position propagated to the catalogue's own epoch; the δ row with epoch_dec_*. d and the block-diagonal Σ are the row's
+    pm*_{hip,hg,gaia}, errors × factor, and correlations; H = [[1, 0], [0, 1]] three times: γ = the barycentre's (pmra, pmdec), which `variables` names
+    in that order. It only builds L, d, Σ, H. The conventions are recalled, not read from the reference's hgca-linfit.jl; perspective
+    acceleration, the non-linear parallax terms and the catalogue's frame rotation are not modelled."""
+    h = {k: float(np.asarray(x).reshape(-1)[0]) for k, x in dict(hgca).items()}
+    epoch_yr, cpsi, spsi, sres, parf = (np.asarray(x, dtype=np.float64).reshape(-1) for x in hip)
+    g = [np.asarray(x, dtype=np.float64).reshape(-1) for x in gaia]
+    tg, psi, pfg = g[:3]
+    sg = g[3] if len(g) > 3 else None
+    th = (epoch_yr - 2000.0) * _JULIAN_YEAR + _J2000_MJD
+    ug, vg = np.sin(psi), np.cos(psi)
+    FH, tref_h = mission_refit(th, cpsi, spsi, parf, sres)
+    FG, tref_g = mission_refit(tg, ug, vg, pfg, sg)
+    nh, ng = th.size, tg.size
+    L = np.zeros((6, nh + ng))
+    L[0, :nh], L[1, :nh] = FH[3], FH[4]
+    L[4, nh:], L[5, nh:] = FG[3], FG[4]
+    to_mjd = lambda yr: (yr - 2000.0) * _JULIAN_YEAR + _J2000_MJD      # noqa: E731
+    for row, pos, pm, key in ((2, 0, 3, "ra"), (3, 1, 4, "dec")):
+        e_h, e_g = h[f"epoch_{key}_hip"], h[f"epoch_{key}_gaia"]
+        tau_h, tau_g = (to_mjd(e_h) - tref_h) / _JULIAN_YEAR, (to_mjd(e_g) - tref_g) / _JULIAN_YEAR
+        L[row, :nh] = -(FH[pos] + tau_h * FH[pm]) / (e_g - e_h)
+        L[row, nh:] = (FG[pos] + tau_g * FG[pm]) / (e_g - e_h)
+    d, cov = np.zeros(6), np.zeros((6, 6))
+    for b, tag in enumerate(("hip", "hg", "gaia")):
+        sa, sd, rho = h[f"pmra_{tag}_error"] * factor, h[f"pmdec_{tag}_error"] * factor, h[f"pmra_pmdec_{tag}"]
+        d[2 * b], d[2 * b + 1] = h[f"pmra_{tag}"], h[f"pmdec_{tag}"]
+        cov[2 * b:2 * b + 2, 2 * b:2 * b + 2] = [[sa * sa, rho * sa * sd], [rho * sa * sd, sd * sd]]
+    H = np.tile(np.eye(2), (3, 1))
+    return CatalogueFitObs(np.concatenate([th, tg]), np.concatenate([cpsi, ug]), np.concatenate([spsi, vg]), L, d, cov, H, mode=mode, variables=variables, name=name)
+
+
+HGCAObs = hgca_obs

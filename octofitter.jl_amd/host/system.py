@@ -25,7 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .observations import AbstractObs, AlongScanAstromObs, normalizename
+from .observations import AbstractObs, AlongScanAstromObs, CatalogueFitObs, normalizename
 
 _EL_KEYS = (("a",), ("e",), ("i",), ("ω", "w", "omega"), ("Ω", "O", "Omega"), ("tp",), ("M",), ("plx",), ("mass",))
 # ThieleInnesOrbit(; e, tp, M, plx, A, B, F, G): the constants [mas] travel in the rows of a, i, ω, Ω (include/octofitter_hip.h)
@@ -84,7 +84,12 @@ class BatchedLnLike:
         j = 1
         # along-scan absolute astrometry is a term of the draws library's expression program, not a table of the dataset: left out here
         self.scan_obs = [obs for obs in system.observations if isinstance(obs, AlongScanAstromObs)]
-        dataset_obs = [obs for obs in system.observations if not isinstance(obs, AlongScanAstromObs)]
+        # … and so is the catalogue fit on refitted scans (the draws library's eighteenth part)
+        self.pma_obs = [obs for obs in system.observations if isinstance(obs, CatalogueFitObs)]
+        if self.scan_obs and self.pma_obs:
+            raise ValueError("a system with both a CatalogueFitObs and an AlongScanAstromObs is not on the device path: a draws handle binds one "
+                             "table to its expression program (octo_draws_pma_bind, octo_draws_scan_bind)")
+        dataset_obs = [obs for obs in system.observations if not isinstance(obs, (AlongScanAstromObs, CatalogueFitObs))]
         for obs in dataset_obs:
             self.epoch_start_index_mapping[id(obs)] = j
             j += len(obs)
@@ -98,7 +103,7 @@ class BatchedLnLike:
         self.obs_entries = []   # (obs, planet_index or -1, planet_name or None, θ_obs key)
         for ip, pl in enumerate(system.planets):
             for obs in pl.observations:
-                if obs.kind in (capi.RV_ABS, capi.RV_ABS_MARG, capi.HGCA) or isinstance(obs, AlongScanAstromObs):
+                if obs.kind in (capi.RV_ABS, capi.RV_ABS_MARG, capi.HGCA) or isinstance(obs, (AlongScanAstromObs, CatalogueFitObs)):
                     raise ValueError(f"{type(obs).__name__} is a system-level observation")
                 self.obs_entries.append((obs, ip, pl.name, normalizename(obs.likelihoodname())))
         for obs in dataset_obs:
