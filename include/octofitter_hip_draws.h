@@ -1129,6 +1129,98 @@ int32_t octo_draws_pma_values_device(octo_draws* h, const double* d_elems, int64
 int32_t octo_draws_pma_bind(octo_draws* h, int32_t mode, const octo_draws_bind* binds, int32_t n_binds);
 int32_t octo_draws_pma_unbind(octo_draws* h);
 
+/* ---- The nineteenth: a radial-velocity table of the star under a Gaussian process with celerite kernels — the reference's StarAbsoluteRVObs with a
+ * gaussian_process that returns a Celerite kernel: log N(r; 0, K) of the residuals by the semiseparable recursion, O(n·R²) a walker, and its exact
+ * gradient in reverse mode. The functions are stated in full so that a restatement elsewhere (tests/gp_reference.py: the DENSE normal in mpmath, and the
+ * recursion in NumPy) and the device compute the same function. The table is held beside the scan and catalogue tables, independent of them.
+ *
+ * Table      n rows, 1 <= n <= 65536. Row i: epoch t_i [MJD], non-decreasing; rv_i [m/s]; σ_i > 0 [m/s]; K design coefficients c_i[0 … K − 1],
+ *            0 <= K <= OCTO_DRAWS_GP_MAX_K (the offset's column of ones, the trend basis); c is [K][n]. The planets' descriptors and the constants as
+ *            for octo_draws_scan_set. A term list of 1 <= J <= OCTO_DRAWS_GP_MAX_TERMS kinds.
+ * Terms      a term occupies slots, R = Σ slots <= OCTO_DRAWS_GP_MAX_SLOTS, and reads hyperparameters hyper[h·ld + w], H = Σ (2 | 4 | 3) rows in term
+ *            order. With x = d·(t_i − t_1) (the origin is row 1: any origin is exact for a stationary kernel, this one keeps the phases small):
+ *              OCTO_DRAWS_GP_REAL     1 slot   (a, c)         k(τ) = a·e^{−cτ}                          Ũ = a, Ṽ = 1, rate c
+ *              OCTO_DRAWS_GP_COMPLEX  2 slots  (a, b, c, d)   k(τ) = e^{−cτ}(a·cos dτ + b·sin dτ)       Ũ = (a cos x + b sin x, a sin x − b cos x),
+ *                                                                                                       Ṽ = (cos x, sin x), rate c on both
+ *              OCTO_DRAWS_GP_SHO      2 slots  (S0, Q, ω0)    decided PER WALKER: Q > ½ is a COMPLEX with f = √(4Q² − 1), a = S0·ω0·Q, b = a/f,
+ *                                                             c = ω0/(2Q), d = c·f; Q < ½ is two REAL slots with f = √(1 − 4Q²),
+ *                                                             a± = ½·S0·ω0·Q·(1 ± 1/f), c± = ω0/(2Q)·(1 ∓ f); at Q = ½ the coefficients are not
+ *                                                             finite and the walker is invalid. Lanes of one wave may sit on both sides of ½.
+ * Model      η_i = Σ_k c_i[k]·β_k + Σ_p f_p·K_p·V_p(t_i), f_p = −mass_p·mjup2msol/M_p (0 with has_mass = 0), K_p the semi-amplitude and V_p =
+ *            cos(ν + ω) + e·cos ω: the main library's absolute-RV rule, rv_row's arithmetic on the COLD Kepler solve (the companion libraries' rule).
+ *            OCTO_ORBIT_VISUAL_KEP, OCTO_ORBIT_RADVEL and OCTO_ORBIT_KEP planets with a mass contribute. r_i = rv_i − η_i, A_i = σ_i² + s² + Σ_j a_j
+ *            (a complex pair adds its a once, an SHO below ½ adds a₊ + a₋).
+ * Recursion  φ_i = e^{−c·(t_i − t_{i−1})} per slot, S_1 = 0, f_1 = 0, and in row order
+ *              S_i = φ_iφ_iᵀ ∘ (S_{i−1} + D_{i−1}W_{i−1}W_{i−1}ᵀ)      f_i = φ_i ∘ (f_{i−1} + W_{i−1}z_{i−1})
+ *              D_i = A_i − Ũ_iᵀS_iŨ_i      W_i = (Ṽ_i − S_iŨ_i)/D_i      z_i = r_i − Ũ_i·f_i
+ *              ℓ   = Σ_i (−½·z_i²/D_i − ½·log D_i − ½·log 2π)   = log N(r; 0, K), K_ij = [i = j](σ_i² + s²) + Σ_j k_j(|t_i − t_j|)
+ * Gradient   the exact derivative of ℓ in reverse mode: α = K⁻¹r is the adjoint of −r, so ∂ℓ/∂η_i = α_i; ∂ℓ/∂elems [P·9][ld] from α through each
+ *            planet's sums and the main library's finish; ∂ℓ/∂β_k = Σ_i α_i c_i[k]; ∂ℓ/∂s; ∂ℓ/∂hyper [H][ld] in the terms' OWN parameters (S0, Q, ω0
+ *            of an SHO). The reverse walk never divides by φ (a seasonal gap has φ down to exactly 0): the state a row hands to the next,
+ *            (S + D·W·Wᵀ, f + W·z), is kept every OCTO_DRAWS_GP_SEGMENT rows by the forward pass, and the reverse pass recomputes a segment's states
+ *            forward from its checkpoint before it walks the segment backward.
+ * Invalid    a non-finite input, an element outside the main library's domain, s < 0, a rate c <= 0, a non-finite coefficient, a D_i that is not
+ *            > 0 and finite (the kernel is not positive definite there), a non-finite ℓ: ℓ = −Inf and a zero gradient for that walker; never a
+ *            status, never another walker's bits.
+ * Order      the row-parallel passes (η, and the planets' and β's sums against α) cut the rows into tasks of OCTO_DRAWS_SCAN_ROWS and add in row
+ *            order, then task order; the recursion is in row order by construction. No atomics: a walker's outputs depend on its own column alone,
+ *            bit for bit, in any batch and with any ld. There is no marginal mode: the reference's marginalised RV has no Gaussian process.
+ *
+ * octo_draws_gp_set copies the table to the device; it needs neither a model nor a context. A second call replaces the first; octo_draws_gp_clear
+ * removes it (no-op when nothing is set). Both drop a binding.
+ * OCTO_EINVAL: NULL handle; a NULL array (c may be NULL with K = 0); n, K, n_planets or n_terms out of range; σ <= 0; a non-finite entry; epochs that
+ * decrease; an unknown orbit kind or term kind. OCTO_ENOTSUP: an OCTO_ORBIT_THIELE_INNES planet with a mass (as the main library answers an RV table
+ * on such a planet). */
+#define OCTO_DRAWS_GP_MAX_K 4
+#define OCTO_DRAWS_GP_MAX_TERMS 4
+#define OCTO_DRAWS_GP_MAX_SLOTS 8
+#define OCTO_DRAWS_GP_SEGMENT 16
+#define OCTO_DRAWS_GP_REAL 0
+#define OCTO_DRAWS_GP_COMPLEX 1
+#define OCTO_DRAWS_GP_SHO 2
+int32_t octo_draws_gp_set(octo_draws* h, const octo_planet_desc* planets, int32_t n_planets, const octo_consts* consts /*NULL = octo_consts_default*/,
+                          const double* t, const double* rv, const double* sigma, const double* c /*[K][n]*/, int32_t K, int64_t n,
+                          const int32_t* term_kinds, int32_t n_terms);
+int32_t octo_draws_gp_clear(octo_draws* h);
+
+/* The doubles of the handle's work array that one evaluation of W walkers needs (−1: an argument out of range):
+ *   ldw·(n + 1 + [grad]·((⌈n/OCTO_DRAWS_GP_SEGMENT⌉ + OCTO_DRAWS_GP_SEGMENT)·(R'(R' + 1)/2 + R') + ⌈n/OCTO_DRAWS_SCAN_ROWS⌉·(4 + 6·n_planets)))
+ * ldw = W rounded up to whole waves, R' = n_slots rounded up to 2, 4 or 8 (the kernels' instantiations; a padding slot changes no bit). The residuals
+ * (then α) and the validity; with a gradient the checkpoints, one segment's states, and the row tasks' sums. */
+int64_t octo_draws_gp_work_doubles(int64_t n, int32_t n_slots, int32_t n_planets, int64_t W, int32_t grad);
+
+/* ℓ [W] and the gradients of W walkers on DEVICE buffers, asynchronous on hip_stream: no host synchronisation, no allocation once the handle's work
+ * array holds octo_draws_gp_work_doubles. d_hyper and d_g_hyper are [H][ld], d_beta and d_g_beta [K][ld], d_jitter (NULL: 0) and d_g_jitter [W]. Every
+ * gradient output may be NULL; with all of them NULL no reverse pass runs and nothing is stored for one, and ℓ has the gradient call's bits.
+ * accumulate = 1 ADDS ℓ into d_ll and the element adjoints into d_g_elems (an invalid walker adds −Inf and 0); the other gradients are always stored.
+ * accumulate = 0 stores 0 + the value, so that accumulating into zeroed outputs gives the same bits.
+ * OCTO_EINVAL: NULL handle; no table; W < 0, ld < W; NULL d_elems, d_hyper or d_ll, or NULL d_beta with K > 0, with W > 0. */
+int32_t octo_draws_gp_eval_device(octo_draws* h, const double* d_elems, int64_t ld, int64_t W, const double* d_hyper, const double* d_beta,
+                                  const double* d_jitter, double* d_ll, double* d_g_elems, double* d_g_hyper, double* d_g_beta, double* d_g_jitter,
+                                  int32_t accumulate, void* hip_stream);
+/* The twin on HOST buffers, blocking, through the handle's staging ((2·P·9 + 2·H + 2·K + 3)·ld doubles) on its own stream; accumulate = 0. */
+int32_t octo_draws_gp_eval(octo_draws* h, const double* elems, int64_t ld, int64_t W, const double* hyper, const double* beta, const double* jitter,
+                           double* ll, double* g_elems, double* g_hyper, double* g_beta, double* g_jitter);
+
+/* The model values η [n][ld_out] of W walkers (d_beta NULL: the planets alone) and, with d_mu, the process's conditional mean at the table's epochs,
+ * μ_i = r_i − (σ_i² + s²)·α_i [n][ld_out] (residual plots subtract it); d_eta or d_mu may be NULL, d_hyper and d_jitter are read for d_mu alone.
+ * Asynchronous on hip_stream. An invalid walker's column is not defined. OCTO_EINVAL: NULL handle; no table; W < 0, ld < W, ld_out < W; NULL d_elems,
+ * both outputs NULL, or d_mu without d_hyper, with W > 0. */
+int32_t octo_draws_gp_values_device(octo_draws* h, const double* d_elems, int64_t ld, int64_t W, const double* d_hyper, const double* d_beta,
+                                    const double* d_jitter, double* d_eta /*[n][ld_out]*/, double* d_mu /*[n][ld_out]*/, int64_t ld_out, void* hip_stream);
+
+/* The table as a term of the handle's expression program, exactly as octo_draws_scan_bind: ℓ_gp is added to the likelihood that octo_eval_device
+ * returns (it is tempered with it and survives a healed prior) and its adjoints to the inputs' gradient. binds names the nodes the table reads,
+ * OCTO_DRAWS_BIND_NODE only: n_binds = H + K + 1, the hyperparameter nodes in term order, the β nodes in column order, then the jitter node. The bound
+ * nodes become input rows behind the program's own, so with nothing bound no launch and no work array differs. octo_draws_program_set,
+ * octo_draws_program_clear, octo_draws_gp_set and octo_draws_gp_clear drop the binding; octo_draws_gp_unbind is a no-op when nothing is bound. A
+ * transition that was open is never resumed across a change of the binding. ONE bound table a handle: with a scan or catalogue table bound
+ * octo_draws_gp_bind answers OCTO_ENOTSUP, and so do octo_draws_scan_bind and octo_draws_pma_bind with this table bound.
+ * OCTO_EINVAL: NULL handle; no table; no program, or one whose n_planets is not the table's; n_binds not as above; a binding that is not a NODE or
+ * whose node is out of range. */
+int32_t octo_draws_gp_bind(octo_draws* h, const octo_draws_bind* binds, int32_t n_binds);
+int32_t octo_draws_gp_unbind(octo_draws* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -338,7 +338,7 @@ int32_t octo_draws_destroy(octo_draws* h) {
         }
         if (release) (void)hipStreamDestroy(h->stream);
     }
-    for (void* p : std::initializer_list<void*>{h->own_priors, h->own_pc, h->own_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice, h->d_prog, h->d_prog_tab, h->d_ncull, h->d_nest, h->d_de, h->d_oftis, h->d_oftis_rows, h->d_scan_rows, h->d_scan, h->d_scan_hst, h->d_scan_binds, h->d_pma_rows, h->d_pma, h->d_pma_hst, h->d_pma_binds})
+    for (void* p : std::initializer_list<void*>{h->own_priors, h->own_pc, h->own_ic, h->d_chunk, h->d_arr, h->d_out, h->d_hmc, h->d_hst, h->d_lbf, h->d_lbd, h->d_pf, h->d_pfb, h->d_mom, h->d_nuts, h->d_diag, h->d_slice, h->d_prog, h->d_prog_tab, h->d_ncull, h->d_nest, h->d_de, h->d_oftis, h->d_oftis_rows, h->d_scan_rows, h->d_scan, h->d_scan_hst, h->d_scan_binds, h->d_pma_rows, h->d_pma, h->d_pma_hst, h->d_pma_binds, h->d_gp_rows, h->d_gp, h->d_gp_hst, h->d_gp_binds})
         (void)hipFree(p);
     delete h;
     return OCTO_OK;

@@ -24,6 +24,7 @@
 // calls its draws_scan_accumulate (below) between octo_eval_device and k_prog_bwd while a table is bound.
 // The eighteenth part, the catalogue proper-motion anomaly (octo_draws_pma.hip), takes the same and hands the program draws_pma_accumulate; its table
 // algebra is octo_draws_pma_host.h.
+// The nineteenth part, the Gaussian-process RV term (octo_draws_gp.hip), takes the same and hands the program draws_gp_accumulate.
 // It stays under csrc/draws/: csrc/companion/ holds only what EVERY companion library shares.
 #pragma once
 
@@ -390,6 +391,18 @@ struct octo_draws : CompanionBase {
     double* d_pma_hst = nullptr; int64_t cap_pma_hst = 0;
     int32_t pma_bound = 0, pma_n_bind = 0;
     double* d_pma_binds = nullptr; int64_t cap_pma_binds = 0;
+    // the Gaussian-process RV term (octo_draws_gp.hip) while octo_draws_gp_set holds (gp_n = 0: not set): the rows {t, rv, σ², c[0 … 3], 0} on the device,
+    // the shape (J terms of R slots and H hyperparameters; RP = the instantiation's slots), the terms' kinds and every slot's role, the planets'
+    // descriptors and constants, the work array, the device side of the host-buffer twin, and the binding to the expression program as for the scan table.
+    double* d_gp_rows = nullptr; int64_t cap_gp_rows = 0;
+    int32_t gp_n = 0, gp_K = 0, gp_P = 0, gp_J = 0, gp_R = 0, gp_RP = 0, gp_H = 0;
+    int32_t gp_term[OCTO_DRAWS_GP_MAX_TERMS] = {}, gp_slot[OCTO_DRAWS_GP_MAX_SLOTS] = {};
+    int32_t gp_kind[OCTO_MAX_PLANETS] = {}, gp_mass[OCTO_MAX_PLANETS] = {};
+    octo_consts gp_consts = {};
+    double* d_gp = nullptr; int64_t cap_gp = 0;
+    double* d_gp_hst = nullptr; int64_t cap_gp_hst = 0;
+    int32_t gp_bound = 0, gp_n_bind = 0;
+    double* d_gp_binds = nullptr; int64_t cap_gp_binds = 0;
 };
 
 // What octo_draws_ofti.hip takes from octo_draws.hip (defined there, not exported): k_draw's launches into θ alone, and the two halves of pass 2 of the
@@ -406,6 +419,8 @@ OCTO_DRAWS_INTERNAL int draws_accept_pass(octo_draws* h, hipStream_t st, const d
 OCTO_DRAWS_INTERNAL int draws_scan_accumulate(octo_draws* h, hipStream_t st, const double* inputs, double* g_in, double* ll, int64_t ldw, int64_t W, int32_t n_in);
 // … and from octo_draws_pma.hip, the same for the bound catalogue table: ℓ_pma into ll, the element adjoints into g_in, ∂ℓ/∂γ stored behind the n_in rows
 OCTO_DRAWS_INTERNAL int draws_pma_accumulate(octo_draws* h, hipStream_t st, const double* inputs, double* g_in, double* ll, int64_t ldw, int64_t W, int32_t n_in);
+// … and from octo_draws_gp.hip for the bound Gaussian-process table: ℓ_gp into ll, the element adjoints into g_in, ∂ℓ/∂(hyper, β, s) stored behind the n_in rows
+OCTO_DRAWS_INTERNAL int draws_gp_accumulate(octo_draws* h, hipStream_t st, const double* inputs, double* g_in, double* ll, int64_t ldw, int64_t W, int32_t n_in);
 
 namespace {
 

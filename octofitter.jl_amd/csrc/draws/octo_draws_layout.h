@@ -261,6 +261,33 @@ inline PmaStaging pma_staging(Carve& c, int64_t P, int64_t K, int64_t ld) {
     return {c.take(9 * P * ld), c.take(9 * P * ld), c.take(K * ld), c.take(K * ld), c.take(K * ld), c.take(ld)};
 }
 
+// The Gaussian-process RV term (octo_draws_gp.hip), d_gp: (n + 1 + [grad]·((n_seg + SEGMENT)·n_state + n_tasks·n_sums))·ldw, n_state = R'(R' + 1)/2 + R'
+// of the R' = 2, 4 or 8 slots the kernels are instantiated for, n_seg = ⌈n/SEGMENT⌉, n_tasks = ⌈n/SCAN_ROWS⌉, n_sums = 4 + 6·P. The residuals r_i of
+// k_gp_rows, which k_gp_back replaces row by row with α_i; every walker's validity (1 or 0) from k_gp_factor; with a gradient the state (S + D·W·Wᵀ packed,
+// f + W·z) handed to the first row of every segment, the states handed to each row of the segment k_gp_back is walking, and the partial sums of k_gp_adj,
+// task-major: the K <= 4 sums Σ α_i c_i[k], then six a planet (GE, GM, GT, GC, GK, GW of the main library's finish). The kernels take it by value.
+struct GpWork {
+    double* res;        // [n][ldw]
+    double* ok;         // [ldw]
+    double* check;      // [ldw/64][n_seg][n_state][64]: a wave's states lie together, so their offsets are constants of the kernel
+    double* seg;        // [ldw/64][SEGMENT][n_state][64]
+    double* part;       // [n_tasks][n_sums][ldw]
+};
+inline GpWork gp_work(Carve& c, int64_t n, int64_t n_state, int64_t n_seg, int64_t segment, int64_t n_tasks, int64_t n_sums, int64_t ldw, int64_t grad) {
+    return {c.take(n * ldw), c.take(ldw), c.take(grad ? n_seg * n_state * ldw : 0), c.take(grad ? segment * n_state * ldw : 0), c.take(grad ? n_tasks * n_sums * ldw : 0)};
+}
+
+// The device side of octo_draws_gp_eval, d_gp_hst: (2·P·9 + 2·H + 2·K + 3)·ld
+struct GpStaging {
+    double *elems, *g_elems;       // [P·9][ld]
+    double *hyper, *g_hyper;       // [H][ld]
+    double *beta, *g_beta;         // [K][ld]
+    double *jitter, *g_jitter, *ll;      // [ld]
+};
+inline GpStaging gp_staging(Carve& c, int64_t P, int64_t H, int64_t K, int64_t ld) {
+    return {c.take(9 * P * ld), c.take(9 * P * ld), c.take(H * ld), c.take(H * ld), c.take(K * ld), c.take(K * ld), c.take(ld), c.take(ld), c.take(ld)};
+}
+
 // The convergence diagnostics of K rows (octo_draws_diag.hip), d_diag: 2K(P + S) + 10KM + 4K·T·(nblk + 1) + 5K. N draws of M = 2W split chains a row,
 // S = M·N used draws, P = the power of two the sort pads them to, T = the lags rounded up to whole blocks of 16, nblk = ⌈M/256⌉. The kernels take it
 // by value: its members and their order are their argument layout.

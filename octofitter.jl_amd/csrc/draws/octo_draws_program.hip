@@ -225,6 +225,8 @@ ProgArgs program_args(const octo_draws* h, const double* d_theta_t, int64_t ld, 
         a.binds = (const octo_draws_bind*)h->d_scan_binds; a.n_in += h->scan_n_bind;
     } else if (h->pma_bound) {      // … or a bound catalogue table (octo_draws_pma.hip), the same way: one bound table a handle
         a.binds = (const octo_draws_bind*)h->d_pma_binds; a.n_in += h->pma_n_bind;
+    } else if (h->gp_bound) {       // … or a bound Gaussian-process RV table (octo_draws_gp.hip)
+        a.binds = (const octo_draws_bind*)h->d_gp_binds; a.n_in += h->gp_n_bind;
     }
     return a;
 }
@@ -239,6 +241,7 @@ int32_t octo_draws_program_clear(octo_draws* h) {
     h->prog_n_ops = h->prog_n_in = h->prog_n_el = h->prog_n_terms = h->prog_planets = 0;
     h->scan_bound = 0; h->scan_n_bind = 0;      // a bound scan table names this program's nodes
     h->pma_bound = 0; h->pma_n_bind = 0;        // … and so does a bound catalogue table
+    h->gp_bound = 0; h->gp_n_bind = 0;          // … and a bound Gaussian-process RV table
     h->nuts_depth = 0; h->slice_passes = 0; h->lbf_m = 0; h->pf_W = 0; h->de_open = false;      // a transition is never resumed on another target
     return OCTO_OK;
 }
@@ -334,6 +337,8 @@ int32_t octo_draws_program_logpost_device(octo_draws* h, const double* d_theta_t
         if (int rc = draws_scan_accumulate(h, st, a.k.inputs, d_grad ? a.k.g_in : nullptr, a.k.ll, ldw, W, h->prog_n_in)) return rc;
     if (h->pma_bound)       // ℓ_pma likewise (octo_draws_pma.hip)
         if (int rc = draws_pma_accumulate(h, st, a.k.inputs, d_grad ? a.k.g_in : nullptr, a.k.ll, ldw, W, h->prog_n_in)) return rc;
+    if (h->gp_bound)        // ℓ_gp likewise (octo_draws_gp.hip)
+        if (int rc = draws_gp_accumulate(h, st, a.k.inputs, d_grad ? a.k.g_in : nullptr, a.k.ll, ldw, W, h->prog_n_in)) return rc;
     hipLaunchKernelGGL(k_prog_bwd, grid, block, d_grad ? lds : 0, st, a);
     OCHK(h, hipGetLastError());
     return OCTO_OK;

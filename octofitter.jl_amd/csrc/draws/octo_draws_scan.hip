@@ -582,6 +582,7 @@ int32_t octo_draws_scan_bind(octo_draws* h, int32_t mode, const octo_draws_bind*
     if (int rc = check_scan_mode(h, who, mode)) return rc;
     if (!h->prog_ops || !h->ctx) return fail(h, OCTO_EINVAL, std::string(who) + ": the handle has no program (octo_draws_program_set)");
     if (h->pma_bound) return fail(h, OCTO_ENOTSUP, std::string(who) + ": a catalogue table is bound (octo_draws_pma_bind): one bound table a handle");
+    if (h->gp_bound) return fail(h, OCTO_ENOTSUP, std::string(who) + ": a Gaussian-process RV table is bound (octo_draws_gp_bind): one bound table a handle");
     if (h->prog_planets != h->scan_P)
         return fail(h, OCTO_EINVAL, std::string(who) + ": the program has " + std::to_string(h->prog_planets) + " planets, the table " + std::to_string(h->scan_P));
     const int32_t want = mode == OCTO_DRAWS_SCAN_MARGINAL ? 1 : h->scan_K + 1;

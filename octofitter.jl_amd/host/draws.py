@@ -85,6 +85,13 @@ PMA_MAX_Q = 8                      # OCTO_DRAWS_PMA_MAX_Q: catalogue values of a
 PMA_MAX_K = 4                      # OCTO_DRAWS_PMA_MAX_K: its linear parameters γ
 PMA_SAMPLED, PMA_MARGINAL = 0, 1
 PMA_MODES = {"sampled": PMA_SAMPLED, "marginal": PMA_MARGINAL}
+GP_MAX_K = 4                       # OCTO_DRAWS_GP_MAX_K: design columns of a Gaussian-process RV table
+GP_MAX_TERMS = 4                   # OCTO_DRAWS_GP_MAX_TERMS: celerite terms of its kernel
+GP_MAX_SLOTS = 8                   # OCTO_DRAWS_GP_MAX_SLOTS: their slots (REAL 1, COMPLEX 2, SHO 2)
+GP_SEGMENT = 16                    # OCTO_DRAWS_GP_SEGMENT: rows between two checkpoints of the recursion
+GP_REAL, GP_COMPLEX, GP_SHO = 0, 1, 2
+GP_N_HYPER = {GP_REAL: 2, GP_COMPLEX: 4, GP_SHO: 3}
+GP_N_SLOTS = {GP_REAL: 1, GP_COMPLEX: 2, GP_SHO: 2}
 OFTI_OUTPUTS = ("A", "B", "F", "G", "A_mean", "B_mean", "F_mean", "G_mean", "alpha", "a_ti", "i", "ω", "Ω", "P_d", "M_dyn", "logml")      # the rows of d_out, in order
 DIAG_RHAT, DIAG_ESS_BULK, DIAG_ESS_TAIL, DIAG_RHAT_BASIC, DIAG_ESS_BASIC, DIAG_Q05, DIAG_Q50, DIAG_Q95, DIAG_N_STATS = range(9)      # OCTO_DRAWS_DIAG_*
 PT_ACC_COLUMNS = ("n", "A", "n_f", "m_f", "s_f", "n_b", "m_b", "s_b")      # the columns of d_acc [T − 1][8]
@@ -180,6 +187,14 @@ _SIGS = {
     "octo_draws_pma_values_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "octo_draws_pma_bind": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "octo_draws_pma_unbind": (C.c_int32, [C.c_void_p]),
+    "octo_draws_gp_set": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + [capi.c_double_p] * 4 + [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32]),
+    "octo_draws_gp_clear": (C.c_int32, [C.c_void_p]),
+    "octo_draws_gp_work_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "octo_draws_gp_eval_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 8 + [C.c_int32, C.c_void_p]),
+    "octo_draws_gp_eval": (C.c_int32, [C.c_void_p, capi.c_double_p, C.c_int64, C.c_int64] + [capi.c_double_p] * 8),
+    "octo_draws_gp_values_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
+    "octo_draws_gp_bind": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "octo_draws_gp_unbind": (C.c_int32, [C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -358,6 +373,7 @@ class PriorDraws(companion.Handle):
         self._created(self.lib.octo_draws_create(ctx, m, self._c_priors, self.D, self.device_index, C.byref(self._h)))
         self.scan_shape = None      # (n, K, P) of the scan table while one is set
         self.pma_shape = None       # (n, Q, K, P) of the catalogue table while one is set
+        self.gp_shape = None        # (n, K, P, H, R) of the Gaussian-process RV table while one is set
         if program is not None:
             self.program_set(*program)
             scan = getattr(model, "_scan", None)
@@ -372,6 +388,12 @@ class PriorDraws(companion.Handle):
                 obs, nodes = pma
                 self.pma_set([(d["orbit_kind"], d["has_mass"]) for d in model.ln_like.planet_desc], obs.t, obs.u, obs.v, obs.L, obs.d, obs.cov, obs.H)
                 self.pma_bind(nodes, obs.mode)
+            gp = getattr(model, "_gp", None)
+            if gp is not None and program[0] is getattr(model, "program", None):      # the model's Gaussian-process RV observation: a term of its program
+                obs, nodes = gp
+                self.gp_set([(d["orbit_kind"], d["has_mass"]) for d in model.ln_like.planet_desc], obs.table["epoch"], obs.table["rv"], obs.table["σ_rv"],
+                            obs.gp_columns if obs.gp_columns.shape[0] else None, obs.gp_terms)
+                self.gp_bind(nodes)
 
     # ---- derived variables (include/octofitter_hip_draws.h, "Derived variables"): a handle made from a model, without its device model
     def program_set(self, prog, binds):
@@ -716,6 +738,109 @@ class PriorDraws(companion.Handle):
     def pma_unbind(self):
         """octo_draws_pma_unbind"""
         self._check(self.lib.octo_draws_pma_unbind(self._h))
+
+    # ---- the Gaussian-process RV term (include/octofitter_hip_draws.h, "The nineteenth"): any handle; the binding needs a program
+    def gp_set(self, planets, t, rv, sigma, columns=None, terms=(GP_SHO,), consts=None):
+        """octo_draws_gp_set: the RV table (host arrays of one length n, t non-decreasing; columns [K, n] or None) for the planets
+        [(orbit_kind, has_mass)] under a celerite kernel of the term kinds `terms` (GP_REAL, GP_COMPLEX, GP_SHO). consts: a capi.OctoConsts."""
+        cols = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in (t, rv, sigma)]
+        n = cols[0].size
+        if any(c.size != n for c in cols):
+            raise ValueError("gp_set: the columns must have one length")
+        cm = np.zeros((0, n)) if columns is None else np.ascontiguousarray(columns, dtype=np.float64).reshape(-1, n)
+        K = int(cm.shape[0])
+        terms = [int(k) for k in terms]
+        kinds = (C.c_int32 * max(len(terms), 1))(*terms)
+        desc = (capi.OctoPlanetDesc * max(len(planets), 1))(*[capi.OctoPlanetDesc(int(k), int(bool(m))) for k, m in planets])
+        self._check(self.lib.octo_draws_gp_set(self._h, C.cast(desc, C.c_void_p), len(planets), None if consts is None else C.cast(C.pointer(consts), C.c_void_p),
+                                               *[capi._dptr(c) for c in cols], capi._dptr(cm if K else None), K, n, kinds, len(terms)))
+        self.gp_shape = (n, K, len(planets), sum(GP_N_HYPER[k] for k in terms), sum(GP_N_SLOTS[k] for k in terms))
+
+    def gp_clear(self):
+        """octo_draws_gp_clear"""
+        self._check(self.lib.octo_draws_gp_clear(self._h))
+        self.gp_shape = None
+
+    def gp_work_doubles(self, W, grad=True):
+        """octo_draws_gp_work_doubles of the table that is set"""
+        n, K, P, H, R = self.gp_shape
+        return int(self.lib.octo_draws_gp_work_doubles(n, R, P, int(W), int(bool(grad))))
+
+    def _gp_inputs(self, what, elems, hyper, beta):
+        n, K, P, H, R = self.gp_shape
+        _, W, ld = chain_matrix(elems, P * capi.N_EL, self.device, what, "elems")
+        for name, x, rows in (("hyper", hyper, H), ("beta", beta, K)):
+            if x is not None and rows:
+                _, Wx, ldx = chain_matrix(x, rows, self.device, what, name)
+                if Wx != W or (rows > 1 and W and ldx != ld):
+                    raise ValueError(f"{what}: {name} must have elems' width and row distance")
+        return W, ld
+
+    def gp_eval(self, elems, hyper, beta=None, jitter=None, grad=True, accumulate=False, out=None, stream=None):
+        """ℓ and its gradients of the W columns of elems (torch float64 [P·9, W] on the handle's device, rows contiguous; hyper [H, W] and beta [K, W]
+        with the same row distance, jitter [W] or None = 0): dict(ll [W], g_elems [P·9, W], g_hyper [H, W], g_beta [K, W], g_jitter [W]); the
+        gradients absent with grad=False. accumulate: ll and g_elems are ADDED into out["ll"] and out["g_elems"]. Asynchronous on `stream`."""
+        n, K, P, H, R = self.gp_shape
+        W, ld = self._gp_inputs("gp_eval", elems, hyper, beta)
+        out = dict(out or {})
+        if "ll" not in out:
+            if accumulate:
+                raise ValueError("gp_eval: accumulate needs out['ll']")
+            out["ll"] = self._out(W)
+        if grad:
+            out.setdefault("g_elems", self._out(W, P * capi.N_EL, ld))
+            out.setdefault("g_hyper", self._out(W, H, ld))
+            out.setdefault("g_jitter", self._out(W))
+            if K:
+                out.setdefault("g_beta", self._out(W, K, ld))
+        self._check(self.lib.octo_draws_gp_eval_device(self._h, elems.data_ptr(), ld, W, hyper.data_ptr(), ptr(beta) if K else None, ptr(jitter), out["ll"].data_ptr(),
+                                                       ptr(out.get("g_elems")), ptr(out.get("g_hyper")), ptr(out.get("g_beta")), ptr(out.get("g_jitter")),
+                                                       int(bool(accumulate)), self._stream(stream, self.device)))
+        self._keep = (elems, hyper, beta, jitter, out)
+        return out
+
+    def gp_eval_host(self, elems, hyper, beta=None, jitter=None, grad=True):
+        """octo_draws_gp_eval: the same on NumPy arrays (elems [P·9, W], hyper [H, W], beta [K, W], jitter [W]), blocking."""
+        n, K, P, H, R = self.gp_shape
+        elems = np.ascontiguousarray(elems, dtype=np.float64).reshape(P * capi.N_EL, -1)
+        W = elems.shape[1]
+        hyper = np.ascontiguousarray(hyper, dtype=np.float64).reshape(H, W)
+        beta = None if beta is None or not K else np.ascontiguousarray(beta, dtype=np.float64).reshape(K, W)
+        jitter = None if jitter is None else np.ascontiguousarray(jitter, dtype=np.float64).reshape(W)
+        out = dict(ll=np.empty(W))
+        if grad:
+            out.update(g_elems=np.empty((P * capi.N_EL, W)), g_hyper=np.empty((H, W)), g_jitter=np.empty(W))
+            if K:
+                out["g_beta"] = np.empty((K, W))
+        self._check(self.lib.octo_draws_gp_eval(self._h, capi._dptr(elems), W, W, capi._dptr(hyper), capi._dptr(beta), capi._dptr(jitter), capi._dptr(out["ll"]),
+                                                capi._dptr(out.get("g_elems")), capi._dptr(out.get("g_hyper")), capi._dptr(out.get("g_beta")),
+                                                capi._dptr(out.get("g_jitter"))))
+        return out
+
+    def gp_values(self, elems, hyper=None, beta=None, jitter=None, mean=False, stream=None):
+        """The model values η [n, W] at the W columns of elems (beta None: the planets alone); with mean=True (η, μ), μ [n, W] the process's conditional
+        mean at the table's epochs under hyper and jitter. Asynchronous on `stream`."""
+        n, K, P, H, R = self.gp_shape
+        W, ld = self._gp_inputs("gp_values", elems, hyper, beta)
+        if mean and hyper is None:
+            raise ValueError("gp_values: the conditional mean needs hyper")
+        eta = self._out(W, n)
+        mu = self._out(W, n) if mean else None
+        self._check(self.lib.octo_draws_gp_values_device(self._h, elems.data_ptr(), ld, W, ptr(hyper), ptr(beta) if K else None, ptr(jitter), eta.data_ptr(), ptr(mu),
+                                                         max(W, 1), self._stream(stream, self.device)))
+        self._keep = (elems, hyper, beta, jitter, eta, mu)
+        return (eta, mu) if mean else eta
+
+    def gp_bind(self, nodes):
+        """octo_draws_gp_bind: the table becomes a term of the handle's program. nodes: the program's node indices of the hyperparameters in term
+        order, of the β parameters in column order, and then of the jitter."""
+        from . import derived
+        bs = (derived.OctoDrawsBind * max(len(nodes), 1))(*[derived.OctoDrawsBind(derived.BIND_NODE, int(k), 0.0) for k in nodes])
+        self._check(self.lib.octo_draws_gp_bind(self._h, C.cast(bs, C.c_void_p), len(nodes)))
+
+    def gp_unbind(self):
+        """octo_draws_gp_unbind"""
+        self._check(self.lib.octo_draws_gp_unbind(self._h))
 
     def momentum(self, seed, step, n, inv_mass=None, chain0=0, stream=None):
         """The momenta p [D, n] of chains chain0 … chain0 + n − 1 at `step`: standard normals of the counter generator over √inv_mass."""

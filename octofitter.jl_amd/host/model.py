@@ -55,8 +55,9 @@ class LogDensityModel:
         has_derived = any(isinstance(v, derived.Derived) for b in blocks for v in b.values())
         self._scan = None      # (AlongScanAstromObs, its program nodes) of a system with along-scan absolute astrometry
         self._pma = None       # (CatalogueFitObs, its program nodes) of a system with a catalogue fit on refitted scans
+        self._gp = None        # (StarAbsoluteRVObs with a gaussian_process, its program nodes) of a system with a Gaussian-process RV table
         try:
-            if has_derived or fn.scan_obs or fn.pma_obs:      # a scan or catalogue table is a term of the expression program: such a model always has one
+            if has_derived or fn.scan_obs or fn.pma_obs or fn.gp_obs:      # a scan, catalogue or GP table is a term of the expression program: such a model always has one
                 if consts is not None:
                     raise NotImplementedError("a model with Derived variables, along-scan astrometry or a catalogue fit uses the library's default constants (octo_consts_default)")
                 self._build_program(system, fn, sysvars)
@@ -224,6 +225,26 @@ class LogDensityModel:
             if obs.mode == "sampled" and len(obs.gamma_variables) != obs.H.shape[1]:
                 raise KeyError(f"CatalogueFitObs {obs.name!r}: variables must name its {obs.H.shape[1]} γ parameters in column order")
             self._pma = (obs, [prog.node(ns[nm]) for nm in obs.gamma_variables])
+        if fn.gp_obs:
+            if len(fn.gp_obs) > 1:
+                raise NotImplementedError("one Gaussian-process RV observation a system: the draws handle holds one such table")
+            from . import gp
+            obs = fn.gp_obs[0]
+            ov, ns = obs.variables or {}, obs_ns[id(obs)]
+            obs.classify_trend(list(ov))
+            kernel = obs.gaussian_process(ns)      # traced again, on the model's own nodes: log-parameterised variables arrive as exp nodes
+            kernel = gp.Celerite(kernel) if isinstance(kernel, gp.Term) else kernel
+            if not isinstance(kernel, gp.Celerite) or kernel.kinds != obs.gp_terms:
+                raise NotImplementedError(f"StarAbsoluteRVObs {obs.name!r}: gaussian_process must return the same Celerite kernel for every θ_obs")
+            hyper = [prog.node(p) for p in kernel.params]
+            cols, beta = [], []
+            if "offset" in ov:
+                cols.append(np.ones(len(obs))); beta.append(prog.node(ns["offset"]))
+            if obs.trend_coef is not None:
+                cols.append(np.asarray(obs.trend_basis, dtype=np.float64)); beta.append(prog.node(ns[obs.trend_coef]))
+            obs.gp_columns = np.array(cols, dtype=np.float64).reshape(len(cols), len(obs))
+            jitter = prog.node(ns["jitter"]) if "jitter" in ov else const(0.0)[1]
+            self._gp = (obs, hyper + beta + [jitter])
         self.program, self._binds = prog, binds
         pr = (capi.OctoPrior * self.D)()
         for k, p in enumerate(self.priors):

@@ -168,10 +168,16 @@ class _RVBase(AbstractObs):
     nuisance_names = ("offset", "jitter")
 
     def __init__(self, observations, *, name, variables=None, trend_function=None, gaussian_process=None):
+        self.gaussian_process, self.gp_terms, self.gp_columns = None, None, None
         if gaussian_process is not None:
-            # The GP branch (rv-absolute.jl:205-315) is host-side Julia code and out of scope for the kernel; the Julia
-            # shim leaves such an observation on the reference's CPU path.
-            raise NotImplementedError("gaussian_process observations are not on the HIP path")
+            # The GP branch (rv-absolute.jl:205-315): a closure that returns a Celerite kernel (host/gp.py) is traced, and the observation becomes
+            # a term of the draws library's expression program (include/octofitter_hip_draws.h, "The nineteenth"). Anything else — None, an
+            # AbstractGPs-style object, a relative or marginalised RV — is not on the HIP path; the Julia shim leaves it on the reference's CPU path.
+            from . import gp
+            kernel = gp.probe(gaussian_process, list(variables or {})) if type(self) is StarAbsoluteRVObs and callable(gaussian_process) else None
+            if kernel is None:
+                raise NotImplementedError("gaussian_process observations are not on the HIP path")
+            self.gaussian_process, self.gp_terms = gaussian_process, kernel.kinds
         if trend_function is not None and not callable(trend_function):
             raise TypeError("trend_function must be callable: (θ_obs, epoch) -> m/s")
         # rv-absolute.jl:69, rv-relative.jl:64, rv-absolute-margin.jl:52: default (θ_obs, epoch) -> 0

@@ -89,7 +89,12 @@ class BatchedLnLike:
         if self.scan_obs and self.pma_obs:
             raise ValueError("a system with both a CatalogueFitObs and an AlongScanAstromObs is not on the device path: a draws handle binds one "
                              "table to its expression program (octo_draws_pma_bind, octo_draws_scan_bind)")
-        dataset_obs = [obs for obs in system.observations if not isinstance(obs, (AlongScanAstromObs, CatalogueFitObs))]
+        # … and an absolute-RV table under a Gaussian process (the nineteenth part)
+        self.gp_obs = [obs for obs in system.observations if getattr(obs, "gaussian_process", None) is not None]
+        if self.gp_obs and (self.scan_obs or self.pma_obs):
+            raise ValueError("a system with a Gaussian-process RV observation beside an AlongScanAstromObs or a CatalogueFitObs is not on the device path: "
+                             "a draws handle binds one table to its expression program")
+        dataset_obs = [obs for obs in system.observations if not isinstance(obs, (AlongScanAstromObs, CatalogueFitObs)) and obs not in self.gp_obs]
         for obs in dataset_obs:
             self.epoch_start_index_mapping[id(obs)] = j
             j += len(obs)
