@@ -1221,6 +1221,50 @@ int32_t octo_draws_gp_values_device(octo_draws* h, const double* d_elems, int64_
 int32_t octo_draws_gp_bind(octo_draws* h, const octo_draws_bind* binds, int32_t n_binds);
 int32_t octo_draws_gp_unbind(octo_draws* h);
 
+/* ---- The twentieth: the same table under DENSE kernels — the reference's StarAbsoluteRVObs with a gaussian_process that returns an AbstractGPs /
+ * KernelFunctions kernel, the quasi-periodic one of its RV tutorial first. No semiseparable form exists, so ℓ = log N(r; 0, K) comes from a dense
+ * Cholesky factor, O(n³) a walker, one workgroup a walker (csrc/draws/octo_draws_gpd.hip). No new entry point but the work formula: octo_draws_gp_set,
+ * _clear, _eval_device, _eval, _values_device, _bind and _unbind take a dense term list as they take a celerite one. The table, the model η, r, β, the
+ * planets' rule, accumulate and the binding (n_binds = H + K + 1, the hyperparameter nodes in term order) are the nineteenth part's, word for word.
+ *
+ * Terms      kinds from 16 up; a list holds 1 <= J <= OCTO_DRAWS_GP_MAX_TERMS of them (H <= 16) and is EITHER celerite (kinds 0 … 2) OR dense: a mixed
+ *            list is OCTO_EINVAL, and so is every other kind (3 … 15, 21 …). A celerite list takes the nineteenth part's kernels and keeps its bits.
+ *            With τ = |t_i − t_j| and the hyper rows in the order given:
+ *              OCTO_DRAWS_GP_SE             (a, ℓ)         k(τ) = a²·exp(−τ²/(2ℓ²))
+ *              OCTO_DRAWS_GP_MATERN32       (a, ℓ)         k(τ) = a²·(1 + u)·e^{−u},           u = √3·τ/ℓ
+ *              OCTO_DRAWS_GP_MATERN52       (a, ℓ)         k(τ) = a²·(1 + u + u²/3)·e^{−u},    u = √5·τ/ℓ
+ *              OCTO_DRAWS_GP_PERIODIC       (a, P, r)      k(τ) = a²·exp(−sin²(πτ/P)/(2r²))
+ *              OCTO_DRAWS_GP_QUASIPERIODIC  (a, ℓ, P, r)   k(τ) = a²·exp(−τ²/(2ℓ²) − sin²(πτ/P)/(2r²))
+ *            These are KernelFunctions.jl's SqExponentialKernel, Matern32Kernel, Matern52Kernel and PeriodicKernel(r = [r]) under ScaleTransform(1/ℓ)
+ *            and ScaleTransform(1/P), scaled by a²; the quasi-periodic one is the tutorial's η₁²·SqExponential(τ/η₂)·Periodic(τ/η₃; r = η₄). The formulas
+ *            are recalled, not pinned against the running reference.
+ * Function   K_ij = [i = j]·(σ_i² + s²) + Σ_terms k(|t_i − t_j|), K = L·Lᵀ, y = L⁻¹r, ℓ = −½·yᵀy − Σ_j log L_jj − (n/2)·log 2π, α = L⁻ᵀy = K⁻¹r.
+ * Gradient   ∂ℓ/∂η_i = α_i, through the nineteenth part's passes to elements and β. ∂ℓ/∂h = ½·Σ_ij (α_iα_j − K⁻¹_ij)·∂K_ij/∂h with the closed forms
+ *              ∂k/∂a = 2k/a (written 2a·…, so a = 0 is no division)    ∂k/∂ℓ = k·τ²/ℓ³ (SE, QP) · a²·u²·e^{−u}/ℓ (M32) · a²·u²(1 + u)·e^{−u}/(3ℓ) (M52)
+ *              ∂k/∂P = k·sin(πτ/P)·cos(πτ/P)·πτ/(P²r²)                  ∂k/∂r = k·sin²(πτ/P)/r³
+ *            and ∂ℓ/∂s = s·(Σ α_i² − tr K⁻¹). K⁻¹ is formed in place of L (the inverse of L, then its product with its transpose); no finite difference.
+ * Invalid    what the nineteenth part calls invalid in elements, β and s; a non-finite hyperparameter; ℓ, P or r <= 0; a non-finite a²; a pivot K_jj −
+ *            Σ L_jm² that is not > 0 and finite: ℓ = −Inf and a zero gradient for that walker; never a status, never another walker's bits.
+ * Order      right-looking: column j is scaled, then the trailing triangle takes its rank-1 update, so every element receives its updates in column
+ *            order whatever thread makes them; y is the factorisation's row n. Every dot product of the inverse is one thread's, in index order; the
+ *            contraction gives each thread a fixed set of pairs and adds the threads' partials by a fixed tree (in a wave, then the four waves in wave
+ *            order). No atomics: a walker's bits depend on its own column alone, in any batch, with any ld, at any block index.
+ * Sizes      a table of n <= OCTO_DRAWS_GP_DENSE_LDS_ROWS rows keeps the packed lower triangle, n(n + 1)/2 doubles, and four vectors of n in the
+ *            workgroup's LDS (8·(n(n + 1)/2 + 4n + 128) bytes: 155 392 at 192 rows, of the 163 840 a workgroup of this device may hold; octo_draws_gp_set
+ *            answers OCTO_ENOTSUP on a device that gives less). A longer one, up to OCTO_DRAWS_GP_DENSE_MAX_N rows, runs the same kernel bodies on
+ *            triangles in the work array: a functional fallback, O(n³) traffic through L2 / HBM, unblocked. More rows: OCTO_EINVAL. */
+#define OCTO_DRAWS_GP_SE 16
+#define OCTO_DRAWS_GP_MATERN32 17
+#define OCTO_DRAWS_GP_MATERN52 18
+#define OCTO_DRAWS_GP_PERIODIC 19
+#define OCTO_DRAWS_GP_QUASIPERIODIC 20
+#define OCTO_DRAWS_GP_DENSE_LDS_ROWS 192
+#define OCTO_DRAWS_GP_DENSE_MAX_N 2048
+/* The doubles of the handle's work array that one evaluation of W walkers of a dense table needs (−1: an argument out of range; n > DENSE_MAX_N too):
+ *   ldw·(n + 1 + [grad]·⌈n/OCTO_DRAWS_SCAN_ROWS⌉·(4 + 6·n_planets)) + [n > OCTO_DRAWS_GP_DENSE_LDS_ROWS]·W·n(n + 1)/2
+ * ldw = W rounded up to whole waves. The residuals (then α) and the validity; with a gradient the row tasks' sums; the triangles of a long table. */
+int64_t octo_draws_gp_dense_work_doubles(int64_t n, int32_t n_planets, int64_t W, int32_t grad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ from .host import derived  # noqa: F401,E402
 from .host.derived import Derived  # noqa: F401,E402
 from .host import gp  # noqa: F401,E402
 from .host.gp import RealTerm, ComplexTerm, SHOTerm, Celerite  # noqa: F401,E402
+from .host.gp import SqExpTerm, Matern32Term, Matern52Term, PeriodicTerm, QuasiPeriodicTerm, DenseKernel, GP  # noqa: F401,E402
 from .host.model import LogDensityModel  # noqa: F401,E402
 from .host.callers import (guess_starting_position, octofit_rejection, rejection_evaluate_likelihoods, pointwise_like,  # noqa: F401,E402
                            guess_starting_position_device, octofit_rejection_device, simulate_tables, posterior_predictive,

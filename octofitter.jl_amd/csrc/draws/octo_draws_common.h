@@ -396,6 +396,7 @@ struct octo_draws : CompanionBase {
     // descriptors and constants, the work array, the device side of the host-buffer twin, and the binding to the expression program as for the scan table.
     double* d_gp_rows = nullptr; int64_t cap_gp_rows = 0;
     int32_t gp_n = 0, gp_K = 0, gp_P = 0, gp_J = 0, gp_R = 0, gp_RP = 0, gp_H = 0;
+    int32_t gp_dense = 0;      // the terms are dense kinds (octo_draws_gpd.hip: a workgroup a walker); R = RP = 0 and gp_slot is not read
     int32_t gp_term[OCTO_DRAWS_GP_MAX_TERMS] = {}, gp_slot[OCTO_DRAWS_GP_MAX_SLOTS] = {};
     int32_t gp_kind[OCTO_MAX_PLANETS] = {}, gp_mass[OCTO_MAX_PLANETS] = {};
     octo_consts gp_consts = {};

@@ -16,36 +16,18 @@
 //   k_gp_adj         the grid of k_gp_rows: Σ α_i c_i[k], and per planet a second cold solve and the six sums of rv_row against ∂ℓ/∂η_i = α_i.
 //   k_gp_finish      the tasks' sums in task order and planet_finish per planet: ∂ℓ/∂(a, e, i, ω, Ω, tp, M, plx, mass), and ∂ℓ/∂β.
 // No atomics, and neither the row partition nor the segments depend on W: a walker's bits depend on its column alone.
-#include "octo_draws_common.h"
-
-namespace gp_dev {      // the companions' device routines under a name of their own: that header and octo_draws_common.h both define a wave_sum
-#include "octo_companion_device.h"
-}
+// A table under DENSE kernels (the twentieth part) keeps this unit's table, C ABI, k_gp_rows, k_gp_adj and k_gp_finish and puts octo_draws_gpd.hip's kernels
+// between them (gp_launch); the argument block GpArgs and the row record are in octo_draws_gp_shared.h.
+#include "octo_draws_gp_shared.h"
 
 namespace {
 using gp_dev::dev_consts;
 using gp_dev::walker_setup;
 
-constexpr int GP_ROWS = OCTO_DRAWS_SCAN_ROWS, GP_K = OCTO_DRAWS_GP_MAX_K, GP_J = OCTO_DRAWS_GP_MAX_TERMS, GP_S = OCTO_DRAWS_GP_MAX_SLOTS, GP_G = OCTO_DRAWS_GP_SEGMENT;
-constexpr int GROWW = 8;                       // a row record: {t, rv, σ², c[4] (0 behind K), 0}
-constexpr int GP_PL = 6;                       // a planet's sums in the work array: GE, GM, GT, GC, GK, GW
 using FinL = Layout<2, true, false, KM_RVABS>;      // the main library's sums of a planet under an absolute-RV table: U1 … U6 (0 here), GE, GM, GT, GC, GK, GW
 static_assert(FinL::PL_N == 12 && FinL::GE == 6 && FinL::GW == 11, "six RV sums behind the six astrometric ones");
 enum { SLOT_REAL = 0, SLOT_FIRST, SLOT_SECOND, SLOT_PAD };      // a slot's role: wave-uniform
 enum { CO_A = 0, CO_B, CO_C, CO_D, CO_ROT, N_CO };             // a slot's coefficients in LDS, [N_CO][R'][64]
-
-struct GpArgs {
-    const double* rows;            // [n][GROWW]
-    int32_t n, K, P, J, H, accumulate, n_tasks, n_sums, n_seg;
-    int32_t term[GP_J], slot[GP_S];
-    int32_t orbit_kind[MAXP], has_mass[MAXP];
-    DevConsts c;
-    const double* elems; int64_t ld, W, ldw;
-    const double *hyper, *beta, *jitter;      // [H][ld], [K][ld] or null, [W] or null
-    GpWork k;
-    double *ll, *g_elems, *g_hyper, *g_beta, *g_jitter;
-    double *eta, *mu; int64_t ld_out;
-};
 
 __device__ __forceinline__ bool gp_contributes(const GpArgs& a, int p) {      // wave-uniform
     const int kind = a.orbit_kind[p];
@@ -607,14 +589,22 @@ int gp_launch(octo_draws* h, hipStream_t st, const double* d_elems, int64_t ld, 
     GpArgs a = gp_args(h, d_elems, ld, W, ldw);
     const bool grad = d_g_elems || d_g_hyper || d_g_beta || d_g_jitter, back = grad || d_mu, seq = d_ll || back;
     const int RP = h->gp_RP;
-    if (int rc = grow_to(h, h->d_gp, h->cap_gp, a.k, gp_work, (int64_t)a.n, (int64_t)(RP * (RP + 1) / 2 + RP), (int64_t)a.n_seg, (int64_t)GP_G, (int64_t)a.n_tasks,
-                         (int64_t)a.n_sums, ldw, (int64_t)back)) return rc;
+    if (h->gp_dense) {      // no checkpoints and no states; the triangles of a long table
+        GpdWork d;
+        if (int rc = grow_to(h, h->d_gp, h->cap_gp, d, gpd_work, (int64_t)a.n, (int64_t)a.n_tasks, (int64_t)a.n_sums, ldw, W,
+                             (int64_t)(a.n > OCTO_DRAWS_GP_DENSE_LDS_ROWS), (int64_t)grad)) return rc;
+        a.k = GpWork{d.res, d.ok, nullptr, nullptr, d.part};
+        a.tri = d.tri;
+    } else if (int rc = grow_to(h, h->d_gp, h->cap_gp, a.k, gp_work, (int64_t)a.n, (int64_t)(RP * (RP + 1) / 2 + RP), (int64_t)a.n_seg, (int64_t)GP_G, (int64_t)a.n_tasks,
+                                (int64_t)a.n_sums, ldw, (int64_t)back)) return rc;
     a.hyper = d_hyper; a.beta = d_beta; a.jitter = d_jitter; a.accumulate = accumulate;
     a.ll = d_ll; a.g_elems = d_g_elems; a.g_hyper = d_g_hyper; a.g_beta = d_g_beta; a.g_jitter = d_g_jitter;
     a.eta = d_eta; a.mu = d_mu; a.ld_out = ld_out;
     const dim3 grid((unsigned)(ldw / WAVE), (unsigned)a.n_tasks), tiles((unsigned)(ldw / WAVE)), block(WAVE);
     hipLaunchKernelGGL(k_gp_rows, grid, block, 0, st, a);
-    if (seq) {
+    if (h->gp_dense) {
+        if (int rc = draws_gpd_launch(h, st, &a, d_ll != nullptr, back)) return rc;
+    } else if (seq) {
         if (RP == 2) gp_sequential<2>(a, st, true, back, back);
         else if (RP == 4) gp_sequential<4>(a, st, true, back, back);
         else gp_sequential<8>(a, st, true, back, back);
@@ -642,7 +632,7 @@ extern "C" {
 int32_t octo_draws_gp_clear(octo_draws* h) {
     if (!h) return OCTO_EINVAL;
     gp_drop_binding(h);
-    h->gp_n = 0; h->gp_K = 0; h->gp_P = 0; h->gp_J = 0; h->gp_R = 0; h->gp_RP = 0; h->gp_H = 0;
+    h->gp_n = 0; h->gp_K = 0; h->gp_P = 0; h->gp_J = 0; h->gp_R = 0; h->gp_RP = 0; h->gp_H = 0; h->gp_dense = 0;
     return OCTO_OK;
 }
 
@@ -660,15 +650,19 @@ int32_t octo_draws_gp_set(octo_draws* h, const octo_planet_desc* planets, int32_
         if (kind != OCTO_ORBIT_VISUAL_KEP && kind != OCTO_ORBIT_RADVEL && kind != OCTO_ORBIT_THIELE_INNES && kind != OCTO_ORBIT_KEP)
             return fail(h, OCTO_EINVAL, who + "planet " + std::to_string(p) + ": unknown orbit kind " + std::to_string(kind));
     }
-    int32_t slot[GP_S], R = 0, H = 0;
+    int32_t slot[GP_S], R = 0, H = 0, n_dense = 0;
     for (int j = 0; j < n_terms; ++j) {
         const int kind = term_kinds[j];
+        if (gp_dense_kind(kind)) { ++n_dense; H += gp_dense_n_hyper(kind); continue; }      // the twentieth part: no slots
         if (kind != OCTO_DRAWS_GP_REAL && kind != OCTO_DRAWS_GP_COMPLEX && kind != OCTO_DRAWS_GP_SHO)
             return fail(h, OCTO_EINVAL, who + "term " + std::to_string(j) + ": unknown kind " + std::to_string(kind));
         if (kind == OCTO_DRAWS_GP_REAL) { slot[R++] = SLOT_REAL; H += 2; }
         else { slot[R++] = SLOT_FIRST; slot[R++] = SLOT_SECOND; H += kind == OCTO_DRAWS_GP_COMPLEX ? 4 : 3; }      // R <= 2·GP_J = GP_S
     }
     static_assert(2 * GP_J <= GP_S, "every term list fits the slots");
+    if (n_dense != 0 && n_dense != n_terms) return fail(h, OCTO_EINVAL, who + "a term list is celerite kinds alone or dense kinds alone");
+    const bool dense = n_dense != 0;
+    if (dense && n > OCTO_DRAWS_GP_DENSE_MAX_N) return fail(h, OCTO_EINVAL, who + "a dense term list needs n <= OCTO_DRAWS_GP_DENSE_MAX_N rows");
     for (int r = R; r < GP_S; ++r) slot[r] = SLOT_PAD;
     std::vector<double> rows((size_t)n * GROWW, 0.0);
     for (int64_t r = 0; r < n; ++r) {
@@ -688,7 +682,9 @@ int32_t octo_draws_gp_set(octo_draws* h, const octo_planet_desc* planets, int32_
     if (consts) cst = *consts;
     else if (octo_consts_default(&cst) != OCTO_OK) return fail(h, OCTO_EINVAL, who + "octo_consts_default failed");
     OCHK(h, hipSetDevice(h->device));
-    if (gp_padded(R) == 8 && hipFuncSetAttribute((const void*)k_gp_back<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gp_back_lds<8>()) != hipSuccess) {
+    if (dense) {
+        if (int rc = draws_gpd_prepare(h, n)) return rc;
+    } else if (gp_padded(R) == 8 && hipFuncSetAttribute((const void*)k_gp_back<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gp_back_lds<8>()) != hipSuccess) {
         (void)hipGetLastError();      // beyond the default limit of dynamic LDS: raised for the one kernel that needs it
         return fail(h, OCTO_ENOTSUP, who + "eight slots need more LDS per block than this device gives");
     }
@@ -696,7 +692,8 @@ int32_t octo_draws_gp_set(octo_draws* h, const octo_planet_desc* planets, int32_
     if (int rc = grow(h, h->d_gp_rows, h->cap_gp_rows, (int64_t)rows.size())) return rc;
     OCHK(h, hipStreamSynchronize(h->stream));
     OCHK(h, hipMemcpy(h->d_gp_rows, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
-    h->gp_n = (int32_t)n; h->gp_K = K; h->gp_P = n_planets; h->gp_J = n_terms; h->gp_R = R; h->gp_RP = gp_padded(R); h->gp_H = H; h->gp_consts = cst;
+    h->gp_n = (int32_t)n; h->gp_K = K; h->gp_P = n_planets; h->gp_J = n_terms; h->gp_R = R; h->gp_RP = dense ? 0 : gp_padded(R); h->gp_H = H; h->gp_consts = cst;
+    h->gp_dense = dense ? 1 : 0;
     for (int j = 0; j < n_terms; ++j) h->gp_term[j] = term_kinds[j];
     for (int r = 0; r < GP_S; ++r) h->gp_slot[r] = slot[r];
     for (int p = 0; p < n_planets; ++p) { h->gp_kind[p] = planets[p].orbit_kind; h->gp_mass[p] = planets[p].has_mass ? 1 : 0; }
@@ -707,6 +704,13 @@ int64_t octo_draws_gp_work_doubles(int64_t n, int32_t n_slots, int32_t n_planets
     if (n < 1 || n > 65536 || n_slots < 1 || n_slots > GP_S || n_planets < 1 || n_planets > OCTO_MAX_PLANETS || W < 0 || W > MAX_CHAINS) return -1;
     const int64_t RP = gp_padded(n_slots), ldw = (W + WAVE - 1) / WAVE * WAVE;
     return carve_size(gp_work, n, RP * (RP + 1) / 2 + RP, (n + GP_G - 1) / GP_G, (int64_t)GP_G, (n + GP_ROWS - 1) / GP_ROWS, (int64_t)(GP_K + GP_PL * n_planets), ldw,
+                      (int64_t)(grad ? 1 : 0));
+}
+
+int64_t octo_draws_gp_dense_work_doubles(int64_t n, int32_t n_planets, int64_t W, int32_t grad) {
+    if (n < 1 || n > OCTO_DRAWS_GP_DENSE_MAX_N || n_planets < 1 || n_planets > OCTO_MAX_PLANETS || W < 0 || W > MAX_CHAINS) return -1;
+    const int64_t ldw = (W + WAVE - 1) / WAVE * WAVE;
+    return carve_size(gpd_work, n, (n + GP_ROWS - 1) / GP_ROWS, (int64_t)(GP_K + GP_PL * n_planets), ldw, W, (int64_t)(n > OCTO_DRAWS_GP_DENSE_LDS_ROWS),
                       (int64_t)(grad ? 1 : 0));
 }
 

@@ -277,6 +277,19 @@ inline GpWork gp_work(Carve& c, int64_t n, int64_t n_state, int64_t n_seg, int64
     return {c.take(n * ldw), c.take(ldw), c.take(grad ? n_seg * n_state * ldw : 0), c.take(grad ? segment * n_state * ldw : 0), c.take(grad ? n_tasks * n_sums * ldw : 0)};
 }
 
+// … with dense kernels (octo_draws_gpd.hip), on d_gp as well: (n + 1 + [grad]·n_tasks·n_sums)·ldw + [global]·W·n(n+1)/2. The residuals (then α), the validity and
+// the row tasks' sums as above; no checkpoints, no states. A table of more than OCTO_DRAWS_GP_DENSE_LDS_ROWS rows (global) keeps every walker's packed lower
+// triangle here, walker-major; a shorter one keeps it in the workgroup's LDS.
+struct GpdWork {
+    double* res;        // [n][ldw]
+    double* ok;         // [ldw]
+    double* part;       // [n_tasks][n_sums][ldw]
+    double* tri;        // [W][n(n+1)/2]
+};
+inline GpdWork gpd_work(Carve& c, int64_t n, int64_t n_tasks, int64_t n_sums, int64_t ldw, int64_t W, int64_t global, int64_t grad) {
+    return {c.take(n * ldw), c.take(ldw), c.take(grad ? n_tasks * n_sums * ldw : 0), c.take(global ? W * (n * (n + 1) / 2) : 0)};
+}
+
 // The device side of octo_draws_gp_eval, d_gp_hst: (2·P·9 + 2·H + 2·K + 3)·ld
 struct GpStaging {
     double *elems, *g_elems;       // [P·9][ld]

@@ -92,6 +92,11 @@ GP_SEGMENT = 16                    # OCTO_DRAWS_GP_SEGMENT: rows between two che
 GP_REAL, GP_COMPLEX, GP_SHO = 0, 1, 2
 GP_N_HYPER = {GP_REAL: 2, GP_COMPLEX: 4, GP_SHO: 3}
 GP_N_SLOTS = {GP_REAL: 1, GP_COMPLEX: 2, GP_SHO: 2}
+# the dense kinds (include/octofitter_hip_draws.h, "The twentieth"): a term list is celerite kinds alone or dense kinds alone
+GP_SE, GP_MATERN32, GP_MATERN52, GP_PERIODIC, GP_QUASIPERIODIC = 16, 17, 18, 19, 20
+GP_DENSE_N_HYPER = {GP_SE: 2, GP_MATERN32: 2, GP_MATERN52: 2, GP_PERIODIC: 3, GP_QUASIPERIODIC: 4}      # (a, ℓ) · (a, ℓ) · (a, ℓ) · (a, P, r) · (a, ℓ, P, r)
+GP_DENSE_LDS_ROWS = 192            # OCTO_DRAWS_GP_DENSE_LDS_ROWS: the longest dense table whose triangle a workgroup keeps in LDS
+GP_DENSE_MAX_N = 2048              # OCTO_DRAWS_GP_DENSE_MAX_N
 OFTI_OUTPUTS = ("A", "B", "F", "G", "A_mean", "B_mean", "F_mean", "G_mean", "alpha", "a_ti", "i", "ω", "Ω", "P_d", "M_dyn", "logml")      # the rows of d_out, in order
 DIAG_RHAT, DIAG_ESS_BULK, DIAG_ESS_TAIL, DIAG_RHAT_BASIC, DIAG_ESS_BASIC, DIAG_Q05, DIAG_Q50, DIAG_Q95, DIAG_N_STATS = range(9)      # OCTO_DRAWS_DIAG_*
 PT_ACC_COLUMNS = ("n", "A", "n_f", "m_f", "s_f", "n_b", "m_b", "s_b")      # the columns of d_acc [T − 1][8]
@@ -190,6 +195,7 @@ _SIGS = {
     "octo_draws_gp_set": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + [capi.c_double_p] * 4 + [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32]),
     "octo_draws_gp_clear": (C.c_int32, [C.c_void_p]),
     "octo_draws_gp_work_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "octo_draws_gp_dense_work_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
     "octo_draws_gp_eval_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 8 + [C.c_int32, C.c_void_p]),
     "octo_draws_gp_eval": (C.c_int32, [C.c_void_p, capi.c_double_p, C.c_int64, C.c_int64] + [capi.c_double_p] * 8),
     "octo_draws_gp_values_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
@@ -373,7 +379,8 @@ class PriorDraws(companion.Handle):
         self._created(self.lib.octo_draws_create(ctx, m, self._c_priors, self.D, self.device_index, C.byref(self._h)))
         self.scan_shape = None      # (n, K, P) of the scan table while one is set
         self.pma_shape = None       # (n, Q, K, P) of the catalogue table while one is set
-        self.gp_shape = None        # (n, K, P, H, R) of the Gaussian-process RV table while one is set
+        self.gp_shape = None        # (n, K, P, H, R) of the Gaussian-process RV table while one is set; R = 0 under dense kernels
+        self.gp_dense = False       # its terms are dense kinds
         if program is not None:
             self.program_set(*program)
             scan = getattr(model, "_scan", None)
@@ -742,7 +749,8 @@ class PriorDraws(companion.Handle):
     # ---- the Gaussian-process RV term (include/octofitter_hip_draws.h, "The nineteenth"): any handle; the binding needs a program
     def gp_set(self, planets, t, rv, sigma, columns=None, terms=(GP_SHO,), consts=None):
         """octo_draws_gp_set: the RV table (host arrays of one length n, t non-decreasing; columns [K, n] or None) for the planets
-        [(orbit_kind, has_mass)] under a celerite kernel of the term kinds `terms` (GP_REAL, GP_COMPLEX, GP_SHO). consts: a capi.OctoConsts."""
+        [(orbit_kind, has_mass)] under a celerite kernel of the term kinds `terms` (GP_REAL, GP_COMPLEX, GP_SHO) or a dense one (GP_SE, GP_MATERN32,
+        GP_MATERN52, GP_PERIODIC, GP_QUASIPERIODIC; n <= GP_DENSE_MAX_N), never both. consts: a capi.OctoConsts."""
         cols = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in (t, rv, sigma)]
         n = cols[0].size
         if any(c.size != n for c in cols):
@@ -754,16 +762,20 @@ class PriorDraws(companion.Handle):
         desc = (capi.OctoPlanetDesc * max(len(planets), 1))(*[capi.OctoPlanetDesc(int(k), int(bool(m))) for k, m in planets])
         self._check(self.lib.octo_draws_gp_set(self._h, C.cast(desc, C.c_void_p), len(planets), None if consts is None else C.cast(C.pointer(consts), C.c_void_p),
                                                *[capi._dptr(c) for c in cols], capi._dptr(cm if K else None), K, n, kinds, len(terms)))
-        self.gp_shape = (n, K, len(planets), sum(GP_N_HYPER[k] for k in terms), sum(GP_N_SLOTS[k] for k in terms))
+        self.gp_dense = bool(terms) and all(k in GP_DENSE_N_HYPER for k in terms)      # the library refused a mixed list
+        self.gp_shape = (n, K, len(planets), sum(GP_DENSE_N_HYPER[k] if self.gp_dense else GP_N_HYPER[k] for k in terms),
+                         0 if self.gp_dense else sum(GP_N_SLOTS[k] for k in terms))
 
     def gp_clear(self):
         """octo_draws_gp_clear"""
         self._check(self.lib.octo_draws_gp_clear(self._h))
-        self.gp_shape = None
+        self.gp_shape, self.gp_dense = None, False
 
     def gp_work_doubles(self, W, grad=True):
         """octo_draws_gp_work_doubles of the table that is set"""
         n, K, P, H, R = self.gp_shape
+        if self.gp_dense:
+            return int(self.lib.octo_draws_gp_dense_work_doubles(n, P, int(W), int(bool(grad))))
         return int(self.lib.octo_draws_gp_work_doubles(n, R, P, int(W), int(bool(grad))))
 
     def _gp_inputs(self, what, elems, hyper, beta):

@@ -87,8 +87,114 @@ class Celerite:
         return [p for t in self.terms for p in t.params]
 
 
+# ---- dense kernels (include/octofitter_hip_draws.h, "The twentieth"): the reference's AbstractGPs / KernelFunctions kernels, no semiseparable form
+#
+#     gaussian_process=lambda θ: GP(QuasiPeriodicTerm(a=derived.exp(θ.log_η1), l=θ.η2, P=θ.η3, r=θ.η4))
+#
+# mirrors `θ_obs -> GP(θ_obs.η₁^2 * (SqExponentialKernel() ∘ ScaleTransform(1/θ_obs.η₂)) * (PeriodicKernel(r=[θ_obs.η₄]) ∘ ScaleTransform(1/θ_obs.η₃)))`.
+SE, MATERN32, MATERN52, PERIODIC, QUASIPERIODIC = 16, 17, 18, 19, 20      # OCTO_DRAWS_GP_SE … _QUASIPERIODIC
+
+
+class DenseTerm:
+    kind = None
+    names = ()
+
+    def __init__(self, *params):
+        if len(params) != len(self.names):
+            raise TypeError(f"{type(self).__name__} takes {', '.join(self.names)}")
+        self.params = tuple(derived.Sym.of(p) for p in params)
+
+    def __add__(self, other):
+        return DenseKernel(self) + other
+
+    __radd__ = lambda self, other: DenseKernel(other) + self
+
+
+class SqExpTerm(DenseTerm):
+    """k(τ) = a²·exp(−τ²/(2l²))"""
+    kind, names = SE, ("a", "l")
+
+    def __init__(self, a, l):
+        super().__init__(a, l)
+
+
+class Matern32Term(DenseTerm):
+    """k(τ) = a²·(1 + u)·exp(−u), u = √3·τ/l"""
+    kind, names = MATERN32, ("a", "l")
+
+    def __init__(self, a, l):
+        super().__init__(a, l)
+
+
+class Matern52Term(DenseTerm):
+    """k(τ) = a²·(1 + u + u²/3)·exp(−u), u = √5·τ/l"""
+    kind, names = MATERN52, ("a", "l")
+
+    def __init__(self, a, l):
+        super().__init__(a, l)
+
+
+class PeriodicTerm(DenseTerm):
+    """k(τ) = a²·exp(−sin²(πτ/P)/(2r²))"""
+    kind, names = PERIODIC, ("a", "P", "r")
+
+    def __init__(self, a, P, r):
+        super().__init__(a, P, r)
+
+
+class QuasiPeriodicTerm(DenseTerm):
+    """k(τ) = a²·exp(−τ²/(2l²) − sin²(πτ/P)/(2r²)): the reference's RV tutorial kernel for an active star"""
+    kind, names = QUASIPERIODIC, ("a", "l", "P", "r")
+
+    def __init__(self, a, l, P, r):
+        super().__init__(a, l, P, r)
+
+
+class DenseKernel:
+    """A sum of dense terms. A celerite term does not add to it: the device factors one kind of kernel a table."""
+
+    def __init__(self, *terms):
+        flat = []
+        for t in terms:
+            if isinstance(t, DenseKernel):
+                flat += t.terms
+            elif isinstance(t, DenseTerm):
+                flat.append(t)
+            else:
+                raise TypeError(f"a dense kernel is a sum of SqExpTerm, Matern32Term, Matern52Term, PeriodicTerm and QuasiPeriodicTerm, not {type(t).__name__}")
+        if not flat:
+            raise TypeError("a dense kernel needs at least one term")
+        self.terms = flat
+
+    def __add__(self, other):
+        return DenseKernel(self, other)
+
+    __radd__ = lambda self, other: DenseKernel(other, self)
+
+    kinds = Celerite.kinds
+    params = Celerite.params
+
+
+def as_kernel(x):
+    """x as a Celerite or a DenseKernel (a single term becomes a sum of one), or None"""
+    if isinstance(x, Term):
+        return Celerite(x)
+    if isinstance(x, DenseTerm):
+        return DenseKernel(x)
+    return x if isinstance(x, (Celerite, DenseKernel)) else None
+
+
+def GP(kernel):
+    """Pass-through, so that a closure reads as the reference's `GP(kernel)` does."""
+    k = as_kernel(kernel)
+    if k is None:
+        raise TypeError(f"GP takes a kernel of this module, not {type(kernel).__name__}")
+    return k
+
+
 def probe(closure, names):
-    """The kernel `closure` returns for symbolic θ_obs with the variables `names`, or None when it is not a Celerite kernel (or cannot be traced)."""
+    """The kernel `closure` returns for symbolic θ_obs with the variables `names` — a Celerite or a DenseKernel — or None when it is neither (or cannot
+    be traced)."""
     ns = derived.Namespace("θ_obs")
     for k, name in enumerate(names):
         ns._set(name, derived.theta(k))
@@ -96,6 +202,4 @@ def probe(closure, names):
         kernel = closure(ns)
     except (TypeError, AttributeError):
         return None
-    if isinstance(kernel, Term):
-        kernel = Celerite(kernel)
-    return kernel if isinstance(kernel, Celerite) else None
+    return as_kernel(kernel)

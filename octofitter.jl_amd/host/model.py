@@ -233,9 +233,9 @@ class LogDensityModel:
             ov, ns = obs.variables or {}, obs_ns[id(obs)]
             obs.classify_trend(list(ov))
             kernel = obs.gaussian_process(ns)      # traced again, on the model's own nodes: log-parameterised variables arrive as exp nodes
-            kernel = gp.Celerite(kernel) if isinstance(kernel, gp.Term) else kernel
-            if not isinstance(kernel, gp.Celerite) or kernel.kinds != obs.gp_terms:
-                raise NotImplementedError(f"StarAbsoluteRVObs {obs.name!r}: gaussian_process must return the same Celerite kernel for every θ_obs")
+            kernel = gp.as_kernel(kernel)      # a Celerite or a DenseKernel
+            if kernel is None or kernel.kinds != obs.gp_terms:
+                raise NotImplementedError(f"StarAbsoluteRVObs {obs.name!r}: gaussian_process must return the same kernel for every θ_obs")
             hyper = [prog.node(p) for p in kernel.params]
             cols, beta = [], []
             if "offset" in ov:

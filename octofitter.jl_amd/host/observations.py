@@ -170,9 +170,10 @@ class _RVBase(AbstractObs):
     def __init__(self, observations, *, name, variables=None, trend_function=None, gaussian_process=None):
         self.gaussian_process, self.gp_terms, self.gp_columns = None, None, None
         if gaussian_process is not None:
-            # The GP branch (rv-absolute.jl:205-315): a closure that returns a Celerite kernel (host/gp.py) is traced, and the observation becomes
-            # a term of the draws library's expression program (include/octofitter_hip_draws.h, "The nineteenth"). Anything else — None, an
-            # AbstractGPs-style object, a relative or marginalised RV — is not on the HIP path; the Julia shim leaves it on the reference's CPU path.
+            # The GP branch (rv-absolute.jl:205-315): a closure that returns a Celerite kernel or a dense one (host/gp.py: GP(QuasiPeriodicTerm(…)))
+            # is traced, and the observation becomes a term of the draws library's expression program (include/octofitter_hip_draws.h, "The
+            # nineteenth" and "The twentieth"). Anything else — None, an object of another package, a relative or marginalised RV — is not on the
+            # HIP path; the Julia shim leaves it on the reference's CPU path.
             from . import gp
             kernel = gp.probe(gaussian_process, list(variables or {})) if type(self) is StarAbsoluteRVObs and callable(gaussian_process) else None
             if kernel is None:

@@ -13,6 +13,14 @@ profiles/gp_throughput.txt.
                    alone costs.
   what it replaces the float64 NumPy recursion and reverse pass of tests/gp_reference.py on the host, once, at W = 64 (and n <= 1 000: it is O(n·R²·W)
                    interpreted row by row).
+    python tools/gp_bench.py --dense --resources    # no GPU: the k_gpd_* kernels -> profiles/gp_dense_kernel_resources.txt
+    timeout -k 10 300 python tools/gp_bench.py --dense --rows 50,192,193 && timeout -k 10 300 python tools/gp_bench.py --dense --rows 500 --append \
+        && timeout -k 10 600 python tools/gp_bench.py --dense --rows 1000 --append
+
+  --dense          the dense kernels (csrc/draws/octo_draws_gpd.hip) -> profiles/gp_dense_throughput.txt: one quasi-periodic term on n = 50 / LDS_ROWS / LDS_ROWS + 1 /
+                   500 / 1 000 rows, W = 64 and 1 024, forward and forward + gradient; beside each the same rows under a celerite SHO on the device, and
+                   numpy.linalg.cholesky on the [W, n, n] stack on the host (what a caller does today; skipped where the stack exceeds 2 GB). Each step is a
+                   process of its own under its own time limit, chained with &&, as above.
 The header records the hashes of the sources the figures belong to, and the kernels' registers and LDS as --resources wrote them. No figure is a pass
 condition.
 """
@@ -90,12 +98,112 @@ def bench(pkg, reps, lines):
                 fn.close()
 
 
+DENSE_RESOURCES = ROOT / "profiles" / "gp_dense_kernel_resources.txt"
+DENSE_OUT = ROOT / "profiles" / "gp_dense_throughput.txt"
+DENSE_SIZES = (64, 1024)
+HOST_STACK_LIMIT = 2e9      # bytes of the [W, n, n] stack beyond which the host's Cholesky is skipped
+
+
+def write_dense_resources():
+    import draws_build
+    built = draws_build.kernels()
+    lines = ["k_gpd_* of liboctofitter_hip_draws.so as built for gfx950: VGPRs (AGPRs) · static LDS bytes (the triangle and the vectors are dynamic: "
+             "8·(n(n + 1)/2 + 4n + 128) with the triangle in LDS, 8·(4n + 128) with it in the work array) · code bytes",
+             "OCTO_DRAWS_GP_DENSE_LDS_ROWS = 192: 155 392 bytes of the 163 840 a workgroup may hold"]
+    for family in sorted(k for k in built if k.startswith("k_gpd_")):
+        for r in built[family]:
+            lines.append(f"  {r['name'].replace('void ', ''):40s} {r['vgpr_count']:4d} ({r['agpr_count']}) · {r['group_segment_fixed_size']:6d} · {r['code_bytes']:6d}"
+                         f" · spills {r['vgpr_spill_count']} · scratch instructions {r['scratch_instructions']}")
+    DENSE_RESOURCES.write_text("\n".join(lines) + "\n")
+    print(DENSE_RESOURCES.read_text())
+
+
+def dense_rows():
+    import gpd_reference as dref
+    return (50, dref.LDS_ROWS, dref.LDS_ROWS + 1, 500, 1000)
+
+
+def bench_dense(pkg, rows, reps, lines):
+    """one quasi-periodic term on n rows, W = 64 and 1 024, forward and forward + gradient; beside it the same rows under a celerite SHO on the device and
+    numpy.linalg.cholesky on the [W, n, n] stack on the host (what a caller does today)"""
+    import torch
+    import gp_cases as gc
+    import gp_reference as gref
+    import gpd_cases as dc
+    import gpd_reference as dref
+    from hmc_bench import event_times
+    rng = np.random.default_rng(SEED)
+    planets = [(gref.RADVEL, 1)]
+    with pkg.PriorDraws(priors=[pkg.Uniform(0.0, 1.0)]) as pd:
+        for n in rows:
+            t = np.sort(rng.uniform(55000.0, 55000.0 + 4.0 * n, n))
+            tab = gref.table(t, rng.normal(size=n) * 8.0, rng.uniform(0.5, 3.0, n), np.ones((1, n)))
+            lines.append(f"\nn = {n:,d} rows ({'triangle in LDS' if n <= dref.LDS_ROWS else 'triangle in the work array'}), one quasi-periodic term, 1 planet, K = 1")
+            for W in DENSE_SIZES:
+                k = reps if n <= dref.LDS_ROWS + 1 else (3 if n * W <= 100_000 else 2)      # the long tables take seconds a call: the first call below warms them
+                warm = 5 if n <= dref.LDS_ROWS + 1 else (1 if n * W <= 100_000 else 0)
+                elems = torch.as_tensor(gc.draw_elements(rng, planets, W), device=pd.device)
+                hy = dc.draw_hyper(rng, [dref.QUASIPERIODIC], W)
+                beta = torch.as_tensor(rng.normal(size=(1, W)), device=pd.device)
+                jit_h = rng.uniform(0.1, 2.0, W)
+                jit = torch.as_tensor(jit_h, device=pd.device)
+                sho = torch.as_tensor(gc.draw_hyper(rng, [gref.SHO], W, "over"), device=pd.device)
+                for grad in (False, True):
+                    pd.gp_set(planets, tab["t"], tab["rv"], tab["sigma"], tab["c"], [dref.QUASIPERIODIC])
+                    hyper = torch.as_tensor(hy, device=pd.device)
+                    out = pd.gp_eval(elems, hyper, beta, jit, grad=grad)
+                    med, lo, hi = event_times(lambda: pd.gp_eval(elems, hyper, beta, jit, grad=grad, out=out), k, warmup=warm)
+                    work = pd.gp_work_doubles(W, grad=grad) * 8 / 2 ** 20
+                    pd.gp_set(planets, tab["t"], tab["rv"], tab["sigma"], tab["c"], [gref.SHO])
+                    out = pd.gp_eval(elems, sho, beta, jit, grad=grad)
+                    cmed = event_times(lambda: pd.gp_eval(elems, sho, beta, jit, grad=grad, out=out), max(k, 5))[0]
+                    lines.append(f"  W = {W:>6,d} {'fwd+grad' if grad else 'fwd     '}: {med * 1e3:10.3f} ms (min {lo * 1e3:.3f}, max {hi * 1e3:.3f}, of {k}) · "
+                                 f"a celerite SHO on the same rows {cmed * 1e3:8.3f} ms · work array {work:9.1f} MiB")
+                    print(lines[-1], flush=True)
+                if 8.0 * W * n * n <= HOST_STACK_LIMIT:
+                    tau = np.abs(tab["t"][:, None] - tab["t"][None, :])
+                    t0 = time.perf_counter()
+                    stack = np.stack([dref.kernel_np(dref.QUASIPERIODIC, hy[:, w], tau)[0] + np.diag(tab["sigma"] ** 2 + jit_h[w] ** 2) for w in range(W)])
+                    t1 = time.perf_counter()
+                    np.linalg.cholesky(stack)
+                    lines.append(f"  W = {W:>6,d} the host: building the [W, n, n] stack {(t1 - t0) * 1e3:9.1f} ms, numpy.linalg.cholesky on it {(time.perf_counter() - t1) * 1e3:9.1f} ms")
+                else:
+                    lines.append(f"  W = {W:>6,d} the host: skipped, the [W, n, n] stack is {8.0 * W * n * n / 1e9:.1f} GB")
+                print(lines[-1], flush=True)
+
+
+def main_dense(args):
+    import torch
+    from __graft_entry__ import kernel_source_hash, load_package
+    from slice_bench import draws_source_hash
+    if not torch.cuda.is_available():
+        raise SystemExit("gp_bench: no GPU: a timing is a run on the device")
+    out = Path(args.out) if args.out else DENSE_OUT
+    rows = [int(x) for x in args.rows.split(",")] if args.rows else list(dense_rows())
+    lines = []
+    if not args.append:
+        lines = [f"Gaussian-process RV term under dense kernels on {torch.cuda.get_device_name(0)}: HIP events around one call, median of {args.reps} (fewer on the long tables)",
+                 f"main library source hash {kernel_source_hash()[:16]} · draws library source hash {draws_source_hash()[:16]}"]
+        if DENSE_RESOURCES.exists():
+            lines += ["", DENSE_RESOURCES.read_text().rstrip()]
+    bench_dense(load_package(), rows, args.reps, lines)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    with open(out, "a" if args.append else "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "gp_throughput.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--resources", action="store_true")
+    ap.add_argument("--dense", action="store_true", help="the dense kernels (octo_draws_gpd.hip): profiles/gp_dense_throughput.txt, with --resources profiles/gp_dense_kernel_resources.txt")
+    ap.add_argument("--rows", default=None, help="--dense: the table lengths of this step, comma-separated (default: 50, LDS_ROWS, LDS_ROWS + 1, 500, 1000)")
+    ap.add_argument("--append", action="store_true", help="--dense: append to the output of an earlier step")
     args = ap.parse_args()
+    if args.dense:
+        return write_dense_resources() if args.resources else main_dense(args)
+    args.out = args.out or str(ROOT / "profiles" / "gp_throughput.txt")
     if args.resources:
         return write_resources()
     import torch
